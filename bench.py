@@ -67,7 +67,13 @@ def parse():
                                                            'ranks it heard from (tests/test_bench_launch.py)')
     ap.add_argument('--roofline-only', action='store_true', help='only the roofline legs (north-star conv + the dominant kernels of the step), '
                                                                  'no training step: what tools/profile_round.sh profiles separately from the step')
-    return ap.parse_args()
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step returned (loss, loss parts, gradient norm, weights after Adam, activations) '
+                         'as DIR/<name>.npy, float32 / float64, at most 64 MB in all (large arrays: a fixed seeded sample, see dump_outputs)')
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be >= 1')
+    return a
 
 
 def _time_conv(hip, xs, w, b, ys, iters, warm_ms=0.0):
@@ -434,6 +440,54 @@ def host_unblocked_ms(mrdis, cfg, dev, B, M, adv, steps=4, graph=False):
     return round(float(np.median(ts[2:])), 1)
 
 
+DUMP_BUDGET_BYTES = 48 * 2**20       # --dump-outputs: all arrays together (+ a 128-byte .npy header each) stay under 64 MB
+
+
+def dump_outputs(out_dir, model, step, loss, parts, aux):
+    """--dump-outputs: what a caller of the timed step received from its last call -- the loss, every loss part, the last clip's
+    [sum g^2, #non-finite], the weights after the optimizer step (all parameters flattened in model.parameters() order) and the
+    activations in aux (None on a graph replay) -- as <out_dir>/<name>.npy, float64 kept, everything else as float32.  The byte budget
+    is shared over the arrays, the small ones whole and the rest evenly; an array larger than its share is written as that many elements at sorted flat (NCHW-order)
+    indices drawn without replacement by numpy.random.default_rng(crc32(name)): the same elements in every run with the same
+    arguments, whatever the build.  Returns {name: [elements written, elements in the array]}."""
+    import zlib
+    arrays = [('loss', loss)]
+    arrays += [(f'part_{k}', v) for k, v in sorted(parts.items())]
+    if step.last_grad_norm_sq is not None:
+        arrays.append(('grad_norm_sq', step.last_grad_norm_sq))
+    arrays.append(('weights', torch.cat([p.detach().reshape(-1) for p in model.parameters()])))
+
+    def walk(name, v):
+        if isinstance(v, torch.Tensor):
+            arrays.append((name, v))
+        elif isinstance(v, (list, tuple)):
+            for i, u in enumerate(v):
+                walk(f'{name}_{i}', u)
+    for k, v in sorted((aux or {}).items()):
+        walk(f'aux_{k}', v)
+    width = {name: 8 if t.dtype == torch.float64 else 4 for name, t in arrays}
+    share, left = {}, DUMP_BUDGET_BYTES - 128 * len(arrays)
+    for i, (name, t) in enumerate(sorted(arrays, key=lambda nt: nt[1].numel() * width[nt[0]])):     # smallest first; what they leave goes to the rest
+        share[name] = min(t.numel(), max(1, left // (len(arrays) - i) // width[name]))
+        left -= share[name] * width[name]
+    os.makedirs(out_dir, exist_ok=True)
+    written, total = {}, 0
+    for name, t in arrays:
+        t = t.detach()
+        t = t.double() if t.dtype == torch.float64 else t.float()
+        flat = t.reshape(-1)
+        n = flat.numel()
+        if n > share[name]:
+            idx = np.sort(np.random.default_rng(zlib.crc32(name.encode())).choice(n, share[name], replace=False))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        arr = flat.cpu().numpy() if n > share[name] else t.cpu().numpy()
+        np.save(os.path.join(out_dir, f'{name}.npy'), arr)
+        written[name] = [int(arr.size), int(n)]
+        total += arr.nbytes + 128
+    assert total <= 64 * 10**6, total
+    return written
+
+
 def self_launch(a):
     """`python bench.py --gpus N` (N > 1) outside a launcher: start the N ranks as a CHILD `torch.distributed.run` (never exec: the parent has
     not touched a GPU and does not), forward its output, exit with its return code."""
@@ -562,7 +616,7 @@ def main():
     host_ms = 0.0
     for _ in range(a.steps):
         h0 = time.perf_counter()
-        loss, parts, _ = step(xd, maskd, mimgd, mask, targets=tgt)
+        loss, parts, _aux = step(xd, maskd, mimgd, mask, targets=tgt)
         host_ms += (time.perf_counter() - h0) * 1e3
     torch.cuda.synchronize()
     lib_launches = mrdis.hip.launch_counts()['all'] / a.steps
@@ -596,6 +650,11 @@ def main():
     ms = dt / a.steps * 1e3
     value = B * world / (dt / a.steps)
     host_losses = step.losses_to_host(parts)
+    dumped = None
+    if a.dump_outputs and rank == 0:                # before the extra legs below, which run more steps on the same model
+        dumped = dump_outputs(a.dump_outputs, model, step, loss, parts, _aux)
+        log(f'--dump-outputs: {len(dumped)} arrays in {a.dump_outputs}')
+    del _aux        # the last step's activations keep its autograd graph alive: released here, before the extra legs (the graph leg records a new step)
     # the same step on the direct-convolution kernels only (north_star describes a direct conv; the default policy runs
     # fused Winograd on the big 3x3 layers): reported beside the headline, never as `value`
     ms_direct = None
@@ -711,6 +770,8 @@ def main():
                 out['host_ms_unblocked_graph'] = None
                 out['host_ms_unblocked_graph_error'] = f'{type(ex).__name__}: {ex}'[:200]
             log(f'host_ms_unblocked: {out["host_ms_unblocked"]} ms/step')
+        if dumped is not None:
+            out['dump_outputs'] = {'dir': a.dump_outputs, 'arrays': dumped, 'note': '[elements written, elements in the array]: fewer written = a fixed seeded sample'}
         out['dynamic_lds_bytes'] = mrdis.hip.dynamic_lds()         # per kernel family: what rocprofv3's LDS column cannot show (tools/prof_summary.py merges it in)
         if ddp is not None:
             out['ddp'] = ddp

@@ -1,5 +1,5 @@
 """bf16-operand convolution entry points (fwd / dgrad / wgrad, fp32 and bf16 storage) against torch on bf16-rounded operands: error table over a shape list."""
-import sys; sys.path.insert(0, '/root/repo')
+import os, sys; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import torch, torch.nn.functional as F, mrdis
 hip = mrdis.hip; dev = torch.device('cuda:0')
 def cl(x): return x.to(dev).contiguous(memory_format=torch.channels_last)

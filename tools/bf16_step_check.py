@@ -1,9 +1,9 @@
 """One training step in each compute dtype (f32, bf16m, bf16) against the fp32 reference golden step_b2m4: loss and gradient-norm deviations (the measured bf16 tolerances)."""
-import sys; sys.path.insert(0, '/root/repo')
+import os, sys; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import json, numpy as np, torch, mrdis
 from oracle.gen_golden import make_inputs
 dev = torch.device('cuda:0')
-meta = json.load(open('/root/repo/tests/golden/step_b2m4.json'))
+meta = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'step_b2m4.json')))
 for mode in ('f32', 'bf16m', 'bf16'):
     cfg = dict(mrdis.DEFAULT_CONFIG); cfg.update(contrast_list=[f'm{i}' for i in range(4)], batch_size=16, compute_dtype=mode)
     cfg = mrdis.derive_config(cfg, dev)

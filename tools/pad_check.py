@@ -1,5 +1,5 @@
 """bf16 layers with 16 input channels (padded to 32 inside the kernels): timing of the padded path at the bench shapes."""
-import sys; sys.path.insert(0, '/root/repo')
+import os, sys; ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__))); sys.path.insert(0, ROOT)
 import torch, mrdis
 hip = mrdis.hip; dev = torch.device('cuda:0'); B16 = torch.bfloat16
 def timeit(fn, iters=5):
