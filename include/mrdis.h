@@ -72,7 +72,8 @@ int mrdis_version(void);
  *           tools/ use it for A/B; results agree to fp32 rounding);
  *   "debug_nopack" (MRDIS_DEBUG_NOPACK, default 0): 1 = the four output-parity classes of a stride-2 data gradient as four launches
  *           instead of one (bit-identical results; A/B switch);
- *   other "debug_*": kernel-selection overrides used by tools/ (see csrc/mrdis_elem.hip OPT_DEFS).
+ *   other "debug_*": kernel-selection overrides used by tools/ (see csrc/mrdis_elem.hip OPT_DEFS);
+ *   "zsearch_grid" (MRDIS_ZSEARCH_GRID, default 0): workgroups of mrdis_cosine_top1: 0 = min(gallery tiles, 1024), k > 0 = min(k, tiles, 2048) (results do not depend on it).
  * set: 0 or MRDIS_EINVAL (unknown name); get: the value, or MRDIS_EINVAL for an unknown name.  Not synchronised with launches
  * in flight on other threads. */
 int mrdis_set_option(const char* name, long long value);
@@ -81,7 +82,7 @@ long long mrdis_get_option(const char* name);
  * "wino2" | "wino2_spade" (pipelined F(2x2)), "wino4" | "wino4_spade" (F(4x4) 64-cout forms), "wino4n" | "wino4r" (32-cout forms: shared transform / register-fed),
  * "wino_wgrad" | "wino_wgrad2" (F(2x2) weight gradient), "wino4_wgrad" (F(3x3,4x4)); "bconv3" | "bconv3_spade" | "bconv4" | "bconv4_spade" (bf16 3x3 forms);
  * "split6_c4" | "split6_c16" | "split6_wgrad16" | "split6_co4" | "split6_c3d" | "split6_w3d" | "split6_tap" (option split6: the 4 -> C kernel, the 32 -> 16 forward, its weight gradient, the
- * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "all" (every kernel launch of the library).  MRDIS_EINVAL for an unknown name.  Diagnostics: the parity tests
+ * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "zsearch" (mrdis_cosine_top1); "all" (every kernel launch of the library).  MRDIS_EINVAL for an unknown name.  Diagnostics: the parity tests
  * use it to prove that the form under test is the one that ran. */
 long long mrdis_launch_count(const char* family);
 void mrdis_launch_count_reset(void);
@@ -470,6 +471,22 @@ int mrdis_groupnorm_relu_bwd_add(const float* dy, int lddy, const float* x, int 
  * Backward: dx = sum of the 8 children of dy (d skip = dy needs no kernel).                                       */
 int mrdis_upsample2x_add_fwd(const float* x, const float* skip, float* y, int N, int D, int H, int W, int C, void* stream);
 int mrdis_upsample2x_bwd(const float* dy, float* dx, int N, int D, int H, int W, int C, void* stream);
+
+/* Nearest-neighbour search of the missing-modality evaluation (model.py:3396-3415 compute_nearest_neighbour_z_by_s /
+ * compute_cosine, called per query from main_missing.py:414-426), csrc/mrdis_zsearch.hip.  For each query q < Q (Q <= 64):
+ *   out_idx[q] = argmax over gallery rows n with gallery_label[n] != query_label[q] of
+ *                cos(g_n, q) = sum g_n*q / (norm(g_n) * norm(q)),  norm(x) = max(sqrt(sum x^2 + 1e-8), 1e-8),
+ *   out_cos[q] = that cosine; equal cosines: the smaller n (torch.argmax's first occurrence); every row excluded: -1 and -inf.
+ * gallery (N, D) fp32 with row stride ldg >= D (floats), query (Q, D) dense fp32, labels int32.  One launch reads the gallery
+ * once for all queries (fp32 MFMA dot tiles); out_cos is bit-identical across launches and across grid sizes (option
+ * "zsearch_grid").  workspace: >= mrdis_cosine_top1_workspace(N, D, Q) bytes, 16-byte aligned, used by this entry point ONLY;
+ * its first 4 bytes are an arrival counter that must be zero before the first launch (zero the buffer once when allocating
+ * it): every launch leaves it zero again.  Launches sharing one workspace must be stream-ordered.
+ * Launch counter family "zsearch".                                                                                       */
+size_t mrdis_cosine_top1_workspace(int N, int D, int Q);
+int mrdis_cosine_top1(const float* gallery, long long ldg, const int* gallery_label, int N, int D,
+                      const float* query, const int* query_label, int Q,
+                      int* out_idx, float* out_cos, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -104,6 +104,8 @@ _SIGS = {
     'mrdis_groupnorm_relu_bwd_add': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _Z, _I, _L, _I, _I, _I, _P]),
     'mrdis_upsample2x_add_fwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_upsample2x_bwd': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    'mrdis_cosine_top1_workspace': (_Z, [_I, _I, _I]),
+    'mrdis_cosine_top1': (_I, [_P, _L, _P, _I, _I, _P, _P, _I, _P, _P, _P, _Z, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -143,7 +145,7 @@ def get_option(name):
 # every switch of csrc/mrdis_elem.hip OPT_DEFS (tests/test_abi.py checks that the library knows each name)
 OPTION_NAMES = ('wino', 'nt_mb', 'wino_pipe', 'wino_u', 'wino4', 'wino4r', 'bconv4', 'split6', 'debug_no16', 'debug_nothin', 'debug_noc4', 'debug_nodma',
                 'debug_no16_3d', 'debug_bilgen', 'debug_now16', 'debug_nopack', 'debug_mode', 'debug_bn', 'debug_kc', 'debug_bm', 'debug_c4_tw',
-                'debug_wgsplit', 'debug_bn3', 'debug_kc3', 'c4_grid', 'debug_c4_blocks')
+                'debug_wgsplit', 'debug_bn3', 'debug_kc3', 'c4_grid', 'debug_c4_blocks', 'zsearch_grid')
 
 
 def options_snapshot():
@@ -159,7 +161,8 @@ def options_restore(snap):
 
 KERNEL_FAMILIES = WINO_FAMILIES = ('wino', 'wino_spade', 'wino2', 'wino2_spade', 'wino4', 'wino4_spade', 'wino4n', 'wino4r', 'wino_wgrad', 'wino_wgrad2', 'wino4_wgrad', 'bconv3', 'bconv3_spade', 'bconv4', 'bconv4_spade',
                                    'split6_c4', 'split6_c16', 'split6_wgrad16', 'split6_co4', 'split6_c3d', 'split6_w3d', 'split6_tap',
-                                   'all')        # 'all': every kernel launch of the library (bench.py: library_launches_per_step)
+                                   'all',        # 'all': every kernel launch of the library (bench.py: library_launches_per_step)
+                                   'zsearch')    # mrdis_cosine_top1 (nearest-neighbour modality-code search)
 
 
 def stream_fill(t, value=0.0):
@@ -1244,3 +1247,37 @@ def upsample2x_bwd(dy):
     dx = empty_ndhwc(N, C, D2 // 2, H2 // 2, W2 // 2, dy.device)
     _chk(load().mrdis_upsample2x_bwd(dy.data_ptr(), dx.data_ptr(), N, D2 // 2, H2 // 2, W2 // 2, C, _stream()), 'upsample2x_bwd')
     return dx
+
+
+# ---------------------------------------------------------------- nearest-neighbour modality-code search
+_ZS_WS = {}       # (device, raw stream) -> zero-initialised workspace of mrdis_cosine_top1 (its arrival counter must start at 0; every launch leaves it 0)
+
+
+def cosine_top1(gallery, gallery_label, query, query_label):
+    """For each query row: the gallery row of highest cosine (reference compute_cosine, model.py:3407-3415) among the rows whose label differs
+    from the query's; equal cosines -> the smaller index.  gallery (N, D) fp32 with unit column stride (row stride >= D), query (Q <= 64, D),
+    labels int32 on the device.  Returns (idx (Q,) int32, cos (Q,) fp32); a query with every row excluded gets -1 / -inf (include/mrdis.h)."""
+    assert gallery.dtype == torch.float32 and query.dtype == torch.float32, (gallery.dtype, query.dtype)
+    assert gallery.dim() == 2 and query.dim() == 2 and gallery.shape[1] == query.shape[1], (gallery.shape, query.shape)
+    assert gallery_label.dtype == torch.int32 and query_label.dtype == torch.int32
+    N, D = gallery.shape
+    Q = query.shape[0]
+    assert gallery_label.shape == (N,) and query_label.shape == (Q,) and 1 <= Q <= 64, (gallery_label.shape, query_label.shape)
+    if gallery.stride(1) != 1 or gallery.stride(0) < D:
+        gallery = gallery.contiguous()
+    query = query.contiguous()
+    gallery_label, query_label = gallery_label.contiguous(), query_label.contiguous()
+    lib = load()
+    dev = gallery.device
+    nb = _ws_bytes(lib.mrdis_cosine_top1_workspace, N, D, Q)
+    if nb == 0:
+        raise MrdisError(f'cosine_top1: unsupported geometry N={N} D={D} Q={Q}')
+    key = (dev, _stream())
+    ws = _ZS_WS.get(key)
+    if ws is None or ws.numel() < nb:
+        ws = _ZS_WS[key] = torch.zeros(max(nb, 1 << 16), dtype=torch.uint8, device=dev)
+    idx = torch.empty(Q, dtype=torch.int32, device=dev)
+    cos = torch.empty(Q, dtype=torch.float32, device=dev)
+    _chk(lib.mrdis_cosine_top1(gallery.data_ptr(), gallery.stride(0), gallery_label.data_ptr(), N, D, query.data_ptr(), query_label.data_ptr(), Q,
+                               idx.data_ptr(), cos.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), 'cosine_top1')
+    return idx, cos

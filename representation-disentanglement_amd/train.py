@@ -6,7 +6,7 @@ functions around `TrainStep` / `EvalStep`.
 What is kept from the reference, statement by statement:
   * seeds (main_missing.py:17-22), config.yaml keys (src/config.yaml), derived keys (:26-28, :75-86)
   * checkpoint directory `<ckpt_root>/<dataset_name>/<model_name>/<time label>` and the saved-yaml merge rule
-    (:30-58; keys `phase` / `continue_train` always come from the current file)
+    (:30-58; keys `phase` / `continue_train` (and this implementation's `eval_info`) always come from the current file)
   * Adam(lr, wd 1e-5, amsgrad) + ReduceLROnPlateau(min, 0.1, patience 5, min_lr 1e-5) (:118-119), optimizer_d_s (:121-122)
   * continue_train / test: `load_checkpoint_by_key` for optimizer, scheduler, model[, optimizer_d_s] (:125-135,
     util.py:870-892), name + shape filtered model load (util.py:895-903)
@@ -38,7 +38,7 @@ import torch.distributed as dist
 import yaml
 
 from .data import BatchLoader, SliceDataset, VolumeStore, load_idx_list
-from .trainer import (DEFAULT_CONFIG, LOSS_KEYS, EvalStep, TrainStep, make_train_step, build_model, derive_config, load_checkpoint_model,
+from .trainer import (DEFAULT_CONFIG, LOSS_KEYS, EVAL_INFOS, EvalStep, ZGallery, build_z_gallery, TrainStep, make_train_step, build_model, derive_config, load_checkpoint_model,
                       load_config_yaml, save_checkpoint)
 
 SEED = 10                                                                   # main_missing.py:18
@@ -163,7 +163,7 @@ def setup_config(config_path='config.yaml', overrides=None, ckpt_root='../ckpt/'
         flag, saved = load_config_yaml(os.path.join(config['ckpt_path'], 'config.yaml'))
         if flag:
             for k, v in saved.items():                                      # :45-51
-                if k in ('phase', 'continue_train') or k not in config:
+                if k in ('phase', 'continue_train', 'eval_info') or k not in config:    # eval_info: per invocation, like phase
                     continue
                 config[k] = v
             config = derive_config(config, device)
@@ -356,10 +356,35 @@ class Run:
             self.log(f'epoch {epoch}: train {loss_all["all"]:.4f}, val monitor {monitor:.4f}, lr {self.optimizer.lr:g}, best {is_best}')
         return self
 
+    def z_gallery_path(self, set_):
+        return os.path.join(self.config['ckpt_path'], 'result_' + set_, 'z_gallery.pt')        # main_missing.py:371 res_path
+
+    def z_gallery(self, set_, max_batches=502):
+        """the ZGallery of `set_`: loaded from ckpt_path/result_<set>/z_gallery.pt, or built by one encoder pass over the set and saved there
+        (the reference reads the results_all.h5 of an earlier save_res run, main_missing.py:374-382)."""
+        path = self.z_gallery_path(set_)
+        if os.path.exists(path):
+            return ZGallery.load(path, self.config['device'])
+        loader = self.loaders[set_]
+        batches = loader.batches(limit=max_batches) if hasattr(loader, 'batches') else loader
+        g = build_z_gallery(self.model, batches, self.config)
+        g.save(path)
+        self.log(f'z gallery of {set_}: {len(g)} slices of {len(g.subjects)} subjects -> {path}')
+        return g
+
     # ---- main_missing.py:337-609 (losses + reconstruction metrics; no result dump)
-    def evaluate(self, phase='val', set_='val', max_batches=502):
+    def evaluate(self, phase='val', set_='val', max_batches=502, info=''):
+        """info = 'nearest_neighbour' | 'mean' (main_missing.py:409-426): the input reconstructions decode with a modality code searched in (or
+        averaged over) the z gallery of `set_` (Run.z_gallery), other subjects only.  World size 1 only."""
         loader = self.loaders['val'] if phase == 'val' else self.loaders[set_]
         cfg = self.config
+        step = self.eval_step
+        if info:
+            if info not in EVAL_INFOS:
+                raise ValueError(f'evaluate(info={info!r}): one of {EVAL_INFOS}')
+            if self.world > 1 or (dist.is_available() and dist.is_initialized()):
+                raise NotImplementedError(f'evaluate(info={info!r}) under a process group: the z gallery is not sharded; evaluate on one process')
+            step = EvalStep(self.model, cfg, info=info, gallery=self.z_gallery(set_, max_batches))
         acc, n_iter, met = None, 0, {'rmse': [], 'psnr': [], 'ssim': []}
         # the reference stops after global batch 501 (:562-563).  The cap is applied by the loader, on the GLOBAL batch index and before any meta of a later
         # batch is drawn, so every rank walks the same `max_batches` batches and leaves the host generators in the same state (a cap tested per rank after
@@ -369,7 +394,8 @@ class Run:
             if sample.get('batch_index', it) >= max_batches:
                 break
             targets = sample['targets'] if cfg['lambda_recon_y'] > 0 else None
-            loss, parts, metrics, _ = self.eval_step(sample['inputs'], sample['mask'], sample['mask_img'], sample.get('mask_host'), targets=targets)
+            kw = dict(subj_id=sample['subj_id']) if info else {}
+            loss, parts, metrics, _ = step(sample['inputs'], sample['mask'], sample['mask_img'], sample.get('mask_host'), targets=targets, **kw)
             vec = torch.stack([parts[k].float().reshape(()) for k in LOSS_KEYS])
             acc = vec if acc is None else acc + vec
             for k in met:
@@ -415,7 +441,7 @@ def main(argv=None):
         if config['phase'] == 'train':                                      # :611-614
             run.train()
         else:
-            stat = run.evaluate(phase='test', set_='test')
+            stat = run.evaluate(phase='test', set_='test', info=config.get('eval_info') or '')
             if run.rank == 0:
                 print(stat)
     finally:

@@ -37,6 +37,7 @@ DEFAULT_CONFIG = {
     'backend': 'hip', 'is_patch_gan': False,
     'graph': None,                     # true: steady-state iterations as HIP-graph replays (trainer.GraphedTrainStep); None: MRDIS_GRAPH decides (default off)
     'compute_dtype': 'f32',            # BASELINE configs[2]: 'bf16' = bf16 activations + bf16 MFMA operands + fp32 accumulate; 'bf16m' = bf16 MFMA operands only
+    'eval_info': '',                   # phase: test -- '' | 'nearest_neighbour' | 'mean': decode with a searched / mean modality code (main_missing.py:409-426; EvalStep)
 }
 
 
@@ -570,11 +571,8 @@ LOSS_KEYS = ('recon_y', 'recon_y_fused', 'recon_x', 'recon_x_mix', 'kl', 'latent
              'adv_s', 'adv_s_d', 'all')
 
 
-def forward_losses(model, config, inputs, mask, mask_img, mask_host, phase='train', targets=None):
-    """main_missing.py:165-251 (phase='train') / :389-505 (phase='test') for the loss set with non-zero
-    weight in config.yaml."""
-    M = len(config['contrast_list'])
-    c = 2 * config['block_size'] + 1
+def split_inputs(inputs, M, c):
+    """the (B, M c, H, W) batch as M per-contrast (B, c, H, W) tensors (main_missing.py:166-168)."""
     inputs_list = [inputs[:, i * c:(i + 1) * c] for i in range(M)]                               # :166-168 (views)
     if _PLANAR_INPUTS and M > 1 and inputs.is_cuda and inputs.is_contiguous(memory_format=torch.channels_last):
         # one pass that turns the (B, H, W, M c) batch into M dense (B, H, W, c) blocks: a c-channel slice of the interleaved tensor
@@ -583,6 +581,16 @@ def forward_losses(model, config, inputs, mask, mask_img, mask_host, phase='trai
         B, _, H, W = inputs.shape
         planar = inputs.permute(0, 2, 3, 1).reshape(B, H, W, M, c).permute(3, 0, 1, 2, 4).contiguous()
         inputs_list = [planar[i].permute(0, 3, 1, 2) for i in range(M)]
+    return inputs_list
+
+
+def forward_losses(model, config, inputs, mask, mask_img, mask_host, phase='train', targets=None, z_recon=None):
+    """main_missing.py:165-251 (phase='train') / :389-505 (phase='test') for the loss set with non-zero
+    weight in config.yaml.  z_recon (evaluation with info = 'nearest_neighbour' | 'mean', :409-426): a function
+    (si_list, zi_list) -> the M modality codes the two input reconstructions decode with instead of zi_list."""
+    M = len(config['contrast_list'])
+    c = 2 * config['block_size'] + 1
+    inputs_list = split_inputs(inputs, M, c)
     p = config['p']
     dev = inputs.device
     zero = torch.zeros((), device=dev)
@@ -594,8 +602,9 @@ def forward_losses(model, config, inputs, mask, mask_img, mask_host, phase='trai
         ops.premix_all(model, model._type_table)
     si_list = model.compute_anatomy_encoding(inputs_list, mask_img)                              # :175
     zi_list, mu_list, lv_list = model.compute_modality_encoding(inputs_list, si_list, phase=phase)     # :176 / :400
-    xi_fake_list = model.reconstruct_input_si_zi(si_list, zi_list)                               # :177
-    xi_fake_mix_list = model.reconstruct_input_si_zj(si_list, zi_list)                           # :178
+    z_dec = zi_list if z_recon is None else z_recon(si_list, zi_list)                            # :425-426 substitute z_find
+    xi_fake_list = model.reconstruct_input_si_zi(si_list, z_dec)                                 # :177
+    xi_fake_mix_list = model.reconstruct_input_si_zj(si_list, z_dec)                             # :178
     parts = {k: zero for k in LOSS_KEYS}
     loss = zero
     if config['lambda_kl'] > 0:
@@ -639,6 +648,8 @@ def forward_losses(model, config, inputs, mask, mask_img, mask_host, phase='trai
     parts['all'] = loss
     aux = dict(si_list=si_list, zi_list=zi_list, mu_list=mu_list, lv_list=lv_list, xi_fake_list=xi_fake_list,
                xi_fake_mix_list=xi_fake_mix_list, y_list=y_list)
+    if z_recon is not None:
+        aux['z_find'] = z_dec
     return loss, parts, aux
 
 
@@ -1006,28 +1017,181 @@ def make_train_step(model, config, **kw):
     return GraphedTrainStep(step) if want else step
 
 
+EVAL_INFOS = ('', 'nearest_neighbour', 'mean')
+
+
+def nn_source_contrast(i):
+    """contrast whose compact anatomy code searches the modality code of missing contrast i: abs(1 - i), the reference's rule
+    (main_missing.py:414), kept as is -- for M = 4 it maps contrasts 0, 1, 2, 3 to 1, 0, 1, 2."""
+    return abs(1 - i)
+
+
+class ZGallery:
+    """Gallery of the missing-modality evaluation (main_missing.py:374-382): per slice of an earlier pass over a set, the compact anatomy
+    code of every contrast and its modality code.
+      s_compact (N, M, D) fp32: model.compute_compact_s of each contrast's s (max-pooling is per sample, so compacting the saved maps
+                row by row as the reference does is the same thing);
+      z         (N, M, Z) fp32: the modality encoder's mu (what phase='test' returns);
+      subject   (N,) int32: index into `subjects` (the loader's subj_id strings);
+      slice_idx (N,) int64.
+    All on one device.  Per-subject sums of z for info = 'mean' are computed once, on first use."""
+
+    def __init__(self, s_compact, z, subject, slice_idx, subjects):
+        self.s_compact, self.z, self.subject, self.slice_idx = s_compact, z, subject, slice_idx
+        self.subjects = [str(x) for x in subjects]
+        self._code = {n: k for k, n in enumerate(self.subjects)}
+        self._sums = self._present = None
+        assert s_compact.dim() == 3 and z.dim() == 3 and s_compact.shape[:2] == z.shape[:2], (s_compact.shape, z.shape)
+        assert subject.dtype == torch.int32 and subject.shape == (s_compact.shape[0],)
+
+    def __len__(self):
+        return self.s_compact.shape[0]
+
+    def codes(self, subj_ids):
+        """host list of subject codes of subj_id strings; a subject the gallery does not hold gets -1 (excludes nothing)."""
+        return [self._code.get(str(x), -1) for x in subj_ids]
+
+    def save(self, path):
+        os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+        torch.save({'s_compact': self.s_compact.cpu(), 'z': self.z.cpu(), 'subject': self.subject.cpu(), 'slice_idx': self.slice_idx.cpu(),
+                    'subjects': list(self.subjects)}, path)
+        return path
+
+    @classmethod
+    def load(cls, path, device):
+        d = torch.load(path, map_location='cpu', weights_only=True)
+        return cls(d['s_compact'].to(device), d['z'].to(device), d['subject'].to(device), d['slice_idx'].to(device), d['subjects'])
+
+    def _check_search_space(self, codes):
+        if self._present is None:
+            self._present = set(self.subject.cpu().tolist())           # once per gallery: no per-batch host sync
+        present = self._present
+        for c in codes:
+            if not (present - {c}):
+                raise ValueError(f'z gallery: every row belongs to the query subject {self.subjects[c]!r}; nothing to search')
+
+    def nearest(self, query_s, codes, src):
+        """(B,) int32 gallery rows of highest cosine between query_s (B, D) and s_compact[:, src], rows of the query's own subject excluded."""
+        self._check_search_space(codes)
+        qlab = torch.tensor(codes, dtype=torch.int32).to(query_s.device, non_blocking=True)
+        idx, _ = hip.cosine_top1(self.s_compact[:, src], self.subject, query_s.float(), qlab)
+        return idx
+
+    def mean_z(self, codes, i):
+        """(B, Z): mean of z[:, i] over the rows of every subject but the query's (main_missing.py:421 compute_mean_z_by_s)."""
+        self._check_search_space(codes)
+        if self._sums is None:
+            S = len(self.subjects)
+            zd = self.z.double()
+            sums = torch.zeros((S,) + tuple(zd.shape[1:]), dtype=torch.float64, device=zd.device).index_add_(0, self.subject.long(), zd)
+            counts = torch.bincount(self.subject.long(), minlength=S).double()
+            self._sums = (sums, counts, zd.sum(0), float(len(self)))
+        sums, counts, total, n = self._sums
+        out = []
+        for c in codes:
+            if c < 0:
+                out.append(total[i] / n)
+            else:
+                out.append((total[i] - sums[c, i]) / (n - counts[c]))
+        return torch.stack(out).float()
+
+
+def _encode_batch(model, config, inputs, mask_img):
+    """anatomy + modality encoders of one batch in eval mode (no decoder): (si_list, mu_list)."""
+    M = len(config['contrast_list'])
+    inputs_list = split_inputs(inputs, M, 2 * config['block_size'] + 1)
+    if hasattr(model, 'premix'):
+        model.premix('enc')
+    else:
+        ops.premix_all(model, model._type_table)
+    si_list = model.compute_anatomy_encoding(inputs_list, mask_img)
+    zi_list, _, _ = model.compute_modality_encoding(inputs_list, si_list, phase='test')          # phase='test': z = mu
+    return si_list, zi_list
+
+
+@torch.no_grad()
+def build_z_gallery(run_or_model, loader, config=None, max_batches=None):
+    """ZGallery of one no_grad eval-mode pass over `loader` (the reference's earlier save_res run: s_list / z_list of results_all.h5),
+    through the anatomy and modality encoders only.  `run_or_model`: a train.Run (its config is used) or a model with `config` given."""
+    model = getattr(run_or_model, 'model', run_or_model)
+    config = config if config is not None else run_or_model.config
+    was = model.training
+    flush_batch_counters()
+    model.eval()
+    s_rows, z_rows, subj, sl, names, code = [], [], [], [], [], {}
+    try:
+        with ops.mix_cache():
+            for k, sample in enumerate(loader):
+                if max_batches is not None and k >= max_batches:
+                    break
+                si_list, zi_list = _encode_batch(model, config, sample['inputs'], sample['mask_img'])
+                s_rows.append(torch.stack([model.compute_compact_s(s) for s in si_list], 1))
+                z_rows.append(torch.stack([z.float() for z in zi_list], 1))
+                for sid in sample['subj_id']:
+                    sid = str(sid)
+                    if sid not in code:
+                        code[sid] = len(names); names.append(sid)
+                    subj.append(code[sid])
+                sl.append(torch.as_tensor(sample['slice_idx']).reshape(-1).to(torch.int64))
+    finally:
+        model.train(was)
+    if not s_rows:
+        raise RuntimeError('build_z_gallery: the loader yielded no batch')
+    dev = s_rows[0].device
+    return ZGallery(torch.cat(s_rows).float().contiguous(), torch.cat(z_rows).contiguous(), torch.tensor(subj, dtype=torch.int32).to(dev),
+                    torch.cat([x.to(dev) for x in sl]), names)
+
+
 class EvalStep:
     """evaluate() of the reference for one batch (main_missing.py:337-517): model.eval() (BatchNorm on
     running statistics), no_grad, z = mu, the same loss set, plus the reconstruction metrics of the
     cross-modality (mix) reconstructions (:520-528) computed on the device instead of shipping both
     stacks to skimage on the host (util.py:935-978): per image (channel 0 of each sample) min-shifted,
     data range = max of the shifted target; keys as in the reference ('rmse' holds the MSE, as there).
-    Returns (loss, parts, metrics, aux); metrics values are (M(M-1)B,) device tensors in the reference order."""
+    Returns (loss, parts, metrics, aux); metrics values are (M(M-1)B,) device tensors in the reference order.
 
-    def __init__(self, model, config):
-        self.model, self.config = model, config
+    info = 'nearest_neighbour' | 'mean' (:409-426, needs `gallery`, a ZGallery, and `subj_id` per batch): the two input reconstructions
+    decode with z_find instead of the slice's own modality code; z_find[i] is the z[:, i] of the gallery row whose compact s of contrast
+    nn_source_contrast(i) is nearest (cosine) to the query's, rows of the query's own subject excluded -- one mrdis_cosine_top1 launch per
+    distinct source contrast -- or, for 'mean', the mean z[:, i] over every other subject's rows.  Losses and metrics follow unchanged
+    (sim_z and latent_z still see the slice's own codes, as in the reference).  aux['z_find'] holds the codes used.  World size 1 only."""
+
+    def __init__(self, model, config, info='', gallery=None):
+        if info not in EVAL_INFOS:
+            raise ValueError(f'EvalStep info={info!r}: one of {EVAL_INFOS}')
+        if info and dist.is_available() and dist.is_initialized():
+            raise NotImplementedError(f'evaluation with info={info!r} under a process group: the z gallery is not sharded; evaluate on one process')
+        if info and gallery is None:
+            raise ValueError(f'EvalStep info={info!r} needs a ZGallery (build_z_gallery)')
+        self.model, self.config, self.info, self.gallery = model, config, info, gallery
+
+    def _z_find(self, si_list, zi_list, codes):
+        M = len(si_list)
+        g = self.gallery
+        if self.info == 'mean':
+            return [g.mean_z(codes, i).to(zi_list[i].dtype) for i in range(M)]
+        idx = {}
+        for src in sorted({nn_source_contrast(i) for i in range(M)}):
+            idx[src] = g.nearest(self.model.compute_compact_s(si_list[src]), codes, src)
+        return [g.z[idx[nn_source_contrast(i)].long(), i].to(zi_list[i].dtype) for i in range(M)]
 
     @torch.no_grad()
-    def __call__(self, inputs, mask, mask_img, mask_host=None, targets=None):
+    def __call__(self, inputs, mask, mask_img, mask_host=None, targets=None, subj_id=None):
         model, cfg = self.model, self.config
         if mask_host is None:
             mask_host = mask.cpu()
+        z_recon = None
+        if self.info:
+            if subj_id is None or len(subj_id) != inputs.shape[0]:
+                raise ValueError(f'EvalStep info={self.info!r} needs the subj_id of every sample of the batch')
+            codes = self.gallery.codes(subj_id)
+            z_recon = lambda si_list, zi_list: self._z_find(si_list, zi_list, codes)      # noqa: E731
         was = model.training
         flush_batch_counters()
         model.eval()
         try:
             with ops.mix_cache():
-                loss, parts, aux = forward_losses(model, cfg, inputs, mask, mask_img, mask_host, phase='test', targets=targets)
+                loss, parts, aux = forward_losses(model, cfg, inputs, mask, mask_img, mask_host, phase='test', targets=targets, z_recon=z_recon)
                 M = len(cfg['contrast_list'])
                 c = 2 * cfg['block_size'] + 1
                 rows, k = [], 0
