@@ -126,17 +126,43 @@ def test_conv_winograd_forced(mrdis, case):
     hip.set_option('wino', 0)
     y_direct = hip.conv2d_fwd(cl(x.detach()), w_tck, b.to(dev()), 3, 3, 1, 1)
     hip.set_option('wino', 2)
+
+    def ran(*fams):              # the counted kernel families that launched since the last call: exactly `fams`
+        c = {f: n for f, n in hip.launch_counts(reset=True).items() if n and f not in ('all', 'zsearch')}
+        assert set(c) == set(fams), (fams, c)
+
+    hip.launch_counts(reset=True)
     y_w = hip.conv2d_fwd(cl(x.detach()), w_tck, b.to(dev()), 3, 3, 1, 1)
+    ran('wino2' if Co > 32 else 'wino')                        # the pipelined form for > 32 couts (option wino_pipe), else the phase-by-phase one
     assert not torch.equal(y_w, y_direct)                      # really another kernel
     close(y_w, y, rtol=1e-4, what='winograd fwd')
     close(y_w, y_direct, rtol=1e-4, what='winograd vs direct')
     close(hip.conv2d_fwd(cl(x.detach()), w_tck, b.to(dev()), 3, 3, 1, 1, lrelu=True), F.leaky_relu(y, 0.2), rtol=1e-4, what='fwd+lrelu')
+    ran('wino2' if Co > 32 else 'wino')
     close(hip.conv2d_bwd_data(cl(gy), w_tkc, (H, W), 3, 3, 1, 1), x.grad, rtol=1e-4, what='winograd dgrad')
+    ran('wino2' if Ci > 32 else 'wino')                        # (the data gradient produces Ci channels)
     dw, db = hip.conv2d_bwd_weight(cl(x.detach()), cl(gy), 3, 3, 1, 1, need_bias=True)     # Winograd where Ci / Co are 32 / 64 multiples
+    blocked = (Ci % 64 == 0 and Co % 32 == 0) or (Ci % 32 == 0 and Co % 64 == 0)          # (plan_wino_wgrad's blockings)
+    f22 = 'wino_wgrad2' if Ci % 64 == 0 and Co % 64 == 0 else 'wino_wgrad'
+    f44 = Ci % 32 == 0 and Co % 64 == 0 and H % 8 == 0 and W % 8 == 0           # F(4x4) weight gradient: only where its grid test (option wino4 = 1) says so
+    # (outside the Winograd blockings this proves only that no Winograd weight-gradient kernel ran: the uncounted kernels that take the call instead
+    #  are told apart in tests/test_gpu_conv_paths.py)
+    c = {f for f, n in hip.launch_counts(reset=True).items() if n and f not in ('all', 'zsearch')}
+    assert c == ({f22} if blocked else set()) or (f44 and c == {'wino4_wgrad'}), (blocked, f22, c)
     close(dw, to_tck(w.grad), rtol=2e-4, what='winograd wgrad')
     close(db, gy.sum((0, 2, 3)), rtol=2e-4, what='dbias')
     wide = cl(torch.cat([rnd((N, 8, H, W), 9), x.detach()], 1))          # channel slice: ld = Ci + 8
     close(hip.conv2d_fwd(wide[:, 8:], w_tck, None, 3, 3, 1, 1), y - b.view(1, -1, 1, 1), rtol=1e-4, what='strided view')
+
+
+def check_bf16_dgrad(got, gy, w, H, W, what):
+    """a bf16 data gradient element by element against float64 on the bf16-rounded operands (tests/conv_check.py; kappa of the bf16 kernels'
+    data gradient, tests/conv_check.py KAPPA)"""
+    import conv_check as CC
+    from fixtures import dump_measured
+    ref, A = CC.dgrad_ref(CC.bf16_round(gy), CC.bf16_round(w), (H, W), 1, 1)
+    dump_measured('conv_path_margins.jsonl', dict(row=what, kernel='bconv3|bconv4', op='dgrad', out='dx', ratio=CC.ratio(got, ref, A, CC.U_BF16)))
+    CC.check(got, ref, A, max(CC.KAPPA[('bconv3', 'dgrad')], CC.KAPPA[('bconv4', 'dgrad')]), u_out=CC.U_BF16, what=what)
 
 
 @pytest.mark.parametrize('case', [(2, 32, 64, 23, 37), (3, 64, 40, 50, 33), (1, 96, 16, 9, 70), (6, 128, 256, 64, 64), (2, 64, 32, 40, 96)], ids=str)
@@ -162,6 +188,8 @@ def test_bf16_pipelined_conv_bit_identical(mrdis, case):
         assert torch.equal(out[0][1], out[1][1])
     ref = F.leaky_relu(F.conv2d(x.to(B16).float(), w.to(B16).float(), b, 1, 1), 0.2)
     close(out[1][0].float(), ref, rtol=1.5e-2, what='bf16 pipelined fwd vs torch on bf16-rounded operands')
+    if out[1][1] is not None:
+        check_bf16_dgrad(out[1][1], gy, w, H, W, 'bf16 pipelined dgrad')
 
 
 BCONV4_CASES = [(2, 32, 64, 23, 37), (3, 64, 40, 50, 33), (1, 96, 16, 9, 70), (6, 128, 256, 64, 64), (2, 64, 32, 40, 96), (5, 32, 72, 16, 32), (1, 64, 128, 130, 67),
@@ -197,6 +225,8 @@ def test_bf16_lds_dma_conv_bit_identical(mrdis, case):
             assert torch.equal(out[0][2], out[mode][2]), mode
     ref = F.leaky_relu(F.conv2d(x.to(B16).float(), w.to(B16).float(), b, 1, 1), 0.2)
     close(out[2][0].float(), ref, rtol=1.5e-2, what='bf16 LDS-DMA fwd vs torch on bf16-rounded operands')
+    if out[2][2] is not None:
+        check_bf16_dgrad(out[2][2], gy, w, H, W, 'bf16 LDS-DMA dgrad')
     # a channel-slice input view (ld > Cin) whose last pixel ends exactly at the descriptor's record count, and an output slice of a wider buffer
     if Co % 8 == 0:
         wide_in = cl(torch.cat([rnd((N, 8, H, W), 9), x], 1)).to(B16)
@@ -266,8 +296,11 @@ def test_gb_spade_fused_epilogue(mrdis, case):
         assert hip.gb_spade_fwd(x, w_tck, b, z, 1e-5) is None          # too few tile blocks for the Winograd policy: the caller falls back
         return
     hip.set_option('wino', 2)                           # Winograd wherever the kernel applies (the size policy is tested at scale)
+    hip.launch_counts(reset=True)
     res = hip.gb_spade_fwd(x, w_tck, b, z, 1e-5)
     assert res is not None
+    c = {f for f, n in hip.launch_counts().items() if n and f not in ('all', 'zsearch')}
+    assert c == {'wino2_spade'}, c                      # the SPADE epilogue of the pipelined F(2x2) kernel (no F(4x4) image given)
     mix, gamma, mean, rstd = res
     close(gamma, gb[:, :C].cpu(), rtol=2e-5, what='gamma')
     close(mix, mix_ref.cpu(), rtol=2e-5, what='mix')
