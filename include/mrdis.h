@@ -488,6 +488,30 @@ int mrdis_cosine_top1(const float* gallery, long long ldg, const int* gallery_la
                       const float* query, const int* query_label, int Q,
                       int* out_idx, float* out_cos, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- the `others` variants of the reference (config.yaml:67-70), csrc/mrdis_encs.hip.
+ * mod_enc_s: the modality encoder's first layer reads cat([x, s], 1) (model.py:2374) from its two sources: x (N,H,W,Cx) view with
+ * pixel stride ldx, s (N,H,W,Cs) view with pixel stride lds.  Filters are those of the concatenated layer: w_tck [T][Cx+Cs][Co],
+ * w_tkc [T][Co][Cx+Cs], input channel ci < Cx from x, ci >= Cx from s (T = kh * kw <= 9, Cx + Cs <= 32, Co <= 16, stride <= 2).
+ * fp32 FMA.  Forward with optional fused LeakyReLU(0.2); the data gradient writes ds and, unless dx is NULL, dx (dy is the gradient
+ * of the pre-activation output); the weight gradient writes dw_tck and, unless dbias is NULL, the bias gradient (added to dbias when
+ * accumulate_bias), via per-workgroup slabs in `workspace` (>= the query's bytes, 16-byte aligned) summed in a fixed order.
+ * Launch counter family "conv2src".                                                                                     */
+int mrdis_conv2d_2src_fwd(const float* x, int ldx, int Cx, const float* s, int lds, int Cs, const float* w_tck, const float* bias,
+                          float* y, int ldy, int N, int H, int W, int Co, int kh, int kw, int stride, int pad, int lrelu, void* stream);
+int mrdis_conv2d_2src_bwd_data(const float* dy, int lddy, const float* w_tkc, float* dx, int lddx, int Cx, float* ds, int ldds, int Cs,
+                               int N, int H, int W, int Co, int kh, int kw, int stride, int pad, void* stream);
+size_t mrdis_conv2d_2src_bwd_weight_workspace(int N, int H, int W, int Cx, int Cs, int Co, int kh, int kw, int stride, int pad);
+int mrdis_conv2d_2src_bwd_weight(const float* x, int ldx, int Cx, const float* s, int lds, int Cs, const float* dy, int lddy,
+                                 float* dw_tck, float* dbias, int accumulate_bias, void* workspace, size_t workspace_bytes,
+                                 int N, int H, int W, int Co, int kh, int kw, int stride, int pad, void* stream);
+/* ana_dec_act (model.py:3145-3153) on (P, C) views: softplus = F.softplus (beta 1, threshold 20: y = x where x > 20, log1p(exp(x))
+ * otherwise; backward dy * e^x / (e^x + 1), dy where x > 20); softmax = F.softmax(s, 1) with no mask channel (C <= 8), backward
+ * ds = out * (dout - sum(dout * out)).  Launch counter family "ana_act".                                                 */
+int mrdis_softplus_fwd(const float* x, int ldx, float* y, int ldy, long long P, int C, void* stream);
+int mrdis_softplus_bwd(const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, long long P, int C, void* stream);
+int mrdis_softmax_fwd(const float* s, int lds, float* out, int ldo, long long P, int C, void* stream);
+int mrdis_softmax_bwd(const float* dout, int lddo, const float* out, int ldo, float* ds, int ldds, long long P, int C, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

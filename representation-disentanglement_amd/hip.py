@@ -106,6 +106,14 @@ _SIGS = {
     'mrdis_upsample2x_bwd': (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_cosine_top1_workspace': (_Z, [_I, _I, _I]),
     'mrdis_cosine_top1': (_I, [_P, _L, _P, _I, _I, _P, _P, _I, _P, _P, _P, _Z, _P]),
+    'mrdis_conv2d_2src_fwd': (_I, [_P, _I, _I, _P, _I, _I, _P, _P, _P, _I] + [_I] * 9 + [_P]),
+    'mrdis_conv2d_2src_bwd_data': (_I, [_P, _I, _P, _P, _I, _I, _P, _I, _I] + [_I] * 8 + [_P]),
+    'mrdis_conv2d_2src_bwd_weight_workspace': (_Z, [_I] * 10),
+    'mrdis_conv2d_2src_bwd_weight': (_I, [_P, _I, _I, _P, _I, _I, _P, _I, _P, _P, _I, _P, _Z] + [_I] * 8 + [_P]),
+    'mrdis_softplus_fwd': (_I, [_P, _I, _P, _I, _L, _I, _P]),
+    'mrdis_softplus_bwd': (_I, [_P, _I, _P, _I, _P, _I, _L, _I, _P]),
+    'mrdis_softmax_fwd': (_I, [_P, _I, _P, _I, _L, _I, _P]),
+    'mrdis_softmax_bwd': (_I, [_P, _I, _P, _I, _P, _I, _L, _I, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -163,6 +171,9 @@ KERNEL_FAMILIES = WINO_FAMILIES = ('wino', 'wino_spade', 'wino2', 'wino2_spade',
                                    'split6_c4', 'split6_c16', 'split6_wgrad16', 'split6_co4', 'split6_c3d', 'split6_w3d', 'split6_tap',
                                    'all',        # 'all': every kernel launch of the library (bench.py: library_launches_per_step)
                                    'zsearch')    # mrdis_cosine_top1 (nearest-neighbour modality-code search)
+# the kernels of the `others` variants (csrc/mrdis_encs.hip): the modality encoder's two-source first layer (mod_enc_s) and the anatomy
+# activations (ana_dec_act).  Kept out of KERNEL_FAMILIES, whose every entry the convolution-path table must cover.
+VARIANT_FAMILIES = ('conv2src', 'ana_act')
 
 
 def stream_fill(t, value=0.0):
@@ -190,7 +201,7 @@ def dynamic_lds():
 def launch_counts(reset=False):
     """{family: launches since load / the last reset} of the Winograd, bf16 LDS-DMA and six-product (split6) kernel families (include/mrdis.h mrdis_launch_count)"""
     lib = load()
-    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES}
+    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES}
     if reset:
         lib.mrdis_launch_count_reset()
     return out
@@ -1281,3 +1292,108 @@ def cosine_top1(gallery, gallery_label, query, query_label):
     _chk(lib.mrdis_cosine_top1(gallery.data_ptr(), gallery.stride(0), gallery_label.data_ptr(), N, D, query.data_ptr(), query_label.data_ptr(), Q,
                                idx.data_ptr(), cos.data_ptr(), ws.data_ptr(), ws.numel(), _stream()), 'cosine_top1')
     return idx, cos
+
+
+# ---------------------------------------------------------------- the `others` variants (csrc/mrdis_encs.hip)
+def _f32_nhwc(t, what):
+    if t.dtype is not torch.float32:
+        raise MrdisError(f'{what}: fp32 activations only (got {t.dtype})')
+    return nhwc(t)
+
+
+def conv2d_2src_fwd(x, s, w_tck, bias, kh, kw, stride, pad, lrelu=False, out=None):
+    """the layer of filter w_tck [T][Cx+Cs][Co] on cat([x, s], 1) without the concatenation: x (N,Cx,H,W), s (N,Cs,H,W) NHWC views.
+    out: an NHWC view (N,Co,Ho,Wo) to write into (a channel slice of a wider buffer qualifies); default a new tensor."""
+    x, ldx = _f32_nhwc(x, 'conv2d_2src_fwd x'); s, lds = _f32_nhwc(s, 'conv2d_2src_fwd s')
+    N, Cx, H, W = x.shape
+    Cs = s.shape[1]
+    assert s.shape[0] == N and tuple(s.shape[2:]) == (H, W), (x.shape, s.shape)
+    Co = w_tck.shape[2]
+    assert w_tck.shape[:2] == (kh * kw, Cx + Cs) and w_tck.is_contiguous(), (w_tck.shape, Cx, Cs)
+    Ho, Wo = conv_out_hw(H, W, kh, kw, stride, pad)
+    y, ldy = _out_view(empty_nhwc(N, Co, Ho, Wo, x.device) if out is None else out)
+    _chk(load().mrdis_conv2d_2src_fwd(_ptr(x), ldx, Cx, _ptr(s), lds, Cs, _ptr(w_tck), _ptr(bias), _ptr(y), ldy, N, H, W, Co, kh, kw, stride, pad,
+                                      1 if lrelu else 0, _stream()), 'conv2d_2src_fwd')
+    return y
+
+
+def conv2d_2src_bwd_data(dy, w_tkc, Cx, Cs, in_hw, kh, kw, stride, pad, need_dx=True, dx_out=None, ds_out=None):
+    """-> (dx or None, ds): the data gradients of the two sources of conv2d_2src_fwd (dy: gradient of the pre-activation output)"""
+    dy, lddy = _f32_nhwc(dy, 'conv2d_2src_bwd_data dy')
+    N, Co = dy.shape[:2]
+    H, W = in_hw
+    assert w_tkc.shape == (kh * kw, Co, Cx + Cs) and w_tkc.is_contiguous(), (w_tkc.shape, Co, Cx, Cs)
+    ds, ldds = _out_view(empty_nhwc(N, Cs, H, W, dy.device) if ds_out is None else ds_out)
+    dx, lddx = (None, Cx)
+    if need_dx:
+        dx, lddx = _out_view(empty_nhwc(N, Cx, H, W, dy.device) if dx_out is None else dx_out)
+    _chk(load().mrdis_conv2d_2src_bwd_data(_ptr(dy), lddy, _ptr(w_tkc), _ptr(dx), lddx, Cx, _ptr(ds), ldds, Cs, N, H, W, Co, kh, kw, stride, pad,
+                                           _stream()), 'conv2d_2src_bwd_data')
+    return dx, ds
+
+
+def conv2d_2src_bwd_weight(x, s, dy, kh, kw, stride, pad, need_bias=True, bias_sink=None, dw_out=None):
+    """-> (dw_tck [T][Cx+Cs][Co], dbias or None).  bias_sink: a (Co,) buffer the bias gradient is ADDED to (then dbias is None)."""
+    x, ldx = _f32_nhwc(x, 'conv2d_2src_bwd_weight x'); s, lds = _f32_nhwc(s, 'conv2d_2src_bwd_weight s')
+    dy, lddy = _f32_nhwc(dy, 'conv2d_2src_bwd_weight dy')
+    N, Cx, H, W = x.shape
+    Cs, Co = s.shape[1], dy.shape[1]
+    lib = load()
+    nb = _ws_bytes(lib.mrdis_conv2d_2src_bwd_weight_workspace, N, H, W, Cx, Cs, Co, kh, kw, stride, pad)
+    if nb == 0:
+        raise MrdisError(f'conv2d_2src_bwd_weight: unsupported geometry Cx={Cx} Cs={Cs} Co={Co} k={kh}x{kw} stride={stride}')
+    ws = _ws(nb, x.device)
+    dw = torch.empty((kh * kw, Cx + Cs, Co), dtype=torch.float32, device=x.device) if dw_out is None else dw_out
+    assert dw.is_contiguous() and dw.numel() == kh * kw * (Cx + Cs) * Co
+    sink = bias_sink if need_bias else None
+    db = torch.empty(Co, dtype=torch.float32, device=x.device) if (need_bias and sink is None) else None
+    _chk(lib.mrdis_conv2d_2src_bwd_weight(_ptr(x), ldx, Cx, _ptr(s), lds, Cs, _ptr(dy), lddy, _ptr(dw), _ptr(sink if sink is not None else db),
+                                          1 if sink is not None else 0, _ptr(ws), nb, N, H, W, Co, kh, kw, stride, pad, _stream()),
+         'conv2d_2src_bwd_weight')
+    return dw, db
+
+
+def _out_view(t):
+    """(t, ld) for an output NHWC view that the kernel writes in place (never a silent copy)"""
+    v, ld = nhwc(t)
+    if v is not t:
+        raise MrdisError('output buffers must be NHWC views (channels_last, or a channel slice of one)')
+    return v, ld
+
+
+def _act_views(what, *ts):
+    return [_f32_nhwc(t, what) for t in ts]
+
+
+def softplus_fwd(x, out=None):
+    """F.softplus(x) (beta 1, threshold 20) over an NHWC view"""
+    (x, ldx), = _act_views('softplus_fwd', x)
+    N, C, H, W = x.shape
+    y, ldy = _out_view(empty_nhwc(N, C, H, W, x.device) if out is None else out)
+    _chk(load().mrdis_softplus_fwd(_ptr(x), ldx, _ptr(y), ldy, N * H * W, C, _stream()), 'softplus_fwd')
+    return y
+
+
+def softplus_bwd(dy, x, out=None):
+    (dy, lddy), (x, ldx) = _act_views('softplus_bwd', dy, x)
+    N, C, H, W = x.shape
+    dx, lddx = _out_view(empty_nhwc(N, C, H, W, x.device) if out is None else out)
+    _chk(load().mrdis_softplus_bwd(_ptr(dy), lddy, _ptr(x), ldx, _ptr(dx), lddx, N * H * W, C, _stream()), 'softplus_bwd')
+    return dx
+
+
+def softmax_fwd(s, out=None):
+    """F.softmax(s, 1) over the channels of an NHWC view (C <= 8)"""
+    (s, lds), = _act_views('softmax_fwd', s)
+    N, C, H, W = s.shape
+    y, ldy = _out_view(empty_nhwc(N, C, H, W, s.device) if out is None else out)
+    _chk(load().mrdis_softmax_fwd(_ptr(s), lds, _ptr(y), ldy, N * H * W, C, _stream()), 'softmax_fwd')
+    return y
+
+
+def softmax_bwd(dout, out_fwd, out=None):
+    (dout, lddo), (o, ldo) = _act_views('softmax_bwd', dout, out_fwd)
+    N, C, H, W = o.shape
+    ds, ldds = _out_view(empty_nhwc(N, C, H, W, o.device) if out is None else out)
+    _chk(load().mrdis_softmax_bwd(_ptr(dout), lddo, _ptr(o), ldo, _ptr(ds), ldds, N * H * W, C, _stream()), 'softmax_bwd')
+    return ds

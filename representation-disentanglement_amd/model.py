@@ -111,6 +111,19 @@ class CondConv2d(nn.Module):
             outs.append(ops.conv2d(inputs[i:i + 1], w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu))
         return torch.cat(outs, 0)
 
+    def forward_2src(self, x, s, inputs_type, lrelu=False):
+        """forward(cat([x, s], 1), inputs_type) with the concatenation never written (ops.conv2d_2src): the modality encoder's first
+        layer under others.mod_enc_s (model.py:2374).  Same expert mixing as forward(); per-sample types take the per-sample path."""
+        kh, kw = self.kernel_size
+        B = x.shape[0]
+        if B == 1 or inputs_type.stride(0) == 0:
+            w_tck, w_tkc = self.mixed_uniform(inputs_type)
+            return ops.conv2d_2src(x, s, w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu)
+        outs = []
+        for i in range(B):
+            w_tck, w_tkc = self._mixed(inputs_type[i:i + 1])
+            outs.append(ops.conv2d_2src(x[i:i + 1], s[i:i + 1], w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu))
+        return torch.cat(outs, 0)
 
     def forward_grouped(self, x, types, lrelu=False):
         """x: G sample blocks (block g belongs to the batch-constant type tensor types[g]) -> the G outputs, batch-concatenated:
@@ -141,6 +154,13 @@ class HipConv2d(nn.Conv2d):
         one = torch.ones(1, dtype=torch.float32, device=x.device)
         w_tck, w_tkc = ops.cached_mix((id(self), 0, 0), lambda: ops.mix_experts(self.weight.unsqueeze(0), one))
         return ops.conv2d(x, w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu)
+
+    def forward_2src(self, x, s, lrelu=False):
+        """forward(cat([x, s], 1)) from the two sources (ops.conv2d_2src)"""
+        kh, kw = self.kernel_size
+        one = torch.ones(1, dtype=torch.float32, device=x.device)
+        w_tck, w_tkc = ops.cached_mix((id(self), 0, 0), lambda: ops.mix_experts(self.weight.unsqueeze(0), one))
+        return ops.conv2d_2src(x, s, w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu)
 
 
 def Conv2d(is_cond):
@@ -423,17 +443,26 @@ class ModalityEncoderNew(nn.Module):
         self.log_var = nn.Linear(2 * c, z_size)
 
     def forward(self, xi, si, inputs_type=None):
-        x = xi if self.s_num_ch == 0 else torch.cat([xi, si], 1)
-        for i in range(5):
-            conv = getattr(self, f'conv{i + 1}')
-            x = conv(x, inputs_type, lrelu=True) if self.is_cond else conv(x, lrelu=True)   # :2374-2383
+        t = (inputs_type,) if self.is_cond else ()
+        if self.s_num_ch == 0:
+            x = self.conv1(xi, *t, lrelu=True)
+        else:
+            # others.mod_enc_s: conv1 reads cat([x_i, s_i], 1) (:2374) -- from its two sources, the concatenation is never written
+            if si is None or si.shape[1] != self.s_num_ch:
+                raise ValueError(f'the modality encoder reads the {self.s_num_ch}-channel anatomy maps (others.mod_enc_s); got '
+                                 f'{None if si is None else tuple(si.shape)}')
+            x = self.conv1.forward_2src(xi, si, *t, lrelu=True)
+        for i in range(1, 5):
+            x = getattr(self, f'conv{i + 1}')(x, *t, lrelu=True)                              # :2374-2383
         # `view(-1, 5*6*128)` flattens NCHW order (:2396): make that order physical (tiny tensor)
         x = x.contiguous(memory_format=torch.contiguous_format).reshape(x.shape[0], -1).float()     # bf16 storage: the Linears stay fp32
         x = self.fcs(x)
         return self.mean(x), self.log_var(x)
 
     def forward_grouped(self, xi, types):
-        """the G per-modality calls on the batch-concatenated input (the Linear layers are type-independent)"""
+        """the G per-modality calls on the batch-concatenated input (the Linear layers are type-independent).  Encoders that read the
+        anatomy maps (others.mod_enc_s) are not grouped: their first layer is the two-source convolution, which takes one filter per call
+        (MultimodalModel.compute_modality_encoding runs them per modality)."""
         assert self.s_num_ch == 0 and self.is_cond
         x = xi
         for i in range(5):
@@ -744,10 +773,19 @@ class MultimodalModel(nn.Module):
         others = dict(others or {'mod_enc_s': True, 'ana_dec_act': 'softmax'})
         others.setdefault('old', False)
         if others['old'] or is_distri_z or shared_inp_dec or s_compact_method != 'max' or \
-                s_sim_method != 'cosine' or z_sim_method != 'cosine' or others.get('mod_enc_s', True) or \
-                others.get('ana_dec_act', 'softmax') != 'softmax' or not others.get('softmax_remove_mask', False):
+                s_sim_method != 'cosine' or z_sim_method != 'cosine' or others.get('ana_dec_act', 'softmax') not in ('softmax', 'softplus'):
             raise NotImplementedError('only the shipped config.yaml graph is built (SURVEY.md section 8a); '
                                       'got a variant that the hot path does not cover')
+        # the `others` variants (config.yaml:67-70): the modality encoder reads the anatomy maps unless mod_enc_s is False
+        # (model.py:2993, :3104: a missing key means True), and the anatomy activation is softplus, plain softmax, or the
+        # softmax with the 100 * mask channel dropped (:3145-3153)
+        mod_enc_s = not ('mod_enc_s' in others and others['mod_enc_s'] == False)      # noqa: E712 -- the reference's test, as written
+        self.variant = ('mod_enc_s+' if mod_enc_s else '') + (
+            'softplus' if others.get('ana_dec_act', 'softmax') == 'softplus' else
+            'softmax_remove_mask' if others.get('softmax_remove_mask', False) else 'softmax')
+        if ops.storage_bf16() and self.variant != 'softmax_remove_mask':
+            raise NotImplementedError(f"compute_dtype 'bf16' (bf16 activations) covers the shipped graph only; the others variant "
+                                      f"{self.variant!r} runs in 'f32' / 'bf16m'")
         H, W = input_size
         if H % 32 or W % 32:
             raise ValueError(f'input_size {input_size} must be a multiple of 32 (five stride-2 stages, model.py:2192)')
@@ -760,7 +798,7 @@ class MultimodalModel(nn.Module):
         self.anatomy_encoder_dec = AnatomyEncoderDecNew(32, s_num_ch, is_cond=is_cond)
         n_mod = 1 if shared_mod_enc else modality_num
         self.modality_encoder_list = nn.ModuleList(
-            [ModalityEncoderNew(in_num_ch, 0, 16, z_size, is_cond, (H // 32) * (W // 32)) for _ in range(n_mod)])  # :3102-3112
+            [ModalityEncoderNew(in_num_ch, s_num_ch if mod_enc_s else 0, 16, z_size, is_cond, (H // 32) * (W // 32)) for _ in range(n_mod)])  # :3102-3112
         dec = [SPADENewNotShared((H, W), in_num_ch, z_size, 128, s_num_ch, is_cond, input_output_act)
                for _ in range(modality_num)]
         dec.append(SPADENewShared((H, W), in_num_ch, z_size, 128, s_num_ch, is_cond))            # :3129-3131
@@ -887,7 +925,10 @@ class MultimodalModel(nn.Module):
         """need_maps = False (the second encoder pass of main_missing.py:228-231 when the modality encoder takes no s): the maps are dead -- nothing reads them,
         no gradient reaches them -- so the pass stops behind the last BatchNorm of the anatomy network (the x2 resize to full resolution, the 64 -> 4
         convolution and the masked softmax of the last block are skipped: 1.5 ms per step at B = 32); the network's state (BatchNorm running statistics,
-        counters) is exactly what the full pass leaves.  Returns [None] * M then."""
+        counters) is exactly what the full pass leaves.  Returns [None] * M then.  Under others.mod_enc_s the modality encoder reads the maps, so
+        need_maps = False is refused.  The output activation is the one others.ana_dec_act selects (ops.anatomy_activation)."""
+        if not need_maps and self.modality_encoder_reads_s():
+            raise ValueError('need_maps=False: the modality encoder reads the anatomy maps (others.mod_enc_s)')
         if self._encoders_grouped():
             M, B = self.modality_num, inputs_list[0].shape[0]
             types = [self._type(i, B) for i in range(M)]
@@ -896,8 +937,8 @@ class MultimodalModel(nn.Module):
             si, _ = self.anatomy_encoder_dec.forward_grouped(feats, types, need_out=need_maps)
             if not need_maps:
                 return [None] * M
-            m_all = mask_img if mask_img is None else mask_img.repeat(M, 1, 1)
-            return list(ops.split_batch(ops.softmax_mask_drop(si, m_all, 100.0), M))
+            m_all = mask_img.repeat(M, 1, 1) if (mask_img is not None and self.variant.endswith('softmax_remove_mask')) else mask_img
+            return list(ops.split_batch(ops.anatomy_activation(si, m_all, self.others), M))
         si_list = []
         B = inputs_list[0].shape[0]
         for i in range(self.modality_num):
@@ -905,7 +946,7 @@ class MultimodalModel(nn.Module):
             enc = self.anatomy_encoder_enc_list[0 if self.shared_ana_enc else i]
             feats = enc(inputs_list[i], t)
             si, _ = self.anatomy_encoder_dec(feats, t, need_out=need_maps)
-            si_list.append(None if not need_maps else ops.softmax_mask_drop(si, mask_img, 100.0))   # :3150-3153
+            si_list.append(None if not need_maps else ops.anatomy_activation(si, mask_img, self.others))   # :3145-3153
         return si_list
 
     # ---- model.py:3159-3162: eps is drawn from the CPU generator, then moved

@@ -1320,6 +1320,91 @@ def softmax_mask_drop(s, mask_img, scale=100.0):
     return _SoftmaxMaskDrop.apply(s, mask_img, scale)
 
 
+# --------------------------------------------------------------------------- the `others` variants (config.yaml:67-70; csrc/mrdis_encs.hip)
+class _Softplus(Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x)
+        return hip.softplus_fwd(x)
+
+    @staticmethod
+    def backward(ctx, dy):
+        (x,) = ctx.saved_tensors
+        return hip.softplus_bwd(dy, x)
+
+
+def softplus(x):
+    """F.softplus(x) -- beta 1, threshold 20 (ana_dec_act 'softplus', model.py:3145-3146)."""
+    return _Softplus.apply(x)
+
+
+class _Softmax(Function):
+    @staticmethod
+    def forward(ctx, s):
+        out = hip.softmax_fwd(s)
+        ctx.save_for_backward(out)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (out,) = ctx.saved_tensors
+        return hip.softmax_bwd(dout, out)
+
+
+def softmax(s):
+    """F.softmax(s, 1) over the channels, no mask channel (ana_dec_act 'softmax' without softmax_remove_mask, model.py:3152-3153)."""
+    return _Softmax.apply(s)
+
+
+def anatomy_activation(si, mask_img, others):
+    """the anatomy network's output activation that `others` selects (model.py:3145-3153)."""
+    act = others.get('ana_dec_act', 'softmax')
+    if act == 'softplus':
+        return softplus(si)
+    if others.get('softmax_remove_mask', False):
+        return softmax_mask_drop(si, mask_img, 100.0)
+    return softmax(si)
+
+
+class _Conv2dTwoSrcFn(Function):
+    """conv(cat([x, s], 1)) with the mixed filter of the concatenated layer, the concatenation never written (mrdis_conv2d_2src_*).
+    The gradient of the filter goes back through the expert mixing like that of every other CondConv2d layer."""
+
+    @staticmethod
+    def forward(ctx, x, s, w_tck, w_tkc, bias, kh, kw, stride, pad, lrelu):
+        y = hip.conv2d_2src_fwd(x, s, w_tck, bias, kh, kw, stride, pad, lrelu)
+        ctx.geom = (kh, kw, stride, pad, lrelu, x.shape[1], s.shape[1], x.shape[2], x.shape[3])
+        ctx.bias_param = bias
+        ctx.save_for_backward(x, s, w_tkc, y if lrelu else None)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        kh, kw, stride, pad, lrelu, Cx, Cs, H, W = ctx.geom
+        x, s, w_tkc, y = ctx.saved_tensors
+        if lrelu:
+            dy = hip.lrelu_bwd(dy, y, 0.2)
+        dx = ds = dw = db = None
+        if ctx.needs_input_grad[0] or ctx.needs_input_grad[1]:
+            dx, ds = hip.conv2d_2src_bwd_data(dy, w_tkc, Cx, Cs, (H, W), kh, kw, stride, pad, need_dx=ctx.needs_input_grad[0])
+            if not ctx.needs_input_grad[1]:
+                ds = None
+        has_bias = ctx.bias_param is not None
+        if ctx.needs_input_grad[2] or (has_bias and ctx.needs_input_grad[4]):
+            sink = _grad_sink(ctx.bias_param) if has_bias else None
+            dw, db = hip.conv2d_2src_bwd_weight(x, s, dy, kh, kw, stride, pad, need_bias=has_bias, bias_sink=sink)
+        return dx, ds, dw, None, db, None, None, None, None, None
+
+
+def conv2d_2src(x, s, w_tck, w_tkc, bias, kh, kw, stride, pad, lrelu=False):
+    """the convolution of filter (w_tck, w_tkc) over cat([x, s], 1) from its two sources (fp32 activations; the kernels run fp32 FMA
+    under every compute dtype)."""
+    if x.dtype != torch.float32 or s.dtype != torch.float32:
+        raise NotImplementedError("others.mod_enc_s: the modality encoder's two-source first layer takes fp32 activations "
+                                  "(compute_dtype 'f32' or 'bf16m')")
+    return _Conv2dTwoSrcFn.apply(x, s, w_tck, w_tkc, bias, kh, kw, stride, pad, lrelu)
+
+
 class _ReconErr(Function):
     @staticmethod
     def forward(ctx, gt, x, p):
