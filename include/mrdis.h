@@ -82,7 +82,7 @@ long long mrdis_get_option(const char* name);
  * "wino2" | "wino2_spade" (pipelined F(2x2)), "wino4" | "wino4_spade" (F(4x4) 64-cout forms), "wino4n" | "wino4r" (32-cout forms: shared transform / register-fed),
  * "wino_wgrad" | "wino_wgrad2" (F(2x2) weight gradient), "wino4_wgrad" (F(3x3,4x4)); "bconv3" | "bconv3_spade" | "bconv4" | "bconv4_spade" (bf16 3x3 forms);
  * "split6_c4" | "split6_c16" | "split6_wgrad16" | "split6_co4" | "split6_c3d" | "split6_w3d" | "split6_tap" (option split6: the 4 -> C kernel, the 32 -> 16 forward, its weight gradient, the
- * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "zsearch" (mrdis_cosine_top1); "all" (every kernel launch of the library).  MRDIS_EINVAL for an unknown name.  Diagnostics: the parity tests
+ * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "zsearch" (mrdis_cosine_top1); "conv2src" | "ana_act" (the others variants); "kl" | "avgpool" (the latent-code options); "all" (every kernel launch of the library).  MRDIS_EINVAL for an unknown name.  Diagnostics: the parity tests
  * use it to prove that the form under test is the one that ran. */
 long long mrdis_launch_count(const char* family);
 void mrdis_launch_count_reset(void);
@@ -511,6 +511,28 @@ int mrdis_softplus_fwd(const float* x, int ldx, float* y, int ldy, long long P, 
 int mrdis_softplus_bwd(const float* dy, int lddy, const float* x, int ldx, float* dx, int lddx, long long P, int C, void* stream);
 int mrdis_softmax_fwd(const float* s, int lds, float* out, int ldo, long long P, int C, void* stream);
 int mrdis_softmax_bwd(const float* dout, int lddo, const float* out, int ldo, float* ds, int ldds, long long P, int C, void* stream);
+
+/* ---- the latent-code options of the loss block (config.yaml:36, 54, 60-61), csrc/mrdis_latent.hip.
+ * Masked KL of the M per-contrast modality codes (M <= MRDIS_KL_MAXM): mu[i], lv[i] (i < M) are HOST arrays of device pointers to (B, Z)
+ * fp32 blocks with row strides ldmu / ldlv.  Prior: pmu = plv = NULL for the standard form 0.5 (exp(lv) + mu^2 - 1 - lv) (model.py:3343-3353);
+ * otherwise the two-Gaussian form 0.5 (-1 + (plv - lv) + (exp(lv) + (mu - pmu)^2) / exp(plv)) (model.py:3362-3382) with the prior of
+ * contrast i, sample b at pmu[i * ldp_m + b * ldp_b + z] (ldp_b = 0: one row per contrast, broadcast over the batch).  weight: (M, B)
+ * dense device table (mask and normalisation, computed on the host).  loss = sum_{i,b} weight[i][b] sum_z kl, written to loss[0] by one
+ * workgroup in a fixed order.  Backward: the upstream gradient is read from the device scalar dloss; dmu[i], dlv[i] are host arrays of
+ * device pointers to (B, Z) outputs with row strides lddmu / lddlv; dpmu / dplv (both NULL, or both given with a prior): dense (M, Z)
+ * sums over the batch when ldp_b = 0, dense (M, B, Z) per-sample gradients otherwise.  One launch each way.  Launch counter family "kl".  */
+#define MRDIS_KL_MAXM 8
+int mrdis_kl_fwd(const float* const* mu, const float* const* lv, int ldmu, int ldlv, const float* pmu, const float* plv, long long ldp_m,
+                 int ldp_b, const float* weight, float* loss, int M, int B, int Z, void* stream);
+int mrdis_kl_bwd(const float* dloss, const float* const* mu, const float* const* lv, int ldmu, int ldlv, const float* pmu, const float* plv,
+                 long long ldp_m, int ldp_b, const float* weight, float* const* dmu, float* const* dlv, int lddmu, int lddlv,
+                 float* dpmu, float* dplv, int M, int B, int Z, void* stream);
+/* k x k mean pooling, stride k, floor (F.avg_pool2d(x, k), model.py:3453-3456) of an NHWC (N,H,W,C) fp32 view with pixel stride ldx; y is
+ * the dense (N, C * (H/k) * (W/k)) compact vector in the NCHW order of the pooled map (view(B, -1)).  Backward: dx = dy / k^2 broadcast
+ * over each window, exactly 0 in the rows / columns the floor leaves out; every element of dx (pixel stride lddx) is written.
+ * Launch counter family "avgpool".                                                                                        */
+int mrdis_avgpool_fwd(const float* x, int ldx, float* y, int N, int H, int W, int C, int k, void* stream);
+int mrdis_avgpool_bwd(const float* dy, float* dx, int lddx, int N, int H, int W, int C, int k, void* stream);
 
 #ifdef __cplusplus
 }

@@ -114,6 +114,10 @@ _SIGS = {
     'mrdis_softplus_bwd': (_I, [_P, _I, _P, _I, _P, _I, _L, _I, _P]),
     'mrdis_softmax_fwd': (_I, [_P, _I, _P, _I, _L, _I, _P]),
     'mrdis_softmax_bwd': (_I, [_P, _I, _P, _I, _P, _I, _L, _I, _P]),
+    'mrdis_kl_fwd': (_I, [_P, _P, _I, _I, _P, _P, _L, _I, _P, _P, _I, _I, _I, _P]),
+    'mrdis_kl_bwd': (_I, [_P, _P, _P, _I, _I, _P, _P, _L, _I, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
+    'mrdis_avgpool_fwd': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    'mrdis_avgpool_bwd': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -174,6 +178,9 @@ KERNEL_FAMILIES = WINO_FAMILIES = ('wino', 'wino_spade', 'wino2', 'wino2_spade',
 # the kernels of the `others` variants (csrc/mrdis_encs.hip): the modality encoder's two-source first layer (mod_enc_s) and the anatomy
 # activations (ana_dec_act).  Kept out of KERNEL_FAMILIES, whose every entry the convolution-path table must cover.
 VARIANT_FAMILIES = ('conv2src', 'ana_act')
+# the kernels of the latent-code options (csrc/mrdis_latent.hip): the masked KL term (lambda_kl, is_distri_z) and the mean compaction
+# (s_compact_method 'mean').  Outside KERNEL_FAMILIES for the same reason.
+LATENT_FAMILIES = ('kl', 'avgpool')
 
 
 def stream_fill(t, value=0.0):
@@ -201,7 +208,7 @@ def dynamic_lds():
 def launch_counts(reset=False):
     """{family: launches since load / the last reset} of the Winograd, bf16 LDS-DMA and six-product (split6) kernel families (include/mrdis.h mrdis_launch_count)"""
     lib = load()
-    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES}
+    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES}
     if reset:
         lib.mrdis_launch_count_reset()
     return out
@@ -1397,3 +1404,107 @@ def softmax_bwd(dout, out_fwd, out=None):
     ds, ldds = _out_view(empty_nhwc(N, C, H, W, o.device) if out is None else out)
     _chk(load().mrdis_softmax_bwd(_ptr(dout), lddo, _ptr(o), ldo, _ptr(ds), ldds, N * H * W, C, _stream()), 'softmax_bwd')
     return ds
+
+
+# ---------------------------------------------------------------- the latent-code options (csrc/mrdis_latent.hip)
+KL_MAXM = 8
+
+
+def _rows_view(t, what):
+    """(t, row stride) of a (B, Z) fp32 device view whose rows are dense"""
+    if t.dtype is not torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
+        raise MrdisError(f'{what}: (B, Z) fp32 views with dense rows only (got {tuple(t.shape)} {t.dtype} strides {t.stride()})')
+    return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
+
+
+def _ptr_array(ts):
+    return (ctypes.c_void_p * len(ts))(*[t.data_ptr() for t in ts])
+
+
+def _blocks(ts, what):
+    """M (B, Z) blocks sharing one row stride -> (host pointer array, ld)"""
+    views = [_rows_view(t, what) for t in ts]
+    lds = {ld for _, ld in views}
+    if len(lds) != 1:
+        ts = [t.contiguous() for t in ts]
+        views = [(t, t.shape[1]) for t in ts]
+    return [v for v, _ in views], views[0][1]
+
+
+def _prior_view(pmu, plv, M, B, Z):
+    """the prior as (pmu, plv, ldp_m, ldp_b): (M, Z) tensors (one row per contrast, broadcast over the batch) or (M, B, Z) (one row per sample)"""
+    if pmu is None:
+        return None, None, 0, 0
+    assert pmu.shape == plv.shape and pmu.dtype == plv.dtype == torch.float32, (pmu.shape, plv.shape)
+    if pmu.dim() == 2:
+        assert tuple(pmu.shape) == (M, Z), (pmu.shape, M, Z)
+        if pmu.stride() != plv.stride() or pmu.stride(1) != 1:
+            pmu, plv = pmu.contiguous(), plv.contiguous()
+        return pmu, plv, pmu.stride(0), 0
+    assert tuple(pmu.shape) == (M, B, Z), (pmu.shape, M, B, Z)
+    if pmu.stride() != plv.stride() or pmu.stride(2) != 1 or pmu.stride(0) == 0 or pmu.stride(1) == 0:
+        pmu, plv = pmu.contiguous(), plv.contiguous()
+    return pmu, plv, pmu.stride(0), pmu.stride(1)
+
+
+def kl_fwd(mu_list, lv_list, weight, pmu=None, plv=None):
+    """-> 0-dim loss: sum_{i,b} weight[i, b] sum_z kl(mu_list[i][b], lv_list[i][b] | prior) (include/mrdis.h mrdis_kl_fwd).
+    mu_list / lv_list: M (B, Z) fp32 views; weight: (M, B); pmu / plv: None (standard), (M, Z) or (M, B, Z) (two-Gaussian)."""
+    M = len(mu_list)
+    if not 1 <= M <= KL_MAXM or len(lv_list) != M:
+        raise MrdisError(f'kl_fwd: 1 .. {KL_MAXM} contrasts (got {M} mu, {len(lv_list)} log-variance blocks)')
+    B, Z = mu_list[0].shape
+    mus, ldmu = _blocks(mu_list, 'kl_fwd mu')
+    lvs, ldlv = _blocks(lv_list, 'kl_fwd log-variance')
+    assert all(tuple(t.shape) == (B, Z) for t in mus + lvs)
+    w = weight.contiguous()
+    assert tuple(w.shape) == (M, B) and w.dtype == torch.float32, (w.shape, w.dtype)
+    pmu, plv, ldp_m, ldp_b = _prior_view(pmu, plv, M, B, Z)
+    loss = torch.empty((), dtype=torch.float32, device=mus[0].device)
+    _chk(load().mrdis_kl_fwd(_ptr_array(mus), _ptr_array(lvs), ldmu, ldlv, _ptr(pmu), _ptr(plv), ldp_m, ldp_b, _ptr(w), _ptr(loss), M, B, Z,
+                             _stream()), 'kl_fwd')
+    return loss
+
+
+def kl_bwd(dloss, mu_list, lv_list, weight, pmu=None, plv=None, need_prior=True):
+    """-> (dmu (M, B, Z), dlv (M, B, Z), dpmu, dplv): the gradients of kl_fwd for the upstream gradient dloss (a 0-dim DEVICE tensor).
+    dpmu / dplv have the prior's shape ((M, Z): summed over the batch), None without a prior or when need_prior is False."""
+    M = len(mu_list)
+    B, Z = mu_list[0].shape
+    mus, ldmu = _blocks(mu_list, 'kl_bwd mu')
+    lvs, ldlv = _blocks(lv_list, 'kl_bwd log-variance')
+    w = weight.contiguous()
+    pmu, plv, ldp_m, ldp_b = _prior_view(pmu, plv, M, B, Z)
+    dev = mus[0].device
+    dmu = torch.empty((M, B, Z), dtype=torch.float32, device=dev)
+    dlv = torch.empty((M, B, Z), dtype=torch.float32, device=dev)
+    dpmu = dplv = None
+    if pmu is not None and need_prior:
+        shape = (M, Z) if ldp_b == 0 else (M, B, Z)
+        dpmu = torch.empty(shape, dtype=torch.float32, device=dev)
+        dplv = torch.empty(shape, dtype=torch.float32, device=dev)
+    g = dloss.reshape(()).float()
+    _chk(load().mrdis_kl_bwd(_ptr(g), _ptr_array(mus), _ptr_array(lvs), ldmu, ldlv, _ptr(pmu), _ptr(plv), ldp_m, ldp_b, _ptr(w),
+                             _ptr_array(list(dmu)), _ptr_array(list(dlv)), Z, Z, _ptr(dpmu), _ptr(dplv), M, B, Z, _stream()), 'kl_bwd')
+    return dmu, dlv, dpmu, dplv
+
+
+def avgpool_fwd(x, k):
+    """F.avg_pool2d(x, k).view(N, -1) of an NHWC fp32 view: the dense (N, C * (H // k) * (W // k)) compact vector"""
+    if x.dtype is not torch.float32:
+        raise MrdisError(f'avgpool_fwd: fp32 maps only (got {x.dtype})')
+    x, ldx = nhwc(x)
+    N, C, H, W = x.shape
+    y = torch.empty((N, C * (H // k) * (W // k)), dtype=torch.float32, device=x.device)
+    _chk(load().mrdis_avgpool_fwd(_ptr(x), ldx, _ptr(y), N, H, W, C, k, _stream()), 'avgpool_fwd')
+    return y
+
+
+def avgpool_bwd(dy, in_shape, k, out=None):
+    """dx (N, C, H, W) NHWC of avgpool_fwd for dy (N, D); out: an NHWC view to write into"""
+    N, C, H, W = in_shape
+    dy = dy.contiguous()
+    assert tuple(dy.shape) == (N, C * (H // k) * (W // k)) and dy.dtype == torch.float32, (dy.shape, in_shape, k)
+    dx, lddx = _out_view(empty_nhwc(N, C, H, W, dy.device) if out is None else out)
+    _chk(load().mrdis_avgpool_bwd(_ptr(dy), _ptr(dx), lddx, N, H, W, C, k, _stream()), 'avgpool_bwd')
+    return dx

@@ -668,6 +668,20 @@ class Discriminator(nn.Module):
         return self.fc(x.contiguous(memory_format=torch.contiguous_format).float())
 
 
+class ModalityDistribution(nn.Module):
+    """model.py:2902-2914 (is_distri_z): the learned per-contrast prior of the modality code, Linear(1, 128) + LeakyReLU(0.2) +
+    Linear(128, 2 z_size) of the contrast label; (mean, log-variance).  fp32 nn.Linear layers, like the modality encoder's fcs."""
+
+    def __init__(self, z_size=16, inter_num_ch=128):
+        super().__init__()
+        self.z_size = z_size
+        self.linear = nn.Sequential(nn.Linear(1, inter_num_ch), nn.LeakyReLU(0.2), nn.Linear(inter_num_ch, 2 * z_size))
+
+    def forward(self, x):
+        feat = self.linear(x.float())
+        return feat[:, :self.z_size], feat[:, self.z_size:]
+
+
 # =============================================================================
 # orchestration + losses: model.py:2916-2970, 3086-3224, 3260-3587
 # =============================================================================
@@ -762,20 +776,33 @@ class MultimodalModel(nn.Module):
     """model.py:2916-3587 for the configuration the reference ships
     (config.yaml: is_cond, shared_ana_enc, shared_mod_enc, shared_inp_dec=False,
     mod_enc_s=False, softmax_remove_mask, 'max' compaction, cosine similarities).
-    Method names and argument order follow the reference."""
+    Method names and argument order follow the reference.
+
+    latent_options = True opts in to the latent-code options of the loss block, is_distri_z (the learned modality prior) and
+    s_compact_method 'mean' (build_model passes it: the config keys select them).  Without it the constructor keeps its earlier
+    contract -- those settings raise like every other graph it does not build -- so a caller that relies on that gets no new behaviour."""
 
     def __init__(self, input_size=(160, 192), modality_num=4, in_num_ch=7, out_num_ch=1, s_num_ch=8, z_size=16,
                  is_discrim_s=False, is_distri_z=False, shared_ana_enc=False, shared_mod_enc=True, shared_inp_dec=True,
                  s_compact_method='max', s_sim_method='cosine', z_sim_method='cosine', is_cond=True,
                  input_output_act='softplus', target_output_act='softplus', target_model_name='U', fuse_method='mean',
-                 device=torch.device('cuda:0'), others=None, is_patch_gan=False, build_output_decoder=False):
+                 device=torch.device('cuda:0'), others=None, is_patch_gan=False, build_output_decoder=False, latent_options=False):
         super().__init__()
         others = dict(others or {'mod_enc_s': True, 'ana_dec_act': 'softmax'})
         others.setdefault('old', False)
-        if others['old'] or is_distri_z or shared_inp_dec or s_compact_method != 'max' or \
+        if s_compact_method == 'vgg' or s_sim_method == 'perceptual':
+            # model.py:2946-2950, 3458-3462, 3417-3446: both read torchvision's ImageNet-pretrained VGG16
+            raise NotImplementedError(f"s_compact_method 'vgg' / s_sim_method 'perceptual' need torchvision's pretrained VGG16 weights "
+                                      f"(model.py:2948), which this package neither ships nor downloads (got s_compact_method="
+                                      f"{s_compact_method!r}, s_sim_method={s_sim_method!r})")
+        # (z_sim_method: the reference never reads it -- its z similarity is cosine for every value; the check below stays as it was)
+        latent = bool(is_distri_z) or s_compact_method == 'mean'
+        if others['old'] or shared_inp_dec or s_compact_method not in ('max', 'mean') or (latent and not latent_options) or \
                 s_sim_method != 'cosine' or z_sim_method != 'cosine' or others.get('ana_dec_act', 'softmax') not in ('softmax', 'softplus'):
             raise NotImplementedError('only the shipped config.yaml graph is built (SURVEY.md section 8a); '
-                                      'got a variant that the hot path does not cover')
+                                      'got a variant that the hot path does not cover' +
+                                      (" (is_distri_z / s_compact_method 'mean' are built with latent_options=True, as build_model passes it)"
+                                       if latent and not latent_options else ''))
         # the `others` variants (config.yaml:67-70): the modality encoder reads the anatomy maps unless mod_enc_s is False
         # (model.py:2993, :3104: a missing key means True), and the anatomy activation is softplus, plain softmax, or the
         # softmax with the 100 * mask channel dropped (:3145-3153)
@@ -791,6 +818,7 @@ class MultimodalModel(nn.Module):
             raise ValueError(f'input_size {input_size} must be a multiple of 32 (five stride-2 stages, model.py:2192)')
         self.input_size, self.modality_num, self.in_num_ch = tuple(input_size), modality_num, in_num_ch
         self.device, self.others, self.is_cond = device, others, is_cond
+        self.s_compact_method, self.is_distri_z = s_compact_method, bool(is_distri_z)
         self.shared_ana_enc, self.shared_mod_enc = shared_ana_enc, shared_mod_enc
         n_ana = 1 if shared_ana_enc else modality_num
         self.anatomy_encoder_enc_list = nn.ModuleList(
@@ -814,6 +842,8 @@ class MultimodalModel(nn.Module):
             self.output_decoder = GANShortGeneratorWithSpatialAttention(s_num_ch, out_num_ch, 64, target_output_act)
         if is_discrim_s:
             self.discrim_s = Discriminator(s_num_ch, 16, (H, W), is_patch_gan)                    # :2966-2967
+        if is_distri_z:
+            self.distri_z = ModalityDistribution(z_size, 128)                                    # :2968-2969, last: same seeded init
         self.to(device)
         self._types = {}
         # modality labels 1..M (model.py:3138) as one table, so CondConv2d can mix all of them at once
@@ -824,13 +854,17 @@ class MultimodalModel(nn.Module):
     _DEAD = ('.convs.',)                               # ModalityEncoderNew.convs: built, never called (model.py:2346-2357)
     _DEAD_LAST_BN = ('anatomy_encoder_dec.output.bn.', 'output_decoder.output.bn.')      # is_last: bn created, not applied (:2189)
 
-    def trainable_parameters(self):
+    def trainable_parameters(self, with_prior=True):
         """The static list of parameters that receive a gradient in a training step: everything that requires grad
         except the reference's dead modules (their state_dict keys and RNG draws exist, their gradients never do).
-        Pinned against the reference by the step goldens (same set of tensors with a gradient)."""
+        Pinned against the reference by the step goldens (same set of tensors with a gradient).
+        with_prior = False: the loss does not read the learned prior (is_distri_z with lambda_kl = 0, main_missing.py:219): distri_z gets no
+        gradient, and torch's Adam leaves it alone -- so it is left out like the dead modules."""
         out = []
         for n, p in self.named_parameters():
             if not p.requires_grad:
+                continue
+            if n.startswith('distri_z.') and not with_prior:
                 continue
             if n.startswith('modality_encoder_list.') and any(d in n for d in self._DEAD):
                 continue
@@ -1159,6 +1193,56 @@ class MultimodalModel(nn.Module):
             return torch.zeros((), device=self.device)
         return (torch.stack(errs) * self._weights(lambda m: [m[:, i] * m[:, j] / float((m[:, i] * m[:, j]).sum()) for i, j in pairs], mh)).sum() / idx
 
+    # ---- the KL term (main_missing.py:219-225): one ops.kl_loss launch each way; the weights carry the mask and the normalisation
+    def compute_kl_loss_list_standard(self, zi_mean_list, zi_log_var_list, mask, mask_host=None):   # :3355-3360
+        """KL against N(0, I) over the M B concatenated rows: sum(kl * mask_all) / sum(mask_all) / M.  (No row present at all: 0, where the
+        reference divides 0 by 0.)"""
+        mh = _host_mask(mask, mask_host)
+        M = len(zi_mean_list)
+
+        def rows_of(m):
+            n = float(m.sum())
+            return [m[:, i] / (M * n) if n > 0 else 0.0 * m[:, i] for i in range(M)]
+        return ops.kl_loss(zi_mean_list, zi_log_var_list, self._weights(rows_of, mh))
+
+    def compute_zi_prior_distribution(self, bs, num_distri, device):                              # :3362-3370
+        """the learned prior of contrasts 1 .. num_distri as lists of (bs, Z) tensors.  The input (i + 1) is the same for every row, so distri_z
+        runs once on the num_distri labels and each row is broadcast (same values as the per-row evaluation; the gradient reaching distri_z is
+        the sum over the rows, as there).  compute_kl_loss_list_two_gaussian reads the (num_distri, Z) rows behind the lists."""
+        label = self.__dict__.get('_prior_label')
+        if label is None or label.shape[0] != num_distri or label.device != torch.device(device):
+            label = self.__dict__['_prior_label'] = torch.arange(1, num_distri + 1, dtype=torch.float32, device=device).view(num_distri, 1)
+        pm, plv = self.distri_z(label)                                        # (num_distri, Z) each
+        pm_list = [pm[i:i + 1].expand(bs, -1) for i in range(num_distri)]
+        plv_list = [plv[i:i + 1].expand(bs, -1) for i in range(num_distri)]
+        for lst, rows in ((pm_list, pm), (plv_list, plv)):
+            for t in lst:
+                t._mrdis_prior_rows = rows
+        return pm_list, plv_list
+
+    def compute_kl_loss_list_two_gaussian(self, z_mean_list, z_log_var_list, z_prior_mean_list, z_prior_log_var_list, mask,
+                                          mask_host=None):                                        # :3372-3382
+        """sum over contrasts i of sum(kl_i * mask[:, i]) / sum(mask[:, i]), divided by M.  A contrast absent from every row contributes 0 (the
+        reference divides 0 by 0 there: DESIGN.md section 5); the division by M stays."""
+        mh = _host_mask(mask, mask_host)
+        M = len(z_mean_list)
+
+        def rows_of(m):
+            out = []
+            for i in range(M):
+                n = float(m[:, i].sum())
+                out.append(m[:, i] / (M * n) if n > 0 else 0.0 * m[:, i])
+            return out
+        pm_rows = getattr(z_prior_mean_list[0], '_mrdis_prior_rows', None)
+        plv_rows = getattr(z_prior_log_var_list[0], '_mrdis_prior_rows', None)
+        if pm_rows is not None and plv_rows is not None and pm_rows.shape[0] == M and \
+                all(getattr(a, '_mrdis_prior_rows', None) is pm_rows and getattr(b, '_mrdis_prior_rows', None) is plv_rows
+                    for a, b in zip(z_prior_mean_list, z_prior_log_var_list)):
+            prior = (pm_rows, plv_rows)                                       # compute_zi_prior_distribution's rows, broadcast in the kernel
+        else:
+            prior = (torch.stack([t.float() for t in z_prior_mean_list]), torch.stack([t.float() for t in z_prior_log_var_list]))   # (M, B, Z)
+        return ops.kl_loss(z_mean_list, z_log_var_list, self._weights(rows_of, mh), prior=prior)
+
     def compute_latent_z_loss(self, zi_mean_list, zi_mean_list_new, mask, mask_host=None):       # :3384-3394
         mh = _host_mask(mask, mask_host)
         terms = [i for i in range(len(zi_mean_list)) if mh[:, i].sum() != 0]
@@ -1174,7 +1258,9 @@ class MultimodalModel(nn.Module):
         yn = torch.sqrt(torch.sum(y * y, 1) + 1e-8).clamp_min(1e-8)
         return torch.sum(x * y, 1) / (xn * yn)
 
-    def compute_compact_s(self, x):                                                              # :3448-3451
+    def compute_compact_s(self, x):                                                              # :3448-3466
+        if self.s_compact_method == 'mean':                                                      # :3453-3456
+            return ops.avg_pool(x, 16)                    # written straight in view(B, -1) order
         # view(B,-1) of the NCHW-logical pooled map: (C, H/16, W/16) order
         p = ops.max_pool(x, 16)
         return p.contiguous(memory_format=torch.contiguous_format).reshape(x.shape[0], -1)

@@ -1443,6 +1443,58 @@ def max_pool(x, k):
     return _MaxPool.apply(x, int(k))
 
 
+
+class _AvgPool(Function):
+    @staticmethod
+    def forward(ctx, x, k):
+        ctx.k, ctx.shape = k, tuple(x.shape)
+        return hip.avgpool_fwd(x, k)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return hip.avgpool_bwd(dy, ctx.shape, ctx.k), None
+
+
+def avg_pool(x, k):
+    """F.avg_pool2d(x, kernel_size=(k, k)).view(B, -1) (model.py:3453-3456, s_compact_method 'mean'): the compact vector in the NCHW order of
+    the pooled map, from the fp32 NHWC maps in one launch (floor: rows / columns beyond k * (H // k) are not read, their gradient is 0)."""
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f"s_compact_method 'mean' pools the fp32 anatomy maps (got {x.dtype})")
+    return _AvgPool.apply(x, int(k))
+
+
+# --------------------------------------------------------------------------- the KL term (lambda_kl; is_distri_z), csrc/mrdis_latent.hip
+class _KLLoss(Function):
+    """sum_{i,b} weight[i, b] sum_z kl: one launch forward, one backward (mu, log-variance and the prior's gradients)."""
+
+    @staticmethod
+    def forward(ctx, weight, pmu, plv, M, *blocks):
+        mu_list, lv_list = blocks[:M], blocks[M:]
+        ctx.M = M
+        ctx.save_for_backward(weight, pmu, plv, *blocks)
+        return hip.kl_fwd(mu_list, lv_list, weight, pmu, plv)
+
+    @staticmethod
+    def backward(ctx, dloss):
+        weight, pmu, plv, *blocks = ctx.saved_tensors
+        M = ctx.M
+        need_prior = pmu is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        dmu, dlv, dpmu, dplv = hip.kl_bwd(dloss, blocks[:M], blocks[M:], weight, pmu, plv, need_prior=need_prior)
+        return (None, dpmu, dplv, None) + tuple(dmu.unbind(0)) + tuple(dlv.unbind(0))
+
+
+def kl_loss(mu_list, lv_list, weights, prior=None):
+    """the masked KL term of the modality codes (main_missing.py:219-225): sum_{i,b} weights[i, b] * sum_z kl(mu_list[i][b], lv_list[i][b]).
+    prior None: KL against N(0, I) (model.py:3343-3353); prior (pmu, plv): the two-Gaussian KL against the learned prior (model.py:3362-3382),
+    (M, Z) -- one row per contrast, broadcast over the batch -- or (M, B, Z).  weights (M, B) carries the mask and the normalisation."""
+    M = len(mu_list)
+    if M != len(lv_list):
+        raise ValueError(f'kl_loss: {M} mean blocks, {len(lv_list)} log-variance blocks')
+    mu_list = [m.float() for m in mu_list]
+    lv_list = [v.float() for v in lv_list]
+    pmu, plv = (None, None) if prior is None else prior
+    return _KLLoss.apply(weights, pmu, plv, M, *mu_list, *lv_list)
+
 # --------------------------------------------------------------------------- mixed-kernel cache
 # The reference re-mixes the experts on every CondConv2d call.  Inside one training step the same
 # (layer, modality type) pair recurs (encoder passes 1 and 2, SPADEShared for every s_i), so the

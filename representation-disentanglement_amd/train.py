@@ -364,7 +364,11 @@ class Run:
         (the reference reads the results_all.h5 of an earlier save_res run, main_missing.py:374-382)."""
         path = self.z_gallery_path(set_)
         if os.path.exists(path):
-            return ZGallery.load(path, self.config['device'])
+            g = ZGallery.load(path, self.config['device'])
+            if g.compact_method == getattr(self.model, 's_compact_method', 'max'):
+                return g
+            self.log(f'z gallery {path}: built with s_compact_method {g.compact_method!r}, the model compacts with '
+                     f'{self.model.s_compact_method!r}: rebuilding it')
         loader = self.loaders[set_]
         batches = loader.batches(limit=max_batches) if hasattr(loader, 'batches') else loader
         g = build_z_gallery(self.model, batches, self.config)

@@ -76,7 +76,8 @@ def build_model(config):
         input_output_act=config['input_output_act'], target_output_act=config['target_output_act'],
         target_model_name=config['target_model_name'], fuse_method=config['fuse_method'], others=config['others'],
         is_patch_gan=config.get('is_patch_gan', False),
-        build_output_decoder=config['lambda_recon_y'] > 0 or config['lambda_recon_y_fused'] > 0)
+        build_output_decoder=config['lambda_recon_y'] > 0 or config['lambda_recon_y_fused'] > 0,
+        latent_options=True)                                  # is_distri_z / s_compact_method come from the config keys
 
 
 # --------------------------------------------------------------------------- synthetic BraTS-shaped data
@@ -607,8 +608,6 @@ def forward_losses(model, config, inputs, mask, mask_img, mask_host, phase='trai
     xi_fake_mix_list = model.reconstruct_input_si_zj(si_list, z_dec)                             # :178
     parts = {k: zero for k in LOSS_KEYS}
     loss = zero
-    if config['lambda_kl'] > 0:
-        raise NotImplementedError('the kl loss is outside the hot path (lambda_kl = 0 in config.yaml)')
     if config['lambda_recon_y_fused'] > 0:
         # main_missing.py:201-208: reconstruct_output_si_fused returns sum(mask) rows (boolean-index quirk), so the
         # loss against B targets raises in the reference for every M > 1
@@ -629,6 +628,14 @@ def forward_losses(model, config, inputs, mask, mask_img, mask_host, phase='trai
     if config['lambda_recon_x_mix'] > 0:
         parts['recon_x_mix'] = model.compute_recon_loss_x_mix_list(inputs_list, xi_fake_mix_list, mask, p, mask_host)
         loss = loss + config['lambda_recon_x_mix'] * parts['recon_x_mix']
+    if config['lambda_kl'] > 0:                                                                  # :219-225 (train) / :474-480 (test)
+        if config['is_distri_z']:
+            pm_list, plv_list = model.compute_zi_prior_distribution(inputs.shape[0], M, dev)
+            parts['kl'] = model.compute_kl_loss_list_two_gaussian(mu_list, lv_list, pm_list, plv_list, mask, mask_host)
+        else:
+            parts['kl'] = model.compute_kl_loss_list_standard(mu_list, lv_list, mask, mask_host)
+        if phase == 'train':                                   # the reference's evaluate() reports kl but leaves it out of the loss (:474-480)
+            loss = loss + config['lambda_kl'] * parts['kl']
     if config['lambda_latent_z'] > 0:                                                            # :228-233
         # (the maps of this second pass are read by the modality encoder only under others.mod_enc_s: otherwise the pass runs for its BatchNorm state alone)
         dead_maps = _SKIP_DEAD_MAPS and hasattr(model, 'modality_encoder_reads_s') and not model.modality_encoder_reads_s()
@@ -675,7 +682,8 @@ class TrainStep:
         self.model, self.config = model, config
         ops.set_compute_dtype(config.get('compute_dtype', 'f32'))
         self.accum = max(1, 16 // config['batch_size'])                                          # :282 (guarded for B > 16)
-        used = model.trainable_parameters() if hasattr(model, 'trainable_parameters') else None
+        # (the learned prior, is_distri_z, gets a gradient only through the KL term: with lambda_kl = 0 it stays out of the arena, as torch's Adam skips it)
+        used = model.trainable_parameters(with_prior=config.get('lambda_kl', 0) > 0) if hasattr(model, 'trainable_parameters') else None
         order = model.completion_groups() if hasattr(model, 'completion_groups') else None
         self.optimizer = ArenaAdam(model.parameters(), lr=config['lr'], weight_decay=1e-5, used=used, order=order)   # :118
         if used is not None and hasattr(model, 'gated_parameter_groups'):
@@ -1033,11 +1041,14 @@ class ZGallery:
                 row by row as the reference does is the same thing);
       z         (N, M, Z) fp32: the modality encoder's mu (what phase='test' returns);
       subject   (N,) int32: index into `subjects` (the loader's subj_id strings);
-      slice_idx (N,) int64.
+      slice_idx (N,) int64;
+      compact_method: the model's s_compact_method the codes were compacted with ('max' | 'mean'): a gallery is searched only with query
+                codes of the same method (galleries saved before the tag existed are 'max', the only method then).
     All on one device.  Per-subject sums of z for info = 'mean' are computed once, on first use."""
 
-    def __init__(self, s_compact, z, subject, slice_idx, subjects):
+    def __init__(self, s_compact, z, subject, slice_idx, subjects, compact_method='max'):
         self.s_compact, self.z, self.subject, self.slice_idx = s_compact, z, subject, slice_idx
+        self.compact_method = str(compact_method)
         self.subjects = [str(x) for x in subjects]
         self._code = {n: k for k, n in enumerate(self.subjects)}
         self._sums = self._present = None
@@ -1054,13 +1065,21 @@ class ZGallery:
     def save(self, path):
         os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
         torch.save({'s_compact': self.s_compact.cpu(), 'z': self.z.cpu(), 'subject': self.subject.cpu(), 'slice_idx': self.slice_idx.cpu(),
-                    'subjects': list(self.subjects)}, path)
+                    'subjects': list(self.subjects), 'compact_method': self.compact_method}, path)
         return path
 
     @classmethod
     def load(cls, path, device):
         d = torch.load(path, map_location='cpu', weights_only=True)
-        return cls(d['s_compact'].to(device), d['z'].to(device), d['subject'].to(device), d['slice_idx'].to(device), d['subjects'])
+        return cls(d['s_compact'].to(device), d['z'].to(device), d['subject'].to(device), d['slice_idx'].to(device), d['subjects'],
+                   d.get('compact_method', 'max'))
+
+    def check_compact_method(self, model):
+        """raise unless the gallery's compact codes were made by the compaction `model` makes its query codes with"""
+        want = getattr(model, 's_compact_method', 'max')
+        if self.compact_method != want:
+            raise ValueError(f"z gallery: its compact anatomy codes were made with s_compact_method {self.compact_method!r}, the model's "
+                             f"is {want!r}; codes of the two methods are not comparable -- rebuild the gallery (build_z_gallery)")
 
     def _check_search_space(self, codes):
         if self._present is None:
@@ -1139,7 +1158,7 @@ def build_z_gallery(run_or_model, loader, config=None, max_batches=None):
         raise RuntimeError('build_z_gallery: the loader yielded no batch')
     dev = s_rows[0].device
     return ZGallery(torch.cat(s_rows).float().contiguous(), torch.cat(z_rows).contiguous(), torch.tensor(subj, dtype=torch.int32).to(dev),
-                    torch.cat([x.to(dev) for x in sl]), names)
+                    torch.cat([x.to(dev) for x in sl]), names, getattr(model, 's_compact_method', 'max'))
 
 
 class EvalStep:
@@ -1163,6 +1182,8 @@ class EvalStep:
             raise NotImplementedError(f'evaluation with info={info!r} under a process group: the z gallery is not sharded; evaluate on one process')
         if info and gallery is None:
             raise ValueError(f'EvalStep info={info!r} needs a ZGallery (build_z_gallery)')
+        if info == 'nearest_neighbour':
+            gallery.check_compact_method(model)
         self.model, self.config, self.info, self.gallery = model, config, info, gallery
 
     def _z_find(self, si_list, zi_list, codes):
