@@ -301,6 +301,7 @@ static int launch_tapconv3d_t(const Conv3dParams& p, size_t lds, int nblk, hipSt
             return MRDIS_ELAUNCH;
         attr_set = true;
     }
+    mrdis_count(MRDIS_CNT_DIRECT3D);
     MRDIS_LAUNCH((tapconv3d_kernel<KC, BN>), dim3(nblk), dim3(256), lds, s, p);
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
@@ -460,6 +461,7 @@ static int launch_conv3d16_t(const Conv3dParams& p, size_t lds, int nblk, int nb
             return MRDIS_ELAUNCH;
         attr_set = true;
     }
+    mrdis_count(MRDIS_CNT_C3D16);
     MRDIS_LAUNCH((conv3d16_kernel<KC>), dim3(nblk), dim3(256), lds, s, p, nboxes);
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
@@ -1243,6 +1245,7 @@ static int launch_wgrad3d_t(const Wgrad3dPlan& pl, hipStream_t s) {
             return MRDIS_ELAUNCH;
         attr_set = true;
     }
+    mrdis_count(MRDIS_CNT_WGRAD3D);
     MRDIS_LAUNCH((wgrad3d_kernel<J>), dim3(pl.p.splits * pl.p.base), dim3(256), pl.lds, s, pl.p);
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
@@ -1287,6 +1290,7 @@ extern "C" int mrdis_conv3d_bwd_weight(const float* x, int ldx, const float* dy,
             q.slab = reinterpret_cast<float*>(workspace);
             q.bias_slab = dbias ? q.slab + p16.slab_floats : nullptr;
             const int nblk = q.splits * q.nCi * q.nCo;
+            mrdis_count(MRDIS_CNT_WGRAD3D16);
             if (p16.CW == 16) MRDIS_LAUNCH((wgrad3d16_kernel<16>), dim3(nblk), dim3(256), p16.lds, s, q);
             else if (p16.CW == 8) MRDIS_LAUNCH((wgrad3d16_kernel<8>), dim3(nblk), dim3(256), p16.lds, s, q);
             else MRDIS_LAUNCH((wgrad3d16_kernel<4>), dim3(nblk), dim3(256), p16.lds, s, q);

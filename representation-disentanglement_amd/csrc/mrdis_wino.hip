@@ -698,6 +698,7 @@ int mrdis_run_wino_wgrad3d(const float* x, int ldx, const float* dy, int lddy, f
     for (int kd = 0; kd < 3; ++kd) {
         p.kd = kd;
         p.bias_slab = (dbias && kd == 1) ? bias_slab : nullptr;
+        mrdis_count(MRDIS_CNT_WINO_WGRAD3D);
         if (pl.wci == 4 && pl.wco == 2) MRDIS_LAUNCH((wino_wgrad_kernel<4, 2, true>), dim3(nblk), dim3(512), pl.lds, s, p);
         else if (pl.wci == 4) MRDIS_LAUNCH((wino_wgrad_kernel<4, 1, true>), dim3(nblk), dim3(256), pl.lds, s, p);
         else MRDIS_LAUNCH((wino_wgrad_kernel<2, 2, true>), dim3(nblk), dim3(256), pl.lds, s, p);

@@ -181,6 +181,12 @@ VARIANT_FAMILIES = ('conv2src', 'ana_act')
 # the kernels of the latent-code options (csrc/mrdis_latent.hip): the masked KL term (lambda_kl, is_distri_z) and the mean compaction
 # (s_compact_method 'mean').  Outside KERNEL_FAMILIES for the same reason.
 LATENT_FAMILIES = ('kl', 'avgpool')
+# the uncounted-until-now kernels of the 3-D convolutions (csrc/mrdis_conv3d.hip, mrdis_wino.hip): the tap-table direct kernel (tapconv3d_kernel),
+# the 16-cout fp32 kernel (conv3d16_kernel), the generic and narrow weight gradients (wgrad3d_kernel, wgrad3d16_kernel; their reductions are not
+# counted) and the hybrid Winograd weight gradient (one count per depth-tap launch, three per call).  The hybrid 3-D Winograd forward / data
+# gradient keeps counting under 'wino_spade' and the six-product 3-D kernels under 'split6_c3d' / 'split6_w3d' (KERNEL_FAMILIES): renaming
+# them would only churn the 2-D table.  Outside KERNEL_FAMILIES for the same reason as the tables above (tests/test_gpu_conv3d_paths.py covers them).
+CONV3D_FAMILIES = ('direct3d', 'c3d16', 'wgrad3d', 'wgrad3d16', 'wino_wgrad3d')
 
 
 def stream_fill(t, value=0.0):
@@ -208,7 +214,7 @@ def dynamic_lds():
 def launch_counts(reset=False):
     """{family: launches since load / the last reset} of the Winograd, bf16 LDS-DMA and six-product (split6) kernel families (include/mrdis.h mrdis_launch_count)"""
     lib = load()
-    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES}
+    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + CONV3D_FAMILIES}
     if reset:
         lib.mrdis_launch_count_reset()
     return out
@@ -1153,10 +1159,25 @@ def adam_amsgrad_step(p, g, m, v, vmax, lr, beta1, beta2, eps, weight_decay, ste
 
 
 # ================================================================ 3-D path (NDHWC, torch.channels_last_3d)
-def ndhwc(t):
-    """(tensor, ld) of a logical (N,C,D,H,W) fp32 tensor stored NDHWC (channels_last_3d); copies if it is not."""
+def ndhwc_ld(t):
+    """pixel stride (elements) of a logical (N,C,D,H,W) tensor whose memory is NDHWC -- dense or a channel slice of a wider buffer -- else None"""
+    N, C, D, H, W = t.shape
+    s = t.stride()
+    ld = s[4] if W > 1 else (s[3] if H > 1 else (s[2] if D > 1 else (s[0] if N > 1 else C)))
+    ok = (ld >= C and (C == 1 or s[1] == 1) and (W == 1 or s[4] == ld) and (H == 1 or s[3] == W * ld) and
+          (D == 1 or s[2] == H * W * ld) and (N == 1 or s[0] == D * H * W * ld))
+    return ld if ok else None
+
+
+def ndhwc(t, keep_slice=False):
+    """(tensor, ld) of a logical (N,C,D,H,W) fp32 tensor stored NDHWC (channels_last_3d); copies if it is not.
+    keep_slice: a channel slice of a wider NDHWC buffer goes through as it is, with its pixel stride as ld (no copy)."""
     assert t.dim() == 5 and t.dtype == torch.float32, (t.shape, t.dtype)
     N, C, D, H, W = t.shape
+    if keep_slice:
+        ld = ndhwc_ld(t)
+        if ld is not None:
+            return t, ld
     want = (D * H * W * C, 1, H * W * C, W * C, C)
     if any(t.shape[i] > 1 and t.stride()[i] != want[i] for i in range(5)):
         t = t.permute(0, 2, 3, 4, 1).contiguous().permute(0, 4, 1, 2, 3)
@@ -1171,34 +1192,52 @@ def _out3(D, H, W, k, stride, pad):
     return tuple((v + 2 * pad - k) // stride + 1 for v in (D, H, W))
 
 
-def conv3d_fwd(x, w_tck, bias, k, stride, pad, residual=None):
-    x, ldx = ndhwc(x)
+def _out_view3(out, shape, what):
+    """(out, ld) of a caller's output view: NDHWC, dense or a channel slice of a wider buffer (written in place, never copied)"""
+    assert out.dtype == torch.float32 and tuple(out.shape) == tuple(shape), (what, tuple(out.shape), tuple(shape))
+    ld = ndhwc_ld(out)
+    assert ld is not None, f'{what}: `out` must be an NDHWC view'
+    return out, ld
+
+
+def conv3d_fwd(x, w_tck, bias, k, stride, pad, residual=None, out=None, keep_slices=False):
+    """out: an NDHWC view to write (e.g. a channel slice of a wider buffer, passed with its ld); keep_slices: x / residual channel slices go
+    in with their ld instead of as dense copies"""
+    x, ldx = ndhwc(x, keep_slices)
     N, Ci, D, H, W = x.shape
     Co = w_tck.shape[2]
     Do, Ho, Wo = _out3(D, H, W, k, stride, pad)
-    y = empty_ndhwc(N, Co, Do, Ho, Wo, x.device)
+    if out is None:
+        y, ldy = empty_ndhwc(N, Co, Do, Ho, Wo, x.device), Co
+    else:
+        y, ldy = _out_view3(out, (N, Co, Do, Ho, Wo), 'conv3d_fwd')
     ldr = 0
     if residual is not None:
-        residual, ldr = ndhwc(residual)
+        residual, ldr = ndhwc(residual, keep_slices)
         assert tuple(residual.shape) == tuple(y.shape)
-    _chk(load().mrdis_conv3d_fwd(x.data_ptr(), ldx, w_tck.data_ptr(), _ptr(bias), _ptr(residual), ldr, y.data_ptr(), Co,
+    _chk(load().mrdis_conv3d_fwd(x.data_ptr(), ldx, w_tck.data_ptr(), _ptr(bias), _ptr(residual), ldr, y.data_ptr(), ldy,
                                  N, D, H, W, Ci, Co, k, stride, pad, _stream()), 'conv3d_fwd')
     return y
 
 
-def conv3d_bwd_data(dy, w_tkc, in_shape, k, stride, pad):
-    dy, lddy = ndhwc(dy)
+def conv3d_bwd_data(dy, w_tkc, in_shape, k, stride, pad, out=None, keep_slices=False):
+    """out / keep_slices: as conv3d_fwd (dx into a caller's NDHWC view; a dy channel slice with its ld)"""
+    dy, lddy = ndhwc(dy, keep_slices)
     N, Ci, D, H, W = in_shape
     Co = dy.shape[1]
-    dx = empty_ndhwc(N, Ci, D, H, W, dy.device)
-    _chk(load().mrdis_conv3d_bwd_data(dy.data_ptr(), lddy, w_tkc.data_ptr(), dx.data_ptr(), Ci,
+    if out is None:
+        dx, lddx = empty_ndhwc(N, Ci, D, H, W, dy.device), Ci
+    else:
+        dx, lddx = _out_view3(out, (N, Ci, D, H, W), 'conv3d_bwd_data')
+    _chk(load().mrdis_conv3d_bwd_data(dy.data_ptr(), lddy, w_tkc.data_ptr(), dx.data_ptr(), lddx,
                                       N, D, H, W, Ci, Co, k, stride, pad, _stream()), 'conv3d_bwd_data')
     return dx
 
 
-def conv3d_bwd_weight(x, dy, k, stride, pad, want_bias):
-    x, ldx = ndhwc(x)
-    dy, lddy = ndhwc(dy)
+def conv3d_bwd_weight(x, dy, k, stride, pad, want_bias, out=None, keep_slices=False):
+    """out: caller-owned (dw [k^3][Ci][Co] contiguous, db [Co] or None) to write; keep_slices: x / dy channel slices with their ld"""
+    x, ldx = ndhwc(x, keep_slices)
+    dy, lddy = ndhwc(dy, keep_slices)
     N, Ci, D, H, W = x.shape
     Co = dy.shape[1]
     lib = load()
@@ -1206,8 +1245,13 @@ def conv3d_bwd_weight(x, dy, k, stride, pad, want_bias):
     if need == 0:
         raise MrdisError('conv3d_bwd_weight: unsupported geometry')
     ws = _ws(need, x.device)
-    dw = torch.empty((k * k * k, Ci, Co), dtype=torch.float32, device=x.device)
-    db = torch.empty((Co,), dtype=torch.float32, device=x.device) if want_bias else None
+    if out is None:
+        dw = torch.empty((k * k * k, Ci, Co), dtype=torch.float32, device=x.device)
+        db = torch.empty((Co,), dtype=torch.float32, device=x.device) if want_bias else None
+    else:
+        dw, db = out
+        assert dw.dtype == torch.float32 and tuple(dw.shape) == (k * k * k, Ci, Co) and dw.is_contiguous(), (dw.shape, dw.dtype)
+        assert (db is not None) == bool(want_bias) and (db is None or (db.dtype == torch.float32 and tuple(db.shape) == (Co,) and db.is_contiguous()))
     _chk(lib.mrdis_conv3d_bwd_weight(x.data_ptr(), ldx, dy.data_ptr(), lddy, dw.data_ptr(), _ptr(db), ws.data_ptr(), ws.numel(),
                                      N, D, H, W, Ci, Co, k, stride, pad, _stream()), 'conv3d_bwd_weight')
     return dw, db

@@ -55,6 +55,35 @@ def wgrad_ref(x, dy, kh, kw, stride, pad):
     return dw, A, dy.sum((0, 2, 3)), dy.abs().sum((0, 2, 3))
 
 
+def fwd_ref3d(x, w, b, stride, pad, residual=None):
+    """x (N, Ci, D, H, W), w (Co, Ci, kd, kh, kw), b (Co,) or None, residual (N, Co, Do, Ho, Wo) or None -> (ref, A); a fused residual adds |res| to A"""
+    x, w = x.double(), w.double()
+    ref = F.conv3d(x, w, None if b is None else b.double(), stride, pad)
+    A = F.conv3d(x.abs(), w.abs(), None if b is None else b.double().abs(), stride, pad)
+    if residual is not None:
+        ref = ref + residual.double()
+        A = A + residual.double().abs()
+    return ref, A
+
+
+def dgrad_ref3d(dy, w, in_dhw, stride, pad):
+    """data gradient of conv3d(x, w, stride, pad) for x of spatial extent in_dhw -> (ref, A)"""
+    dy, w = dy.double(), w.double()
+    shape = (dy.shape[0], w.shape[1]) + tuple(in_dhw)
+    ref = torch.nn.grad.conv3d_input(shape, w, dy, stride, pad)
+    A = torch.nn.grad.conv3d_input(shape, w.abs(), dy.abs(), stride, pad)
+    return ref, A
+
+
+def wgrad_ref3d(x, dy, k, stride, pad):
+    """(dw (Co, Ci, k, k, k), A_dw, db (Co,), A_db)"""
+    x, dy = x.double(), dy.double()
+    shape = (dy.shape[1], x.shape[1], k, k, k)
+    dw = torch.nn.grad.conv3d_weight(x, shape, dy, stride, pad)
+    A = torch.nn.grad.conv3d_weight(x.abs(), shape, dy.abs(), stride, pad)
+    return dw, A, dy.sum((0, 2, 3, 4)), dy.abs().sum((0, 2, 3, 4))
+
+
 def ratio(got, ref, A, u_out=0.0, extra=None):
     """worst (|got - ref| - u_out |ref| - extra) / (u A) over the elements: the kappa this result needs (inf for a non-finite element)"""
     got = got.detach().double().cpu()
@@ -145,4 +174,19 @@ KAPPA = {
     ('c4_mixed', 'dgrad'):         150,    #  35.43
     ('wgrad_co4b', 'wgrad'):         1,    #   0.07
     ('wgrad_c4_mixed', 'wgrad'):     1,    #   0.07
+    # 3-D (tests/test_gpu_conv3d_paths.py; profiles/conv3d_path_margins.txt).  'wino_spade' is the hybrid 3-D Winograd (F(2x2) in (h, w), direct
+    # in depth) under the name its counter carries; 'direct3d_s2' the tap-table kernel on the eight stride-2 parity classes of the data gradient.
+    ('split6_c3d', 'fwd'):          20,    #   4.09
+    ('split6_c3d', 'dgrad'):        25,    #   5.21
+    ('split6_w3d', 'wgrad'):         1,    #   0.10
+    ('c3d16', 'fwd'):               25,    #   5.62
+    ('c3d16', 'dgrad'):             20,    #   4.26
+    ('direct3d', 'fwd'):            25,    #   5.62
+    ('direct3d', 'dgrad'):          15,    #   3.37
+    ('direct3d_s2', 'dgrad'):       15,    #   3.63
+    ('wino_spade', 'fwd'):           8,    #   1.86
+    ('wino_spade', 'dgrad'):         6,    #   1.36
+    ('wino_wgrad3d', 'wgrad'):      25,    #   5.87
+    ('wgrad3d', 'wgrad'):            7,    #   1.75
+    ('wgrad3d16', 'wgrad'):          5,    #   1.15
 }

@@ -86,8 +86,10 @@ def test_option_and_counter_tables_match_the_library(mrdis):
     for name, v in snap.items():
         hip.set_option(name, v)                    # raises on a name the library does not know
     assert lib.mrdis_set_option(b'no_such_option', 1) == -1
-    for fam in hip.KERNEL_FAMILIES:
+    for fam in hip.KERNEL_FAMILIES + hip.CONV3D_FAMILIES:
         assert lib.mrdis_launch_count(fam.encode()) >= 0, fam
+    assert not set(hip.CONV3D_FAMILIES) & set(hip.KERNEL_FAMILIES + hip.VARIANT_FAMILIES + hip.LATENT_FAMILIES)
+    assert set(hip.CONV3D_FAMILIES) <= set(hip.launch_counts())
     assert lib.mrdis_launch_count(b'no_such_family') == -1
     assert isinstance(hip.dynamic_lds(), dict)
     import ctypes

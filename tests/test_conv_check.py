@@ -1,6 +1,7 @@
 """The element-wise float64 bound of tests/conv_check.py against the max-scaled close() of tests/test_gpu_ops.py, on the CPU: faults planted into a
 float64 convolution result that a wrong tail mask or a mis-offset epilogue would produce are caught by the new bound and passed by close() at the
-rtol the suite uses for that dtype; clean fp32- and bf16-rounded results pass the new bound (it is not vacuous); a coarse fault fails both."""
+rtol the suite uses for that dtype; clean fp32- and bf16-rounded results pass the new bound (it is not vacuous); a coarse fault fails both.
+The 3-D references (fwd_ref3d, dgrad_ref3d, wgrad_ref3d) get the same treatment, plus a tap lost on one depth face of the volume."""
 import pytest
 import torch
 
@@ -87,5 +88,65 @@ def test_reference_gradients_match_autograd():
         y.backward(dy)
         dx, Adx = CC.dgrad_ref(dy, w.detach(), (H, W), s, p)
         dw, Adw, db, Adb = CC.wgrad_ref(x.detach(), dy, k, k, s, p)
+        assert torch.allclose(dx, x.grad) and torch.allclose(dw, w.grad) and torch.allclose(db, b.grad)
+        assert (Adx >= dx.abs() - 1e-12).all() and (Adw >= dw.abs() - 1e-12).all() and (Adb >= db.abs()).all()
+
+
+# ---------------------------------------------------------------- 3-D (tests/test_gpu_conv3d_paths.py)
+def layer3d(Ci, Co=20, N=2, D=5, H=6, W=7, seed=0, residual=False):
+    g = torch.Generator().manual_seed(seed)
+    x = torch.randn(N, Ci, D, H, W, generator=g, dtype=torch.float64)
+    w = torch.randn(Co, Ci, 3, 3, 3, generator=g, dtype=torch.float64) * (27 * Ci) ** -0.5
+    b = torch.randn(Co, generator=g, dtype=torch.float64) * 0.1
+    res = torch.randn(N, Co, D, H, W, generator=g, dtype=torch.float64) if residual else None
+    ref, A = CC.fwd_ref3d(x, w, b, 1, 1, res)
+    return x, w, b, ref, A
+
+
+@pytest.mark.parametrize('Ci,residual', [(16, False), (128, True)])
+def test_clean_3d_results_pass_the_bound(Ci, residual):
+    _, _, _, ref, A = layer3d(Ci, residual=residual)
+    r = CC.check(stored(ref, 'fp32'), ref, A, KAPPA, what='clean 3-D')
+    assert r <= 1.0, r
+
+
+@pytest.mark.parametrize('Ci,residual', [(16, False), (128, True)])
+def test_3d_cout_tail_fault_caught_by_the_bound_missed_by_close(Ci, residual):
+    """the last 4 couts of a Co = 20 3-D result scaled by 1 + 1e-4: passes the 1e-3 max-scaled check tests/test_gpu_3d.py uses"""
+    _, _, _, ref, A = layer3d(Ci, residual=residual)
+    got = stored(ref, 'fp32').clone()
+    got[:, -4:] *= 1 + 1e-4
+    close(got, ref, rtol=1e-3, what='close() passes the fault')
+    new_check_catches(got, ref, A, 'fp32')
+
+
+@pytest.mark.parametrize('face', ['first', 'last'])
+def test_3d_tap_dropped_on_a_depth_face_fails_the_bound(face):
+    """one depth tap of the last 8 input channels lost on the first (or last) D plane only -- the tap that reads the real neighbouring plane,
+    not the zero padding: a wrong depth-halo mask in a box at the volume boundary"""
+    Ci = 64
+    x, w, b, ref, A = layer3d(Ci, D=6, H=5, W=6)
+    d, r, src = (0, 2, 1) if face == 'first' else (-1, 0, -2)        # out plane, depth tap, the input plane that tap reads
+    lost = torch.einsum('nchw,oc->nohw', x[:, -8:, src], w[:, -8:, r, 1, 1])
+    got = stored(ref, 'fp32').clone()
+    got[:, :, d, 1:, :] -= lost[:, :, 1:, :]          # (every row but the first: the fault is confined to part of one face)
+    new_check_catches(got, ref, A, 'fp32')
+
+
+def test_3d_reference_gradients_match_autograd():
+    """the 3-D data- and weight-gradient references are the adjoints of the forward one; the fused residual enters ref and A"""
+    g = torch.Generator().manual_seed(5)
+    for (Ci, Co, s, D, H, W) in [(5, 6, 1, 4, 5, 6), (4, 10, 2, 5, 7, 6), (3, 8, 2, 1, 3, 4)]:
+        x = torch.randn(2, Ci, D, H, W, generator=g, dtype=torch.float64, requires_grad=True)
+        w = torch.randn(Co, Ci, 3, 3, 3, generator=g, dtype=torch.float64, requires_grad=True)
+        b = torch.randn(Co, generator=g, dtype=torch.float64, requires_grad=True)
+        y = torch.nn.functional.conv3d(x, w, b, s, 1)
+        res = torch.randn(y.shape, generator=g, dtype=torch.float64)
+        ref, A = CC.fwd_ref3d(x.detach(), w.detach(), b.detach(), s, 1, res)
+        assert torch.allclose(ref, y.detach() + res) and (A >= ref.abs() - 1e-12).all()
+        dy = torch.randn(y.shape, generator=g, dtype=torch.float64)
+        y.backward(dy)
+        dx, Adx = CC.dgrad_ref3d(dy, w.detach(), (D, H, W), s, 1)
+        dw, Adw, db, Adb = CC.wgrad_ref3d(x.detach(), dy, 3, s, 1)
         assert torch.allclose(dx, x.grad) and torch.allclose(dw, w.grad) and torch.allclose(db, b.grad)
         assert (Adx >= dx.abs() - 1e-12).all() and (Adw >= dw.abs() - 1e-12).all() and (Adb >= db.abs()).all()

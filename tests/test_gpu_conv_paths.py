@@ -31,9 +31,9 @@ PAD_C = 8           # channels on each side of the input / output slices
 NOT_IN_TABLE = {
     'all': 'every launch of the library, not a kernel',
     'zsearch': 'nearest-neighbour code search, not a convolution (tests/test_gpu_zsearch.py)',
-    'wino_spade': '3-D only: counts mrdis_run_wino3d, the hybrid 3-D Winograd of mrdis_conv3d_fwd / _bwd_data (tests/test_gpu_3d.py), despite its name',
-    'split6_c3d': '3-D only: mrdis_conv3d_s6.hip forward / data gradient, checked against float64 in tests/test_gpu_3d.py',
-    'split6_w3d': '3-D only: mrdis_conv3d_s6.hip weight gradient, checked against float64 in tests/test_gpu_3d.py',
+    'wino_spade': '3-D only: counts mrdis_run_wino3d, the hybrid 3-D Winograd of mrdis_conv3d_fwd / _bwd_data, despite its name (tests/test_gpu_conv3d_paths.py)',
+    'split6_c3d': '3-D only: mrdis_conv3d_s6.hip forward / data gradient, checked element-wise against float64 in tests/test_gpu_conv3d_paths.py',
+    'split6_w3d': '3-D only: mrdis_conv3d_s6.hip weight gradient, checked element-wise against float64 in tests/test_gpu_conv3d_paths.py',
 }
 
 KAPPA = CC.KAPPA
