@@ -14,6 +14,12 @@ the named workload is dropped (the reference's own 160x192 crop is available wit
 --fit crop).  Weak scaling: per-GPU batch fixed, gradients mean-all-reduced over RCCL.
 Inputs are synthetic BraTS-shaped slices already resident in HBM; weights random-init.
 
+A plain run sets up, warms up, times the K steps, writes --dump-outputs if asked and prints the line.  Everything
+else the benchmark measures -- the roofline legs (with their rocprofv3 PMC child passes), the same step on direct kernels
+only / without the six-product split / as graph replays, host_ms_unblocked and the CPU baseline -- runs only under
+--full, after the timed steps except the step-kernel roofline, which runs before the model is built; the --no-* options
+drop single legs of --full.
+
 One JSON line is printed by rank 0 (see DESIGN.md "Measurement").
 """
 import argparse
@@ -58,15 +64,17 @@ def parse():
                          "fp32 accumulate / statistics / master weights / optimizer) | bf16m (bf16 MFMA operands on fp32 activations)")
     ap.add_argument('--graph', action='store_true', help='the timed steps as HIP-graph replays (trainer.GraphedTrainStep; also MRDIS_GRAPH=1): forward, losses, backward, clip, Adam '
                                                          'recorded once after two eager iterations; >= 3 untimed warm-up steps are run so that the timed region only replays')
-    ap.add_argument('--no-graph-leg', action='store_true', help='skip the extra graph-replay timing beside the (eager) headline')
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-roofline', action='store_true')
+    ap.add_argument('--full', action='store_true', help='also run everything beside the headline: roofline legs (+ PMC child passes), direct-only / split6-off / '
+                                                        'graph-replay step timings, host_ms_unblocked, CPU baseline (off: the run does only what the headline needs)')
+    ap.add_argument('--no-graph-leg', action='store_true', help='with --full: skip the extra graph-replay timing beside the (eager) headline')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: skip the CPU baseline')
+    ap.add_argument('--no-roofline', action='store_true', help='with --full: skip the roofline legs and host_ms_unblocked')
     ap.add_argument('--no-pmc', action='store_true', help='do not run the two rocprofv3 --pmc child passes that measure roofline.traffic in this run (the stored number is reported instead)')
-    ap.add_argument('--no-direct', action='store_true', help='skip the extra direct-kernels-only (wino = 0) timing')
+    ap.add_argument('--no-direct', action='store_true', help='with --full: skip the extra direct-kernels-only (wino = 0) and split6 = 0 timings and the graph-replay timing')
     ap.add_argument('--dry-run', action='store_true', help='launcher rehearsal without a GPU: every rank joins a gloo group and reports in; rank 0 prints the '
                                                            'ranks it heard from (tests/test_bench_launch.py)')
     ap.add_argument('--roofline-only', action='store_true', help='only the roofline legs (north-star conv + the dominant kernels of the step), '
-                                                                 'no training step: what tools/profile_round.sh profiles separately from the step')
+                                                                 'no training step, with or without --full: what tools/profile_round.sh profiles separately from the step')
     ap.add_argument('--dump-outputs', metavar='DIR', default=None,
                     help='after the timed steps, write what the last timed step returned (loss, loss parts, gradient norm, weights after Adam, activations) '
                          'as DIR/<name>.npy, float32 / float64, at most 64 MB in all (large arrays: a fixed seeded sample, see dump_outputs)')
@@ -520,7 +528,7 @@ def dry_run(a, world, rank):
     dist.all_gather(got, mine)
     if rank == 0:
         print(json.dumps({'dry_run': True, 'n_gpus': world, 'rccl_ranks': dist.get_world_size(), 'backend': 'gloo (dry run)',
-                          'ranks_reported': sorted(int(t) for t in got), 'steps': a.steps, 'warmup': a.warmup}), flush=True)
+                          'ranks_reported': sorted(int(t) for t in got), 'steps': a.steps, 'warmup': a.warmup, 'full': a.full}), flush=True)
     dist.barrier()
     dist.destroy_process_group()
 
@@ -570,7 +578,8 @@ def main():
     cfg = mrdis.derive_config(cfg, dev)
     # the step's dominant kernels at the step's shapes (before the model exists: 1.6 GB of operands of their own)
     # (world == 1 only: at N > 1 rank 0's extra legs run AFTER the process group is destroyed, so that no other rank waits in an RCCL barrier for them)
-    rstep = roofline_step(mrdis, dev, B, H, W, a.dtype, pmc_inrun=(not a.no_pmc and a.dtype == 'f32')) if (world == 1 and not a.no_roofline) else None
+    rstep = roofline_step(mrdis, dev, B, H, W, a.dtype, pmc_inrun=(not a.no_pmc and a.dtype == 'f32')) \
+        if ((a.full or a.roofline_only) and world == 1 and not a.no_roofline) else None
     torch.cuda.empty_cache()
     if a.roofline_only:
         assert world == 1
@@ -658,7 +667,7 @@ def main():
     # the same step on the direct-convolution kernels only (north_star describes a direct conv; the default policy runs
     # fused Winograd on the big 3x3 layers): reported beside the headline, never as `value`
     ms_direct = None
-    if not a.no_direct and a.dtype == 'f32' and mrdis.hip.get_option('wino') != 0:
+    if a.full and not a.no_direct and a.dtype == 'f32' and mrdis.hip.get_option('wino') != 0:
         prev = mrdis.hip.get_option('wino')
         mrdis.hip.set_option('wino', 0)
         nd = max(2, min(a.steps, 5))
@@ -678,7 +687,7 @@ def main():
     # the four-channel thin layers with fp32 MFMA (option split6 = 0) instead of the six-product bf16 split the default policy uses for them: same run, same
     # box, a few steps -- beside the headline, with the loss both ways (the split is accepted only at the exact kernels' own error level: tests)
     split6 = None
-    if a.dtype == 'f32' and not a.no_direct and mrdis.hip.get_option('split6') != 0:
+    if a.full and a.dtype == 'f32' and not a.no_direct and mrdis.hip.get_option('split6') != 0:
         prev6 = mrdis.hip.get_option('split6')
         mrdis.hip.set_option('split6', 0)
         nd = max(2, min(a.steps, 5))
@@ -702,7 +711,7 @@ def main():
 
     # the same step as HIP-graph replays (or, under --graph, eagerly): beside the headline, never as `value`
     graph_leg = None
-    if not a.no_graph_leg and not a.no_direct and world == 1:
+    if a.full and not a.no_graph_leg and not a.no_direct and world == 1:
         try:
             nd = max(2, min(a.steps, 5))
             other = eager_step if graph_on else mrdis.GraphedTrainStep(eager_step, warm=1)
@@ -725,7 +734,7 @@ def main():
         out = {
             'metric': 'MR slices/sec (train step, recon+adv+latent losses)' if adv else 'MR slices/sec (train step, recon+latent losses, lambda_adv_s=0)',
             'value': round(value, 3), 'unit': 'slices/s', 'n_gpus': world,
-            'rccl_ranks': dist.get_world_size() if world > 1 else 1, 'steps': a.steps, 'warmup': a.warmup,
+            'rccl_ranks': dist.get_world_size() if world > 1 else 1, 'steps': a.steps, 'warmup': a.warmup, 'full': a.full,
             'ms_per_step': round(ms, 2), 'higher_is_better': True, 'scaling': 'weak', 'vs_baseline': None,
             'dtype': {'f32': 'f32', 'bf16': 'bf16 (bf16 activations + MFMA operands, f32 accumulate / statistics / master weights)',
                       'bf16m': 'bf16 MFMA operands / f32 accumulate / f32 storage'}[a.dtype], 'data': 'synthetic',
@@ -762,7 +771,7 @@ def main():
                                         '(profiles/*_dispatch_counts_*.txt has every dispatch from rocprofv3)')
         out['host_enqueue_ms_per_step'] = round(host_ms, 1)
         out['host_enqueue_note'] = 'host time inside step() during the timed region: mostly waiting on the full launch queue (the step is GPU-bound); host_ms_unblocked is the cost proper'
-        if world == 1 and not a.no_roofline:
+        if a.full and world == 1 and not a.no_roofline:
             out['host_ms_unblocked'] = host_unblocked_ms(mrdis, cfg, dev, B, M, adv)
             try:
                 out['host_ms_unblocked_graph'] = host_unblocked_ms(mrdis, cfg, dev, B, M, adv, graph=True)
@@ -781,7 +790,7 @@ def main():
         dist.barrier()
         dist.destroy_process_group()        # ranks 1..N-1 are done here; rank 0's extra legs below keep nobody waiting
     if rank == 0:
-        if not a.no_roofline:
+        if a.full and not a.no_roofline:
             if rstep is None:
                 rstep = roofline_step(mrdis, dev, B, H, W, a.dtype)
             out['roofline'] = roofline_conv(mrdis, dev, pmc_inrun=(world == 1 and not a.no_pmc))
@@ -790,7 +799,7 @@ def main():
             log(f'roofline_step: {rstep}')
             if world > 1:
                 out['roofline_note'] = 'N > 1: both roofline legs ran on rank 0 after destroy_process_group() (outside the timed region, no rank waiting); PMC traffic passes are N = 1 only'
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out['cpu_baseline'] = cpu_baseline(M, H, W, adv)
         print(json.dumps(out), flush=True)
 

@@ -45,3 +45,13 @@ def test_world_size_that_differs_from_gpus_is_refused():
     r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--dry-run'], env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode != 0 and 'WORLD_SIZE' in r.stderr
     assert not _json_lines(r.stdout)
+
+
+def test_full_is_off_by_default_and_forwarded_to_the_ranks():
+    for extra, want in (([], False), (['--full'], True)):
+        r = subprocess.run([sys.executable, BENCH, '--gpus', '2', '--steps', '2', '--warmup', '1', '--dry-run'] + extra, env=_env(),
+                           capture_output=True, text=True, timeout=300)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1 and lines[0]['ranks_reported'] == [0, 1]
+        assert lines[0]['full'] is want

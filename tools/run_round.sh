@@ -13,9 +13,9 @@ for step in "$@"; do
     tests)      python -m pytest tests -m gpu -x -q > $OUT/pytest.log 2>&1; rc=$?; tail -4 $OUT/pytest.log ;;
     tests:*)    python -m pytest tests -m gpu -x -q -k "${step#tests:}" > $OUT/pytest_k.log 2>&1; rc=$?; tail -15 $OUT/pytest_k.log ;;
     smoke)      python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1; rc=$?; tail -1 $OUT/smoke.log ;;
-    bench)      python bench.py > $OUT/bench_f32.json 2> $OUT/bench_f32.err; rc=$?; grep "timed:" $OUT/bench_f32.err ;;
+    bench)      python bench.py --full > $OUT/bench_f32.json 2> $OUT/bench_f32.err; rc=$?; grep "timed:" $OUT/bench_f32.err ;;
     bench_fast) python bench.py --no-cpu-baseline --no-roofline --no-direct > $OUT/bench_f32_fast.json 2> $OUT/bench_f32_fast.err; rc=$?; grep "timed:" $OUT/bench_f32_fast.err ;;
-    bench_bf16) python bench.py --dtype bf16 --no-cpu-baseline > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; rc=$?; grep "timed:" $OUT/bench_bf16.err ;;
+    bench_bf16) python bench.py --full --dtype bf16 --no-cpu-baseline > $OUT/bench_bf16.json 2> $OUT/bench_bf16.err; rc=$?; grep "timed:" $OUT/bench_bf16.err ;;
     bench_drop) python bench.py --drop --no-cpu-baseline --no-roofline --no-direct > $OUT/bench_drop.json 2> $OUT/bench_drop.err; rc=$?; grep "timed:" $OUT/bench_drop.err ;;
     rehearsal)  python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29511 tools/ddp_rehearsal.py > $OUT/ddp_rehearsal.txt 2>&1; rc=$?; grep "ddp rehearsal" $OUT/ddp_rehearsal.txt ;;
     layers)     python tools/layer_bench.py > $OUT/layer_bench_f32.txt 2>&1; rc=$?; tail -5 $OUT/layer_bench_f32.txt ;;
