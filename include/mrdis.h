@@ -82,7 +82,7 @@ long long mrdis_get_option(const char* name);
  * "wino2" | "wino2_spade" (pipelined F(2x2)), "wino4" | "wino4_spade" (F(4x4) 64-cout forms), "wino4n" | "wino4r" (32-cout forms: shared transform / register-fed),
  * "wino_wgrad" | "wino_wgrad2" (F(2x2) weight gradient), "wino4_wgrad" (F(3x3,4x4)); "bconv3" | "bconv3_spade" | "bconv4" | "bconv4_spade" (bf16 3x3 forms);
  * "split6_c4" | "split6_c16" | "split6_wgrad16" | "split6_co4" | "split6_c3d" | "split6_w3d" | "split6_tap" (option split6: the 4 -> C kernel, the 32 -> 16 forward, its weight gradient, the
- * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "zsearch" (mrdis_cosine_top1); "conv2src" | "ana_act" (the others variants); "kl" | "avgpool" (the latent-code options);
+ * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "zsearch" (mrdis_cosine_top1); "conv2src" | "ana_act" (the others variants); "kl" | "avgpool" (the latent-code options); "chatt" | "symdiff" | "rgate" (the attention output decoders);
  * "direct3d" | "c3d16" | "wgrad3d" | "wgrad3d16" | "wino_wgrad3d" (the 3-D tap-table, 16-cout, generic and narrow weight-gradient kernels and the hybrid
  * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "all" (every kernel launch of the library).  MRDIS_EINVAL for an unknown name.  Diagnostics: the parity tests
  * use it to prove that the form under test is the one that ran. */
@@ -535,6 +535,30 @@ int mrdis_kl_bwd(const float* dloss, const float* const* mu, const float* const*
  * Launch counter family "avgpool".                                                                                        */
 int mrdis_avgpool_fwd(const float* x, int ldx, float* y, int N, int H, int W, int C, int k, void* stream);
 int mrdis_avgpool_bwd(const float* dy, float* dx, int lddx, int N, int H, int W, int C, int k, void* stream);
+
+/* ---- the attention output decoders 'U+SA+CA' / 'U+SSA+CA' (model.py:1002-1137, 1389-1433), csrc/mrdis_outdec.hip.  fp32 NHWC views with
+ * pixel strides (channel slices allowed); float4 forms when every pointer is 16-byte aligned and every stride and C are multiples of 4.
+ * Channel attention + the decoder level's skip sum: a = sigmoid(W_up relu(W_down mean_hw(x) + b_down) + b_up), out = (1 + a[b, c]) x + s.
+ * x, s, out: (B, HW, C) views (out: typically channels [0, C) of the level's concatenation buffer); wd (Hd, C), bd (Hd), wu (C, Hd), bu (C):
+ * the nn.Linear parameters, dense.  Writes pool (B, C), hid (B, Hd, after the ReLU) and a (B, C), dense: what the backward reads.  Three
+ * launches (partial sums over fixed pixel chunks, the mean and the MLP for all rows, the combine).  Backward: dx = (1 + a) dy + dpool / HW
+ * with the MLP backward in between; the weight and bias gradients are WRITTEN (sums over the batch in a fixed order); the gradient of s
+ * is dy itself.  Workspace: mrdis_chatt_workspace bytes, for either direction.  Launch counter family "chatt" (one count per call). */
+size_t mrdis_chatt_workspace(int B, long long HW, int C, int Hd);
+int mrdis_chatt_fwd(const float* x, int ldx, const float* s, int lds, const float* wd, const float* bd, const float* wu, const float* bu,
+                    float* out, int ldo, float* pool, float* hid, float* a, void* ws, size_t ws_bytes, int B, long long HW, int C, int Hd,
+                    void* stream);
+int mrdis_chatt_bwd(const float* dy, int lddy, const float* x, int ldx, const float* a, const float* hid, const float* pool,
+                    const float* wd, const float* wu, float* dx, int lddx, float* dwd, float* dbd, float* dwu, float* dbu,
+                    void* ws, size_t ws_bytes, int B, long long HW, int C, int Hd, void* stream);
+/* gd = |g - flip_H(g)| of a (B, H, W, C) view; backward dg[h] = sgn(g[h] - g[H-1-h]) (dgd[h] + dgd[H-1-h]), sgn(0) = 0.  Family "symdiff". */
+int mrdis_symdiff_fwd(const float* g, int ldg, float* gd, int ldo, int B, int H, int W, int C, void* stream);
+int mrdis_symdiff_bwd(const float* dgd, int lddgd, const float* g, int ldg, float* dg, int lddg, int B, int H, int W, int C, void* stream);
+/* out = (1 + up2(alpha)) x: x (B, H, W, C) with H, W even, alpha a dense (B, H/2, W/2) map, up2 the x2 bilinear resize with align_corners=False.
+ * Backward: dx = (1 + up2(alpha)) dy and rsum (B, H, W) dense = sum_c dy x (dalpha = the bilinear backward of rsum).  Family "rgate". */
+int mrdis_rgate_fwd(const float* x, int ldx, const float* alpha, float* out, int ldo, int B, int H, int W, int C, void* stream);
+int mrdis_rgate_bwd(const float* dy, int lddy, const float* x, int ldx, const float* alpha, float* dx, int lddx, float* rsum,
+                    int B, int H, int W, int C, void* stream);
 
 #ifdef __cplusplus
 }

@@ -32,6 +32,7 @@ enum { MRDIS_CNT_WINO, MRDIS_CNT_WINO_SPADE, MRDIS_CNT_WINO2, MRDIS_CNT_WINO2_SP
        MRDIS_CNT_SPLIT6_C4, MRDIS_CNT_SPLIT6_C16, MRDIS_CNT_SPLIT6_WGRAD16, MRDIS_CNT_SPLIT6_CO4, MRDIS_CNT_SPLIT6_C3D, MRDIS_CNT_SPLIT6_W3D, MRDIS_CNT_SPLIT6_TAP, MRDIS_CNT_ZSEARCH,
        MRDIS_CNT_CONV2SRC, MRDIS_CNT_ANA_ACT /* mrdis_encs.hip: the others-variant kernels */,
        MRDIS_CNT_KL, MRDIS_CNT_AVGPOOL /* mrdis_latent.hip: the KL term and mean compaction */,
+       MRDIS_CNT_CHATT, MRDIS_CNT_SYMDIFF, MRDIS_CNT_RGATE /* mrdis_outdec.hip: the attention output decoders */,
        MRDIS_CNT_DIRECT3D, MRDIS_CNT_C3D16, MRDIS_CNT_WGRAD3D, MRDIS_CNT_WGRAD3D16, MRDIS_CNT_WINO_WGRAD3D /* mrdis_conv3d.hip / mrdis_wino.hip: the 3-D kernels */,
        MRDIS_CNT_ALL /* every launch of the library */, MRDIS_CNT_COUNT };
 void mrdis_count(int id);

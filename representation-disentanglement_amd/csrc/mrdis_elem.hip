@@ -1985,7 +1985,7 @@ namespace {
 const char* const CNT_NAMES[MRDIS_CNT_COUNT] = {"wino", "wino_spade", "wino2", "wino2_spade", "wino4", "wino4_spade", "wino4n", "wino4r",
                                                 "wino_wgrad", "wino_wgrad2", "wino4_wgrad", "bconv3", "bconv3_spade", "bconv4", "bconv4_spade",
                                                 "split6_c4", "split6_c16", "split6_wgrad16", "split6_co4", "split6_c3d", "split6_w3d", "split6_tap", "zsearch",
-                                                "conv2src", "ana_act", "kl", "avgpool",
+                                                "conv2src", "ana_act", "kl", "avgpool", "chatt", "symdiff", "rgate",
                                                 "direct3d", "c3d16", "wgrad3d", "wgrad3d16", "wino_wgrad3d", "all"};
 long long g_counts[MRDIS_CNT_COUNT];
 }  // namespace

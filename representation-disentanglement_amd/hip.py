@@ -118,6 +118,13 @@ _SIGS = {
     'mrdis_kl_bwd': (_I, [_P, _P, _P, _I, _I, _P, _P, _L, _I, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
     'mrdis_avgpool_fwd': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_avgpool_bwd': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'mrdis_chatt_workspace': (_Z, [_I, _L, _I, _I]),
+    'mrdis_chatt_fwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _Z, _I, _L, _I, _I, _P]),
+    'mrdis_chatt_bwd': (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _Z, _I, _L, _I, _I, _P]),
+    'mrdis_symdiff_fwd': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    'mrdis_symdiff_bwd': (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
+    'mrdis_rgate_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'mrdis_rgate_bwd': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -181,6 +188,9 @@ VARIANT_FAMILIES = ('conv2src', 'ana_act')
 # the kernels of the latent-code options (csrc/mrdis_latent.hip): the masked KL term (lambda_kl, is_distri_z) and the mean compaction
 # (s_compact_method 'mean').  Outside KERNEL_FAMILIES for the same reason.
 LATENT_FAMILIES = ('kl', 'avgpool')
+# the kernels of the attention output decoders 'U+SA+CA' / 'U+SSA+CA' (csrc/mrdis_outdec.hip): channel attention with the skip sum, the
+# symmetric difference of the gate and the residual gate.  Outside KERNEL_FAMILIES for the same reason.
+OUTDEC_FAMILIES = ('chatt', 'symdiff', 'rgate')
 # the uncounted-until-now kernels of the 3-D convolutions (csrc/mrdis_conv3d.hip, mrdis_wino.hip): the tap-table direct kernel (tapconv3d_kernel),
 # the 16-cout fp32 kernel (conv3d16_kernel), the generic and narrow weight gradients (wgrad3d_kernel, wgrad3d16_kernel; their reductions are not
 # counted) and the hybrid Winograd weight gradient (one count per depth-tap launch, three per call).  The hybrid 3-D Winograd forward / data
@@ -214,7 +224,7 @@ def dynamic_lds():
 def launch_counts(reset=False):
     """{family: launches since load / the last reset} of the Winograd, bf16 LDS-DMA and six-product (split6) kernel families (include/mrdis.h mrdis_launch_count)"""
     lib = load()
-    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + CONV3D_FAMILIES}
+    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES}
     if reset:
         lib.mrdis_launch_count_reset()
     return out
@@ -1552,3 +1562,99 @@ def avgpool_bwd(dy, in_shape, k, out=None):
     dx, lddx = _out_view(empty_nhwc(N, C, H, W, dy.device) if out is None else out)
     _chk(load().mrdis_avgpool_bwd(_ptr(dy), _ptr(dx), lddx, N, H, W, C, k, _stream()), 'avgpool_bwd')
     return dx
+
+
+# ---------------------------------------------------------------- the attention output decoders (csrc/mrdis_outdec.hip)
+def _dense_f32(t, shape, what):
+    if t.dtype is not torch.float32 or tuple(t.shape) != tuple(shape):
+        raise MrdisError(f'{what}: fp32 {tuple(shape)} expected (got {tuple(t.shape)} {t.dtype})')
+    return t.contiguous()
+
+
+def chatt_fwd(x, s, wd, bd, wu, bu, out=None):
+    """channel attention + skip sum: a = sigmoid(wu relu(wd mean_hw(x) + bd) + bu), out = (1 + a[b, c]) x + s (include/mrdis.h mrdis_chatt_fwd).
+    x, s: (B, C, H, W) NHWC views; out: an NHWC view to write into (a channel slice of a wider buffer qualifies).
+    -> (out, pool (B, C), hid (B, Hd), a (B, C)): the last three are what chatt_bwd reads."""
+    (x, ldx), (s, lds) = _act_views('chatt_fwd', x, s)
+    B, C, H, W = x.shape
+    if tuple(s.shape) != (B, C, H, W):
+        raise MrdisError(f'chatt_fwd: x {tuple(x.shape)} and s {tuple(s.shape)} differ')
+    Hd = wd.shape[0]
+    wd, bd = _dense_f32(wd, (Hd, C), 'chatt_fwd W_down'), _dense_f32(bd, (Hd,), 'chatt_fwd b_down')
+    wu, bu = _dense_f32(wu, (C, Hd), 'chatt_fwd W_up'), _dense_f32(bu, (C,), 'chatt_fwd b_up')
+    o, ldo = _out_view(empty_nhwc(B, C, H, W, x.device) if out is None else out)
+    assert tuple(o.shape) == (B, C, H, W) and o.dtype == torch.float32, (o.shape, o.dtype)
+    dev = x.device
+    pool = torch.empty((B, C), dtype=torch.float32, device=dev)
+    hid = torch.empty((B, Hd), dtype=torch.float32, device=dev)
+    a = torch.empty((B, C), dtype=torch.float32, device=dev)
+    lib = load()
+    nb = _ws_bytes(lib.mrdis_chatt_workspace, B, H * W, C, Hd)
+    ws = _ws(nb, dev)
+    _chk(lib.mrdis_chatt_fwd(_ptr(x), ldx, _ptr(s), lds, _ptr(wd), _ptr(bd), _ptr(wu), _ptr(bu), _ptr(o), ldo, _ptr(pool), _ptr(hid), _ptr(a),
+                             _ptr(ws), nb, B, H * W, C, Hd, _stream()), 'chatt_fwd')
+    return o, pool, hid, a
+
+
+def chatt_bwd(dy, x, a, hid, pool, wd, wu):
+    """-> (dx, dwd, dbd, dwu, dbu) of chatt_fwd for the upstream gradient dy (an NHWC view); the gradient of s is dy itself"""
+    (dy, lddy), (x, ldx) = _act_views('chatt_bwd', dy, x)
+    B, C, H, W = x.shape
+    Hd = hid.shape[1]
+    wd, wu = _dense_f32(wd, (Hd, C), 'chatt_bwd W_down'), _dense_f32(wu, (C, Hd), 'chatt_bwd W_up')
+    dev = x.device
+    dx = empty_nhwc(B, C, H, W, dev)
+    dwd = torch.empty((Hd, C), dtype=torch.float32, device=dev)
+    dbd = torch.empty((Hd,), dtype=torch.float32, device=dev)
+    dwu = torch.empty((C, Hd), dtype=torch.float32, device=dev)
+    dbu = torch.empty((C,), dtype=torch.float32, device=dev)
+    lib = load()
+    nb = _ws_bytes(lib.mrdis_chatt_workspace, B, H * W, C, Hd)
+    ws = _ws(nb, dev)
+    _chk(lib.mrdis_chatt_bwd(_ptr(dy), lddy, _ptr(x), ldx, _ptr(a), _ptr(hid), _ptr(pool), _ptr(wd), _ptr(wu), _ptr(dx), C, _ptr(dwd), _ptr(dbd),
+                             _ptr(dwu), _ptr(dbu), _ptr(ws), nb, B, H * W, C, Hd, _stream()), 'chatt_bwd')
+    return dx, dwd, dbd, dwu, dbu
+
+
+def symdiff_fwd(g, out=None):
+    """|g - g.flip(2)| of an NHWC view (include/mrdis.h mrdis_symdiff_fwd)"""
+    (g, ldg), = _act_views('symdiff_fwd', g)
+    B, C, H, W = g.shape
+    o, ldo = _out_view(empty_nhwc(B, C, H, W, g.device) if out is None else out)
+    _chk(load().mrdis_symdiff_fwd(_ptr(g), ldg, _ptr(o), ldo, B, H, W, C, _stream()), 'symdiff_fwd')
+    return o
+
+
+def symdiff_bwd(dgd, g, out=None):
+    (dgd, lddgd), (g, ldg) = _act_views('symdiff_bwd', dgd, g)
+    B, C, H, W = g.shape
+    dg, lddg = _out_view(empty_nhwc(B, C, H, W, g.device) if out is None else out)
+    _chk(load().mrdis_symdiff_bwd(_ptr(dgd), lddgd, _ptr(g), ldg, _ptr(dg), lddg, B, H, W, C, _stream()), 'symdiff_bwd')
+    return dg
+
+
+def _alpha_map(alpha, B, H, W, what):
+    if alpha.dtype is not torch.float32 or tuple(alpha.shape) != (B, 1, H // 2, W // 2):
+        raise MrdisError(f'{what}: alpha must be fp32 (B, 1, H/2, W/2) = {(B, 1, H // 2, W // 2)} (got {tuple(alpha.shape)} {alpha.dtype})')
+    return alpha.contiguous()
+
+
+def rgate_fwd(x, alpha, out=None):
+    """(1 + up2(alpha)) * x: x (B, C, H, W) NHWC view with even H, W; alpha (B, 1, H/2, W/2); up2 = bilinear x2, align_corners=False"""
+    (x, ldx), = _act_views('rgate_fwd', x)
+    B, C, H, W = x.shape
+    al = _alpha_map(alpha, B, H, W, 'rgate_fwd')
+    o, ldo = _out_view(empty_nhwc(B, C, H, W, x.device) if out is None else out)
+    _chk(load().mrdis_rgate_fwd(_ptr(x), ldx, _ptr(al), _ptr(o), ldo, B, H, W, C, _stream()), 'rgate_fwd')
+    return o
+
+
+def rgate_bwd(dy, x, alpha):
+    """-> (dx, dalpha (B, 1, H/2, W/2)) of rgate_fwd: dx element-wise, dalpha = the bilinear backward of sum_c dy * x"""
+    (dy, lddy), (x, ldx) = _act_views('rgate_bwd', dy, x)
+    B, C, H, W = x.shape
+    al = _alpha_map(alpha, B, H, W, 'rgate_bwd')
+    dx = empty_nhwc(B, C, H, W, x.device)
+    r = empty_nhwc(B, 1, H, W, x.device)
+    _chk(load().mrdis_rgate_bwd(_ptr(dy), lddy, _ptr(x), ldx, _ptr(al), _ptr(dx), C, _ptr(r), B, H, W, C, _stream()), 'rgate_bwd')
+    return dx, bilinear_bwd(r, (H // 2, W // 2), False)

@@ -712,11 +712,15 @@ class LegacyUpConcat(nn.Module):
                                 HipConv2d(in_num_ch, out_num_ch, 3, 1, padding=1))
         self.bn = BatchNorm2d(out_num_ch)
 
-    def forward(self, x_down, x_up):
+    def forward(self, x_down, x_up, buf=None):
+        """buf: the level's concatenation buffer whose first channels x_down was written into (the channel-attention decoders): BatchNorm
+        writes the rest and ops.cat_join returns the buffer, no concatenation copy.  Training mode only (BatchNorm's `into`)."""
         x_up = ops.bilinear(self.act(x_up), (2 * x_up.shape[2], 2 * x_up.shape[3]), True)
         x_up = self.up[1](x_up)
         if self.is_last:
             return x_up
+        if buf is not None:
+            return ops.cat_join(x_down, self.bn(x_up, into=(buf, x_down.shape[1])), buf)
         return torch.cat([x_down, self.bn(x_up)], 1)
 
 
@@ -738,13 +742,27 @@ class SpatialAttentionLayer(nn.Module):
         return self.W_out(alpha_up * x), alpha_up
 
 
+def _target_act(output_activation):
+    """the decoders' output activation (model.py:370-378): 'no' -> empty Sequential (BraTS / z-score data, main_missing.py:80), 'softplus' ->
+    nn.Softplus (any other data with norm_type 'mean'), applied through ops.softplus.  'sigmoid' / 'tanh' are not reachable from
+    main_missing.py and are not built."""
+    if output_activation == 'no':
+        return nn.Sequential()
+    if output_activation == 'softplus':
+        return nn.Softplus()
+    raise NotImplementedError(f"target_output_act {output_activation!r}: only 'no' and 'softplus' (main_missing.py:75-80) are built")
+
+
+def _apply_target_act(act, y):
+    return ops.softplus(y) if isinstance(act, nn.Softplus) else act(y)
+
+
 class GANShortGeneratorWithSpatialAttention(nn.Module):
-    """model.py:341-390, `output_activation='no'` (BraTS / z-score data, main_missing.py:80) -> empty Sequential."""
+    """model.py:341-390 ('U+SA'), output activation 'no' or 'softplus' (_target_act)."""
 
     def __init__(self, in_num_ch, out_num_ch, first_num_ch=64, output_activation='no'):
         super().__init__()
-        if output_activation != 'no':
-            raise NotImplementedError("only target_output_act 'no' (main_missing.py:80 for BraTS / z-score) is on the path")
+        act = _target_act(output_activation)
         c = first_num_ch
         self.down_1 = nn.Sequential(HipConv2d(in_num_ch, c, 4, 2, padding=1), nn.LeakyReLU(0.2, inplace=True))
         self.down_2 = LegacyConvBNAct(c, 2 * c)
@@ -760,7 +778,7 @@ class GANShortGeneratorWithSpatialAttention(nn.Module):
         self.att_1 = SpatialAttentionLayer(c, 4 * c, c)
         self.up_1 = LegacyUpConcat(4 * c, c)
         self.output = LegacyUpConcat(2 * c, out_num_ch, is_last=True)
-        self.output_act = nn.Sequential()
+        self.output_act = act
 
     def forward(self, x):
         d1 = self.down_1[0](x, lrelu=True)                 # conv + LeakyReLU(0.2) fused in the epilogue
@@ -769,7 +787,137 @@ class GANShortGeneratorWithSpatialAttention(nn.Module):
         c3, a3 = self.att_3(d3, u4); u3 = self.up_3(c3, u4)
         c2, a2 = self.att_2(d2, u3); u2 = self.up_2(c2, u3)
         c1, a1 = self.att_1(d1, u2); u1 = self.up_1(c1, u2)
-        return self.output_act(self.output(None, u1)), {'alpha_4': a4, 'alpha_3': a3, 'alpha_2': a2, 'alpha_1': a1}
+        return _apply_target_act(self.output_act, self.output(None, u1)), {'alpha_4': a4, 'alpha_3': a3, 'alpha_2': a2, 'alpha_1': a1}
+
+
+# =============================================================================
+# output decoders 'U', 'U+SA+CA', 'U+SSA+CA': model.py:261-299, 1002-1137, 1389-1433
+# =============================================================================
+def _down_path(c, in_num_ch):
+    """down_1 .. down_5 of every GANShortGenerator* (model.py:263-271), in the reference's order"""
+    return [('down_1', nn.Sequential(HipConv2d(in_num_ch, c, 4, 2, padding=1), nn.LeakyReLU(0.2, inplace=True))),
+            ('down_2', LegacyConvBNAct(c, 2 * c)), ('down_3', LegacyConvBNAct(2 * c, 4 * c)),
+            ('down_4', LegacyConvBNAct(4 * c, 8 * c)), ('down_5', LegacyConvBNAct(8 * c, 8 * c, activation='no'))]
+
+
+class GANShortGenerator(nn.Module):
+    """model.py:261-299 ('U'): the 'U+SA' U-Net without attention, the skip of level k is down_k itself."""
+
+    def __init__(self, in_num_ch, out_num_ch, first_num_ch=64, output_activation='softplus'):
+        super().__init__()
+        c = first_num_ch
+        for name, m in _down_path(c, in_num_ch):
+            self.add_module(name, m)
+        self.up_4 = LegacyUpConcat(8 * c, 8 * c)
+        self.up_3 = LegacyUpConcat(16 * c, 4 * c)
+        self.up_2 = LegacyUpConcat(8 * c, 2 * c)
+        self.up_1 = LegacyUpConcat(4 * c, c)
+        self.output = LegacyUpConcat(2 * c, out_num_ch, is_last=True)
+        self.output_act = _target_act(output_activation)
+
+    def forward(self, x):
+        d1 = self.down_1[0](x, lrelu=True)
+        d2 = self.down_2(d1); d3 = self.down_3(d2); d4 = self.down_4(d3); d5 = self.down_5(d4)
+        u4 = self.up_4(d4, d5); u3 = self.up_3(d3, u4); u2 = self.up_2(d2, u3); u1 = self.up_1(d1, u2)
+        return _apply_target_act(self.output_act, self.output(None, u1)), {}
+
+
+class ChannelAttentionLayer(nn.Module):
+    """model.py:1417-1433 (squeeze and excitation): a = sigmoid(W_up relu(W_down mean_hw(x))), out = (1 + a[b, c]) * x.  W_down / W_up stay
+    nn.Linear parameters (same init draws and state_dict keys); forward and backward run in csrc/mrdis_outdec.hip.
+    forward(x, s) returns out + s: the decoders only ever use the sum with the spatial branch (model.py:1058-1070), so it is one pass, written
+    into channels [0, C) of `into`'s buffer when given.  The attention vector itself (the reference's second output) is not returned."""
+
+    def __init__(self, in_num_ch, sample_factor=16):
+        super().__init__()
+        self.W_down = nn.Linear(in_num_ch, in_num_ch // sample_factor)
+        self.W_up = nn.Linear(in_num_ch // sample_factor, in_num_ch)
+
+    def forward(self, x, s, into=None):
+        return ops.channel_attention_skip(x, s, self.W_down.weight, self.W_down.bias, self.W_up.weight, self.W_up.bias, into)
+
+
+class SymmetryGateResidualSpatialAttentionLayer(nn.Module):
+    """model.py:1389-1415 (is_bn=True, the decoders' setting): gd = |g - flip_H(g)|, alpha = sigmoid(W_psi relu(W_g g + W_g_diff gd)) at the
+    gate's resolution, out = W_out((1 + up2(alpha)) * x), up2 = bilinear x2 with align_corners=False.  No W_x.  The symmetric difference and
+    the residual gate are HIP kernels (csrc/mrdis_outdec.hip); the gate-resolution 1x1 convolutions, ReLU and sigmoid are the 'U+SA' ops.
+    Returns (out, alpha) with alpha at the gate's resolution (the reference returns it upsampled; nothing reads it)."""
+
+    def __init__(self, in_num_ch, gate_num_ch, inter_num_ch, sample_factor=(2, 2)):
+        super().__init__()
+        self.W_g = HipConv2d(gate_num_ch, inter_num_ch, 1, 1)
+        self.W_g_diff = HipConv2d(gate_num_ch, inter_num_ch, 1, 1)
+        self.W_psi = HipConv2d(inter_num_ch, 1, 1, 1)
+        self.W_out = nn.Sequential(HipConv2d(in_num_ch, in_num_ch, 1, 1), BatchNorm2d(in_num_ch))
+
+    def forward(self, x, g):
+        if tuple(x.shape[2:]) != (2 * g.shape[2], 2 * g.shape[3]):
+            raise ValueError(f'the gate {tuple(g.shape)} must be at half the resolution of x {tuple(x.shape)}')
+        gd = ops.symmetric_difference(g)
+        alpha = torch.sigmoid(self.W_psi(F.relu(self.W_g(g) + self.W_g_diff(gd))))
+        return self.W_out(ops.residual_gate(x, alpha)), alpha
+
+
+class _GANShortGeneratorChannelAttention(nn.Module):
+    """the two channel-attention decoders (model.py:1002-1137): level k's skip is att_k_c(down_k) + att_k_s(down_k, gate), the gate being
+    the level's up-path input.  Modules in the reference's __init__ order (att_k_c, att_k_s, up_k per level), so seeded inits and
+    checkpoints match.  In training the skip sum is written straight into the level's concatenation buffer (ops.cat_join)."""
+
+    spatial_layer = None
+
+    def __init__(self, in_num_ch, out_num_ch, first_num_ch=64, output_activation='softplus'):
+        super().__init__()
+        c = first_num_ch
+        for name, m in _down_path(c, in_num_ch):
+            self.add_module(name, m)
+        S = self.spatial_layer
+        self.att_4_c = ChannelAttentionLayer(8 * c, 8)
+        self.att_4_s = S(8 * c, 8 * c, 8 * c)
+        self.up_4 = LegacyUpConcat(8 * c, 8 * c)
+        self.att_3_c = ChannelAttentionLayer(4 * c, 4)
+        self.att_3_s = S(4 * c, 16 * c, 4 * c)
+        self.up_3 = LegacyUpConcat(16 * c, 4 * c)
+        self.att_2_c = ChannelAttentionLayer(2 * c, 2)
+        self.att_2_s = S(2 * c, 8 * c, 2 * c)
+        self.up_2 = LegacyUpConcat(8 * c, 2 * c)
+        self.att_1_c = ChannelAttentionLayer(c, 1)
+        self.att_1_s = S(c, 4 * c, c)
+        self.up_1 = LegacyUpConcat(4 * c, c)
+        self.output = LegacyUpConcat(2 * c, out_num_ch, is_last=True)
+        self.output_act = _target_act(output_activation)
+
+    def _level(self, att_c, att_s, up, x, g):
+        s, alpha = att_s(x, g)
+        if self.training and x.is_cuda and ops.cat_elision():
+            N, C, H, W = x.shape
+            buf = ops.hip.empty_nhwc(N, C + up.up[1].out_channels, H, W, x.device, x.dtype)
+            return up(att_c(x, s, into=(buf, 0)), g, buf=buf), alpha
+        return up(att_c(x, s), g), alpha
+
+    def forward(self, x):
+        d1 = self.down_1[0](x, lrelu=True)
+        d2 = self.down_2(d1); d3 = self.down_3(d2); d4 = self.down_4(d3); d5 = self.down_5(d4)
+        u4, a4 = self._level(self.att_4_c, self.att_4_s, self.up_4, d4, d5)
+        u3, a3 = self._level(self.att_3_c, self.att_3_s, self.up_3, d3, u4)
+        u2, a2 = self._level(self.att_2_c, self.att_2_s, self.up_2, d2, u3)
+        u1, a1 = self._level(self.att_1_c, self.att_1_s, self.up_1, d1, u2)
+        return _apply_target_act(self.output_act, self.output(None, u1)), {'alpha_4': a4, 'alpha_3': a3, 'alpha_2': a2, 'alpha_1': a1}
+
+
+class GANShortGeneratorWithChannelAttentionAllAndSpatialAttention(_GANShortGeneratorChannelAttention):
+    """model.py:1070-1137 ('U+SA+CA'): the spatial branch is SpatialAttentionLayer."""
+    spatial_layer = SpatialAttentionLayer
+
+
+class GANShortGeneratorWithChannelAttentionAllAndSymmetrySpatialAttention(_GANShortGeneratorChannelAttention):
+    """model.py:1002-1068 ('U+SSA+CA'): the spatial branch is SymmetryGateResidualSpatialAttentionLayer."""
+    spatial_layer = SymmetryGateResidualSpatialAttentionLayer
+
+
+OUTPUT_DECODERS = {'U': GANShortGenerator, 'U+SA': GANShortGeneratorWithSpatialAttention,
+                   'U+SA+CA': GANShortGeneratorWithChannelAttentionAllAndSpatialAttention,
+                   'U+SSA+CA': GANShortGeneratorWithChannelAttentionAllAndSymmetrySpatialAttention}      # model.py:2955-2964
+FUSE_METHODS = {'mean': 1, 'max': 1, 'mean-max-min': 3}                                                   # fuse_num_ch, model.py:2951-2954
 
 
 class MultimodalModel(nn.Module):
@@ -835,11 +983,14 @@ class MultimodalModel(nn.Module):
         # position (after the input decoders, before the discriminator, model.py:2955-2967) so seeds give the same init
         self.fuse_method = fuse_method
         if build_output_decoder:
+            if target_model_name not in OUTPUT_DECODERS:
+                raise ValueError(f'target_model_name {target_model_name!r}: not one of {sorted(OUTPUT_DECODERS)} (model.py:2955-2965)')
+            if fuse_method not in FUSE_METHODS:
+                raise ValueError(f'fuse_method {fuse_method!r}: not one of {sorted(FUSE_METHODS)} (model.py:3244-3254)')
             if ops.storage_bf16():
-                raise NotImplementedError("compute_dtype 'bf16' (bf16 activations) covers the shipped loss set; the 'U+SA' output decoder runs in 'f32' / 'bf16m'")
-            if target_model_name != 'U+SA' or fuse_method != 'mean':
-                raise NotImplementedError("output decoder: only target_model_name 'U+SA' with fuse_method 'mean' (config.yaml:64, 66)")
-            self.output_decoder = GANShortGeneratorWithSpatialAttention(s_num_ch, out_num_ch, 64, target_output_act)
+                raise NotImplementedError(f"compute_dtype 'bf16' (bf16 activations) covers the shipped loss set; the {target_model_name!r} output "
+                                          f"decoder runs in 'f32' / 'bf16m'")
+            self.output_decoder = OUTPUT_DECODERS[target_model_name](FUSE_METHODS[fuse_method] * s_num_ch, out_num_ch, 64, target_output_act)
         if is_discrim_s:
             self.discrim_s = Discriminator(s_num_ch, 16, (H, W), is_patch_gan)                    # :2966-2967
         if is_distri_z:
@@ -1095,7 +1246,7 @@ class MultimodalModel(nn.Module):
         return out
 
     # ---- model.py:3230-3258.  QUIRK: `si_cat[mask == 1]` flattens (batch, modality) into ONE axis, so "fusion" is a
-    # mean over a singleton axis: every present (b, m) anatomy map becomes its own sample and the output has sum(mask)
+    # mean (max, or mean / max / min concatenated) over a singleton axis: every present (b, m) anatomy map becomes its own sample and the output has sum(mask)
     # rows (b-major).  Only the per-modality caller (mask = ones(B, 1)) gives B rows; main_missing.py:203 with M > 1
     # cannot run in the reference either.  The row selection uses the host mask (no device sync).
     def reconstruct_output_si_fused(self, si_list, mask, mask_host=None):
@@ -1105,6 +1256,8 @@ class MultimodalModel(nn.Module):
         flat = si_cat.reshape((-1,) + tuple(si_cat.shape[2:]))
         if len(rows) != flat.shape[0]:
             flat = flat.index_select(0, ops.to_device(torch.from_numpy(rows), flat.device))
+        if self.fuse_method == 'mean-max-min':
+            flat = torch.cat([flat, flat, flat], 1)        # mean, max and min over the singleton axis are the map itself
         return self.output_decoder(flat.contiguous(memory_format=torch.channels_last))[0]
 
     def reconstruct_output_si(self, si_list):

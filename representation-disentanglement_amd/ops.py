@@ -1495,6 +1495,74 @@ def kl_loss(mu_list, lv_list, weights, prior=None):
     pmu, plv = (None, None) if prior is None else prior
     return _KLLoss.apply(weights, pmu, plv, M, *mu_list, *lv_list)
 
+# --------------------------------------------------------------------------- the attention output decoders (csrc/mrdis_outdec.hip)
+class _ChannelAttnSkip(Function):
+    """ChannelAttentionLayer (model.py:1417-1433) and the skip sum of its decoder level: (1 + a[b, c]) * x + s, a = sigmoid(W_up relu(W_down
+    mean_hw(x))).  into = (buf, c0): the result is written into channels [c0, c0 + C) of `buf` and returned as that view (the level's
+    concatenation, completed by BatchNorm with `into` and ops.cat_join).  The gradient of s is the upstream gradient itself."""
+
+    @staticmethod
+    def forward(ctx, x, s, wd, bd, wu, bu, into=None):
+        out = None if into is None else into[0][:, into[1]:into[1] + x.shape[1]]
+        y, pool, hid, a = hip.chatt_fwd(x, s, wd, bd, wu, bu, out=out)
+        ctx.save_for_backward(x, wd, wu, pool, hid, a)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, wd, wu, pool, hid, a = ctx.saved_tensors
+        dx, dwd, dbd, dwu, dbu = hip.chatt_bwd(dy, x, a, hid, pool, wd, wu)
+        return dx, dy, dwd, dbd, dwu, dbu, None
+
+
+def channel_attention_skip(x, s, w_down, b_down, w_up, b_up, into=None):
+    """(1 + a) * x + s for the fp32 NHWC maps x, s: the channel-attention output of model.py:1431-1432 plus the spatial branch, in three launches
+    forward and three backward (csrc/mrdis_outdec.hip)"""
+    if x.dtype != torch.float32 or s.dtype != torch.float32:
+        raise NotImplementedError(f'channel attention runs on fp32 activations (got {x.dtype}, {s.dtype})')
+    return _ChannelAttnSkip.apply(x, s, w_down, b_down, w_up, b_up, into)
+
+
+class _SymDiff(Function):
+    @staticmethod
+    def forward(ctx, g):
+        ctx.save_for_backward(g)
+        return hip.symdiff_fwd(g)
+
+    @staticmethod
+    def backward(ctx, dgd):
+        (g,) = ctx.saved_tensors
+        return hip.symdiff_bwd(dgd, g)
+
+
+def symmetric_difference(g):
+    """torch.abs(g - torch.flip(g, dims=[2])) (model.py:1405-1406) in one launch each way; the gradient follows torch's abs (sgn(0) = 0)"""
+    if g.dtype != torch.float32:
+        raise NotImplementedError(f'the symmetric difference runs on fp32 activations (got {g.dtype})')
+    return _SymDiff.apply(g)
+
+
+class _ResidualGate(Function):
+    @staticmethod
+    def forward(ctx, x, alpha):
+        ctx.save_for_backward(x, alpha)
+        return hip.rgate_fwd(x, alpha)
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, alpha = ctx.saved_tensors
+        dx, dalpha = hip.rgate_bwd(dy, x, alpha)
+        return dx, dalpha
+
+
+def residual_gate(x, alpha):
+    """(1 + F.upsample(alpha, size=x.shape[2:], mode='bilinear')) * x (model.py:1409-1412) for a 1-channel alpha at half resolution: the x2
+    resize is interpolated inside the kernel; backward dx in the same pass as the per-pixel sum that feeds alpha's bilinear backward"""
+    if x.dtype != torch.float32:
+        raise NotImplementedError(f'the residual gate runs on fp32 activations (got {x.dtype})')
+    return _ResidualGate.apply(x, alpha.float())
+
+
 # --------------------------------------------------------------------------- mixed-kernel cache
 # The reference re-mixes the experts on every CondConv2d call.  Inside one training step the same
 # (layer, modality type) pair recurs (encoder passes 1 and 2, SPADEShared for every s_i), so the
