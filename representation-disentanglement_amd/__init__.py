@@ -17,7 +17,7 @@ from . import hip, ops, model, model3d, trainer               # noqa: F401
 from .hip import MrdisError, MrdisLibraryError, LIB_PATH      # noqa: F401
 from .model import (CondConv2d, Conv2d, HipConv2d, BatchNorm2d, Conv_BN_Act_New,          # noqa: F401
                     Act_Deconv_BN_Concat_New, AnatomyEncoderEncNew, AnatomyEncoderDecNew,
-                    ModalityEncoderNew, SPADEBlockNew, SPADENewShared, SPADENewNotShared,
+                    ModalityEncoderNew, SPADEBlockNew, SPADENewShared, SPADENewNotShared, SPADENew,
                     Discriminator, MultimodalModel, expand_type)
 from .trainer import (TrainStep, GraphedTrainStep, make_train_step, regular_mask, EvalStep, ZGallery, build_z_gallery, nn_source_contrast, ArenaAdam, GradAllReduce, DEFAULT_CONFIG, load_config_yaml,   # noqa: F401
                       derive_config, build_model, synthetic_batch, fit_to_model, forward_losses,

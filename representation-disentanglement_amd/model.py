@@ -629,6 +629,39 @@ class SPADENewNotShared(nn.Module):
                 and self.out.stride == (1, 1))
 
 
+class SPADENew(nn.Module):
+    """model.py:2490-2538: the fully shared input decoder (config.yaml `shared_inp_dec: True`), one module for every (s_i, z_j, type j)
+    reconstruction.  Submodules in the reference's construction order (zi_scaler, sp1 .. sp6, out, out_act; its up1 .. up5 are
+    parameter-free nn.Upsample, here _up2), so seeded inits and checkpoints match.  The first half is SPADENewShared's, the second
+    SPADENewNotShared's: the same SPADEBlockNew blocks and kernels."""
+
+    def __init__(self, image_size=(192, 160), in_num_ch=7, z_size=16, z_num_ch=128, s_num_ch=8, is_cond=False,
+                 output_activation='softplus'):
+        super().__init__()
+        self.z_num_ch, self.image_size, self.is_cond = z_num_ch, tuple(image_size), is_cond
+        H, W = image_size
+        self.zi_scaler = nn.Linear(z_size, H * W * z_num_ch // 1024)
+        self.sp1 = SPADEBlockNew((H // 32, W // 32), z_num_ch, z_num_ch, s_num_ch, is_cond)
+        self.sp2 = SPADEBlockNew((H // 16, W // 16), z_num_ch, z_num_ch, s_num_ch, is_cond)
+        self.sp3 = SPADEBlockNew((H // 8, W // 8), z_num_ch, z_num_ch, s_num_ch, is_cond)
+        self.sp4 = SPADEBlockNew((H // 4, W // 4), z_num_ch, z_num_ch // 2, s_num_ch, is_cond)
+        self.sp5 = SPADEBlockNew((H // 2, W // 2), z_num_ch // 2, z_num_ch // 4, s_num_ch, is_cond)
+        self.sp6 = SPADEBlockNew((H, W), z_num_ch // 4, z_num_ch // 8, s_num_ch, is_cond)
+        self.out = Conv2d(is_cond)(z_num_ch // 8, in_num_ch, 1, 1)
+        if output_activation == 'softplus':
+            self.out_act = nn.Softplus()
+        elif output_activation == 'no':
+            self.out_act = nn.Sequential()
+        else:
+            raise ValueError('No activation in SPADENotShared')          # (sic, model.py:2525)
+
+    head = SPADENewShared.forward          # zi_scaler, sp1 - sp3, x2 resize: the input of sp4 (same InstanceNorm2d defaults as sp3's)
+    tail = SPADENewNotShared.forward       # sp4 - sp6, out, out_act
+
+    def forward(self, si, zi, inputs_type=None):
+        return self.tail(si, self.head(si, zi, inputs_type), inputs_type)
+
+
 # =============================================================================
 # discriminator: model.py:2769-2800
 # =============================================================================
@@ -928,13 +961,15 @@ class MultimodalModel(nn.Module):
 
     latent_options = True opts in to the latent-code options of the loss block, is_distri_z (the learned modality prior) and
     s_compact_method 'mean' (build_model passes it: the config keys select them).  Without it the constructor keeps its earlier
-    contract -- those settings raise like every other graph it does not build -- so a caller that relies on that gets no new behaviour."""
+    contract -- those settings raise like every other graph it does not build -- so a caller that relies on that gets no new behaviour.
+    decoder_options = True opts in the same way to shared_inp_dec=True, the fully shared input decoder (SPADENew, model.py:3114-3121)."""
 
     def __init__(self, input_size=(160, 192), modality_num=4, in_num_ch=7, out_num_ch=1, s_num_ch=8, z_size=16,
                  is_discrim_s=False, is_distri_z=False, shared_ana_enc=False, shared_mod_enc=True, shared_inp_dec=True,
                  s_compact_method='max', s_sim_method='cosine', z_sim_method='cosine', is_cond=True,
                  input_output_act='softplus', target_output_act='softplus', target_model_name='U', fuse_method='mean',
-                 device=torch.device('cuda:0'), others=None, is_patch_gan=False, build_output_decoder=False, latent_options=False):
+                 device=torch.device('cuda:0'), others=None, is_patch_gan=False, build_output_decoder=False, latent_options=False,
+                 decoder_options=False):
         super().__init__()
         others = dict(others or {'mod_enc_s': True, 'ana_dec_act': 'softmax'})
         others.setdefault('old', False)
@@ -945,12 +980,18 @@ class MultimodalModel(nn.Module):
                                       f"{s_compact_method!r}, s_sim_method={s_sim_method!r})")
         # (z_sim_method: the reference never reads it -- its z similarity is cosine for every value; the check below stays as it was)
         latent = bool(is_distri_z) or s_compact_method == 'mean'
-        if others['old'] or shared_inp_dec or s_compact_method not in ('max', 'mean') or (latent and not latent_options) or \
+        shared_inp_dec = bool(shared_inp_dec)
+        if others['old'] or (shared_inp_dec and not decoder_options) or s_compact_method not in ('max', 'mean') or (latent and not latent_options) or \
                 s_sim_method != 'cosine' or z_sim_method != 'cosine' or others.get('ana_dec_act', 'softmax') not in ('softmax', 'softplus'):
             raise NotImplementedError('only the shipped config.yaml graph is built (SURVEY.md section 8a); '
                                       'got a variant that the hot path does not cover' +
                                       (" (is_distri_z / s_compact_method 'mean' are built with latent_options=True, as build_model passes it)"
-                                       if latent and not latent_options else ''))
+                                       if latent and not latent_options else '') +
+                                      (" (shared_inp_dec=True is built with decoder_options=True, as build_model passes it)"
+                                       if shared_inp_dec and not decoder_options else ''))
+        if shared_inp_dec and ops.storage_bf16():
+            raise NotImplementedError("compute_dtype 'bf16' (bf16 activations) covers the split input decoders only; shared_inp_dec=True "
+                                      "runs in 'f32' / 'bf16m'")
         # the `others` variants (config.yaml:67-70): the modality encoder reads the anatomy maps unless mod_enc_s is False
         # (model.py:2993, :3104: a missing key means True), and the anatomy activation is softplus, plain softmax, or the
         # softmax with the 100 * mask channel dropped (:3145-3153)
@@ -967,7 +1008,7 @@ class MultimodalModel(nn.Module):
         self.input_size, self.modality_num, self.in_num_ch = tuple(input_size), modality_num, in_num_ch
         self.device, self.others, self.is_cond = device, others, is_cond
         self.s_compact_method, self.is_distri_z = s_compact_method, bool(is_distri_z)
-        self.shared_ana_enc, self.shared_mod_enc = shared_ana_enc, shared_mod_enc
+        self.shared_ana_enc, self.shared_mod_enc, self.shared_inp_dec = shared_ana_enc, shared_mod_enc, shared_inp_dec
         n_ana = 1 if shared_ana_enc else modality_num
         self.anatomy_encoder_enc_list = nn.ModuleList(
             [AnatomyEncoderEncNew(in_num_ch, 32, is_cond) for _ in range(n_ana)])                 # :3086-3100
@@ -975,9 +1016,12 @@ class MultimodalModel(nn.Module):
         n_mod = 1 if shared_mod_enc else modality_num
         self.modality_encoder_list = nn.ModuleList(
             [ModalityEncoderNew(in_num_ch, s_num_ch if mod_enc_s else 0, 16, z_size, is_cond, (H // 32) * (W // 32)) for _ in range(n_mod)])  # :3102-3112
-        dec = [SPADENewNotShared((H, W), in_num_ch, z_size, 128, s_num_ch, is_cond, input_output_act)
-               for _ in range(modality_num)]
-        dec.append(SPADENewShared((H, W), in_num_ch, z_size, 128, s_num_ch, is_cond))            # :3129-3131
+        if shared_inp_dec:
+            dec = [SPADENew((H, W), in_num_ch, z_size, 128, s_num_ch, is_cond, input_output_act)]      # :3117-3121
+        else:
+            dec = [SPADENewNotShared((H, W), in_num_ch, z_size, 128, s_num_ch, is_cond, input_output_act)
+                   for _ in range(modality_num)]
+            dec.append(SPADENewShared((H, W), in_num_ch, z_size, 128, s_num_ch, is_cond))        # :3129-3131
         self.input_decoder_list = nn.ModuleList(dec)
         # output_decoder: only when a lambda_recon_y* weight is set (config.yaml:27-28 ships 0); built in the reference's
         # position (after the input decoders, before the discriminator, model.py:2955-2967) so seeds give the same init
@@ -1029,8 +1073,10 @@ class MultimodalModel(nn.Module):
         """[(name, [root modules])]: the CondConv2d layers under each entry are mixed by one launch right before the entry's first
         use in a step and their gradients are taken apart by one backward node per entry."""
         M = self.modality_num
-        g = [('enc', list(self.anatomy_encoder_enc_list) + [self.anatomy_encoder_dec] + list(self.modality_encoder_list)),
-             ('dec_shared', [self.input_decoder_list[-1]])]
+        g = [('enc', list(self.anatomy_encoder_enc_list) + [self.anatomy_encoder_dec] + list(self.modality_encoder_list))]
+        if self.shared_inp_dec:
+            return g + [('dec', [self.input_decoder_list[0]])]             # SPADENew: one decoder, one group
+        g.append(('dec_shared', [self.input_decoder_list[-1]]))
         g += [(f'dec{i}', [self.input_decoder_list[i]]) for i in range(M)]
         return g
 
@@ -1046,10 +1092,13 @@ class MultimodalModel(nn.Module):
         call order (each is done when its last SPADE block has back-propagated), then the shared decoder, then everything that the
         FIRST encoder pass uses (encoders, discriminator: complete only at the very end).  The optimizer lays the gradient arena out
         in this order and the data-parallel reducer cuts its buckets at the group boundaries, so a bucket can leave as soon as
-        its group's backward node has run."""
+        its group's backward node has run.  shared_inp_dec: the one decoder (SPADENew), then the rest."""
         M = self.modality_num
-        groups = [list(self.input_decoder_list[i].parameters()) for i in reversed(range(M))]
-        groups.append(list(self.input_decoder_list[-1].parameters()))
+        if self.shared_inp_dec:
+            groups = [list(self.input_decoder_list[0].parameters())]
+        else:
+            groups = [list(self.input_decoder_list[i].parameters()) for i in reversed(range(M))]
+            groups.append(list(self.input_decoder_list[-1].parameters()))
         seen = {id(p) for g in groups for p in g}
         groups.append([p for p in self.parameters() if id(p) not in seen])
         return groups
@@ -1057,7 +1106,10 @@ class MultimodalModel(nn.Module):
     def gated_parameter_groups(self):
         """group i = the parameters of input decoder i (SPADENewNotShared): they get a gradient only from batches in which
         modality i is present (every loss term through decoder i is masked by mask[:, i], model.py:3319-3341, 3388);
-        torch's Adam leaves such a parameter alone (grad None), and so does the arena step (ArenaAdam.set_gates)."""
+        torch's Adam leaves such a parameter alone (grad None), and so does the arena step (ArenaAdam.set_gates).
+        shared_inp_dec: none -- the one decoder serves every loss term, so it gets a gradient from every batch that has a term at all."""
+        if self.shared_inp_dec:
+            return []
         return [list(self.input_decoder_list[i].parameters()) for i in range(self.modality_num)]
 
     def active_decoders(self, mask_host):
@@ -1067,6 +1119,8 @@ class MultimodalModel(nn.Module):
         skipped pair a term reads the reconstruction of an EARLIER (decoder, type) pair and that decoder gets the gradient."""
         mh = _host_mask(None, mask_host)
         M = self.modality_num
+        if self.shared_inp_dec:                                             # (1,): the one decoder, active when any recon_x term is
+            return np.array([float(mh.sum() > 0)], dtype=np.float32)
         act = (mh.sum(0) > 0).astype(np.float32)                           # recon_x / latent_z terms of modality i
         pairs = [(i, j) for i in range(M) for j in range(M) if i != j]      # order of reconstruct_input_si_zj's outputs
         idx = 0
@@ -1216,10 +1270,38 @@ class MultimodalModel(nn.Module):
             return (list(si_list), list(zi_list), outs)
         return ops.step_cache(key, make)[2]
 
+    def _shared_dec_all(self, si_list, zi_list):
+        """shared_inp_dec: every (s_i, z_j, type j) reconstruction of the step through the one SPADENew (model.py:3195, :3216), or None
+        outside the grouped path.  The pairs that share the label j share every mixed filter of the decoder, and nothing couples
+        samples (InstanceNorm is per sample), so the decoder runs ONCE per label on the M batch-concatenated anatomy maps: M calls at
+        batch M B instead of M^2 at batch B, the same arithmetic per sample."""
+        if not ops.grouped_applies():
+            return None
+        key = ('shdec', id(si_list[0]), id(zi_list[0]))
+
+        def make():
+            M, B = self.modality_num, si_list[0].shape[0]
+            self.premix('dec')
+            dec = self.input_decoder_list[0]
+            s_cat = torch.cat(list(si_list), 0)
+            outs = {}
+            for j in range(M):
+                y = dec(s_cat, zi_list[j].repeat(M, 1), self._type(j, M * B))
+                for i, part in enumerate(ops.split_batch(y, M)):
+                    outs[(i, j)] = part
+            return (list(si_list), list(zi_list), outs)
+        return ops.step_cache(key, make)[2]
+
     # ---- model.py:3187-3203
     def reconstruct_input_si_zi(self, si_list, zi_list):
         out = []
         B = si_list[0].shape[0]
+        if self.shared_inp_dec:                                            # :3195
+            allo = self._shared_dec_all(si_list, zi_list)
+            if allo is not None:
+                return [allo[(i, i)] for i in range(self.modality_num)]
+            self.premix('dec')
+            return [self.input_decoder_list[0](si_list[i], zi_list[i], self._type(i, B)) for i in range(self.modality_num)]
         allo = self._notshared_all(si_list, zi_list)
         if allo is not None:
             return [allo[(i, i)] for i in range(self.modality_num)]
@@ -1233,6 +1315,13 @@ class MultimodalModel(nn.Module):
     def reconstruct_input_si_zj(self, si_list, zi_list):
         out = []
         B = si_list[0].shape[0]
+        M = self.modality_num
+        if self.shared_inp_dec:                                            # :3216
+            allo = self._shared_dec_all(si_list, zi_list)
+            if allo is not None:
+                return [allo[(i, j)] for i in range(M) for j in range(M) if i != j]
+            self.premix('dec')
+            return [self.input_decoder_list[0](si_list[i], zi_list[j], self._type(j, B)) for i in range(M) for j in range(M) if i != j]
         allo = self._notshared_all(si_list, zi_list)
         if allo is not None:
             return [allo[(i, j)] for i in range(self.modality_num) for j in range(self.modality_num) if i != j]

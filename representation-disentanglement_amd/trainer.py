@@ -77,7 +77,8 @@ def build_model(config):
         target_model_name=config['target_model_name'], fuse_method=config['fuse_method'], others=config['others'],
         is_patch_gan=config.get('is_patch_gan', False),
         build_output_decoder=config['lambda_recon_y'] > 0 or config['lambda_recon_y_fused'] > 0,
-        latent_options=True)                                  # is_distri_z / s_compact_method come from the config keys
+        latent_options=True,                                  # is_distri_z / s_compact_method come from the config keys
+        decoder_options=True)                                 # and shared_inp_dec
 
 
 # --------------------------------------------------------------------------- synthetic BraTS-shaped data
