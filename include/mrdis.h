@@ -74,8 +74,8 @@ int mrdis_version(void);
  *           instead of one (bit-identical results; A/B switch);
  *   other "debug_*": kernel-selection overrides used by tools/ (see csrc/mrdis_elem.hip OPT_DEFS);
  *   "zsearch_grid" (MRDIS_ZSEARCH_GRID, default 0): workgroups of mrdis_cosine_top1: 0 = min(gallery tiles, 1024), k > 0 = min(k, tiles, 2048) (results do not depend on it).
- * set: 0 or MRDIS_EINVAL (unknown name); get: the value, or MRDIS_EINVAL for an unknown name.  Not synchronised with launches
- * in flight on other threads. */
+ * set: 0 or MRDIS_EINVAL (unknown name); get: the value, or MRDIS_EINVAL for an unknown name.  Safe from any thread: a change
+ * applies to launches that start after the call returns (a launch already in progress on another thread may still see the old value). */
 int mrdis_set_option(const char* name, long long value);
 long long mrdis_get_option(const char* name);
 /* Launches since load / the last reset of one kernel family (counted on the host at launch): "wino" | "wino_spade" (phase-by-phase F(2x2)),

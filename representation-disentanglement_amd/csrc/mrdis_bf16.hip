@@ -268,12 +268,7 @@ __global__ __launch_bounds__(256, 2) void bconv_pack_kernel(const BConvPack pk) 
 }
 template <int KC, int WAVES_C, int WP, int WC, typename TS>
 static int launch_bconv_pack_t(const BConvLaunch (&L)[4], hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)bconv_pack_kernel<KC, WAVES_C, WP, WC, TS>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-            return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
+    if (!mrdis_lds_optin((const void*)bconv_pack_kernel<KC, WAVES_C, WP, WC, TS>, 128 * 1024)) return MRDIS_ELAUNCH;
     BConvPack pk;
     int gx = 0; size_t lds = 0;
     for (int k = 0; k < 4; ++k) { pk.c[k] = L[k].p; pk.g[k] = L[k].g; pk.grid[k] = L[k].grid; if (L[k].grid > gx) gx = L[k].grid; if (L[k].lds > lds) lds = L[k].lds; }
@@ -284,16 +279,11 @@ static int launch_bconv_pack_t(const BConvLaunch (&L)[4], hipStream_t s) {
 
 template <int KC, int WAVES_C, int WP, int WC, typename TS>
 static int launch_bconv_t(const TapConvParams& p, const BConvGeom& g, int grid, size_t lds, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)bconv_kernel<KC, WAVES_C, WP, WC, TS>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-            return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
+    if (!mrdis_lds_optin((const void*)bconv_kernel<KC, WAVES_C, WP, WC, TS>, 128 * 1024)) return MRDIS_ELAUNCH;
 #ifdef BCONV_ABLATIONS
     if (KC == 32 && WP == 2 && WC == 2) {
         const int abl = (int)mrdis_opt(MRDIS_OPT_MODE);
-#define BA(a) if (abl == a) { hipFuncSetAttribute((const void*)bconv_kernel<KC, WAVES_C, WP, WC, TS, a>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024); \
+#define BA(a) if (abl == a) { mrdis_lds_optin((const void*)bconv_kernel<KC, WAVES_C, WP, WC, TS, a>, 128 * 1024); \
         MRDIS_LAUNCH((bconv_kernel<KC, WAVES_C, WP, WC, TS, a>), dim3(grid), dim3(256), lds, s, p, g); MRDIS_CHECK_LAUNCH(); return MRDIS_OK; }
         BA(1) BA(2) BA(4) BA(8) BA(16) BA(6) BA(14) BA(15) BA(30)
 #undef BA
@@ -307,15 +297,6 @@ template <int KC, int WAVES_C, int WP, int WC>
 static int launch_bconv(const TapConvParams& p, const BConvGeom& g, int grid, size_t lds, hipStream_t s) {
     return p.dtype == MRDIS_DT_BF16 ? launch_bconv_t<KC, WAVES_C, WP, WC, __bf16>(p, g, grid, lds, s)
                                     : launch_bconv_t<KC, WAVES_C, WP, WC, float>(p, g, grid, lds, s);
-}
-
-static int bconv_ncu() {
-    static int ncu = 0;
-    if (!ncu) {
-        hipDeviceProp_t prop; int dev = 0; (void)hipGetDevice(&dev);
-        ncu = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return ncu;
 }
 
 int mrdis_run_bconv3(const TapConvParams& t, hipStream_t s);      // mrdis_bf16p.hip
@@ -355,8 +336,8 @@ int mrdis_run_bconv(TapConvParams p, int dh_max, int dw_max, hipStream_t s, BCon
             return (((long long)p.N * p.A * p.B + bm - 1) / bm) * ((p.Cout + bn - 1) / bn);
         };
         if (md != 0 && (long long)p.N * p.A * p.B <= 16384) {      // (64 -> 128 stride 2 onto 32x32 re-stages its big halo tile per cout tile: 44 -> 53 us)
-            if (c.wc == 2 && blocks(c) < 2LL * bconv_ncu()) c.wc = 1;
-            if (c.wp == 2 && blocks(c) < 2LL * bconv_ncu()) c.wp = 1;
+            if (c.wc == 2 && blocks(c) < 2LL * mrdis_cu_count()) c.wc = 1;
+            if (c.wp == 2 && blocks(c) < 2LL * mrdis_cu_count()) c.wp = 1;
         }
     }
     int BM = 32 * c.wp * (4 / c.waves_c);          // positions per workgroup
@@ -394,7 +375,7 @@ int mrdis_run_bconv(TapConvParams p, int dh_max, int dw_max, hipStream_t s, BCon
     g.tiles = (int)tiles; g.nchunks = p.Cin / KC;
     const size_t lds = lds_bytes(KC);
     int per_cu = (int)((150 * 1024) / (lds + 1024)); if (per_cu > 2) per_cu = 2; if (per_cu < 1) per_cu = 1;
-    long long per_cot = (long long)bconv_ncu() * per_cu / p.coTiles; if (per_cot < 1) per_cot = 1;
+    long long per_cot = (long long)mrdis_cu_count() * per_cu / p.coTiles; if (per_cot < 1) per_cot = 1;
     if (per_cot > tiles) per_cot = tiles;
     g.tile_stride = (int)per_cot;
     const int grid = (int)per_cot * p.coTiles;
@@ -1175,7 +1156,7 @@ static int plan_bwgrad_s2(BWgradPlanS2& pl, int N, int H, int W, int Ci, int Co,
     }
     if (tbase != TT) return MRDIS_EUNSUPPORTED;
     // the four classes together fill the chip: a quarter of the workgroups each
-    long long splits = mrdis_cdiv(bconv_ncu(), 4LL * pl.pk.c[0].nCiB * pl.pk.c[0].nCoB);
+    long long splits = mrdis_cdiv(mrdis_cu_count(), 4LL * pl.pk.c[0].nCiB * pl.pk.c[0].nCoB);
     if (splits > tiles) splits = tiles;
     if (splits < 1) splits = 1;
     for (int cls = 0; cls < 4; ++cls) pl.pk.c[cls].splits = (int)splits;
@@ -1203,8 +1184,7 @@ static int run_bwgrad_s2(const void* x, int ldx, const void* dy, int lddy, float
         p.bias_slab = (dbias && cls == 0) ? slab + pl.slab_floats : nullptr;       // every class walks all of dy: one of them sums its columns
     }
 #define BWP_CASE(a, b_, HF) if (pl.wci == a && pl.wco == b_ && (Ci == 16) == HF) { \
-        static bool attr_set = false; \
-        if (!attr_set) { if (hipFuncSetAttribute((const void*)bwgrad_pack_kernel<a, b_, HF>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) return MRDIS_ELAUNCH; attr_set = true; } \
+        if (!mrdis_lds_optin((const void*)bwgrad_pack_kernel<a, b_, HF>, 128 * 1024)) return MRDIS_ELAUNCH; \
         MRDIS_LAUNCH((bwgrad_pack_kernel<a, b_, HF>), dim3(pl.grid, 4), dim3(512), pl.lds, s, pl.pk); }
     BWP_CASE(1, 1, true) else BWP_CASE(1, 2, true) else BWP_CASE(1, 1, false) else BWP_CASE(1, 2, false) else BWP_CASE(2, 1, false) else BWP_CASE(2, 2, false)
     else return MRDIS_EUNSUPPORTED;
@@ -1253,7 +1233,7 @@ static int plan_bwgrad(BWgradPlan& pl, int N, int H, int W, int Ci, int Co, int 
     if (npix * (4 * pl.wci) > (long long)(pl.wci == 2 ? 4 : 2) * 512) return MRDIS_EUNSUPPORTED;
     pl.lds = 2 * 32 * ((size_t)pl.wco * 128 + (size_t)pl.wci * npix);
     if (pl.lds < 8 * 16 * 64 * 4) pl.lds = 8 * 16 * 64 * 4;          // the epilogue's wave-reduction buffer / bias scratch
-    long long splits = mrdis_cdiv(bconv_ncu(), (long long)p.nCiB * p.nCoB);
+    long long splits = mrdis_cdiv(mrdis_cu_count(), (long long)p.nCiB * p.nCoB);
     if (splits > tiles) splits = tiles;
     if (splits < 1) splits = 1;
     p.splits = (int)splits;
@@ -1294,8 +1274,7 @@ int mrdis_run_bwgrad(const void* x, int ldx, const void* dy, int lddy, float* dw
     p.bias_slab = dbias ? p.slab + pl.slab_floats : nullptr;
     const int grid = p.splits * p.nCiB * p.nCoB;
 #define BW_CASE_H(a, b_, TS, HF) if (pl.wci == a && pl.wco == b_) { \
-        static bool attr_set = false; \
-        if (!attr_set) { if (hipFuncSetAttribute((const void*)bwgrad_kernel<a, b_, TS, HF>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess) return MRDIS_ELAUNCH; attr_set = true; } \
+        if (!mrdis_lds_optin((const void*)bwgrad_kernel<a, b_, TS, HF>, 128 * 1024)) return MRDIS_ELAUNCH; \
         MRDIS_LAUNCH((bwgrad_kernel<a, b_, TS, HF>), dim3(grid), dim3(512), pl.lds, s, p); }
 #define BW_CASE(a, b_, TS) BW_CASE_H(a, b_, TS, false)
     bool done2 = false;
@@ -1310,16 +1289,14 @@ int mrdis_run_bwgrad(const void* x, int ldx, const void* dy, int lddy, float* dw
         const size_t lds3 = 3 * stage3 + 1024 < 32768 ? 32768 : 3 * stage3 + 1024;
         if (canon && xb < 0xffffffe0LL && yb < 0xffffffe0LL && lds3 <= 160 * 1024 && pl.wci * npix3 <= 512 && p.tiles >= 3 * p.splits && mrdis_opt(MRDIS_OPT_MODE) != 3010) {
 #define BW3_CASE(a, b_) if (pl.wci == a && pl.wco == b_) { \
-            static bool attr3 = false; \
-            if (!attr3) { if (hipFuncSetAttribute((const void*)bwgrad3_kernel<a, b_>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return MRDIS_ELAUNCH; attr3 = true; } \
+            if (!mrdis_lds_optin((const void*)bwgrad3_kernel<a, b_>, 160 * 1024)) return MRDIS_ELAUNCH; \
             MRDIS_LAUNCH((bwgrad3_kernel<a, b_>), dim3(grid), dim3(512), lds3, s, p, (unsigned)xb, (unsigned)yb); done2 = true; }
             BW3_CASE(1, 1) else BW3_CASE(1, 2) else BW3_CASE(2, 1) else BW3_CASE(2, 2)
 #undef BW3_CASE
         }
         if (!done2 && canon && xb < 0xffffffe0LL && yb < 0xffffffe0LL && lds2 <= 150 * 1024 && p.tiles >= 2 * p.splits) {
 #define BW2_CASE(a, b_) if (pl.wci == a && pl.wco == b_) { \
-            static bool attr2 = false; \
-            if (!attr2) { if (hipFuncSetAttribute((const void*)bwgrad2_kernel<a, b_>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024) != hipSuccess) return MRDIS_ELAUNCH; attr2 = true; } \
+            if (!mrdis_lds_optin((const void*)bwgrad2_kernel<a, b_>, 150 * 1024)) return MRDIS_ELAUNCH; \
             MRDIS_LAUNCH((bwgrad2_kernel<a, b_>), dim3(grid), dim3(512), lds2 < 32768 ? 32768 : lds2, s, p, (unsigned)xb, (unsigned)yb); done2 = true; }
             BW2_CASE(1, 1) else BW2_CASE(1, 2) else BW2_CASE(2, 1) else BW2_CASE(2, 2)
 #undef BW2_CASE

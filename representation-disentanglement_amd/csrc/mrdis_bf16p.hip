@@ -342,25 +342,19 @@ int mrdis_run_bconv3(const TapConvParams& t, hipStream_t s) {
     if (units > 0x7fffffffLL) return MRDIS_EUNSUPPORTED;
     p.units = (int)units; p.nchunks = t.Cin / P_KC; p.lrelu = (t.epilogue & MRDIS_EPI_LRELU) ? 1 : 0;
     p.wide = (t.Cout % 8 == 0 && t.ldout % 8 == 0 && ((uintptr_t)t.out & 15) == 0 && !mrdis_opt(MRDIS_OPT_NOPACK)) ? 1 : 0;      // (debug_nopack = 1: 8-byte stores, as before)
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MRDIS_ELAUNCH;
-        if (hipFuncSetAttribute((const void*)bconv3_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)bconv3_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return MRDIS_EUNSUPPORTED;
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    const int n_cu = mrdis_cu_count();
     const int grid = units < n_cu ? (int)units : n_cu;
     const size_t lds = 2 * (size_t)(2 * 9 * BN * P_PITCH + 2 * P_XS) + sizeof(float) * P_BIAS;
 #ifdef BCONV3_ABLATIONS
     if (WC == 2) {
         const int abl = (int)mrdis_opt(MRDIS_OPT_MODE);
-#define BA(a) if (abl == a) { (void)hipFuncSetAttribute((const void*)bconv3_kernel<2, a>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+#define BA(a) if (abl == a) { mrdis_lds_optin((const void*)bconv3_kernel<2, a>, 160 * 1024); \
         MRDIS_LAUNCH((bconv3_kernel<2, a>), dim3(grid), dim3(512), lds, s, p); MRDIS_CHECK_LAUNCH(); return MRDIS_OK; }
         BA(1) BA(2) BA(4) BA(8) BA(16) BA(6) BA(14) BA(15) BA(30)
 #undef BA
     }
 #endif
+    if (!mrdis_lds_optin(WC == 2 ? (const void*)bconv3_kernel<2> : (const void*)bconv3_kernel<1>, 160 * 1024)) return MRDIS_EUNSUPPORTED;
     mrdis_count(MRDIS_CNT_BCONV3);
     if (WC == 2) MRDIS_LAUNCH(bconv3_kernel<2>, dim3(grid), dim3(512), lds, s, p);
     else MRDIS_LAUNCH(bconv3_kernel<1>, dim3(grid), dim3(512), lds, s, p);
@@ -388,13 +382,8 @@ int mrdis_run_bconv3_spade(const void* x, int ldx, const void* w_bf16, const flo
     if (units > 0x7fffffffLL) return MRDIS_EUNSUPPORTED;
     p.units = (int)units; p.nchunks = Ci / P_KC; p.lrelu = 0;
     p.wide = (C % 8 == 0 && ldmix % 8 == 0 && ldg % 8 == 0 && ((((uintptr_t)mix) | ((uintptr_t)gamma)) & 15) == 0 && !mrdis_opt(MRDIS_OPT_NOPACK)) ? 1 : 0;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MRDIS_ELAUNCH;
-        if (hipFuncSetAttribute((const void*)bconv3_kernel<2, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return MRDIS_EUNSUPPORTED;
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    if (!mrdis_lds_optin((const void*)bconv3_kernel<2, 0, true>, 160 * 1024)) return MRDIS_EUNSUPPORTED;
+    const int n_cu = mrdis_cu_count();
     const int grid = units < n_cu ? (int)units : n_cu;
     const size_t lds = 2 * (size_t)(2 * 9 * 64 * P_PITCH + 2 * P_XS) + sizeof(float) * P_BIAS;
     mrdis_count(MRDIS_CNT_BCONV3_SPADE);

@@ -413,25 +413,6 @@ namespace {
 constexpr size_t q_lds(int WC, int NW, int KC, int RPW = 2) {
     return 2 * (size_t)(9 * 32 * WC * 2 * KC) + 2 * (size_t)((((RPW * NW + 2) * Q_INW + 1024 / (2 * KC) - 1) / (1024 / (2 * KC))) * 1024) + sizeof(float) * Q_BIAS;
 }
-int q_ncu() {
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return -1;
-        if (hipFuncSetAttribute((const void*)bconv4_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)bconv4_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)bconv4_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)bconv4_kernel<2, false, 0, 8, 32, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)bconv4_kernel<1, false, 0, 8, 32, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)bconv4_kernel<2, false, 0, 8, 32, 2, false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)bconv4_kernel<1, false, 0, 8, 32, 2, false, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)bconv4_kernel<2, false, 0, 8, 32, 2, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)bconv4_kernel<1, false, 0, 8, 32, 2, true, 8>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-            false) return -2;
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
-    return n_cu;
-}
 // The kernel is written for NW waves x KC-channel items (QGeo); only 8 x 32 is instantiated.  Measured and dropped (round 5): TWO independent 4-wave workgroups per CU
 // on 8 x 32 tiles with 16-channel items (63 KB of LDS each), so that one workgroup's epilogue / DMA wait / barrier would run under the other's MFMAs: 102 vs 84 us
 // (128 -> 256 at 64x64), 134 vs 107 us (32 -> 64 at 256x256) -- every workgroup stages its own filter image and an item is half as long (twice the barriers per MFMA);
@@ -470,8 +451,7 @@ int mrdis_run_bconv4(const TapConvParams& t, hipStream_t s) {
     p.N = t.N; p.H = t.Hin; p.W = t.Win; p.Cin = t.Cin; p.ldin = t.ldin; p.Cout = t.Cout; p.ldout = t.ldout;
     p.in_bytes = (unsigned)in_b; p.w_bytes = (unsigned)w_b;
     const int WC = t.Cout > 32 ? 2 : 1, BN = 32 * WC;
-    const int n_cu = q_ncu();
-    if (n_cu < 0) return n_cu == -1 ? MRDIS_ELAUNCH : MRDIS_EUNSUPPORTED;
+    const int n_cu = mrdis_cu_count();
     const bool two = q_two_per_cu(0);
     const int TH = two ? 8 : 16, KC = two ? 16 : 32;
     p.tilesA = mrdis_cdiv(t.Hin, TH); p.tilesB = mrdis_cdiv(t.Win, Q_TW); p.coTiles = mrdis_cdiv(t.Cout, BN);
@@ -484,19 +464,22 @@ int mrdis_run_bconv4(const TapConvParams& t, hipStream_t s) {
     p.prio = mrdis_opt(MRDIS_OPT_MODE) == 3001 ? 1 : (mrdis_opt(MRDIS_OPT_MODE) == 3002 ? 2 : 0);
     p.wide = (t.Cout % 8 == 0 && t.ldout % 8 == 0 && ((uintptr_t)t.out & 15) == 0 && !mrdis_opt(MRDIS_OPT_NOPACK)) ? 1 : 0;
     const int grid = units < slots ? (int)units : slots;
-    mrdis_count(MRDIS_CNT_BCONV4);
 #ifdef BCONV4_ABLATIONS
     p.dbg = g_q_dbg; p.dbg_cap = g_q_dbg_cap;
     if (WC == 2) {
         const int abl = (int)mrdis_opt(MRDIS_OPT_MODE);
-#define QA(a) if (abl == a) { (void)hipFuncSetAttribute((const void*)bconv4_kernel<2, false, a>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
+#define QA(a) if (abl == a) { mrdis_lds_optin((const void*)bconv4_kernel<2, false, a>, 160 * 1024); mrdis_count(MRDIS_CNT_BCONV4); \
         MRDIS_LAUNCH((bconv4_kernel<2, false, a>), dim3(grid), dim3(512), q_lds(2, 8, 32), s, p); MRDIS_CHECK_LAUNCH(); return MRDIS_OK; }
         QA(1) QA(2) QA(4) QA(8) QA(6) QA(14) QA(64) QA(78)
 #undef QA
     }
 #endif
-#define Q_GO(WC_, NW_, RPW_, FL_) do { if (mrdis_opt(MRDIS_OPT_MODE) == 3003) MRDIS_LAUNCH((bconv4_kernel<WC_, false, 0, NW_, 32, RPW_, FL_, 8>), dim3(grid), dim3(64 * NW_), q_lds(WC_, NW_, 32, RPW_), s, p); \
-    else MRDIS_LAUNCH((bconv4_kernel<WC_, false, 0, NW_, 32, RPW_, FL_>), dim3(grid), dim3(64 * NW_), q_lds(WC_, NW_, 32, RPW_), s, p); } while (0)
+#define Q_GO(WC_, NW_, RPW_, FL_) do { if (mrdis_opt(MRDIS_OPT_MODE) == 3003) { \
+        if (!mrdis_lds_optin((const void*)bconv4_kernel<WC_, false, 0, NW_, 32, RPW_, FL_, 8>, 160 * 1024)) return MRDIS_EUNSUPPORTED; \
+        mrdis_count(MRDIS_CNT_BCONV4); MRDIS_LAUNCH((bconv4_kernel<WC_, false, 0, NW_, 32, RPW_, FL_, 8>), dim3(grid), dim3(64 * NW_), q_lds(WC_, NW_, 32, RPW_), s, p); \
+    } else { \
+        if (!mrdis_lds_optin((const void*)bconv4_kernel<WC_, false, 0, NW_, 32, RPW_, FL_>, 160 * 1024)) return MRDIS_EUNSUPPORTED; \
+        mrdis_count(MRDIS_CNT_BCONV4); MRDIS_LAUNCH((bconv4_kernel<WC_, false, 0, NW_, 32, RPW_, FL_>), dim3(grid), dim3(64 * NW_), q_lds(WC_, NW_, 32, RPW_), s, p); } } while (0)
     if (WC == 2) { if (flip) Q_GO(2, 8, 2, true); else Q_GO(2, 8, 2, false); }
     else { if (flip) Q_GO(1, 8, 2, true); else Q_GO(1, 8, 2, false); }
 #undef Q_GO
@@ -518,8 +501,7 @@ int mrdis_run_bconv4_spade(const void* x, int ldx, const void* w_bf16, const flo
     p.N = N; p.H = H; p.W = W; p.Cin = Ci; p.ldin = ldx; p.Cout = 2 * C; p.ldout = ldmix;
     p.z = z; p.ldz = ldz; p.mean = mean; p.rstd = rstd; p.gamma_out = gamma; p.ldg = ldg; p.C = C;
     p.in_bytes = (unsigned)in_b; p.w_bytes = (unsigned)w_b;
-    const int n_cu = q_ncu();
-    if (n_cu < 0) return n_cu == -1 ? MRDIS_ELAUNCH : MRDIS_EUNSUPPORTED;
+    const int n_cu = mrdis_cu_count();
     const bool two = q_two_per_cu(0);
     const int TH = two ? 8 : 16, KC = two ? 16 : 32;
     p.tilesA = mrdis_cdiv(H, TH); p.tilesB = mrdis_cdiv(W, Q_TW); p.coTiles = mrdis_cdiv(C, 32);
@@ -531,6 +513,7 @@ int mrdis_run_bconv4_spade(const void* x, int ldx, const void* w_bf16, const flo
     p.prio = mrdis_opt(MRDIS_OPT_MODE) == 3001 ? 1 : (mrdis_opt(MRDIS_OPT_MODE) == 3002 ? 2 : 0);
     p.wide = (C % 8 == 0 && ldmix % 8 == 0 && ldg % 8 == 0 && ((((uintptr_t)mix) | ((uintptr_t)gamma)) & 15) == 0 && !mrdis_opt(MRDIS_OPT_NOPACK)) ? 1 : 0;
     const int grid = units < slots ? (int)units : slots;
+    if (!mrdis_lds_optin((const void*)bconv4_kernel<2, true>, 160 * 1024)) return MRDIS_EUNSUPPORTED;
     mrdis_count(MRDIS_CNT_BCONV4_SPADE);
     MRDIS_LAUNCH((bconv4_kernel<2, true>), dim3(grid), dim3(512), q_lds(2, 8, 32), s, p);
     MRDIS_CHECK_LAUNCH();

@@ -415,11 +415,7 @@ int mrdis_run_c16(const float* x, int ldx, const float* w_tck, const float* bias
     const int grid = p.ntiles < 512 ? p.ntiles : 512;
     const size_t lds = sizeof(float) * (size_t)C16_NPX * (Ci + 4);
     if (Ci == 32 && (mrdis_opt(MRDIS_OPT_SPLIT6) == 1 || mrdis_opt(MRDIS_OPT_SPLIT6) == 5)) {      // (5: this kernel only)
-        static bool attr_set = false;
-        if (!attr_set) {
-            if (hipFuncSetAttribute((const void*)conv3x3_c16_split6_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess) return MRDIS_ELAUNCH;
-            attr_set = true;
-        }
+        if (!mrdis_lds_optin((const void*)conv3x3_c16_split6_kernel, 72 * 1024)) return MRDIS_ELAUNCH;
         mrdis_count(MRDIS_CNT_SPLIT6_C16);
         MRDIS_LAUNCH(conv3x3_c16_split6_kernel, dim3(grid), dim3(256), (size_t)C16_NPX * 208, s, p);
     } else

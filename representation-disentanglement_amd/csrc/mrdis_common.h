@@ -43,6 +43,13 @@ void mrdis_count(int id);
 void mrdis_note_lds(const char* kernel_expr, size_t bytes);
 #define MRDIS_LAUNCH(kernel, grid, block, lds, s, ...) do { mrdis_count(MRDIS_CNT_ALL); if ((size_t)(lds) != 0) mrdis_note_lds(#kernel, (size_t)(lds)); hipLaunchKernelGGL(kernel, grid, block, lds, s, __VA_ARGS__); } while (0)
 
+// Host setup before a launch (mrdis_elem.hip), cached per kernel ADDRESS (every template instantiation is its own entry) and safe from any
+// thread; the hit path is pointer compares, no lock, no runtime call.  A failed opt-in or query is not cached: the next call asks again.
+int mrdis_cu_count();                                            // CUs of the device (256 if the runtime cannot say); queried once
+bool mrdis_lds_optin(const void* kernel, int bytes);             // the kernel may launch with up to `bytes` of dynamic LDS; false: the runtime refused
+int mrdis_occupancy(const void* kernel, int block, size_t lds);  // workgroups per CU at (block, lds), 0 if the runtime gives no answer;
+                                                                 // lds above 64 KB needs the kernel's opt-in first
+
 static inline int mrdis_cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 // Bijective XCD-aware remap (cdna_hip_programming.md T1): workgroups b and b+8 share an XCD, so

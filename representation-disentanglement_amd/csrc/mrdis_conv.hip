@@ -1310,17 +1310,9 @@ static int run_c4conv(const float* x, int ldx, const float* w, const float* bias
     // three waves per SIMD, so only three of the four are resident at a time -- sizing the grid by their own occupancy (768 workgroups) was slower: 59.6 vs
     // 53.6 us at 256x256, 52.7 vs 51.8 us at 240x240 (the fourth workgroup of a CU starts as the first drains and evens out the tail).  Option c4_grid = k
     // overrides the number per CU.
-    static int occ[3] = {0, 0, 0}, ncu = 0;
-    const int oi = NS;
-    if (!occ[oi]) {
-        int o = 0;
-        if (NS == 2) (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, c4conv_kernel<2, false, true>, 256, 0);
-        else (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&o, c4conv_kernel<1, false, true>, 256, 0);
-        occ[oi] = o > 0 ? o : 2;
-        hipDeviceProp_t prop; int dev = 0; (void)hipGetDevice(&dev);
-        ncu = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    const long long per_cu = mrdis_opt(MRDIS_OPT_C4_GRID) > 0 ? mrdis_opt(MRDIS_OPT_C4_GRID) : occ[oi];
+    const int o = mrdis_occupancy(NS == 2 ? (const void*)c4conv_kernel<2, false, true> : (const void*)c4conv_kernel<1, false, true>, 256, 0);
+    const int ncu = mrdis_cu_count();
+    const long long per_cu = mrdis_opt(MRDIS_OPT_C4_GRID) > 0 ? mrdis_opt(MRDIS_OPT_C4_GRID) : (o > 0 ? o : 2);
     long long cap = (long long)ncu * per_cu / ny; if (cap < ncu) cap = ncu;
     if (blocks > cap) blocks = cap;
     mrdis_opt_note(MRDIS_OPT_C4_BLOCKS, blocks);
@@ -2674,12 +2666,7 @@ extern "C" size_t mrdis_conv2d_bwd_weight_workspace(int N, int H, int W, int Ci,
 template <int J>
 static int launch_wgrad_t(const WgradPlan& pl, hipStream_t s) {
     if (pl.dma) {
-        static bool attr_set = false;
-        if (!attr_set) {      // > 64 KB of dynamic LDS needs the opt-in once per instantiation
-            if (hipFuncSetAttribute((const void*)wgrad_dma_kernel<J>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-                return MRDIS_ELAUNCH;
-            attr_set = true;
-        }
+        if (!mrdis_lds_optin((const void*)wgrad_dma_kernel<J>, 96 * 1024)) return MRDIS_ELAUNCH;
         const bool x_ok = (pl.p.ldx % 4 == 0) && (((uintptr_t)pl.p.x & 15) == 0);
         const bool dy_ok = (pl.p.lddy % 4 == 0) && (((uintptr_t)pl.p.dy & 15) == 0);
         if (x_ok && dy_ok) {
@@ -2760,12 +2747,9 @@ extern "C" int mrdis_conv2d_bwd_weight(const void* x_, int ldx, const void* dy_,
     p.vec_dy = (Co % 4 == 0) && (lddy % 4 == 0) && (((uintptr_t)dy & 15) == 0);
     const bool x_al = (ldx % 4 == 0) && (((uintptr_t)x & 15) == 0), dy_al = (lddy % 4 == 0) && (((uintptr_t)dy & 15) == 0);
     if (pl.thin && pl.thin_dma && x_al && dy_al) {
-        static bool attr_set = false;
-        if (!attr_set) {      // > 64 KB of dynamic LDS needs the opt-in
-            if (hipFuncSetAttribute((const void*)wgrad_thin_dma_kernel<9, 4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
-                return MRDIS_ELAUNCH;
-            attr_set = true;
-        }
+        const void* k = pl.thin == 1 ? (const void*)wgrad_thin_dma_kernel<9, 4, false> : pl.thin_nt == 4 ? (const void*)wgrad_thin_dma_kernel<4, 4, true>
+                                                                                           : (const void*)wgrad_thin_dma_kernel<9, 4, true>;
+        if (!mrdis_lds_optin(k, 96 * 1024)) return MRDIS_ELAUNCH;
         if (pl.thin == 1) MRDIS_LAUNCH((wgrad_thin_dma_kernel<9, 4, false>), dim3(p.splits * p.base), dim3(256), pl.lds_dma, s, p, pl.J, pl.XR);
         else if (pl.thin_nt == 4) MRDIS_LAUNCH((wgrad_thin_dma_kernel<4, 4, true>), dim3(p.splits * p.base), dim3(256), pl.lds_dma, s, p, pl.J, pl.XR);
         else MRDIS_LAUNCH((wgrad_thin_dma_kernel<9, 4, true>), dim3(p.splits * p.base), dim3(256), pl.lds_dma, s, p, pl.J, pl.XR);

@@ -295,12 +295,7 @@ static size_t tapconv3d_lds(const Conv3dParams& p, int KC, int BN) {
 
 template <int KC, int BN>
 static int launch_tapconv3d_t(const Conv3dParams& p, size_t lds, int nblk, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {      // > 64 KB of dynamic LDS needs the opt-in
-        if (hipFuncSetAttribute((const void*)tapconv3d_kernel<KC, BN>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)
-            return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
+    if (!mrdis_lds_optin((const void*)tapconv3d_kernel<KC, BN>, 80 * 1024)) return MRDIS_ELAUNCH;
     mrdis_count(MRDIS_CNT_DIRECT3D);
     MRDIS_LAUNCH((tapconv3d_kernel<KC, BN>), dim3(nblk), dim3(256), lds, s, p);
     MRDIS_CHECK_LAUNCH();
@@ -455,12 +450,7 @@ __global__ __launch_bounds__(256) void conv3d16_kernel(const Conv3dParams p, int
 
 template <int KC>
 static int launch_conv3d16_t(const Conv3dParams& p, size_t lds, int nblk, int nboxes, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)conv3d16_kernel<KC>, hipFuncAttributeMaxDynamicSharedMemorySize, 128 * 1024) != hipSuccess)
-            return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
+    if (!mrdis_lds_optin((const void*)conv3d16_kernel<KC>, 128 * 1024)) return MRDIS_ELAUNCH;
     mrdis_count(MRDIS_CNT_C3D16);
     MRDIS_LAUNCH((conv3d16_kernel<KC>), dim3(nblk), dim3(256), lds, s, p, nboxes);
     MRDIS_CHECK_LAUNCH();
@@ -1239,12 +1229,7 @@ extern "C" size_t mrdis_conv3d_bwd_weight_workspace(int N, int D, int H, int W, 
 
 template <int J>
 static int launch_wgrad3d_t(const Wgrad3dPlan& pl, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)wgrad3d_kernel<J>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)
-            return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
+    if (!mrdis_lds_optin((const void*)wgrad3d_kernel<J>, 80 * 1024)) return MRDIS_ELAUNCH;
     mrdis_count(MRDIS_CNT_WGRAD3D);
     MRDIS_LAUNCH((wgrad3d_kernel<J>), dim3(pl.p.splits * pl.p.base), dim3(256), pl.lds, s, pl.p);
     MRDIS_CHECK_LAUNCH();

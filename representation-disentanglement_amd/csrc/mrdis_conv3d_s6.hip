@@ -210,12 +210,8 @@ int mrdis_run_conv3d16_s6(const Conv3dParams& p_in, long long ptiles_hint, hipSt
     const long long nboxes = (long long)p.N * p.tilesZ * p.tilesA * p.tilesB;
     // small volumes: the generic kernels' 128-position boxes waste fewer positions and fill the chip better
     if (nboxes > 0x7fffffffLL || nboxes < 512 || (long long)p.Z * p.A * p.B < 32768) return MRDIS_EUNSUPPORTED;
-    static int ncu = 0;
-    if (!ncu) {
-        if (hipFuncSetAttribute((const void*)conv3d16_s6_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)S6_LDS) != hipSuccess) return MRDIS_ELAUNCH;
-        hipDeviceProp_t prop; int dev = 0; (void)hipGetDevice(&dev);
-        ncu = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
+    if (!mrdis_lds_optin((const void*)conv3d16_s6_kernel, (int)S6_LDS)) return MRDIS_ELAUNCH;
+    const int ncu = mrdis_cu_count();
     const int nblk = nboxes < ncu ? (int)nboxes : ncu;          // one workgroup per CU (145 KB of LDS)
     mrdis_count(MRDIS_CNT_SPLIT6_C3D);
     MRDIS_LAUNCH(conv3d16_s6_kernel, dim3(nblk), dim3(256), S6_LDS, s, p, (int)nboxes);
@@ -423,12 +419,8 @@ int mrdis_run_wgrad3d16_s6(const float* x, int ldx, const float* dy, int lddy, f
     const long long nt = (long long)N * p.tilesZ * p.tilesA * p.tilesB;
     if (nt > 0x7fffffffLL || nt < 512 || (long long)D * H * W < 32768 || (long long)D * H * W >= 0x7fffffffLL) return MRDIS_EUNSUPPORTED;
     p.numTiles = (int)nt;
-    static int ncu = 0;
-    if (!ncu) {
-        if (hipFuncSetAttribute((const void*)wgrad3d16_s6_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W6D_LDS) != hipSuccess) return MRDIS_ELAUNCH;
-        hipDeviceProp_t prop; int dev = 0; (void)hipGetDevice(&dev);
-        ncu = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
+    if (!mrdis_lds_optin((const void*)wgrad3d16_s6_kernel, (int)W6D_LDS)) return MRDIS_ELAUNCH;
+    const int ncu = mrdis_cu_count();
     const int pairs = p.nCi * p.nCo;
     int splits = ncu / pairs; if (splits < 1) splits = 1;         // one workgroup per CU (155 KB of LDS): splits x slice pairs fill the chip once
     if (splits > p.numTiles) splits = p.numTiles;

@@ -1968,17 +1968,18 @@ int opt_index(const char* name) {
     return -1;
 }
 }  // namespace
-long long mrdis_opt(int id) { return opt_table()[id]; }
-void mrdis_opt_note(int id, long long value) { opt_table()[id] = value; }
+// relaxed atomics: launchers on any thread read the table while mrdis_set_option / mrdis_opt_note write it
+long long mrdis_opt(int id) { return __atomic_load_n(&opt_table()[id], __ATOMIC_RELAXED); }
+void mrdis_opt_note(int id, long long value) { __atomic_store_n(&opt_table()[id], value, __ATOMIC_RELAXED); }
 extern "C" int mrdis_set_option(const char* name, long long value) {
     const int i = opt_index(name);
     if (i < 0) return MRDIS_EINVAL;
-    opt_table()[i] = value;
+    mrdis_opt_note(i, value);
     return MRDIS_OK;
 }
 extern "C" long long mrdis_get_option(const char* name) {
     const int i = opt_index(name);
-    return i < 0 ? (long long)MRDIS_EINVAL : opt_table()[i];
+    return i < 0 ? (long long)MRDIS_EINVAL : mrdis_opt(i);
 }
 
 namespace {
@@ -2026,6 +2027,69 @@ extern "C" int mrdis_dynamic_lds_table(char* buf, int cap) {
         pos += n; ++written;
     }
     return written;
+}
+
+// ---------------------------------------------------------------------------------------------- launch setup (mrdis_common.h)
+int mrdis_cu_count() {
+    static const int ncu = [] {
+        int dev = 0, n = 0;
+        (void)hipGetDevice(&dev);
+        return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
+    }();
+    return ncu;
+}
+
+namespace {
+// Open-addressed tables keyed by kernel address.  Slots are only ever filled, under g_setup_mu, and a slot's key is stored last (release), so a
+// reader that sees the key also sees the rest; an opt-in size only grows and is read atomically.
+constexpr unsigned SETUP_SLOTS = 512;         // power of two, well above the kernels the library can launch
+struct OptinSlot { const void* fn; int bytes; };
+struct OccSlot { const void* fn; int block; size_t lds; int n; };
+OptinSlot g_optin[SETUP_SLOTS];
+OccSlot g_occ[SETUP_SLOTS];
+std::mutex g_setup_mu;
+unsigned setup_hash(const void* fn) { return (unsigned)(((uintptr_t)fn * 0x9E3779B97F4A7C15ull) >> 40); }
+}  // namespace
+
+bool mrdis_lds_optin(const void* kernel, int bytes) {
+    const unsigned h = setup_hash(kernel);
+    for (unsigned i = 0; i < SETUP_SLOTS; ++i) {
+        OptinSlot& e = g_optin[(h + i) % SETUP_SLOTS];
+        const void* fn = __atomic_load_n(&e.fn, __ATOMIC_ACQUIRE);
+        if (fn == kernel && __atomic_load_n(&e.bytes, __ATOMIC_RELAXED) >= bytes) return true;
+        if (!fn || fn == kernel) break;
+    }
+    std::lock_guard<std::mutex> lk(g_setup_mu);
+    OptinSlot* slot = nullptr;             // this kernel's slot or the first free one; none when the table is full (then nothing is cached)
+    for (unsigned i = 0; i < SETUP_SLOTS && !slot; ++i) {
+        OptinSlot& e = g_optin[(h + i) % SETUP_SLOTS];
+        if (!e.fn || e.fn == kernel) slot = &e;
+    }
+    if (slot && slot->fn == kernel && slot->bytes >= bytes) return true;       // another thread opted it in meanwhile
+    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
+    if (slot) { __atomic_store_n(&slot->bytes, bytes, __ATOMIC_RELAXED); __atomic_store_n(&slot->fn, kernel, __ATOMIC_RELEASE); }
+    return true;
+}
+
+int mrdis_occupancy(const void* kernel, int block, size_t lds) {
+    const unsigned h = setup_hash(kernel);
+    for (unsigned i = 0; i < SETUP_SLOTS; ++i) {
+        const OccSlot& e = g_occ[(h + i) % SETUP_SLOTS];
+        const void* fn = __atomic_load_n(&e.fn, __ATOMIC_ACQUIRE);
+        if (!fn) break;
+        if (fn == kernel && e.block == block && e.lds == lds) return e.n;
+    }
+    std::lock_guard<std::mutex> lk(g_setup_mu);
+    OccSlot* slot = nullptr;
+    for (unsigned i = 0; i < SETUP_SLOTS && !slot; ++i) {
+        OccSlot& e = g_occ[(h + i) % SETUP_SLOTS];
+        if (!e.fn || (e.fn == kernel && e.block == block && e.lds == lds)) slot = &e;
+    }
+    if (slot && slot->fn) return slot->n;
+    int n = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, lds) != hipSuccess || n < 1) return 0;
+    if (slot) { slot->block = block; slot->lds = lds; slot->n = n; __atomic_store_n(&slot->fn, kernel, __ATOMIC_RELEASE); }
+    return n;
 }
 
 extern "C" const char* mrdis_strerror(int code) {

@@ -311,11 +311,7 @@ __global__ __launch_bounds__(256) void s6conv_pack_kernel(const S6ConvPack pk) {
 
 template <int KC, int WP, int WC, int XR, int WR>
 int launch_s6conv_t(const TapConvParams& p, const S6ConvGeom& g, int grid, size_t lds, hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)s6conv_kernel<KC, WP, WC, XR, WR>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess) return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
+    if (!mrdis_lds_optin((const void*)s6conv_kernel<KC, WP, WC, XR, WR>, 159 * 1024)) return MRDIS_ELAUNCH;
     MRDIS_LAUNCH((s6conv_kernel<KC, WP, WC, XR, WR>), dim3(grid), dim3(256), lds, s, p, g);
     MRDIS_CHECK_LAUNCH();
     mrdis_count(MRDIS_CNT_SPLIT6_TAP);
@@ -323,11 +319,7 @@ int launch_s6conv_t(const TapConvParams& p, const S6ConvGeom& g, int grid, size_
 }
 template <int KC, int WP, int WC, int XR, int WR>
 int launch_s6conv_pack_t(const S6ConvLaunch (&L)[4], hipStream_t s) {
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)s6conv_pack_kernel<KC, WP, WC, XR, WR>, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess) return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
+    if (!mrdis_lds_optin((const void*)s6conv_pack_kernel<KC, WP, WC, XR, WR>, 159 * 1024)) return MRDIS_ELAUNCH;
     S6ConvPack pk;
     int gx = 0; size_t lds = 0;
     for (int k = 0; k < 4; ++k) { pk.c[k] = L[k].p; pk.g[k] = L[k].g; pk.grid[k] = L[k].grid; if (L[k].grid > gx) gx = L[k].grid; if (L[k].lds > lds) lds = L[k].lds; }
@@ -335,27 +327,6 @@ int launch_s6conv_pack_t(const S6ConvLaunch (&L)[4], hipStream_t s) {
     MRDIS_CHECK_LAUNCH();
     mrdis_count(MRDIS_CNT_SPLIT6_TAP);
     return MRDIS_OK;
-}
-
-int s6t_ncu() {
-    static int ncu = 0;
-    if (!ncu) {
-        hipDeviceProp_t prop; int dev = 0; (void)hipGetDevice(&dev);
-        ncu = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return ncu;
-}
-
-// workgroups of one instantiation a CU holds at a given dynamic LDS size (the runtime's answer: registers AND LDS), cached per (instantiation, form, size)
-template <typename K>
-int s6t_occ_of(K kernel, size_t lds) {
-    static size_t seen_lds[4]; static int seen_n[4]; static int nseen = 0;
-    for (int i = 0; i < nseen; ++i) if (seen_lds[i] == lds) return seen_n[i];
-    int n = 0;
-    if (hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 159 * 1024) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, 256, lds) != hipSuccess || n < 1) n = 1;
-    seen_lds[nseen & 3] = lds; seen_n[nseen & 3] = n; if (nseen < 4) ++nseen;
-    return n;
 }
 
 // w [tap][reduction channel][output channel] fp32 -> the image above; one thread per row (q, g, tap, e)
@@ -413,7 +384,6 @@ int mrdis_run_s6conv(TapConvParams p, const void* image, int taps_img, int dh_ma
     if (mrdis_s6_filter_image_bytes(taps_img, p.Cin, p.Cout) >= 0x7fffffffULL) return MRDIS_EUNSUPPORTED;
     for (int t = 0; t < p.ntaps; ++t) if (p.widx[t] < 0 || p.widx[t] >= taps_img) return MRDIS_EINVAL;
     p.w_bf16 = image;
-    const int ncu = s6t_ncu();
     struct Cfg { int kc, wp, wc, xr, wr; };
     static const Cfg menu[] = {
 #define S6T_MENU(KC_, A_, B_, XR_, WR_) {KC_, A_, B_, XR_, WR_},
@@ -469,12 +439,14 @@ int mrdis_run_s6conv(TapConvParams p, const void* image, int taps_img, int dh_ma
     g.stamps = reinterpret_cast<unsigned long long*>((uintptr_t)(mrdis_opt(MRDIS_OPT_BM) > 0 ? mrdis_opt(MRDIS_OPT_BM) : 0));      // stamp buffer (device pointer) and stamps per wave, via options debug_bm / debug_bn
     g.cap_stamps = (int)mrdis_opt(MRDIS_OPT_BN);
 #endif
-    int per_cu = 1;                                // persistent grid: what the CUs hold at once of THIS instantiation (its registers and its LDS)
-#define S6T_OCC(KC_, A_, B_, XR_, WR_) if (c.kc == KC_ && c.wp == A_ && c.wc == B_ && c.xr == XR_ && c.wr == WR_) \
-        per_cu = defer ? s6t_occ_of(s6conv_pack_kernel<KC_, A_, B_, XR_, WR_>, lds) : s6t_occ_of(s6conv_kernel<KC_, A_, B_, XR_, WR_>, lds);
-    S6T_CASES(S6T_OCC)
-#undef S6T_OCC
-    long long per_cot = (long long)ncu * per_cu / p.coTiles;
+    const void* k = nullptr;                       // persistent grid: what the CUs hold at once of THIS instantiation (its registers and its LDS)
+#define S6T_K(KC_, A_, B_, XR_, WR_) if (c.kc == KC_ && c.wp == A_ && c.wc == B_ && c.xr == XR_ && c.wr == WR_) \
+        k = defer ? (const void*)s6conv_pack_kernel<KC_, A_, B_, XR_, WR_> : (const void*)s6conv_kernel<KC_, A_, B_, XR_, WR_>;
+    S6T_CASES(S6T_K)
+#undef S6T_K
+    int per_cu = mrdis_lds_optin(k, 159 * 1024) ? mrdis_occupancy(k, 256, lds) : 0;
+    if (per_cu < 1) per_cu = 1;
+    long long per_cot = (long long)mrdis_cu_count() * per_cu / p.coTiles;
     if (defer) per_cot /= 4;                       // the four parity classes of a stride-2 data gradient share one launch
     { const long long v = mrdis_opt(MRDIS_OPT_WGSPLIT); if (v > 0) per_cot = v; }      // debug_wgsplit: workgroups per cout tile
     if (per_cot < 1) per_cot = 1;

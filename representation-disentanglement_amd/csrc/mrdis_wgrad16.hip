@@ -524,11 +524,7 @@ int mrdis_run_wgrad16(const float* x, int ldx, const float* dy, int lddy, float*
             q.numTiles = (int)nt6; q.splits = p.splits < q.numTiles ? p.splits : q.numTiles;      // (the slabs of plan_wgrad16: [splits][2][9][256] + [splits][16])
             q.x_bytes = (unsigned)xb; q.dy_bytes = (unsigned)yb;
             const size_t lds6 = 3 * (size_t)(W6_TH * W6_TW * 64) + 3 * (size_t)(W6_YPX * 32);
-            static bool attr_set = false;
-            if (!attr_set) {
-                if (hipFuncSetAttribute((const void*)wgrad16_split6_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) return MRDIS_ELAUNCH;
-                attr_set = true;
-            }
+            if (!mrdis_lds_optin((const void*)wgrad16_split6_kernel, 96 * 1024)) return MRDIS_ELAUNCH;
             mrdis_count(MRDIS_CNT_SPLIT6_WGRAD16);
             MRDIS_LAUNCH(wgrad16_split6_kernel, dim3(q.splits), dim3(256), lds6, s, q);
             MRDIS_CHECK_LAUNCH();

@@ -978,21 +978,13 @@ int mrdis_run_wgrad_c4(const float* x, int ldx, const void* dy, int lddy, float*
     size_t lds = sizeof(float) * ((size_t)4 * p.rowp + (size_t)W * (Co + 16));
     if (lds < red) lds = red;
     if (lds > 72 * 1024) return MRDIS_EUNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {          // > 64 KB of dynamic LDS needs the opt-in (4 -> 32 at W = 256: 65.7 KB)
-        if (hipFuncSetAttribute((const void*)wgrad_c4_kernel<2, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wgrad_c4_kernel<4, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wgrad_c4_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wgrad_c4_kernel<2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wgrad_c4_kernel<4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wgrad_c4_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess)
-            return MRDIS_EUNSUPPORTED;
-        attr_set = true;
-    }
-#define WC4_LAUNCH(nt) { if (dy_bf16) MRDIS_LAUNCH((wgrad_c4_kernel<nt, true>), dim3(p.splits), dim3(256), lds, s, p); \
-                         else MRDIS_LAUNCH((wgrad_c4_kernel<nt, false>), dim3(p.splits), dim3(256), lds, s, p); }
+    // > 64 KB of dynamic LDS needs the opt-in (4 -> 32 at W = 256: 65.7 KB)
+#define WC4_GO(nt, bf) { if (!mrdis_lds_optin((const void*)wgrad_c4_kernel<nt, bf>, 72 * 1024)) return MRDIS_EUNSUPPORTED; \
+                         MRDIS_LAUNCH((wgrad_c4_kernel<nt, bf>), dim3(p.splits), dim3(256), lds, s, p); }
+#define WC4_LAUNCH(nt) { if (dy_bf16) WC4_GO(nt, true) else WC4_GO(nt, false) }
     if (NT == 2) WC4_LAUNCH(2) else if (NT == 4) WC4_LAUNCH(4) else WC4_LAUNCH(8)
 #undef WC4_LAUNCH
+#undef WC4_GO
     MRDIS_CHECK_LAUNCH();
     return mrdis_launch_slab_reduce(p.slab, dw_tck, 36 * Co, Co, p.splits, p.bias_slab, dbias, accumulate_bias, s);
 }
@@ -1059,20 +1051,14 @@ int mrdis_run_dgrad_s2(const float* dy, int lddy, const float* w_tkc, float* dx,
     p.R = mrdis_cdiv(p.Hout, segs); p.segs = mrdis_cdiv(p.Hout, p.R);
     const size_t lds = sizeof(float) * (size_t)(p.Wout + 2) * p.MP;
     if (lds > 72 * 1024) return MRDIS_EUNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)dgrad_s2_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)dgrad_s2_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)dgrad_s2_kernel<3, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)dgrad_s2_kernel<3, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 72 * 1024) != hipSuccess)
-            return MRDIS_EUNSUPPORTED;
-        attr_set = true;
-    }
     const dim3 grid(N * p.segs), block(256);
-    if (kh == 4 && Co == 32) MRDIS_LAUNCH((dgrad_s2_kernel<4, 2>), grid, block, lds, s, p);
-    else if (kh == 4) MRDIS_LAUNCH((dgrad_s2_kernel<4, 1>), grid, block, lds, s, p);
-    else if (Co == 32) MRDIS_LAUNCH((dgrad_s2_kernel<3, 2>), grid, block, lds, s, p);
-    else MRDIS_LAUNCH((dgrad_s2_kernel<3, 1>), grid, block, lds, s, p);
+#define DG_LAUNCH(k, c) { if (!mrdis_lds_optin((const void*)dgrad_s2_kernel<k, c>, 72 * 1024)) return MRDIS_EUNSUPPORTED; \
+                          MRDIS_LAUNCH((dgrad_s2_kernel<k, c>), grid, block, lds, s, p); }
+    if (kh == 4 && Co == 32) DG_LAUNCH(4, 2)
+    else if (kh == 4) DG_LAUNCH(4, 1)
+    else if (Co == 32) DG_LAUNCH(3, 2)
+    else DG_LAUNCH(3, 1)
+#undef DG_LAUNCH
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }

@@ -303,14 +303,9 @@ int mrdis_run_wino(const float* x, int ldx, const float* w, const float* bias, f
     p.coTiles = mrdis_cdiv(Co, 32 * CG);
     const long long nblk = (long long)N * p.nby * p.nbx * p.coTiles;
     if (nblk > 0x7fffffffLL) return MRDIS_EUNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)wino_conv_kernel<1, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wino_conv_kernel<2, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024) != hipSuccess)
-            return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
     const size_t lds = CG == 2 ? wino_lds<2, 4>(p.TBH, p.TBW) : wino_lds<1, 4>(p.TBH, p.TBW);
+    if (!mrdis_lds_optin(CG == 2 ? (const void*)wino_conv_kernel<2, 4> : (const void*)wino_conv_kernel<1, 4>, CG == 2 ? 100 * 1024 : 80 * 1024))
+        return MRDIS_ELAUNCH;
     mrdis_count(MRDIS_CNT_WINO);
     if (CG == 2) MRDIS_LAUNCH((wino_conv_kernel<2, 4>), dim3((int)nblk), dim3(512), lds, s, p);
     else MRDIS_LAUNCH((wino_conv_kernel<1, 4>), dim3((int)nblk), dim3(256), lds, s, p);
@@ -334,14 +329,9 @@ int mrdis_run_wino3d(const float* x, int ldx, const float* w, const float* bias,
     p.coTiles = mrdis_cdiv(Co, 32 * CG);
     const long long nblk = (long long)p.N * p.nby * p.nbx * p.coTiles;
     if (nblk > 0x7fffffffLL) return MRDIS_EUNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)wino_conv_kernel<1, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wino_conv_kernel<2, 4, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024) != hipSuccess)
-            return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
     const size_t lds = CG == 2 ? wino_lds<2, 4>(p.TBH, p.TBW) : wino_lds<1, 4>(p.TBH, p.TBW);
+    if (!mrdis_lds_optin(CG == 2 ? (const void*)wino_conv_kernel<2, 4, true> : (const void*)wino_conv_kernel<1, 4, true>, CG == 2 ? 100 * 1024 : 80 * 1024))
+        return MRDIS_ELAUNCH;
     mrdis_count(MRDIS_CNT_WINO_SPADE);
     if (CG == 2) MRDIS_LAUNCH((wino_conv_kernel<2, 4, true>), dim3((int)nblk), dim3(512), lds, s, p);
     else MRDIS_LAUNCH((wino_conv_kernel<1, 4, true>), dim3((int)nblk), dim3(256), lds, s, p);
@@ -637,14 +627,6 @@ int mrdis_run_wino_wgrad(const float* x, int ldx, const float* dy, int lddy, flo
     p.x = x; p.dy = dy; p.ldx = ldx; p.lddy = lddy;
     p.slab = reinterpret_cast<float*>(workspace);
     p.bias_slab = dbias ? p.slab + (size_t)p.splits * 9 * Ci * Co : nullptr;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)wino_wgrad_kernel<4, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wino_wgrad_kernel<4, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wino_wgrad_kernel<2, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)
-            return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
     int rc2 = MRDIS_EUNSUPPORTED;
     {   // Winograd F(3x3, 4x4) (mrdis_wino4w.hip): 1.78x fewer MFMAs; writes its own number of slabs (<= the plan's) and sets p.splits to it
         const int rc4 = mrdis_launch_wino4_wgrad(p, p.splits, s);
@@ -656,10 +638,13 @@ int mrdis_run_wino_wgrad(const float* x, int ldx, const float* dy, int lddy, flo
         rc2 = mrdis_launch_wino_wgrad2(p, s);
         if (rc2 != MRDIS_OK && rc2 != MRDIS_EUNSUPPORTED) return rc2;
     }
+#define WW_LAUNCH(a, b_, nt, kb) { if (!mrdis_lds_optin((const void*)wino_wgrad_kernel<a, b_>, kb * 1024)) return MRDIS_ELAUNCH; \
+                                   mrdis_count(MRDIS_CNT_WINO_WGRAD); MRDIS_LAUNCH((wino_wgrad_kernel<a, b_>), dim3(nblk), dim3(nt), pl.lds, s, p); }
     if (rc2 == MRDIS_OK) {}
-    else if (pl.wci == 4 && pl.wco == 2) { mrdis_count(MRDIS_CNT_WINO_WGRAD); MRDIS_LAUNCH((wino_wgrad_kernel<4, 2>), dim3(nblk), dim3(512), pl.lds, s, p); }
-    else if (pl.wci == 4) { mrdis_count(MRDIS_CNT_WINO_WGRAD); MRDIS_LAUNCH((wino_wgrad_kernel<4, 1>), dim3(nblk), dim3(256), pl.lds, s, p); }
-    else { mrdis_count(MRDIS_CNT_WINO_WGRAD); MRDIS_LAUNCH((wino_wgrad_kernel<2, 2>), dim3(nblk), dim3(256), pl.lds, s, p); }
+    else if (pl.wci == 4 && pl.wco == 2) WW_LAUNCH(4, 2, 512, 120)
+    else if (pl.wci == 4) WW_LAUNCH(4, 1, 256, 80)
+    else WW_LAUNCH(2, 2, 256, 80)
+#undef WW_LAUNCH
     MRDIS_CHECK_LAUNCH();
     const long long n = 9LL * Ci * Co;
     int SL = 1;
@@ -683,14 +668,9 @@ int mrdis_run_wino_wgrad3d(const float* x, int ldx, const float* dy, int lddy, f
     p.x = x; p.dy = dy; p.ldx = ldx; p.lddy = lddy; p.D = D;
     p.slab = reinterpret_cast<float*>(workspace);
     float* bias_slab = p.slab + (size_t)p.splits * 9 * Ci * Co;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)wino_wgrad_kernel<4, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 120 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wino_wgrad_kernel<4, 1, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wino_wgrad_kernel<2, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024) != hipSuccess)
-            return MRDIS_ELAUNCH;
-        attr_set = true;
-    }
+    const bool w42 = pl.wci == 4 && pl.wco == 2;
+    if (!mrdis_lds_optin(w42 ? (const void*)wino_wgrad_kernel<4, 2, true> : pl.wci == 4 ? (const void*)wino_wgrad_kernel<4, 1, true>
+                             : (const void*)wino_wgrad_kernel<2, 2, true>, w42 ? 120 * 1024 : 80 * 1024)) return MRDIS_ELAUNCH;
     const int nblk = p.splits * p.nCiB * p.nCoB;
     const long long n = 9LL * Ci * Co;
     int SL = 1;
@@ -699,7 +679,7 @@ int mrdis_run_wino_wgrad3d(const float* x, int ldx, const float* dy, int lddy, f
         p.kd = kd;
         p.bias_slab = (dbias && kd == 1) ? bias_slab : nullptr;
         mrdis_count(MRDIS_CNT_WINO_WGRAD3D);
-        if (pl.wci == 4 && pl.wco == 2) MRDIS_LAUNCH((wino_wgrad_kernel<4, 2, true>), dim3(nblk), dim3(512), pl.lds, s, p);
+        if (w42) MRDIS_LAUNCH((wino_wgrad_kernel<4, 2, true>), dim3(nblk), dim3(512), pl.lds, s, p);
         else if (pl.wci == 4) MRDIS_LAUNCH((wino_wgrad_kernel<4, 1, true>), dim3(nblk), dim3(256), pl.lds, s, p);
         else MRDIS_LAUNCH((wino_wgrad_kernel<2, 2, true>), dim3(nblk), dim3(256), pl.lds, s, p);
         MRDIS_CHECK_LAUNCH();

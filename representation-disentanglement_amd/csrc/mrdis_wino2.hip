@@ -423,26 +423,15 @@ int mrdis_run_wino2(const float* x, int ldx, const float* w, const float* bias, 
     p.nblk = (int)nblk;
     if (!mrdis_opt(MRDIS_OPT_WINO_U) || (((uintptr_t)u_img) & 15) != 0) u_img = nullptr;
     p.u_img = u_img; p.u_bytes = wino_u_bytes(Ci, p.coTiles);
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MRDIS_ELAUNCH;
-        if (hipFuncSetAttribute((const void*)wino2_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO2_LDS) != hipSuccess) return MRDIS_EUNSUPPORTED;
-        if (hipFuncSetAttribute((const void*)wino2_kernel<0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO2_LDS) != hipSuccess) return MRDIS_EUNSUPPORTED;
-#ifdef WINO2_ABLATIONS
-#define W2A(a) hipFuncSetAttribute((const void*)wino2_kernel<a>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO2_LDS);
-        W2A(1) W2A(2) W2A(3) W2A(4) W2A(8) W2A(32) W2A(40) W2A(43) W2A(16) W2A(47) W2A(64) W2A(128) W2A(256)
-#undef W2A
-#endif
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    const int n_cu = mrdis_cu_count();
     const int grid = nblk < n_cu ? (int)nblk : n_cu;
 #ifdef WINO2_ABLATIONS
     const int abl = (int)mrdis_opt(MRDIS_OPT_MODE);          // debug_mode doubles as the ablation selector in this build
-#define W2A(a) if (abl == a) { MRDIS_LAUNCH(wino2_kernel<a>, dim3(grid), dim3(NT), WINO2_LDS, s, p); MRDIS_CHECK_LAUNCH(); return MRDIS_OK; }
+#define W2A(a) if (abl == a) { mrdis_lds_optin((const void*)wino2_kernel<a>, (int)WINO2_LDS); MRDIS_LAUNCH(wino2_kernel<a>, dim3(grid), dim3(NT), WINO2_LDS, s, p); MRDIS_CHECK_LAUNCH(); return MRDIS_OK; }
     W2A(1) W2A(2) W2A(3) W2A(4) W2A(8) W2A(32) W2A(40) W2A(43) W2A(16) W2A(47) W2A(64) W2A(128) W2A(256)
 #undef W2A
 #endif
+    if (!mrdis_lds_optin(u_img ? (const void*)wino2_kernel<0, false, true> : (const void*)wino2_kernel<0>, (int)WINO2_LDS)) return MRDIS_EUNSUPPORTED;
     mrdis_count(MRDIS_CNT_WINO2);
     if (u_img) MRDIS_LAUNCH((wino2_kernel<0, false, true>), dim3(grid), dim3(NT), WINO2_LDS, s, p);
     else MRDIS_LAUNCH(wino2_kernel<0>, dim3(grid), dim3(NT), WINO2_LDS, s, p);
@@ -468,17 +457,11 @@ int mrdis_run_wino2_spade(const float* x, int ldx, const float* w, const float* 
     const long long nblk = (long long)N * p.nby * p.nbx * p.coTiles;
     if (nblk > 0x7fffffffLL) return MRDIS_EUNSUPPORTED;
     p.nblk = (int)nblk;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MRDIS_ELAUNCH;
-        if (hipFuncSetAttribute((const void*)wino2_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO2_LDS) != hipSuccess) return MRDIS_EUNSUPPORTED;
-        if (hipFuncSetAttribute((const void*)wino2_kernel<0, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WINO2_LDS) != hipSuccess) return MRDIS_EUNSUPPORTED;
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
     if (!mrdis_opt(MRDIS_OPT_WINO_U) || (((uintptr_t)u_img) & 15) != 0) u_img = nullptr;
     p.u_img = u_img; p.u_bytes = wino_u_bytes(Ci, p.coTiles);
+    const int n_cu = mrdis_cu_count();
     const int grid = nblk < n_cu ? (int)nblk : n_cu;
+    if (!mrdis_lds_optin(u_img ? (const void*)wino2_kernel<0, true, true> : (const void*)wino2_kernel<0, true>, (int)WINO2_LDS)) return MRDIS_EUNSUPPORTED;
     mrdis_count(MRDIS_CNT_WINO2_SPADE);
     if (u_img) MRDIS_LAUNCH((wino2_kernel<0, true, true>), dim3(grid), dim3(NT), WINO2_LDS, s, p);
     else MRDIS_LAUNCH((wino2_kernel<0, true>), dim3(grid), dim3(NT), WINO2_LDS, s, p);
@@ -836,11 +819,7 @@ __global__ __launch_bounds__(512, 1) void wino_wgrad2_kernel(const WinoWgradPara
 int mrdis_launch_wino_wgrad2(const WinoWgradParams& p, hipStream_t s) {
     if (p.D != 0 || p.Ci % 64 != 0 || p.Co % 64 != 0 || p.ldx % 4 != 0 || (((uintptr_t)p.x) & 15) != 0) return MRDIS_EUNSUPPORTED;
     if ((long long)p.N * p.H * p.W * p.ldx >= 0x3fffffffLL || (long long)p.N * p.H * p.W * p.lddy >= 0x3fffffffLL) return MRDIS_EUNSUPPORTED;
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)wino_wgrad2_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WGRAD2_LDS) != hipSuccess) return MRDIS_EUNSUPPORTED;
-        attr_set = true;
-    }
+    if (!mrdis_lds_optin((const void*)wino_wgrad2_kernel, (int)WGRAD2_LDS)) return MRDIS_EUNSUPPORTED;
     int t = p.splits;
     const int s_bx = t % p.nbx; t /= p.nbx;
     const int s_by = t % p.nby;

@@ -774,13 +774,8 @@ int mrdis_run_wino4n(const float* x, int ldx, const float* bias, float* y, int l
     // not (64 -> 32 at 256x256, 537 MB: 474 -> 511 us)
     if (mrdis_opt(MRDIS_OPT_WINO4) < 2 && (long long)N * H * W * Ci * 4 > 300000000LL) return MRDIS_EUNSUPPORTED;
     p.nblk = (int)nblk;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MRDIS_ELAUNCH;
-        if (hipFuncSetAttribute((const void*)wino4n_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4N_LDS) != hipSuccess) return MRDIS_EUNSUPPORTED;
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    if (!mrdis_lds_optin((const void*)wino4n_kernel<0>, (int)W4N_LDS)) return MRDIS_EUNSUPPORTED;
+    const int n_cu = mrdis_cu_count();
     const int grid = nblk < n_cu ? (int)nblk : n_cu;
     mrdis_count(MRDIS_CNT_WINO4N);
     MRDIS_LAUNCH(wino4n_kernel<0>, dim3(grid), dim3(NT4), W4N_LDS, s, p);
@@ -812,23 +807,13 @@ int mrdis_run_wino4(const float* x, int ldx, const float* bias, float* y, int ld
     // 16 x 16 blocks fill it better
     if (mrdis_opt(MRDIS_OPT_WINO4) < 2 && (nblk < 192 || H < 16 || W < 32)) return MRDIS_EUNSUPPORTED;
     p.nblk = (int)nblk;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MRDIS_ELAUNCH;
-        if (hipFuncSetAttribute((const void*)wino4_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4_LDS) != hipSuccess) return MRDIS_EUNSUPPORTED;
-#ifdef WINO4_ABLATIONS
-#define W4A(a) hipFuncSetAttribute((const void*)wino4_kernel<a>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4_LDS);
-        W4A(1) W4A(4) W4A(5) W4A(8) W4A(32) W4A(41) W4A(45) W4A(64) W4A(65) W4A(72) W4A(96) W4A(105) W4A(192) W4A(320) W4A(576) W4A(448) W4A(832)
-#undef W4A
-#endif
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    if (!mrdis_lds_optin((const void*)wino4_kernel<0>, (int)W4_LDS)) return MRDIS_EUNSUPPORTED;
+    const int n_cu = mrdis_cu_count();
     const int grid = nblk < n_cu ? (int)nblk : n_cu;
 #ifdef WINO4_ABLATIONS
     const int abl = (int)mrdis_opt(MRDIS_OPT_MODE);          // debug_mode doubles as the ablation selector in this build
     p.dbg = g_w4_dbg; p.dbg_cap = g_w4_dbg_cap;
-#define W4A(a) if (abl == a) { MRDIS_LAUNCH(wino4_kernel<a>, dim3(grid), dim3(NT4), W4_LDS, s, p); MRDIS_CHECK_LAUNCH(); return MRDIS_OK; }
+#define W4A(a) if (abl == a) { mrdis_lds_optin((const void*)wino4_kernel<a>, (int)W4_LDS); MRDIS_LAUNCH(wino4_kernel<a>, dim3(grid), dim3(NT4), W4_LDS, s, p); MRDIS_CHECK_LAUNCH(); return MRDIS_OK; }
     W4A(1) W4A(4) W4A(5) W4A(8) W4A(32) W4A(41) W4A(45) W4A(64) W4A(65) W4A(72) W4A(96) W4A(105) W4A(192) W4A(320) W4A(576) W4A(448) W4A(832)
 #undef W4A
 #endif
@@ -862,13 +847,8 @@ int mrdis_run_wino4_spade(const float* x, int ldx, const float* bias, const floa
     if (nblk > 0x7fffffffLL) return MRDIS_EUNSUPPORTED;
     if (mrdis_opt(MRDIS_OPT_WINO4) < 2 && (nblk < 192 || H < 16 || W < 32)) return MRDIS_EUNSUPPORTED;
     p.nblk = (int)nblk;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MRDIS_ELAUNCH;
-        if (hipFuncSetAttribute((const void*)wino4_kernel<0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4_LDS) != hipSuccess) return MRDIS_EUNSUPPORTED;
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    if (!mrdis_lds_optin((const void*)wino4_kernel<0, true>, (int)W4_LDS)) return MRDIS_EUNSUPPORTED;
+    const int n_cu = mrdis_cu_count();
     const int grid = nblk < n_cu ? (int)nblk : n_cu;
     mrdis_count(MRDIS_CNT_WINO4_SPADE);
     MRDIS_LAUNCH((wino4_kernel<0, true>), dim3(grid), dim3(NT4), W4_LDS, s, p);

@@ -365,31 +365,19 @@ static int launch_wino4r(Wino4rParams& p, hipStream_t s) {
     if (nblk > 0x7fffffffLL) return MRDIS_EUNSUPPORTED;
     if (mrdis_opt(MRDIS_OPT_WINO4) < 2 && nblk < 192) return MRDIS_EUNSUPPORTED;
     p.nblk = (int)nblk;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0; hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return MRDIS_ELAUNCH;
-        if (hipFuncSetAttribute((const void*)wino4r_kernel<1, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RGeo<1>::LDS) != hipSuccess ||
-            hipFuncSetAttribute((const void*)wino4r_kernel<2, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RGeo<2>::LDS) != hipSuccess)
-            return MRDIS_EUNSUPPORTED;
-#ifdef WINO4_ABLATIONS
-#define W4RA(a) hipFuncSetAttribute((const void*)wino4r_kernel<1, a>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RGeo<1>::LDS); \
-                hipFuncSetAttribute((const void*)wino4r_kernel<2, a>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)RGeo<2>::LDS);
-        W4RA(64) W4RA(1) W4RA(2) W4RA(3) W4RA(4) W4RA(40) W4RA(43) W4RA(47)
-#undef W4RA
-#endif
-        n_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    }
+    if (!mrdis_lds_optin((const void*)wino4r_kernel<NKH, 0>, (int)G::LDS)) return MRDIS_EUNSUPPORTED;
+    const int n_cu = mrdis_cu_count();
     const int grid = nblk < n_cu ? (int)nblk : n_cu;
 #ifdef WINO4_ABLATIONS
     {   // timing-only variants (results wrong), selected by option debug_mode: 1 no patch reads, 2 no filter reads, 4 no MFMAs, 8 | 32 no copies
         const int abl = (int)mrdis_opt(MRDIS_OPT_MODE);
-#define W4RA(a) if (abl == a) { MRDIS_LAUNCH((wino4r_kernel<NKH, a>), dim3(grid), dim3(NTR), G::LDS, s, p); MRDIS_CHECK_LAUNCH(); return MRDIS_OK; }
+#define W4RA(a) if (abl == a) { mrdis_lds_optin((const void*)wino4r_kernel<NKH, a>, (int)G::LDS); MRDIS_LAUNCH((wino4r_kernel<NKH, a>), dim3(grid), dim3(NTR), G::LDS, s, p); MRDIS_CHECK_LAUNCH(); return MRDIS_OK; }
         W4RA(1) W4RA(2) W4RA(3) W4RA(4) W4RA(40) W4RA(43) W4RA(47)
 #undef W4RA
     }
     if (g_w4r_dbg != nullptr) {
         p.dbg = g_w4r_dbg; p.dbg_cap = g_w4r_dbg_cap;
+        mrdis_lds_optin((const void*)wino4r_kernel<NKH, 64>, (int)G::LDS);
         mrdis_count(MRDIS_CNT_WINO4R);
         MRDIS_LAUNCH((wino4r_kernel<NKH, 64>), dim3(grid), dim3(NTR), G::LDS, s, p);
         MRDIS_CHECK_LAUNCH();

@@ -352,11 +352,7 @@ int mrdis_launch_wino4_wgrad(WinoWgradParams& base, int max_splits, hipStream_t 
     if (opt < 2 && (p.ngroups / splits < 24 || splits * p.nCiB * p.nCoB < 192 || p.H < 8 || p.W < 8)) return MRDIS_EUNSUPPORTED;
     p.splits = splits;
     { int t = splits; p.s_gx = t % p.ngx; t /= p.ngx; p.s_gy = t % p.ngy; p.s_n = t / p.ngy; }
-    static bool attr_set = false;
-    if (!attr_set) {
-        if (hipFuncSetAttribute((const void*)wino4_wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)W4W_LDS) != hipSuccess) return MRDIS_EUNSUPPORTED;
-        attr_set = true;
-    }
+    if (!mrdis_lds_optin((const void*)wino4_wgrad_kernel, (int)W4W_LDS)) return MRDIS_EUNSUPPORTED;
 #ifdef WINO4_ABLATIONS
     p.dbg = g_w4w_dbg; p.dbg_cap = g_w4w_dbg_cap;
 #endif

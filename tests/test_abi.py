@@ -110,3 +110,23 @@ def test_library_issues_no_memset_or_memcpy_calls():
             if re.search(r'hipMem(set|cpy)\w*\s*\(', code):
                 bad.append(f'{os.path.basename(f)}:{n}')
     assert not bad, bad
+
+
+def test_launch_setup_lives_in_one_place():
+    """LDS opt-ins, CU counts and occupancy queries go through mrdis_lds_optin / mrdis_cu_count / mrdis_occupancy (mrdis_elem.hip), which cache per
+    kernel address and are safe from any thread: forward launches run on the main thread, backward ones on autograd's.  No launcher keeps a
+    function-local cache of its own (a mutable host static)"""
+    import glob
+    import re
+    root = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'representation-disentanglement_amd', 'csrc')
+    setup_call = re.compile(r'\b(hipFuncSetAttribute|hipGetDeviceProperties|hipDeviceGetAttribute|hipOccupancyMaxActiveBlocksPerMultiprocessor)\b')
+    local_static = re.compile(r'^\s+static\s+(?!(const|constexpr|inline|__device__|__shared__)\b)')
+    bad = []
+    for f in sorted(glob.glob(os.path.join(root, '*.hip')) + glob.glob(os.path.join(root, '*.h'))):
+        if os.path.basename(f) == 'mrdis_elem.hip':
+            continue
+        for n, line in enumerate(open(f), 1):
+            code = line.split('//')[0]
+            if setup_call.search(code) or local_static.search(code):
+                bad.append(f'{os.path.basename(f)}:{n}')
+    assert not bad, bad
