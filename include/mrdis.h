@@ -398,6 +398,20 @@ int mrdis_recon_metrics(const float* target, int ldt, const float* pred, int ldp
 int mrdis_slice_gather(const void* vol_ptrs, const int* slice_idx, const int* drop, float* inputs, int ld_in,
                        float* mask, float* mask_img, int B, int M, int H, int W, int D, int block, void* stream);
 
+/* ---- batch assembly for the 3-D nets: ZeroDoseDataset3D.__getitem__ + default collate (util.py:723-810) in one launch.
+ * Volumes are stored as the reference's h5 file has them, (H, W, D) fp32 with D fastest.  table (B, ld_table) 64-bit words in
+ * device memory, ld_table >= 2 M + 3, per sample: [0, M) volume pointers (0 = contrast missing or dropped), [M, 2M) pointers
+ * to those volumes' fp32 minima inside the depth crop, [2M] target volume pointer (0 = none), [2M+1] bit 0 = flip the H axis,
+ * bit 1 = augment, [2M+2] fp32 bits of scale (low word) and shift (high word).
+ * mode 0: out (B, H, W, Dz, M) (channels-last-3d view of (B, M, H, W, Dz)) = crop [z0, z0 + Dz) of every contrast, zeros where
+ *   absent; with the augment bit v = x * scale + shift (fp32, two roundings) and -10 where the raw value equals the item's raw
+ *   minimum (= `inputs[inputs == inputs.min()] = -10`, see mrdis_volgather.hip); mask (B, M) or NULL = pointer present.  K = 0.
+ * mode 1: targets from the [2M] volume, same crop and flip, zeros if absent, label 4 -> 3 if `relabel`; K = 0: out (B, H, W, Dz);
+ *   K >= 1: out (B, H, W, Dz, K), channel c = (label == c + 1).
+ * M, K <= 64, any H, W, Dz >= 1 (H W D < 2^31).  One kernel launch per call, counted as "volgather".                           */
+int mrdis_volume_gather(const void* table, int ld_table, float* out, float* mask, int B, int M, int H, int W, int D, int z0,
+                        int Dz, int mode, int K, int relabel, void* stream);
+
 /* ---- max_pool2d(kernel k x k, stride k): model.py:3448-3451 ---------------- */
 int mrdis_maxpool_fwd(const float* x, int ldx, float* y, int32_t* argmax, int N, int H, int W, int C,
                       int k, void* stream);

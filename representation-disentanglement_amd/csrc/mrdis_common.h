@@ -19,7 +19,7 @@ enum {
     MRDIS_OPT_WINO, MRDIS_OPT_NT_MB, MRDIS_OPT_WINO_PIPE, MRDIS_OPT_WINO_U, MRDIS_OPT_WINO4, MRDIS_OPT_WINO4R, MRDIS_OPT_BCONV4, MRDIS_OPT_SPLIT6,
     MRDIS_OPT_NO16, MRDIS_OPT_NOTHIN, MRDIS_OPT_NOC4, MRDIS_OPT_NODMA, MRDIS_OPT_NO16_3D, MRDIS_OPT_BILGEN, MRDIS_OPT_NOW16, MRDIS_OPT_NOPACK,
     MRDIS_OPT_MODE, MRDIS_OPT_BN, MRDIS_OPT_KC, MRDIS_OPT_BM, MRDIS_OPT_C4_TW, MRDIS_OPT_WGSPLIT, MRDIS_OPT_BN3, MRDIS_OPT_KC3,
-    MRDIS_OPT_C4_GRID, MRDIS_OPT_C4_BLOCKS, MRDIS_OPT_ZS_GRID,
+    MRDIS_OPT_C4_GRID, MRDIS_OPT_C4_BLOCKS, MRDIS_OPT_ZS_GRID, MRDIS_OPT_VOLGEN,
     MRDIS_OPT_COUNT
 };
 long long mrdis_opt(int id);      // mrdis_elem.hip
@@ -34,6 +34,7 @@ enum { MRDIS_CNT_WINO, MRDIS_CNT_WINO_SPADE, MRDIS_CNT_WINO2, MRDIS_CNT_WINO2_SP
        MRDIS_CNT_KL, MRDIS_CNT_AVGPOOL /* mrdis_latent.hip: the KL term and mean compaction */,
        MRDIS_CNT_CHATT, MRDIS_CNT_SYMDIFF, MRDIS_CNT_RGATE /* mrdis_outdec.hip: the attention output decoders */,
        MRDIS_CNT_DIRECT3D, MRDIS_CNT_C3D16, MRDIS_CNT_WGRAD3D, MRDIS_CNT_WGRAD3D16, MRDIS_CNT_WINO_WGRAD3D /* mrdis_conv3d.hip / mrdis_wino.hip: the 3-D kernels */,
+       MRDIS_CNT_VOLGATHER /* mrdis_volgather.hip: the 3-D batch gather, one count per mrdis_volume_gather call */,
        MRDIS_CNT_ALL /* every launch of the library */, MRDIS_CNT_COUNT };
 void mrdis_count(int id);
 

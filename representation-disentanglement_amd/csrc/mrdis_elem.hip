@@ -1949,6 +1949,7 @@ const OptDef OPT_DEFS[MRDIS_OPT_COUNT] = {
     {"c4_grid", "MRDIS_C4_GRID", 0, 0},      // persistent grid of the Cin = 4 kernels (run_c4conv): 0 = workgroups per CU from the occupancy query of the launched instantiation | k > 0: k workgroups per CU
     {"debug_c4_blocks", "MRDIS_DEBUG_C4_BLOCKS", 0, -1},      // read-only diagnostic: grid.x of the last run_c4conv launch
     {"zsearch_grid", "MRDIS_ZSEARCH_GRID", 0, 0},   // workgroups of mrdis_cosine_top1 (mrdis_zsearch.hip): 0 = min(tiles, 1024) | k > 0: min(k, tiles, 2048)
+    {"debug_volgen", "MRDIS_DEBUG_VOLGEN", 1, 0},   // 1: mrdis_volume_gather always runs its element kernel (mrdis_volgather.hip), never the LDS-tile form
 };
 long long* opt_table() {
     static long long* table = [] {
@@ -1987,7 +1988,7 @@ const char* const CNT_NAMES[MRDIS_CNT_COUNT] = {"wino", "wino_spade", "wino2", "
                                                 "wino_wgrad", "wino_wgrad2", "wino4_wgrad", "bconv3", "bconv3_spade", "bconv4", "bconv4_spade",
                                                 "split6_c4", "split6_c16", "split6_wgrad16", "split6_co4", "split6_c3d", "split6_w3d", "split6_tap", "zsearch",
                                                 "conv2src", "ana_act", "kl", "avgpool", "chatt", "symdiff", "rgate",
-                                                "direct3d", "c3d16", "wgrad3d", "wgrad3d16", "wino_wgrad3d", "all"};
+                                                "direct3d", "c3d16", "wgrad3d", "wgrad3d16", "wino_wgrad3d", "volgather", "all"};
 long long g_counts[MRDIS_CNT_COUNT];
 }  // namespace
 void mrdis_count(int id) { __atomic_fetch_add(&g_counts[id], 1LL, __ATOMIC_RELAXED); }

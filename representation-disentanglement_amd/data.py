@@ -16,6 +16,8 @@ Host-side behaviour follows the reference statement by statement:
   * batch order: `DataLoader(shuffle)` = `RandomSampler` seeded from torch's default generator
     (num_workers = 0, main_missing.py:63), reproduced draw for draw.
 `skull_strip` and the `aug` flip (a `pdb.set_trace()` in the reference, util.py:555-558) are not on the path.
+This module is the 2-D (slice) half; the volume dataset of the 3-D nets (ZeroDoseDataset3D, util.py:723-843), its augmentation included,
+is data3d.py, over the same BatchLoader.
 """
 import numpy as np
 import torch

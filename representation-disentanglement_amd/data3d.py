@@ -1,0 +1,191 @@
+"""Batch assembly of the reference's volume dataset (`src/util.py:723-843`: ZeroDoseDataset3D, ZeroDoseDataAll3D) with the volumes resident in HBM.
+
+The reference builds an item on the host -- an h5 read per contrast, `np.stack`, a flip made by subtracting a zeros array, a float64
+scale/shift pass and an `== min()` pass -- and its training loop would then copy 31 MB per sample (4 x 160 x 192 x 64 fp32) to the GPU.
+Here the volumes are uploaded once, as the h5 file has them ((H, W, D), D fastest), and a batch is ONE gather launch for the inputs and one for
+the targets (`mrdis_volume_gather`, csrc/mrdis_volgather.hip), both driven by one small per-batch table, writing the channels-last-3d layout
+the Conv3d kernels of model3d read.
+
+Host-side behaviour follows the reference statement by statement:
+  * depth crop `[:, :, 45:-46]` (`45:-47` for 'ZeroDose'): z0 = 45, Dz = D - 91 (D - 92)                         util.py:766-769
+  * a contrast missing for a subject gives zeros and mask 0                                                      util.py:771-773
+  * targets: '/PET' (ZeroDose), '/seg' with label 4 -> 3 (BraTS), zeros otherwise                                util.py:777-789
+  * drop-off: `np.random.rand() > 0.8` then `np.random.choice(present, 1)`, only with dropoff and > 1 present      util.py:791-795
+  * aug: `rand() > 0.5` flips H (inputs and targets), `1 + 0.2 (rand() - 0.5)` scales, `0.2 (rand() - 0.5)` shifts,
+    then `inputs[inputs == inputs.min()] = -10` -- same global-RNG call order                                    util.py:798-805
+  * slice_idx = 0                                                                                                util.py:807
+  * batch order: `DataLoader(shuffle)`, reproduced draw for draw by BatchLoader._order.
+The commented-out mean-image imputation (`img_mean`, `BraTS_mean.npy`) and the `missing` argument the reference never reads are not built.
+"""
+import os
+
+import numpy as np
+import torch
+
+from . import hip
+from .data import VolumeStore, BatchLoader
+
+Z0 = 45                     # util.py:766-769
+
+
+class VolumeStore3D(VolumeStore):
+    """`data[subject + '/' + contrast]` of the reference's h5 file, kept on the device in the file's own layout (H, W, D): the depth crop of one
+    (h, w) column is then one contiguous run, which is what the gather kernel reads.  Also keeps every volume's minimum inside a depth crop
+    (the `== min()` rule of the augmentation needs it, csrc/mrdis_volgather.hip), computed on the device when a loader first asks."""
+
+    def __init__(self, device):
+        super().__init__(device)
+        self._mins = {}             # (z0, Dz) -> (fp32 device tensor, {key: row})
+
+    def add(self, key, array_hwd):
+        """key = 'subject/contrast' (h5 path); array in the reference layout (H, W, D)."""
+        a = torch.as_tensor(np.ascontiguousarray(array_hwd), dtype=torch.float32)
+        if a.dim() != 3:
+            raise ValueError('volume must be (H, W, D)')
+        if self.shape is None:
+            self.shape = tuple(a.shape)
+        elif tuple(a.shape) != self.shape:
+            raise ValueError(f'{key}: shape {tuple(a.shape)} != {self.shape}')
+        self.vols[key] = a.to(self.device)
+        self._mins.clear()
+
+    def crop_min_ptr(self, key, z0, Dz):
+        """device address of min(vol[:, :, z0:z0+Dz]) (fp32), 0 for a key the store does not hold.  No host read, no sync."""
+        ent = self._mins.get((z0, Dz))
+        if ent is None:
+            keys = list(self.vols)
+            mins = torch.stack([self.vols[k][:, :, z0:z0 + Dz].amin() for k in keys]) if keys else torch.empty(0, device=self.device)
+            ent = self._mins[(z0, Dz)] = (mins.contiguous(), {k: i for i, k in enumerate(keys)})
+        mins, rows = ent
+        i = rows.get(key)
+        return 0 if i is None else mins.data_ptr() + 4 * i
+
+
+def load_subj_list(path):
+    """util.py:841-843: one subject id per line.  The reference reads the file with `pd.read_csv(path, sep=" ")` WITHOUT `header=None`, so pandas takes
+    the first line as a header and the first subject of every list is never served; kept, since the reference's folds were run that way."""
+    import pandas as pd
+    lines = pd.read_csv(path, sep=' ')
+    return np.array(lines.iloc[:, 0])
+
+
+class VolumeDataset3D:
+    """ZeroDoseDataset3D (util.py:723-810) over a VolumeStore3D: `meta(idx)` is the host part of `__getitem__`."""
+
+    TARGET_KEYS = {'ZeroDose': '/PET', 'BraTS': '/seg'}
+
+    def __init__(self, dataset_name, store, subj_list, contrast_list=('T1',), aug=False, dropoff=False):
+        self.dataset_name, self.store = dataset_name, store
+        self.subj_list, self.contrast_list = list(subj_list), list(contrast_list)
+        self.aug, self.dropoff = aug, dropoff
+
+    def __len__(self):
+        return len(self.subj_list)
+
+    def crop(self):
+        """(z0, Dz) of `[:, :, 45:-46]` (`45:-47` for 'ZeroDose')."""
+        Dz = self.store.shape[2] - Z0 - (47 if self.dataset_name == 'ZeroDose' else 46)
+        if Dz < 1:
+            raise ValueError(f'volumes of depth {self.store.shape[2]} leave nothing inside the crop')
+        return Z0, Dz
+
+    def meta(self, idx, rng=None):
+        """-> (subj_id, slice_idx = 0, volume pointers, dropped contrast or -1, target pointer, flip, scale, shift).  rng: None = the global np.random (the
+        reference's own stream, draw for draw) or the loader's own np.random.RandomState (data-parallel runs, see BatchLoader)."""
+        rng = np.random if rng is None else rng
+        subj_id = str(self.subj_list[idx])
+        ptrs = [self.store.ptr(subj_id + '/' + c) for c in self.contrast_list]
+        mask = np.array([1 if p else 0 for p in ptrs])
+        tkey = self.TARGET_KEYS.get(self.dataset_name)
+        tptr = self.store.ptr(subj_id + tkey) if tkey else 0
+        drop = -1
+        if self.dropoff and mask.sum() > 1:                           # :791-795, same RNG call order
+            if rng.rand() > 0.8:
+                drop = int(rng.choice(np.where(mask == 1)[0], 1)[0])
+        flip, scale, shift = False, 1.0, 0.0
+        if self.aug:                                                  # :798-804
+            flip = bool(rng.rand() > 0.5)
+            scale = 1 + 0.2 * (rng.rand() - 0.5)
+            shift = 0.2 * (rng.rand() - 0.5)
+        return subj_id, 0, ptrs, drop, tptr, flip, scale, shift
+
+
+class VolumeLoader3D(BatchLoader):
+    """DataLoader(dataset, batch_size, shuffle, num_workers=0) of util.py:837-839 over a VolumeDataset3D; yields the reference's sample dict with
+    device tensors: inputs (B, M, H, W, Dz) channels-last-3d, targets (B, H, W, Dz) -- or, with `region_channels` = K, (B, K, H, W, Dz)
+    channels-last-3d with channel c = (label == c + 1), this package's convention for `nvnet_loss` -- mask (B, M), subj_id (list), slice_idx (B,)
+    zeros, plus mask_host and batch_index as in the 2-D loader.  The partial last batch is served.
+
+    Batch order, rank / world / equal_steps and the loader's own stream under world > 1 are BatchLoader's (see its docstring); here that
+    stream carries ALL per-item draws, drop-off and augmentation, for the same reason."""
+
+    def __init__(self, dataset, batch_size, shuffle=False, rank=0, world=1, equal_steps=False, generator=None, region_channels=0):
+        super().__init__(dataset, batch_size, shuffle, rank, world, equal_steps, generator)
+        self.region_channels = int(region_channels)
+
+    def table(self, metas):
+        """the per-batch table of mrdis_volume_gather (include/mrdis.h), on the host, and the host twin of `mask`."""
+        ds, st = self.dataset, self.dataset.store
+        M = len(ds.contrast_list)
+        z0, Dz = ds.crop()
+        B = len(metas)
+        tab = np.zeros((B, 2 * M + 3), dtype=np.int64)
+        mask_host = np.zeros((B, M), dtype=np.float32)                 # host twin of `mask`: a loss may branch on it without a sync
+        for r, (subj_id, _, ptrs, drop, tptr, flip, scale, shift) in enumerate(metas):
+            for m, p in enumerate(ptrs):
+                if p and m != drop:
+                    tab[r, m] = p
+                    tab[r, M + m] = st.crop_min_ptr(subj_id + '/' + ds.contrast_list[m], z0, Dz)
+                    mask_host[r, m] = 1.0
+            tab[r, 2 * M] = tptr
+            tab[r, 2 * M + 1] = (1 if flip else 0) | (2 if ds.aug else 0)
+            bits = np.array([scale, shift], dtype=np.float32).view(np.uint32).astype(np.uint64)
+            tab[r, 2 * M + 2] = (bits[0] | (bits[1] << np.uint64(32))).view(np.int64)
+        return tab, mask_host
+
+    def batches(self, limit=None):
+        ds, st = self.dataset, self.dataset.store
+        H, W, D = st.shape
+        M = len(ds.contrast_list)
+        z0, Dz = ds.crop()
+        dev = st.device
+        for k, _, metas in self.batch_plan(limit):
+            tab, mask_host = self.table(metas)
+            host = torch.from_numpy(tab)
+            if dev.type == 'cuda':
+                host = host.pin_memory()
+            d = host.to(dev, non_blocking=True)                       # one small H2D copy per batch
+            inputs, mask = hip.volume_gather(d, M, H, W, D, z0, Dz)
+            targets = hip.volume_gather(d, M, H, W, D, z0, Dz, targets=True, K=self.region_channels, relabel=ds.dataset_name == 'BraTS')
+            yield {'inputs': inputs, 'targets': targets, 'subj_id': [m[0] for m in metas],
+                   'slice_idx': torch.zeros(len(metas), dtype=torch.int64, device=dev), 'mask': mask, 'mask_host': mask_host,
+                   'batch_index': k}
+
+
+class VolumeData3D:
+    """ZeroDoseDataAll3D (util.py:812-843): the three loaders of a fold.  `aug` reaches the train loader only and `dropoff` not the test loader
+    (util.py:833-835).  The volumes come from `store` (a VolumeStore3D) or, without one, from the reference's h5 file under `data_path`."""
+
+    @staticmethod
+    def file_names(dataset_name, norm_type='mean', fold=0):
+        """-> (h5 file, train list, val list, test list), util.py:814-829.  Any other dataset name raises (the reference leaves `data` unbound)."""
+        if dataset_name == 'BraTS':
+            h5 = 'BraTS_All.h5' if norm_type == 'mean' else 'BraTS_All_zscore_10.h5'
+            return (h5,) + tuple(f'fold_BraTS_3d_{fold}_{s}_noval.txt' for s in ('train', 'val', 'test'))
+        if dataset_name == 'ZeroDose':
+            h5 = 'ZeroDose_FDG_All_1103_norm.h5' if norm_type == 'mean' else 'ZeroDose_FDG_All_1103_zscore_10.h5'
+            return (h5,) + ('ZeroDose_3d_all.txt',) * 3
+        raise ValueError(f'no 3-D dataset {dataset_name!r}: BraTS or ZeroDose')
+
+    def __init__(self, dataset_name, data_path, norm_type='mean', batch_size=16, fold=0, shuffle=True, contrast_list=('T1',), aug=False,
+                 dropoff=False, store=None, device='cuda:0', rank=0, world=1, generator=None, region_channels=0):
+        h5, *lists = self.file_names(dataset_name, norm_type, fold)
+        if store is None:
+            store = VolumeStore3D.from_h5(os.path.join(data_path, h5), device)
+        self.store = store
+        subj = [load_subj_list(os.path.join(data_path, f)) for f in lists]
+        mk = lambda s, a, d: VolumeDataset3D(dataset_name, store, s, contrast_list=contrast_list, aug=a, dropoff=d)
+        kw = dict(rank=rank, world=world, generator=generator, region_channels=region_channels)
+        self.trainLoader = VolumeLoader3D(mk(subj[0], aug, dropoff), batch_size, shuffle=shuffle, equal_steps=True, **kw)
+        self.valLoader = VolumeLoader3D(mk(subj[1], False, dropoff), batch_size, shuffle=False, **kw)
+        self.testLoader = VolumeLoader3D(mk(subj[2], False, False), batch_size, shuffle=False, **kw)

@@ -89,6 +89,7 @@ _SIGS = {
     'mrdis_recon_metrics_workspace': (_Z, [_I, _I]),
     'mrdis_recon_metrics': (_I, [_P, _I, _P, _I, _P, _P, _Z, _I, _I, _I, _P]),
     'mrdis_slice_gather': (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'mrdis_volume_gather': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_bwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_sumsq_workspace': (_Z, []),
@@ -164,7 +165,7 @@ def get_option(name):
 # every switch of csrc/mrdis_elem.hip OPT_DEFS (tests/test_abi.py checks that the library knows each name)
 OPTION_NAMES = ('wino', 'nt_mb', 'wino_pipe', 'wino_u', 'wino4', 'wino4r', 'bconv4', 'split6', 'debug_no16', 'debug_nothin', 'debug_noc4', 'debug_nodma',
                 'debug_no16_3d', 'debug_bilgen', 'debug_now16', 'debug_nopack', 'debug_mode', 'debug_bn', 'debug_kc', 'debug_bm', 'debug_c4_tw',
-                'debug_wgsplit', 'debug_bn3', 'debug_kc3', 'c4_grid', 'debug_c4_blocks', 'zsearch_grid')
+                'debug_wgsplit', 'debug_bn3', 'debug_kc3', 'c4_grid', 'debug_c4_blocks', 'zsearch_grid', 'debug_volgen')
 
 
 def options_snapshot():
@@ -197,6 +198,8 @@ OUTDEC_FAMILIES = ('chatt', 'symdiff', 'rgate')
 # gradient keeps counting under 'wino_spade' and the six-product 3-D kernels under 'split6_c3d' / 'split6_w3d' (KERNEL_FAMILIES): renaming
 # them would only churn the 2-D table.  Outside KERNEL_FAMILIES for the same reason as the tables above (tests/test_gpu_conv3d_paths.py covers them).
 CONV3D_FAMILIES = ('direct3d', 'c3d16', 'wgrad3d', 'wgrad3d16', 'wino_wgrad3d')
+# the 3-D batch gather (csrc/mrdis_volgather.hip): one count per mrdis_volume_gather call, whichever of its two kernels ran.
+DATA_FAMILIES = ('volgather',)
 
 
 def stream_fill(t, value=0.0):
@@ -224,7 +227,7 @@ def dynamic_lds():
 def launch_counts(reset=False):
     """{family: launches since load / the last reset} of the Winograd, bf16 LDS-DMA and six-product (split6) kernel families (include/mrdis.h mrdis_launch_count)"""
     lib = load()
-    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES}
+    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES}
     if reset:
         lib.mrdis_launch_count_reset()
     return out
@@ -1103,6 +1106,23 @@ def slice_gather(vol_ptrs, slice_idx, drop, H, W, D, block):
     _chk(lib.mrdis_slice_gather(_ptr(vol_ptrs), _ptr(slice_idx), _ptr(drop), _ptr(inputs), C, _ptr(mask), _ptr(mask_img),
                                 B, M, H, W, D, block, _stream()), 'slice_gather')
     return inputs, mask, mask_img
+
+
+def volume_gather(table, M, H, W, D, z0, Dz, targets=False, K=0, relabel=False):
+    """table (B, >= 2M+3) int64 on the device (include/mrdis.h mrdis_volume_gather) -> inputs (B,M,H,W,Dz) channels-last-3d and mask (B,M), or
+    with `targets` the label volume (B,H,W,Dz) / its K region channels (B,K,H,W,Dz) channels-last-3d.  One launch."""
+    lib = load()
+    B, ld = table.shape
+    assert table.dtype == torch.int64 and table.is_contiguous()
+    dev = table.device
+    if not targets:
+        out = torch.empty((B, H, W, Dz, M), dtype=torch.float32, device=dev)
+        mask = torch.empty((B, M), dtype=torch.float32, device=dev)
+        _chk(lib.mrdis_volume_gather(_ptr(table), ld, _ptr(out), _ptr(mask), B, M, H, W, D, z0, Dz, 0, 0, 0, _stream()), 'volume_gather')
+        return out.permute(0, 4, 1, 2, 3), mask
+    out = torch.empty((B, H, W, Dz, K) if K else (B, H, W, Dz), dtype=torch.float32, device=dev)
+    _chk(lib.mrdis_volume_gather(_ptr(table), ld, _ptr(out), None, B, M, H, W, D, z0, Dz, 1, K, int(bool(relabel)), _stream()), 'volume_gather')
+    return out.permute(0, 4, 1, 2, 3) if K else out
 
 
 def recon_err_bwd(gt, x, w, p):

@@ -277,7 +277,9 @@ class NVNet3D(nn.Module):
 def nvnet_loss(uout, vout, mu, logvar, x, target):
     """The reference ships no objective for NVNet3D; this is the one of the paper its docstring cites (Myronenko 2018:
     soft Dice of sigmoid(uout) + 0.1 * L2 of the VAE reconstruction + 0.1 * KL), used by bench3d.py and the parity tests
-    to drive the backward pass."""
+    to drive the backward pass.  `target` has one channel per output channel of the net: with out_channels = 3 that is the three region
+    channels (label == 1, label == 2, label == 3) that `VolumeLoader3D(region_channels=3)` writes.  Like the objective itself this is the
+    package's own convention, not the reference's: its 3-D dataset returns the label volume and nothing consumes it."""
     p = torch.sigmoid(uout)
     dice = 1 - 2 * (p * target).sum() / ((p * p).sum() + (target * target).sum() + 1e-6)
     l2 = ((vout - x) ** 2).mean()

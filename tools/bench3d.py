@@ -3,6 +3,11 @@ step (forward, nvnet_loss, backward, Adam on the flat arena) and, with --layers,
 net (forward / data gradient / weight gradient, TFLOP/s against the 157 TFLOP/s fp32 MFMA peak).
 
     python tools/bench3d.py [--size 128] [--batch 4] [--channels 16] [--steps 5] [--layers]
+    python tools/bench3d.py --loader [--batch 4] [--vol 160 192 155]      # the HBM-resident 3-D loader (data3d.py) in front of that step
+
+--loader builds a synthetic BraTS-shaped store, times the one-launch batch gather (mrdis_volume_gather) beside a store-only probe over the same
+buffer and beside the obvious torch composition of the same batch (stack, slice, flip, mul / add, where, permute().contiguous()), then times
+the configs[4]-shaped step fed by a fixed batch and fed by the loader.  One JSON line per measurement.
 """
 import argparse
 import json
@@ -66,6 +71,100 @@ def layer_table(B, S, c, reps):
     return rows
 
 
+def torch_batch(store, ds, metas):
+    """the loader's batch as the obvious torch composition (what a user would write without the gather kernel)"""
+    H, W, D = store.shape
+    z0, Dz = ds.crop()
+    xs = []
+    for sid, _, ptrs, drop, tptr, flip, scale, shift in metas:
+        vols = [store.vols.get(sid + '/' + c) if m != drop else None for m, c in enumerate(ds.contrast_list)]
+        raw = torch.stack([v[:, :, z0:z0 + Dz] if v is not None else torch.zeros(H, W, Dz, device=store.device) for v in vols])
+        if flip:
+            raw = raw.flip(1)
+        x = raw * scale + shift
+        xs.append(torch.where(raw == raw.min(), torch.full_like(x, -10.0), x))
+    return torch.stack(xs).permute(0, 2, 3, 4, 1).contiguous().permute(0, 4, 1, 2, 3)
+
+
+def loader_bench(a):
+    import numpy as np
+    dev = torch.device('cuda:0')
+    H, W, D = a.vol
+    B, M, nsubj = a.batch, 4, 8
+    contrasts = ['T1', 'T1c', 'T2', 'T2_FLAIR']
+    g = torch.Generator().manual_seed(2)
+    store = mrdis.VolumeStore3D(dev)
+    yy, xx = torch.meshgrid(torch.arange(H), torch.arange(W), indexing='ij')
+    inside = (((yy - H / 2) / (0.4 * H)) ** 2 + ((xx - W / 2) / (0.42 * W)) ** 2 <= 1)[:, :, None]
+    for s in range(nsubj):
+        for ci, c in enumerate(contrasts):
+            if (s + ci) % 5 == 0:
+                continue                                     # a missing contrast now and then
+            store.add(f's{s:02d}/{c}', torch.where(inside, torch.randn(H, W, D, generator=g), torch.tensor(-10.0)).numpy())
+        store.add(f's{s:02d}/seg', (torch.randint(0, 5, (H, W, D), generator=g) * inside).float().numpy())
+    ds = mrdis.VolumeDataset3D('BraTS', store, [f's{s:02d}' for s in range(nsubj)], contrasts, aug=True, dropoff=True)
+    loader = mrdis.VolumeLoader3D(ds, B, shuffle=True, region_channels=3)
+    z0, Dz = ds.crop()
+    np.random.seed(1); torch.manual_seed(1)
+    _, _, metas = next(iter(loader.batch_plan()))
+    tab = torch.from_numpy(loader.table(metas)[0]).to(dev)
+    x, _ = mrdis.hip.volume_gather(tab, M, H, W, D, z0, Dz)
+    want = torch_batch(store, ds, [(m[0], m[1], m[2], m[3], m[4], m[5], float(np.float32(m[6])), float(np.float32(m[7]))) for m in metas])
+    assert torch.equal(x, want), 'gather and torch composition disagree'
+    present = sum(1 for m in metas for k, p in enumerate(m[2]) if p and k != m[3])
+    moved = 4.0 * H * W * Dz * (present + B * M)              # bytes the algorithm needs: every present crop read once, the batch written once
+    out_buf = torch.empty(B * H * W * Dz * M, device=dev)
+    t_fill = timeit(lambda: mrdis.hip.stream_fill(out_buf), a.reps)
+    rows = []
+    for gen, name in ((0, 'gather (LDS tile kernel)'), (1, 'gather (element kernel)')):
+        with mrdis.hip.option('debug_volgen', gen):
+            t = timeit(lambda: mrdis.hip.volume_gather(tab, M, H, W, D, z0, Dz), a.reps)
+        rows.append({'metric': name, 'us': round(t, 1), 'moved_mb': round(moved / 1e6, 1), 'tb_per_s': round(moved / t / 1e6, 2)})
+    t_tgt = timeit(lambda: mrdis.hip.volume_gather(tab, M, H, W, D, z0, Dz, targets=True, K=3, relabel=True), a.reps)
+    rows.append({'metric': 'target gather, 3 region channels', 'us': round(t_tgt, 1)})
+    rows.append({'metric': 'store-only probe over the batch buffer', 'us': round(t_fill, 1), 'written_mb': round(4.0 * out_buf.numel() / 1e6, 1),
+                 'tb_per_s': round(4.0 * out_buf.numel() / t_fill / 1e6, 2)})
+    t_torch = timeit(lambda: torch_batch(store, ds, metas), a.reps)
+    rows.append({'metric': 'torch composition of the same batch', 'us': round(t_torch, 1), 'over_gather': round(t_torch / rows[0]['us'], 2)})
+    for r in rows:
+        r['config'] = f'B={B} M={M} {H}x{W}x{D} (Dz={Dz}) fp32'
+        print(json.dumps(r), flush=True)
+    if a.steps < 1:
+        return
+    # the configs[4]-shaped step (NVNet3D, init_channels 16) on this batch shape: fed by one fixed batch, then with the loader in the loop
+    torch.manual_seed(10)
+    model = mrdis.NVNet3D((H, W, Dz), M, 3, a.channels, p=0.2).to(dev).train()
+    opt = mrdis.ArenaAdam(model.parameters(), lr=1e-4, weight_decay=1e-5)
+
+    def step(x, t):
+        loss, _ = mrdis.nvnet_loss(*model(x), x, t)
+        loss.backward()
+        opt.step(fused_clip=True)
+        opt.zero_grad()
+        return loss
+
+    def batches():
+        while True:
+            yield from loader
+
+    it = batches()
+    b0 = next(it)
+    for _ in range(a.warmup):
+        step(b0['inputs'], b0['targets'])
+    res = {}
+    for name in ('fixed batch', 'loader in the loop', 'fixed batch', 'loader in the loop'):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            b = b0 if name == 'fixed batch' else next(it)
+            loss = step(b['inputs'], b['targets'])
+        torch.cuda.synchronize()
+        res.setdefault(name, []).append((time.perf_counter() - t0) / a.steps * 1e3)
+    print(json.dumps({'metric': 'NVNet3D train step, ms (two alternating windows each)', 'fixed_batch': [round(v, 2) for v in res['fixed batch']],
+                      'loader_in_loop': [round(v, 2) for v in res['loader in the loop']], 'steps_per_window': a.steps,
+                      'config': f'B={B} M={M} {H}x{W}x{Dz} fp32, init_channels {a.channels}', 'loss': float(loss.detach())}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--size', type=int, default=128)
@@ -75,12 +174,17 @@ def main():
     ap.add_argument('--warmup', type=int, default=2)
     ap.add_argument('--layers', action='store_true')
     ap.add_argument('--reps', type=int, default=5)
+    ap.add_argument('--loader', action='store_true')
+    ap.add_argument('--vol', type=int, nargs=3, default=[160, 192, 155], help='--loader: H W D of the stored volumes')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs an MI355X (no CPU fallback)'
     dev = torch.device('cuda:0')
     mrdis.hip.load()
     if a.layers:
         layer_table(a.batch, a.size, a.channels, a.reps)
+        return
+    if a.loader:
+        loader_bench(a)
         return
     S, B = a.size, a.batch
     torch.manual_seed(10)
