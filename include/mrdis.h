@@ -84,7 +84,7 @@ long long mrdis_get_option(const char* name);
  * "split6_c4" | "split6_c16" | "split6_wgrad16" | "split6_co4" | "split6_c3d" | "split6_w3d" | "split6_tap" (option split6: the 4 -> C kernel, the 32 -> 16 forward, its weight gradient, the
  * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "zsearch" (mrdis_cosine_top1); "conv2src" | "ana_act" (the others variants); "kl" | "avgpool" (the latent-code options); "chatt" | "symdiff" | "rgate" (the attention output decoders);
  * "direct3d" | "c3d16" | "wgrad3d" | "wgrad3d16" | "wino_wgrad3d" (the 3-D tap-table, 16-cout, generic and narrow weight-gradient kernels and the hybrid
- * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "all" (every kernel launch of the library).  MRDIS_EINVAL for an unknown name.  Diagnostics: the parity tests
+ * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "volgather"; "loss3d" | "segcounts" (the fused 3-D objective, one count per forward and per backward call, and the segmentation counts); "all" (every kernel launch of the library).  MRDIS_EINVAL for an unknown name.  Diagnostics: the parity tests
  * use it to prove that the form under test is the one that ran. */
 long long mrdis_launch_count(const char* family);
 void mrdis_launch_count_reset(void);
@@ -411,6 +411,34 @@ int mrdis_slice_gather(const void* vol_ptrs, const int* slice_idx, const int* dr
  * M, K <= 64, any H, W, Dz >= 1 (H W D < 2^31).  One kernel launch per call, counted as "volgather".                           */
 int mrdis_volume_gather(const void* table, int ld_table, float* out, float* mask, int B, int M, int H, int W, int D, int z0,
                         int Dz, int mode, int K, int relabel, void* stream);
+
+/* ---- objective of the 3-D nets (model3d.nvnet_loss) fused: soft Dice of sigmoid(uout) against `target`, GLOBAL over the batch, plus
+ * w_l2 times the mean squared error of vout against x (csrc/mrdis_loss3d.hip).  uout / target: fp32 of one shape (shape_ut, nd_ut <= 8
+ * extents) and ONE dense memory layout, given by their element strides; vout / x likewise with shape_vx, or both NULL for the Dice-only
+ * form (UNet3D).  Strides that differ inside a pair return MRDIS_EINVAL, a layout with holes MRDIS_EUNSUPPORTED, a base that is not
+ * 16-byte aligned MRDIS_EALIGN: nothing is ever copied.  Any element count (a tail of n % 4 floats is handled).
+ * fwd: ONE pass over the four tensors + a one-workgroup finish.  sums (device, 4 doubles) = { sum p t, sum p^2, sum t^2, sum (v - x)^2 },
+ *   p = sigmoid(uout); terms (device, 3 floats) = { dice = 1 - 2 sums[0] / (sums[1] + sums[2] + 1e-6), l2 = sums[3] / n_vx (0 without vout),
+ *   dice + w_l2 l2 }, evaluated in fp64 and rounded once.  Fixed reduction order through `workspace` (16-byte aligned), no floating-point
+ *   atomics: bit-identical from run to run.
+ * bwd: ONE pass.  du = g [(-2 t / den + 4 sums[0] p / den^2) p (1 - p)], dv = g w_l2 2 (v - x) / n_vx, den = sums[1] + sums[2] + 1e-6,
+ *   written in the layout of uout / vout; g (one float, the gradient of terms[2]) and sums are DEVICE pointers: no host sync.  du or dv
+ *   may be NULL (not wanted).  Each call counts once as "loss3d".                                                                 */
+size_t mrdis_nvnet_loss_workspace(long long n_ut, long long n_vx);
+int mrdis_nvnet_loss_fwd(const float* uout, const long long* stride_u, const float* target, const long long* stride_t,
+                         const long long* shape_ut, int nd_ut, const float* vout, const long long* stride_v, const float* x,
+                         const long long* stride_x, const long long* shape_vx, int nd_vx, double w_l2, double* sums, float* terms,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int mrdis_nvnet_loss_bwd(const float* uout, const long long* stride_u, const float* target, const long long* stride_t,
+                         const long long* shape_ut, int nd_ut, const float* vout, const long long* stride_v, const float* x,
+                         const long long* stride_x, const long long* shape_vx, int nd_vx, double w_l2, const double* sums,
+                         const float* g, float* du, float* dv, void* stream);
+
+/* ---- the integer counts behind the reference's Dice / IoU (compute_segmentation_metrics_single, util.py:980-992).  pred, target:
+ * (B, P, C) fp32, channel fastest (channels-last-3d of (B, C, H, W, D)), target channel c = (label == c + 1).
+ * out (B, C, 3) int32 += { |pred > 0.5 and target == 1|, |pred > 0.5|, |target == 1| } (strictly above 0.5); the caller zeroes `out`.
+ * apply_sigmoid != 0: pred holds logits, the kernel compares sigmoid(pred).  C <= 4, P C < 2^31.  One launch, counted as "segcounts". */
+int mrdis_seg_counts(const float* pred, const float* target, int* out, int B, long long P, int C, int apply_sigmoid, void* stream);
 
 /* ---- max_pool2d(kernel k x k, stride k): model.py:3448-3451 ---------------- */
 int mrdis_maxpool_fwd(const float* x, int ldx, float* y, int32_t* argmax, int N, int H, int W, int C,

@@ -1,0 +1,16 @@
+#!/usr/bin/env python3
+"""Entry point of the 3-D nets (NVNet3D / UNet3D), the counterpart of `main_missing.py`: reads `config3d.yaml` (or the file named first on
+the command line, then key=value overrides), trains with a validation pass per epoch or scores the test set on the MI355X hot path.
+
+    python main_3d.py                            # config3d.yaml in the working directory, else the built-in defaults
+    python main_3d.py cfg3d.yaml epochs=2 batch_size=2 ckpt_path=/tmp/ckpt3d
+    python main_3d.py cfg3d.yaml phase=test
+"""
+import os
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import mrdis  # noqa: E402
+
+if __name__ == '__main__':
+    mrdis.train3d.main()

@@ -35,6 +35,7 @@ enum { MRDIS_CNT_WINO, MRDIS_CNT_WINO_SPADE, MRDIS_CNT_WINO2, MRDIS_CNT_WINO2_SP
        MRDIS_CNT_CHATT, MRDIS_CNT_SYMDIFF, MRDIS_CNT_RGATE /* mrdis_outdec.hip: the attention output decoders */,
        MRDIS_CNT_DIRECT3D, MRDIS_CNT_C3D16, MRDIS_CNT_WGRAD3D, MRDIS_CNT_WGRAD3D16, MRDIS_CNT_WINO_WGRAD3D /* mrdis_conv3d.hip / mrdis_wino.hip: the 3-D kernels */,
        MRDIS_CNT_VOLGATHER /* mrdis_volgather.hip: the 3-D batch gather, one count per mrdis_volume_gather call */,
+       MRDIS_CNT_LOSS3D, MRDIS_CNT_SEGCOUNTS /* mrdis_loss3d.hip: one count per mrdis_nvnet_loss_fwd / _bwd call; one per mrdis_seg_counts call */,
        MRDIS_CNT_ALL /* every launch of the library */, MRDIS_CNT_COUNT };
 void mrdis_count(int id);
 

@@ -1988,7 +1988,7 @@ const char* const CNT_NAMES[MRDIS_CNT_COUNT] = {"wino", "wino_spade", "wino2", "
                                                 "wino_wgrad", "wino_wgrad2", "wino4_wgrad", "bconv3", "bconv3_spade", "bconv4", "bconv4_spade",
                                                 "split6_c4", "split6_c16", "split6_wgrad16", "split6_co4", "split6_c3d", "split6_w3d", "split6_tap", "zsearch",
                                                 "conv2src", "ana_act", "kl", "avgpool", "chatt", "symdiff", "rgate",
-                                                "direct3d", "c3d16", "wgrad3d", "wgrad3d16", "wino_wgrad3d", "volgather", "all"};
+                                                "direct3d", "c3d16", "wgrad3d", "wgrad3d16", "wino_wgrad3d", "volgather", "loss3d", "segcounts", "all"};
 long long g_counts[MRDIS_CNT_COUNT];
 }  // namespace
 void mrdis_count(int id) { __atomic_fetch_add(&g_counts[id], 1LL, __ATOMIC_RELAXED); }

@@ -90,6 +90,10 @@ _SIGS = {
     'mrdis_recon_metrics': (_I, [_P, _I, _P, _I, _P, _P, _Z, _I, _I, _I, _P]),
     'mrdis_slice_gather': (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_volume_gather': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'mrdis_nvnet_loss_workspace': (_Z, [_L, _L]),
+    'mrdis_nvnet_loss_fwd': (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_double, _P, _P, _P, _Z, _P]),
+    'mrdis_nvnet_loss_bwd': (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_double, _P, _P, _P, _P, _P]),
+    'mrdis_seg_counts': (_I, [_P, _P, _P, _I, _L, _I, _I, _P]),
     'mrdis_maxpool_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_bwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_sumsq_workspace': (_Z, []),
@@ -200,6 +204,9 @@ OUTDEC_FAMILIES = ('chatt', 'symdiff', 'rgate')
 CONV3D_FAMILIES = ('direct3d', 'c3d16', 'wgrad3d', 'wgrad3d16', 'wino_wgrad3d')
 # the 3-D batch gather (csrc/mrdis_volgather.hip): one count per mrdis_volume_gather call, whichever of its two kernels ran.
 DATA_FAMILIES = ('volgather',)
+# the fused objective of the 3-D nets and the segmentation counts (csrc/mrdis_loss3d.hip): 'loss3d' counts one per mrdis_nvnet_loss_fwd and one per
+# mrdis_nvnet_loss_bwd call, 'segcounts' one per mrdis_seg_counts call.
+LOSS3D_FAMILIES = ('loss3d', 'segcounts')
 
 
 def stream_fill(t, value=0.0):
@@ -227,7 +234,7 @@ def dynamic_lds():
 def launch_counts(reset=False):
     """{family: launches since load / the last reset} of the Winograd, bf16 LDS-DMA and six-product (split6) kernel families (include/mrdis.h mrdis_launch_count)"""
     lib = load()
-    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES}
+    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES}
     if reset:
         lib.mrdis_launch_count_reset()
     return out
@@ -1123,6 +1130,76 @@ def volume_gather(table, M, H, W, D, z0, Dz, targets=False, K=0, relabel=False):
     out = torch.empty((B, H, W, Dz, K) if K else (B, H, W, Dz), dtype=torch.float32, device=dev)
     _chk(lib.mrdis_volume_gather(_ptr(table), ld, _ptr(out), None, B, M, H, W, D, z0, Dz, 1, K, int(bool(relabel)), _stream()), 'volume_gather')
     return out.permute(0, 4, 1, 2, 3) if K else out
+
+
+def _layout_args(a, b, what):
+    """(stride array of a, of b, shape array, ndim) for the entry points that take two tensors of one shape and check their layout themselves"""
+    if a.dtype != torch.float32 or b.dtype != torch.float32:
+        raise MrdisError(f'{what}: fp32 tensors only, got {a.dtype} and {b.dtype}')
+    if tuple(a.shape) != tuple(b.shape) or not 1 <= a.dim() <= 8:
+        raise MrdisError(f'{what}: shapes {tuple(a.shape)} and {tuple(b.shape)} must be equal (1 to 8 dimensions)')
+    nd = a.dim()
+    arr = _c.c_longlong * nd
+    return arr(*a.stride()), arr(*b.stride()), arr(*a.shape), nd
+
+
+def nvnet_loss_fwd(uout, target, vout=None, x=None, w_l2=0.1):
+    """-> (sums (4,) float64 = [sum p t, sum p^2, sum t^2, sum (v - x)^2], terms (3,) float32 = [dice, l2, dice + w_l2 * l2]), both on the device
+    (include/mrdis.h mrdis_nvnet_loss_fwd).  uout / target and vout / x: one shape and one dense layout per pair, else MrdisError; nothing is copied."""
+    lib = load()
+    su, st, shu, ndu = _layout_args(uout, target, 'nvnet_loss_fwd (uout, target)')
+    if (vout is None) != (x is None):
+        raise MrdisError('nvnet_loss_fwd: vout and x come together or not at all')
+    sv = sx = shv = None
+    ndv = 0
+    if vout is not None:
+        sv, sx, shv, ndv = _layout_args(vout, x, 'nvnet_loss_fwd (vout, x)')
+    dev = uout.device
+    sums = torch.empty(4, dtype=torch.float64, device=dev)
+    terms = torch.empty(3, dtype=torch.float32, device=dev)
+    nb = _ws_bytes(lib.mrdis_nvnet_loss_workspace, uout.numel(), 0 if vout is None else vout.numel())
+    ws = _ws(nb, dev)
+    _chk(lib.mrdis_nvnet_loss_fwd(_ptr(uout), su, _ptr(target), st, shu, ndu, _ptr(vout), sv, _ptr(x), sx, shv, ndv, float(w_l2),
+                                  _ptr(sums), _ptr(terms), _ptr(ws), nb, _stream()), 'nvnet_loss_fwd')
+    return sums, terms
+
+
+def nvnet_loss_bwd(g, sums, uout, target, vout=None, x=None, w_l2=0.1, need_du=True, need_dv=True):
+    """-> (du, dv) in the layouts of uout / vout (None where not wanted); g: the gradient of terms[2], one fp32 value on the device."""
+    lib = load()
+    su, st, shu, ndu = _layout_args(uout, target, 'nvnet_loss_bwd (uout, target)')
+    sv = sx = shv = None
+    ndv = 0
+    if vout is not None:
+        sv, sx, shv, ndv = _layout_args(vout, x, 'nvnet_loss_bwd (vout, x)')
+    need_dv = need_dv and vout is not None
+    if not (need_du or need_dv):
+        return None, None
+    g = g.reshape(1)
+    if g.dtype != torch.float32 or g.device != uout.device:
+        raise MrdisError('nvnet_loss_bwd: the incoming gradient must be one fp32 value on the tensors\' device')
+    du = torch.empty_like(uout) if need_du else None          # (preserve_format: a dense tensor keeps its strides)
+    dv = torch.empty_like(vout) if need_dv else None
+    if (du is not None and du.stride() != uout.stride()) or (dv is not None and dv.stride() != vout.stride()):
+        raise MrdisError('nvnet_loss_bwd: non-dense input')
+    _chk(lib.mrdis_nvnet_loss_bwd(_ptr(uout), su, _ptr(target), st, shu, ndu, _ptr(vout), sv, _ptr(x), sx, shv, ndv, float(w_l2),
+                                  _ptr(sums), _ptr(g), _ptr(du), _ptr(dv), _stream()), 'nvnet_loss_bwd')
+    return du, dv
+
+
+def seg_counts(pred, target, logits=False):
+    """(B, C, 3) int32 on the device = per sample and channel [|pred > 0.5 and target == 1|, |pred > 0.5|, |target == 1|] of (B, C, D, H, W) tensors
+    (include/mrdis.h mrdis_seg_counts); `logits`: the kernel applies the sigmoid.  One launch on channels-last-3d inputs (what the nets and the
+    loader write); an input in any other layout is first COPIED into that layout (`ndhwc`), unlike the objective's entry points, which refuse."""
+    lib = load()
+    if tuple(pred.shape) != tuple(target.shape):
+        raise MrdisError(f'seg_counts: shapes {tuple(pred.shape)} and {tuple(target.shape)} differ')
+    pred, _ = ndhwc(pred); target, _ = ndhwc(target)
+    B, C = pred.shape[:2]
+    P = pred[0, 0].numel()
+    out = torch.zeros((B, C, 3), dtype=torch.int32, device=pred.device)
+    _chk(lib.mrdis_seg_counts(_ptr(pred), _ptr(target), _ptr(out), B, P, C, int(bool(logits)), _stream()), 'seg_counts')
+    return out
 
 
 def recon_err_bwd(gt, x, w, p):

@@ -285,3 +285,57 @@ def nvnet_loss(uout, vout, mu, logvar, x, target):
     l2 = ((vout - x) ** 2).mean()
     kl = (mu ** 2 + logvar.exp() - logvar - 1).sum() / x[0].numel()
     return dice + 0.1 * l2 + 0.1 * kl, {'dice': dice, 'l2': l2, 'kl': kl}
+
+
+# --------------------------------------------------------------------------- fused objective and segmentation metrics (csrc/mrdis_loss3d.hip)
+class _NVNetLossFn(Function):
+    """(dice + 0.1 * l2, dice, l2) of `nvnet_loss` in one pass over uout, target, vout, x; the backward writes both gradients in one pass.
+    Only the first output carries a gradient; the other two are the `parts` for the log."""
+
+    @staticmethod
+    def forward(ctx, uout, target, vout, x):
+        sums, terms = hip.nvnet_loss_fwd(uout, target, vout, x, 0.1)
+        ctx.save_for_backward(uout, target, vout, x, sums)
+        dice, l2 = terms[0], terms[1]
+        ctx.mark_non_differentiable(dice, l2)
+        return terms[2], dice, l2
+
+    @staticmethod
+    def backward(ctx, g, _gd, _gl):
+        uout, target, vout, x, sums = ctx.saved_tensors
+        du, dv = hip.nvnet_loss_bwd(g, sums, uout, target, vout, x, 0.1, need_du=ctx.needs_input_grad[0],
+                                    need_dv=vout is not None and ctx.needs_input_grad[2])
+        return du, None, dv, None
+
+
+def nvnet_loss_hip(uout, vout, mu, logvar, x, target):
+    """`nvnet_loss` with the Dice and reconstruction terms in the fused HIP kernels (mrdis_nvnet_loss_fwd / _bwd): same tuple, same `parts`
+    keys.  uout / target and vout / x must each share one dense memory layout (channels-last-3d as the nets and the loader write them): a
+    mismatch raises `MrdisError`, nothing is copied.  The KL term on the (B, 16) rows stays in torch.  `vout=None` (then mu / logvar may be
+    None too) is the Dice-only objective for `UNet3D`: l2 and kl are zeros."""
+    obj, dice, l2 = _NVNetLossFn.apply(uout, target, vout, x if vout is not None else None)
+    if vout is None or mu is None:
+        kl = torch.zeros((), dtype=torch.float32, device=uout.device)
+        return obj, {'dice': dice, 'l2': l2, 'kl': kl}
+    kl = (mu ** 2 + logvar.exp() - logvar - 1).sum() / x[0].numel()
+    return obj + 0.1 * kl, {'dice': dice, 'l2': l2, 'kl': kl}
+
+
+def seg_metrics_from_counts(counts):
+    """counts (B, C, 3) integers [intersection I, predicted P, labelled T] -> {'dice': (B,), 'iou': (B,)} float64: the reference's
+    compute_segmentation_metrics_single (util.py:980-992), dice_c = (2 I + 1) / (T + P + 1), iou_c = (I + 1) / (T + P - I + 1), averaged over
+    the region channels."""
+    c = np.asarray(counts).astype(np.float64)
+    i, p, t = c[..., 0], c[..., 1], c[..., 2]
+    dice = (2.0 * i + 1) / (t + p + 1)
+    iou = (i + 1) / (t + p - i + 1)
+    return {'dice': torch.from_numpy(dice.mean(axis=1)), 'iou': torch.from_numpy(iou.mean(axis=1))}
+
+
+def seg_metrics(pred_or_logits, target, logits=True):
+    """Dice and IoU per sample of the reference's compute_segmentation_metrics (util.py:946-992): `target` holds the region channels
+    (channel c = (label == c + 1), what `VolumeLoader3D(region_channels=3)` yields), a voxel is predicted where the probability is strictly
+    above 0.5.  The integer counts come from ONE kernel launch (mrdis_seg_counts; `logits`: it applies the sigmoid), the ratios are
+    formed in float64 on the host (one small D2H copy).  Inputs that are not channels-last-3d are copied into that layout first (hip.seg_counts).
+    -> {'dice': (B,), 'iou': (B,)} float64 CPU tensors."""
+    return seg_metrics_from_counts(hip.seg_counts(pred_or_logits, target, logits=logits).cpu().numpy())

@@ -1,0 +1,279 @@
+"""Training and validation entry of the 3-D nets (`NVNet3D` / `UNet3D`), in the style of `train.Run`:
+
+    python main_3d.py [config3d.yaml] [key=value ...]
+
+The reference ships the 3-D networks and their dataset but no loop, objective or metric call for them; what is restated
+here is the package's own: the objective is `nvnet_loss` (Myronenko 2018) -- through the fused HIP kernels (`nvnet_loss_hip`,
+csrc/mrdis_loss3d.hip) unless `fused_loss: false` -- the optimizer is `ArenaAdam` with the fused clip, the validation metric is the reference's
+Dice / IoU (`compute_segmentation_metrics`, util.py:946-992) from the integer counts of `mrdis_seg_counts`, and stat.csv / `epochNNN.pth.tar` /
+`model_best.pth.tar` are written by the same `save_result_stat` / `save_checkpoint` as the 2-D entry.  The best checkpoint is the epoch with the
+highest validation Dice.
+
+A checkpoint also carries the host and device RNG states (np.random, torch default, the torch device generator, the loaders' own generator
+if any), written after the epoch's validation pass: `continue_train` then continues exactly where the run stopped -- the shuffles, augmentation
+draws, dropout masks and VAE noise of epoch k + 1 are those of an uninterrupted run.
+
+World size 1 only: under an initialised process group the constructor raises NotImplementedError.
+"""
+import glob
+import os
+import re
+import sys
+
+import numpy as np
+import torch
+import torch.distributed as dist
+import yaml
+
+from . import hip
+from .data3d import VolumeData3D
+from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, seg_metrics_from_counts
+from .train import parse_overrides, save_config_file, save_result_stat
+from .trainer import ArenaAdam, load_checkpoint_model, save_checkpoint
+
+DEFAULT_CONFIG_3D = {
+    'phase': 'train',                  # train | test (test: load model_best.pth.tar, print the test-set stat)
+    'dataset_name': 'BraTS', 'data_path': '../data/', 'norm_type': 'z-score', 'fold': 0,
+    'contrast_list': ['T1', 'T1c', 'T2', 'T2_FLAIR'], 'batch_size': 4,
+    'model_name': 'NVNet3D',           # NVNet3D | UNet3D (Dice-only objective)
+    'init_channels': 16, 'p': 0.2,
+    'aug': True, 'dropoff': True,
+    'epochs': 300, 'lr': 1e-4, 'weight_decay': 1e-5,
+    'lr_schedule': 'poly',             # none | poly: lr * (1 - epoch / epochs) ** 0.9
+    'fused_loss': True,                # false: the torch composition `nvnet_loss`
+    'ckpt_path': '../ckpt3d/', 'continue_train': False,
+    'ckpt_name': None,                 # checkpoint file to load; None: the last epochNNN.pth.tar (continue_train) / model_best.pth.tar (test)
+    'seed': 10, 'device': 'cuda:0',
+    'max_batches': None,               # cap on the batches of every train / validation / test pass (tests)
+}
+MODEL_NAMES = ('NVNet3D', 'UNet3D')
+LR_SCHEDULES = ('none', 'poly')
+STAT_KEYS = ('loss', 'loss_dice', 'loss_l2', 'loss_kl')
+
+
+def load_config3d(path=None, overrides=None):
+    """DEFAULT_CONFIG_3D <- the yaml file (if `path` is given it must exist) <- overrides; unknown keys are refused."""
+    cfg = dict(DEFAULT_CONFIG_3D)
+    if path is not None:
+        with open(path) as f:
+            cfg.update(yaml.safe_load(f) or {})
+    cfg.update(overrides or {})
+    unknown = sorted(set(cfg) - set(DEFAULT_CONFIG_3D))
+    if unknown:
+        raise KeyError(f'unknown config key(s) {unknown}: one of {sorted(DEFAULT_CONFIG_3D)}')
+    for k, v in cfg.items():                     # yaml reads `lr=1e-4` (no dot) as a string
+        if isinstance(DEFAULT_CONFIG_3D[k], float) and not isinstance(v, bool) and isinstance(v, (str, int)):
+            cfg[k] = float(v)
+    if cfg['model_name'] not in MODEL_NAMES:
+        raise ValueError(f'model_name {cfg["model_name"]!r}: one of {MODEL_NAMES}')
+    if cfg['lr_schedule'] not in LR_SCHEDULES:
+        raise ValueError(f'lr_schedule {cfg["lr_schedule"]!r}: one of {LR_SCHEDULES}')
+    if cfg['phase'] not in ('train', 'test'):
+        raise ValueError(f'phase {cfg["phase"]!r}: train or test')
+    return cfg
+
+
+def parse_argv(argv):
+    """`[config3d.yaml] key=value ...` -> (path or None, overrides), as main_missing.py reads its command line."""
+    argv = list(argv)
+    path = None
+    if argv and '=' not in argv[0]:
+        path = argv.pop(0)
+    return path, parse_overrides(argv)
+
+
+def poly_lr(lr, epoch, epochs):
+    return lr * (1.0 - epoch / float(epochs)) ** 0.9
+
+
+def epoch_lr(config, epoch):
+    return poly_lr(config['lr'], epoch, config['epochs']) if config['lr_schedule'] == 'poly' else config['lr']
+
+
+def dice_loss_torch(uout, target):
+    """the Dice term of `nvnet_loss` alone (UNet3D with fused_loss: false)"""
+    p = torch.sigmoid(uout)
+    return 1 - 2 * (p * target).sum() / ((p * p).sum() + (target * target).sum() + 1e-6)
+
+
+def last_epoch_checkpoint(ckpt_path):
+    """name of the epochNNN.pth.tar with the highest epoch number (by value: 'epoch1000' comes after 'epoch999')"""
+    best = None
+    for fn in glob.glob(os.path.join(ckpt_path, 'epoch*.pth.tar')):
+        m = re.fullmatch(r'epoch(\d+)\.pth\.tar', os.path.basename(fn))
+        if m and (best is None or int(m.group(1)) > best[0]):
+            best = (int(m.group(1)), os.path.basename(fn))
+    if best is None:
+        raise ValueError(f'No correct checkpoint under {ckpt_path}')
+    return best[1]
+
+
+class Run3D:
+    """model + ArenaAdam + the three loaders of a fold, with train() / evaluate().  `store`: a VolumeStore3D instead of the h5 file under
+    `data_path` (the list files are still read from there); `data`: a ready VolumeData3D-like object (trainLoader / valLoader / testLoader)."""
+
+    def __init__(self, config, store=None, data=None, log=print):
+        if dist.is_available() and dist.is_initialized():
+            raise NotImplementedError('Run3D runs on one process only (world size 1): data-parallel 3-D training is not implemented; '
+                                      'start it without a process group')
+        self.config = cfg = load_config3d(None, config)
+        self.log = log
+        self.device = dev = torch.device(cfg['device'])
+        torch.manual_seed(cfg['seed']); np.random.seed(cfg['seed'])
+        if dev.type == 'cuda':
+            torch.cuda.manual_seed(cfg['seed'])
+        if data is None:
+            data = VolumeData3D(cfg['dataset_name'], cfg['data_path'], norm_type=cfg['norm_type'], batch_size=cfg['batch_size'], fold=cfg['fold'],
+                                shuffle=True, contrast_list=cfg['contrast_list'], aug=cfg['aug'], dropoff=cfg['dropoff'], store=store,
+                                device=dev, region_channels=3)
+        self.data = data
+        self.loaders = {'train': data.trainLoader, 'val': data.valLoader, 'test': data.testLoader}
+        ds = data.trainLoader.dataset
+        H, W, _ = ds.store.shape
+        self.input_shape = (H, W, ds.crop()[1])
+        M = len(cfg['contrast_list'])
+        net = NVNet3D if cfg['model_name'] == 'NVNet3D' else UNet3D
+        self.model = net(self.input_shape, M, 3, cfg['init_channels'], p=cfg['p']).to(dev)
+        self.optimizer = ArenaAdam(self.model.parameters(), lr=cfg['lr'], weight_decay=cfg['weight_decay'], used=list(self.model.parameters()))
+        self.start_epoch = -1
+        self.best_dice = -1.0
+        if cfg['continue_train'] or cfg['phase'] == 'test':
+            self._load(cfg['ckpt_name'] or (last_epoch_checkpoint(cfg['ckpt_path']) if cfg['phase'] == 'train' else 'model_best.pth.tar'))
+        if cfg['phase'] == 'train':
+            os.makedirs(cfg['ckpt_path'], exist_ok=True)
+            save_config_file(cfg)
+
+    # ---- RNG states in the checkpoint
+    def _generators(self):
+        return {k: l.generator for k, l in self.loaders.items() if getattr(l, 'generator', None) is not None}
+
+    def rng_state(self):
+        st = {'numpy': np.random.get_state(), 'torch': torch.get_rng_state(),
+              'loaders': {k: g.get_state() for k, g in self._generators().items()}}
+        if self.device.type == 'cuda':
+            st['device'] = torch.cuda.get_rng_state(self.device)
+        return st
+
+    def set_rng_state(self, st):
+        np.random.set_state(st['numpy'])
+        torch.set_rng_state(st['torch'].cpu())
+        if self.device.type == 'cuda' and 'device' in st:
+            torch.cuda.set_rng_state(st['device'].cpu(), self.device)
+        for k, g in self._generators().items():
+            if k in st.get('loaders', {}):
+                g.set_state(st['loaders'][k].cpu())
+
+    def _load(self, name):
+        cfg = self.config
+        fn = os.path.join(cfg['ckpt_path'], name)
+        if not os.path.isfile(fn):
+            raise ValueError(f'No correct checkpoint: {fn}')
+        ck = torch.load(fn, map_location=self.device, weights_only=False)
+        missing = load_checkpoint_model(self.model, ck['model'])
+        if missing:
+            raise ValueError(f'{fn}: {len(missing)} tensors do not fit {cfg["model_name"]} (init_channels {cfg["init_channels"]}), e.g. {missing[:3]}')
+        if cfg['phase'] == 'train':
+            self.optimizer.load_state_dict(ck['optimizer'])
+            self.best_dice = float(ck.get('best_dice', ck['monitor_metric']))
+            if 'rng' in ck:
+                self.set_rng_state(ck['rng'])
+        self.start_epoch = int(ck['epoch'])
+        self.log(f'loaded {name} (epoch {self.start_epoch}, validation dice {float(ck["monitor_metric"]):.4f})')
+
+    # ---- the objective
+    def objective(self, out, x, target):
+        """(loss, [loss, dice term, l2, kl] as a device vector) of one forward"""
+        fused = self.config['fused_loss']
+        if self.config['model_name'] == 'NVNet3D':
+            uout, vout, mu, logvar = out
+            loss, parts = (nvnet_loss_hip if fused else nvnet_loss)(uout, vout, mu, logvar, x, target)
+        else:
+            uout = out[0]
+            if fused:
+                loss, parts = nvnet_loss_hip(uout, None, None, None, x, target)
+            else:
+                loss = dice_loss_torch(uout, target)
+                zero = torch.zeros((), dtype=torch.float32, device=uout.device)
+                parts = {'dice': loss, 'l2': zero, 'kl': zero}
+        vec = torch.stack([loss.detach().reshape(()), parts['dice'].detach().reshape(()), parts['l2'].detach().reshape(()),
+                           parts['kl'].detach().reshape(())])
+        return loss, vec
+
+    def train_step(self, batch):
+        x, target = batch['inputs'], batch['targets']
+        loss, vec = self.objective(self.model(x), x, target)
+        loss.backward()
+        self.optimizer.step(fused_clip=True)
+        self.optimizer.zero_grad()
+        return vec
+
+    def _batches(self, loader):
+        return loader.batches(limit=self.config['max_batches']) if self.config['max_batches'] else iter(loader)
+
+    def train(self):
+        """epochs start_epoch + 1 .. epochs - 1"""
+        return self._train(self.config['epochs'])
+
+    def _train(self, stop):
+        """epochs start_epoch + 1 .. stop - 1; a `stop` below `epochs` ends the run as an interruption would (the schedule still spans `epochs`)"""
+        cfg = self.config
+        for epoch in range(self.start_epoch + 1, min(cfg['epochs'], stop)):
+            self.optimizer.param_groups[0]['lr'] = epoch_lr(cfg, epoch)
+            self.model.train()
+            acc, n = None, 0
+            for batch in self._batches(self.loaders['train']):
+                vec = self.train_step(batch)
+                acc = vec if acc is None else acc + vec             # device accumulators: one D2H copy per epoch
+                n += 1
+            if n == 0:
+                raise RuntimeError(f'epoch {epoch}: the train loader yielded no batch')
+            mean = (acc.double() / n).cpu()
+            train_stat = {k: float(mean[i]) for i, k in enumerate(STAT_KEYS)}
+            if not np.isfinite(train_stat['loss']):
+                raise FloatingPointError(f'epoch {epoch}: loss is {train_stat["loss"]}')
+            save_result_stat(train_stat, cfg, info='epoch[%2d]' % epoch)
+            stat = self.evaluate('val')
+            save_result_stat(stat, cfg, info='val')
+            is_best = stat['dice'] > self.best_dice
+            if is_best:
+                self.best_dice = stat['dice']
+            state = {'epoch': epoch, 'monitor_metric': stat['dice'], 'best_dice': self.best_dice, 'stat': stat,
+                     'optimizer': self.optimizer.state_dict(), 'scheduler': {'lr_schedule': cfg['lr_schedule']},
+                     'model': self.model.state_dict(), 'rng': self.rng_state()}
+            save_checkpoint(state, is_best, cfg['ckpt_path'])
+            self.last_stat = stat
+            self.log(f'epoch {epoch}: train loss {train_stat["loss"]:.4f}, val loss {stat["loss"]:.4f}, dice {stat["dice"]:.4f}, '
+                     f'iou {stat["iou"]:.4f}, lr {self.optimizer.lr:g}, best {is_best}')
+        return self
+
+    def evaluate(self, set_='val'):
+        """eval-mode pass over a loader: the loss means over its batches, the mean Dice / IoU over its volumes"""
+        self.model.eval()
+        acc, n, counts = None, 0, []
+        with torch.no_grad():
+            for batch in self._batches(self.loaders[set_]):
+                x, target = batch['inputs'], batch['targets']
+                out = self.model(x)
+                _, vec = self.objective(out, x, target)
+                counts.append(hip.seg_counts(out[0], target, logits=True))
+                acc = vec if acc is None else acc + vec
+                n += 1
+        if n == 0:
+            raise RuntimeError(f'evaluate({set_!r}): the loader yielded no batch')
+        mean = (acc.double() / n).cpu()
+        stat = {k: float(mean[i]) for i, k in enumerate(STAT_KEYS)}
+        met = seg_metrics_from_counts(torch.cat(counts).cpu().numpy())      # one D2H copy per pass
+        stat['dice'], stat['iou'] = float(met['dice'].mean()), float(met['iou'].mean())
+        return stat
+
+
+def main(argv=None):
+    path, overrides = parse_argv(sys.argv[1:] if argv is None else argv)
+    if path is None and os.path.exists('config3d.yaml'):
+        path = 'config3d.yaml'
+    run = Run3D(load_config3d(path, overrides))
+    if run.config['phase'] == 'train':
+        run.train()
+    else:
+        print(run.evaluate('test'))
+    return run

@@ -4,10 +4,15 @@ net (forward / data gradient / weight gradient, TFLOP/s against the 157 TFLOP/s 
 
     python tools/bench3d.py [--size 128] [--batch 4] [--channels 16] [--steps 5] [--layers]
     python tools/bench3d.py --loader [--batch 4] [--vol 160 192 155]      # the HBM-resident 3-D loader (data3d.py) in front of that step
+    python tools/bench3d.py --loss-only                                   # the objective alone, forward + backward: torch composition vs fused HIP kernels
+    python tools/bench3d.py --fused-loss                                  # the step with the torch objective and with the fused one, alternating windows
 
 --loader builds a synthetic BraTS-shaped store, times the one-launch batch gather (mrdis_volume_gather) beside a store-only probe over the same
 buffer and beside the obvious torch composition of the same batch (stack, slice, flip, mul / add, where, permute().contiguous()), then times
-the configs[4]-shaped step fed by a fixed batch and fed by the loader.  One JSON line per measurement.
+the configs[4]-shaped step fed by a fixed batch and fed by the loader.  --loss-only times `nvnet_loss` + autograd against `nvnet_loss_hip`
+(csrc/mrdis_loss3d.hip) on the net's own output shapes, the two kernels alone (achieved bytes/s from the bytes the algorithm needs) beside the
+store-only probe, and prints both objectives' error against a float64 evaluation.  --fused-loss times the whole step with either objective in
+alternating windows; the torch windows repeat, which gives the box's run-to-run spread.  One JSON line per measurement.
 """
 import argparse
 import json
@@ -165,6 +170,108 @@ def loader_bench(a):
                       'config': f'B={B} M={M} {H}x{W}x{Dz} fp32, init_channels {a.channels}', 'loss': float(loss.detach())}), flush=True)
 
 
+def loss_f64(uout, vout, mu, logvar, x, target):
+    """`nvnet_loss` evaluated in float64 with autograd: (loss, d loss / d uout, d loss / d vout)"""
+    u = uout.detach().double().requires_grad_(True)
+    v = vout.detach().double().requires_grad_(True)
+    loss, _ = mrdis.nvnet_loss(u, v, mu.double(), logvar.double(), x.double(), target.double())
+    loss.backward()
+    return loss.detach(), u.grad, v.grad
+
+
+def loss_inputs(B, S, dev, seed=1):
+    g = torch.Generator().manual_seed(seed)
+    mk = lambda c: torch.randn(B, S, S, S, c, generator=g).to(dev).permute(0, 4, 1, 2, 3)
+    uout, vout, x = mk(3), mk(4), mk(4)
+    t = (torch.rand(B, S, S, S, 3, generator=g) > 0.7).float().to(dev).permute(0, 4, 1, 2, 3)
+    mu, logvar = torch.randn(B, 16, generator=g).to(dev), (0.1 * torch.randn(B, 16, generator=g)).to(dev)
+    return uout, vout, mu, logvar, x, t
+
+
+def loss_bench(a):
+    dev = torch.device('cuda:0')
+    B, S = a.batch, a.size
+    uout, vout, mu, logvar, x, t = loss_inputs(B, S, dev)
+    cfgs = f'{B}x3x{S}^3 + {B}x4x{S}^3 fp32 channels-last-3d'
+
+    def run(fn):
+        u = uout.detach().requires_grad_(True); v = vout.detach().requires_grad_(True)
+        loss, _ = fn(u, v, mu, logvar, x, t)
+        loss.backward()
+        return loss.detach(), u.grad, v.grad
+
+    # parity of both objectives against float64 (the yardstick of tests/test_gpu_loss3d.py)
+    l64, du64, dv64 = loss_f64(uout, vout, mu, logvar, x, t)
+    err = {}
+    for name, fn in (('torch', mrdis.nvnet_loss), ('fused', mrdis.nvnet_loss_hip)):
+        l, du, dv = run(fn)
+        err[name] = dict(loss_rel=float(((l.double() - l64) / l64).abs()), du_max_abs=float((du.double() - du64).abs().max()),
+                         dv_max_abs=float((dv.double() - dv64).abs().max()))
+    print(json.dumps({'metric': 'objective error against float64', 'config': cfgs, 'loss_f64': float(l64), 'du_max_f64': float(du64.abs().max()),
+                      'dv_max_f64': float(dv64.abs().max()), **{f'{k}_{n}': v for n, e in err.items() for k, v in e.items()}}), flush=True)
+    del l64, du64, dv64
+    # forward + backward per call, alternating (torch, fused) x 3: the repeats give the spread
+    rows = {'torch': [], 'fused': []}
+    for _ in range(3):
+        for name, fn in (('torch', mrdis.nvnet_loss), ('fused', mrdis.nvnet_loss_hip)):
+            rows[name].append(round(timeit(lambda: run(fn), a.reps), 1))
+    print(json.dumps({'metric': 'objective forward + backward, us per call (three alternating windows)', 'config': cfgs, 'torch_nvnet_loss': rows['torch'],
+                      'fused_nvnet_loss_hip': rows['fused'], 'reps_per_window': a.reps,
+                      'torch_over_fused': round(min(rows['torch']) / min(rows['fused']), 2)}), flush=True)
+    # the two kernels alone, and the store-only probe over a buffer as large as what the backward writes
+    n1, n2 = uout.numel(), vout.numel()
+    sums, _ = mrdis.hip.nvnet_loss_fwd(uout, t, vout, x)
+    gone = torch.ones(1, device=dev)
+    t_f = timeit(lambda: mrdis.hip.nvnet_loss_fwd(uout, t, vout, x), a.reps)
+    t_b = timeit(lambda: mrdis.hip.nvnet_loss_bwd(gone, sums, uout, t, vout, x), a.reps)
+    buf = torch.empty(n1 + n2, device=dev)
+    t_s = timeit(lambda: mrdis.hip.stream_fill(buf), a.reps)
+    t_e = timeit(lambda: torch.empty_like(uout), a.reps)
+    rd, wr = 4.0 * 2 * (n1 + n2), 4.0 * (n1 + n2)
+    print(json.dumps({'metric': 'mrdis_nvnet_loss_fwd (kernel + finish)', 'us': round(t_f, 1), 'read_mb': round(rd / 1e6, 1), 'tb_per_s': round(rd / t_f / 1e6, 2)}), flush=True)
+    print(json.dumps({'metric': 'mrdis_nvnet_loss_bwd (incl. two torch.empty_like)', 'us': round(t_b, 1), 'read_mb': round(rd / 1e6, 1), 'written_mb': round(wr / 1e6, 1),
+                      'tb_per_s': round((rd + wr) / t_b / 1e6, 2), 'empty_like_us': round(t_e, 1)}), flush=True)
+    print(json.dumps({'metric': 'store-only probe over du + dv bytes', 'us': round(t_s, 1), 'written_mb': round(wr / 1e6, 1), 'tb_per_s': round(wr / t_s / 1e6, 2)}), flush=True)
+    tc = (torch.rand(B, S, S, S, 3, device=dev) > 0.5).float().permute(0, 4, 1, 2, 3)
+    t_c = timeit(lambda: mrdis.hip.seg_counts(uout, tc, logits=True), a.reps)
+    print(json.dumps({'metric': 'mrdis_seg_counts (logits, incl. zeroing the counts)', 'us': round(t_c, 1), 'read_mb': round(8.0 * n1 / 1e6, 1),
+                      'tb_per_s': round(8.0 * n1 / t_c / 1e6, 2)}), flush=True)
+
+
+def step_bench(a):
+    """the NVNet3D step with the torch objective (what the parent ran) and with the fused one: alternating windows torch, fused, torch, fused, torch"""
+    dev = torch.device('cuda:0')
+    S, B = a.size, a.batch
+    torch.manual_seed(10)
+    model = mrdis.NVNet3D((S, S, S), 4, 3, a.channels, p=0.2).to(dev).train()
+    opt = mrdis.ArenaAdam(model.parameters(), lr=1e-4, weight_decay=1e-5)
+    g = torch.Generator().manual_seed(1)
+    x = torch.randn(B, S, S, S, 4, generator=g).to(dev).permute(0, 4, 1, 2, 3)
+    t = (torch.rand(B, S, S, S, 3, generator=g) > 0.7).float().to(dev).permute(0, 4, 1, 2, 3)
+
+    def step(fn):
+        loss, _ = fn(*model(x), x, t)
+        loss.backward()
+        opt.step(fused_clip=True)
+        opt.zero_grad()
+        return loss
+
+    for _ in range(a.warmup):
+        step(mrdis.nvnet_loss); step(mrdis.nvnet_loss_hip)
+    res = {'torch': [], 'fused': []}
+    for name in ('torch', 'fused', 'torch', 'fused', 'torch'):
+        fn = mrdis.nvnet_loss if name == 'torch' else mrdis.nvnet_loss_hip
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.steps):
+            loss = step(fn)
+        torch.cuda.synchronize()
+        res[name].append(round((time.perf_counter() - t0) / a.steps * 1e3, 2))
+    print(json.dumps({'metric': 'NVNet3D train step, ms (alternating windows)', 'torch_objective': res['torch'], 'fused_objective': res['fused'],
+                      'torch_spread_ms': round(max(res['torch']) - min(res['torch']), 2), 'steps_per_window': a.steps,
+                      'config': f'{B}x4x{S}^3 fp32, init_channels {a.channels}, dropout 0.2', 'loss': float(loss.detach())}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--size', type=int, default=128)
@@ -175,6 +282,8 @@ def main():
     ap.add_argument('--layers', action='store_true')
     ap.add_argument('--reps', type=int, default=5)
     ap.add_argument('--loader', action='store_true')
+    ap.add_argument('--loss-only', action='store_true', help='time the objective (forward + backward): torch composition vs fused HIP kernels')
+    ap.add_argument('--fused-loss', action='store_true', help='time the step with the torch objective and with the fused one')
     ap.add_argument('--vol', type=int, nargs=3, default=[160, 192, 155], help='--loader: H W D of the stored volumes')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs an MI355X (no CPU fallback)'
@@ -185,6 +294,12 @@ def main():
         return
     if a.loader:
         loader_bench(a)
+        return
+    if a.loss_only:
+        loss_bench(a)
+        return
+    if a.fused_loss:
+        step_bench(a)
         return
     S, B = a.size, a.batch
     torch.manual_seed(10)
