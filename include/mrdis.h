@@ -72,7 +72,7 @@ int mrdis_version(void);
  *           tools/ use it for A/B; results agree to fp32 rounding);
  *   "debug_nopack" (MRDIS_DEBUG_NOPACK, default 0): 1 = the four output-parity classes of a stride-2 data gradient as four launches
  *           instead of one (bit-identical results; A/B switch);
- *   other "debug_*": kernel-selection overrides used by tools/ (see csrc/mrdis_elem.hip OPT_DEFS);
+ *   other "debug_*": kernel-selection overrides used by tools/ (see csrc/mrdis_common.h MRDIS_OPTIONS);
  *   "zsearch_grid" (MRDIS_ZSEARCH_GRID, default 0): workgroups of mrdis_cosine_top1: 0 = min(gallery tiles, 1024), k > 0 = min(k, tiles, 2048) (results do not depend on it).
  * set: 0 or MRDIS_EINVAL (unknown name); get: the value, or MRDIS_EINVAL for an unknown name.  Safe from any thread: a change
  * applies to launches that start after the call returns (a launch already in progress on another thread may still see the old value). */

@@ -16,10 +16,6 @@
 #include "mrdis_tapconv.h"
 #include <type_traits>
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned bw_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned bw_u32x2 __attribute__((ext_vector_type(2)));
 
 
 __device__ __forceinline__ bf16x8 cvt8(const float4 a, const float4 b) {
@@ -217,7 +213,7 @@ __device__ __forceinline__ void bconv_body(const TapConvParams& p, const BConvGe
                     // tools/micro/store_pattern.hip).  Both lanes of a pair own the same position, so they take the same branches above.
 #pragma unroll
                     for (int j = 0; j < WC; ++j) {
-                        bw_u32x2 pk[4];
+                        u32x2 pk[4];
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const int co = co0 + 32 * (wave_c * WC + j) + 8 * q + 4 * half;
@@ -225,14 +221,13 @@ __device__ __forceinline__ void bconv_body(const TapConvParams& p, const BConvGe
                             if (p.bias && co < p.Cout) { const float4 bb = *reinterpret_cast<const float4*>(p.bias + co); v.x += bb.x; v.y += bb.y; v.z += bb.z; v.w += bb.w; }
                             if (lrelu) { v.x = v.x > 0.f ? v.x : 0.2f * v.x; v.y = v.y > 0.f ? v.y : 0.2f * v.y; v.z = v.z > 0.f ? v.z : 0.2f * v.z; v.w = v.w > 0.f ? v.w : 0.2f * v.w; }
                             bf16x4 r; r[0] = (__bf16)v.x; r[1] = (__bf16)v.y; r[2] = (__bf16)v.z; r[3] = (__bf16)v.w;
-                            pk[q] = __builtin_bit_cast(bw_u32x2, r);
+                            pk[q] = __builtin_bit_cast(u32x2, r);
                         }
 #pragma unroll
                         for (int q = 0; q < 4; q += 2) {
-                            const auto s0 = __builtin_amdgcn_permlane32_swap(pk[q][0], pk[q + 1][0], false, false);
-                            const auto s1 = __builtin_amdgcn_permlane32_swap(pk[q][1], pk[q + 1][1], false, false);
+                            const u32x4 w8 = mrdis_pair8(pk[q], pk[q + 1]);
                             const int co = co0 + 32 * (wave_c * WC + j) + 8 * (q + half);          // this lane's eight consecutive couts
-                            if (co < p.Cout && !(ABL & 16)) *reinterpret_cast<bw_u32x4*>(reinterpret_cast<__bf16*>(dst) + co) = bw_u32x4{s0[0], s1[0], s0[1], s1[1]};
+                            if (co < p.Cout && !(ABL & 16)) *reinterpret_cast<u32x4*>(reinterpret_cast<__bf16*>(dst) + co) = w8;
                         }
                     }
                     continue;
@@ -432,7 +427,6 @@ struct BWgradParams {
 };
 struct BWgradPack { BWgradParams c[4]; };           // the four input-parity classes of a stride-2 layer (blockIdx.y)
 
-typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 template <int WCI, int WCO, typename TS, bool HALF>      // HALF: Ci = 16, the upper half of the 32-channel image stays zero
 __device__ __forceinline__ void bwgrad_body(const BWgradParams& p) {
@@ -621,7 +615,6 @@ __global__ __launch_bounds__(512) void bwgrad_pack_kernel(const BWgradPack pk) {
 // staging offsets are tile-invariant.  Same products, same order per workgroup: results identical to bwgrad_kernel's.
 template <int V_> struct BwIC { static constexpr int value = V_; };
 constexpr unsigned BW_OOB = 0xfffffff0u;
-__device__ __forceinline__ int bw_opaque(int idx) { asm volatile("" : "+v"(idx)); return idx; }
 
 #ifndef BW2_AHEAD
 #define BW2_AHEAD 1
@@ -683,10 +676,10 @@ __global__ __launch_bounds__(512, 1) void bwgrad2_kernel(const BWgradParams p, c
         y_lds[it] = ((qq >> 2) * TP + m) * 32 + 8 * (qq & 3);
         y_rel[it] = 2u * (unsigned)(((nb * p.H + ty) * p.W + tx) * p.lddy + co0 + 8 * qq);
     }
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, dy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_dy = mrdis_buffer_rsrc(p.dy, dy_bytes);
 
-    bw_u32x4 xr[2][XR], yr[2][YR];
+    u32x4 xr[2][XR], yr[2][YR];
     unsigned xo[XR], yo[YR];
     int ltile = split;                                 // load cursor
     auto next_offsets = [&]() {
@@ -723,10 +716,10 @@ __global__ __launch_bounds__(512, 1) void bwgrad2_kernel(const BWgradParams p, c
     auto store1 = [&](auto S_, __bf16* dys, __bf16* xs, int k) {
         constexpr int S = decltype(S_)::value;
         if (k < XR) {
-            if (tid + k * 512 < npix * XQ) *reinterpret_cast<bw_u32x4*>(xs + x_lds[k]) = xr[S][k];
+            if (tid + k * 512 < npix * XQ) *reinterpret_cast<u32x4*>(xs + x_lds[k]) = xr[S][k];
         } else {
-            *reinterpret_cast<bw_u32x4*>(dys + y_lds[k - XR]) = yr[S][k - XR];
-            union { bw_u32x4 u; bf16x8 v; } c; c.u = yr[S][k - XR];
+            *reinterpret_cast<u32x4*>(dys + y_lds[k - XR]) = yr[S][k - XR];
+            union { u32x4 u; bf16x8 v; } c; c.u = yr[S][k - XR];
 #pragma unroll
             for (int j = 0; j < 8; ++j) bsum[j] += (float)c.v[j];
         }
@@ -752,8 +745,8 @@ __global__ __launch_bounds__(512, 1) void bwgrad2_kernel(const BWgradParams p, c
     const int ntile = (p.tiles - split + p.splits - 1) / p.splits;
     auto iteration = [&](auto P_) {
         constexpr int P = decltype(P_)::value;
-        const __bf16* yb = lds + bw_opaque(P * DYS);
-        const __bf16* xb = lds + bw_opaque(2 * DYS + P * XS);
+        const __bf16* yb = lds + mrdis_opaque(P * DYS);
+        const __bf16* xb = lds + mrdis_opaque(2 * DYS + P * XS);
         __bf16* dyn = lds + (P ^ 1) * DYS;
         __bf16* xn = lds + 2 * DYS + (P ^ 1) * XS;
         next_offsets();                               // tile i + 2 -> register set P, one load per MFMA slot
@@ -915,8 +908,8 @@ __global__ __launch_bounds__(512, 1) void bwgrad3_kernel(const BWgradParams p, c
         b_lds[it] = ((qq >> 2) * TP + m) * 32 + 8 * (qq & 3);
     }
     const bool want_bias = p.bias_slab != nullptr && cib == 0;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, dy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_dy = mrdis_buffer_rsrc(p.dy, dy_bytes);
 
     // cursor of the tile whose copy is being issued (wave-uniform scalars)
     int ltile = split;
@@ -934,9 +927,7 @@ __global__ __launch_bounds__(512, 1) void bwgrad3_kernel(const BWgradParams p, c
     };
     auto dma = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned off, unsigned lds_byte) {
         const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_byte);
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(off), "s"(m0v), "s"(rs) : "memory");
+        mrdis_buffer_lds_dma16(m0v, off, rs);
     };
     auto dma1 = [&](int stage, int k_) {               // DMA k_ of NL of the cursor's tile into `stage`: x pieces first, then dy pieces
         if (k_ < NXM) {
@@ -975,7 +966,7 @@ __global__ __launch_bounds__(512, 1) void bwgrad3_kernel(const BWgradParams p, c
     const int ntile = (p.tiles - split + p.splits - 1) / p.splits;
     auto iteration = [&](auto P_) {
         constexpr int P = decltype(P_)::value;          // stage of the tile being multiplied; its copy two tiles ahead goes into stage (P + 2) % 3
-        const __bf16* sb = lds + bw_opaque(P * STAGE);
+        const __bf16* sb = lds + mrdis_opaque(P * STAGE);
         next_tile();
         union Op { bf16x8 v; s16x4 h[2]; };
         constexpr int AD = BW2_AHEAD;
@@ -996,8 +987,8 @@ __global__ __launch_bounds__(512, 1) void bwgrad3_kernel(const BWgradParams p, c
         if (want_bias) {                               // column sums of this tile's dy image (block-uniform branch)
 #pragma unroll
             for (int it = 0; it < YR; ++it) {
-                union { bw_u32x4 u; bf16x8 v; } c;
-                c.u = *reinterpret_cast<const bw_u32x4*>(sb + b_lds[it]);
+                union { u32x4 u; bf16x8 v; } c;
+                c.u = *reinterpret_cast<const u32x4*>(sb + b_lds[it]);
 #pragma unroll
                 for (int j = 0; j < 8; ++j) bsum[j] += (float)c.v[j];
             }

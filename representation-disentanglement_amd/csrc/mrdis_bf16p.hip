@@ -19,27 +19,13 @@
 // Results are bit-identical to bconv_kernel's (same products, same accumulation order).
 #include "mrdis_tapconv.h"
 
-typedef __bf16 bp_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bp_bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned bp_u32x4 __attribute__((ext_vector_type(4)));
-
-typedef unsigned bp_u32x2 __attribute__((ext_vector_type(2)));
 namespace {
-// The two half-waves of a lane pair (e, half) hold the cout groups 8 q + 4 half .. + 3 of one position: two 8-byte pieces per 8 couts.  Swapping
-// group q of the upper half with group q + 1 of the lower half (v_permlane32_swap, one instruction per dword) leaves every lane with 8
-// CONSECUTIVE couts -- half 0: 8 q .. 8 q + 7, half 1: 8 (q + 1) .. 8 (q + 1) + 7 -- i.e. one 16-byte store per lane where there were two 8-byte
-// stores: half as many write requests of twice the size reach L2 (the epilogue is bound by them: 80 of 140 us on the 256x256 level).
-__device__ __forceinline__ bp_u32x4 bp_pair8(bp_u32x2 gq, bp_u32x2 gq1) {
-    const auto s0 = __builtin_amdgcn_permlane32_swap(gq[0], gq1[0], false, false);
-    const auto s1 = __builtin_amdgcn_permlane32_swap(gq[1], gq1[1], false, false);
-    return bp_u32x4{s0[0], s1[0], s0[1], s1[1]};
-}
+// (the epilogue pairs the half-waves' 8-byte pieces into 16-byte stores, mrdis_pair8: it is bound by the write requests, 80 of 140 us on the 256x256 level)
 constexpr int P_KC = 32, P_PITCH = P_KC + 8, P_TH = 8, P_TW = 32, P_TINH = P_TH + 2, P_TINW = P_TW + 2, P_NPIX = P_TINH * P_TINW;
 constexpr int P_XS = P_NPIX * P_PITCH;                 // bf16 elements of one x image
 constexpr int P_BIAS = 1024;
 constexpr unsigned P_OOB = 0xfffffff0u;
 template <int V_> struct PIC { static constexpr int value = V_; };
-__device__ __forceinline__ int p_opaque(int idx) { asm volatile("" : "+v"(idx)); return idx; }
 }  // namespace
 
 struct BConv3Params {
@@ -98,8 +84,8 @@ __global__ __launch_bounds__(512, 1) void bconv3_kernel(const BConv3Params p) {
         const int co_g = SPADE ? ((co >> 5) ? p.C : 0) + (co & 31) : co;
         w_rel[it] = 2u * (unsigned)((p.widx[t < 9 ? t : 0] * p.Cout + co_g) * p.Cin + 8 * q);
     }
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = mrdis_buffer_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = mrdis_buffer_rsrc(p.w, p.w_bytes);
     for (int c = tid; c < P_BIAS; c += NT) Bs[c] = (p.bias != nullptr && c < p.Cout) ? p.bias[c] : 0.f;
 
     const int grid = gridDim.x;
@@ -125,7 +111,7 @@ __global__ __launch_bounds__(512, 1) void bconv3_kernel(const BConv3Params p) {
             l_xorg = 2u * (unsigned)(((n * p.H + l_h0) * p.W + l_w0) * p.ldin);        // wraps for halo origins; added mod 2^32 below
         }
     };
-    bp_u32x4 xr[2][XR], wr[2][WR];
+    u32x4 xr[2][XR], wr[2][WR];
     unsigned xo[XR], wo[WR];                           // byte offsets of the NEXT item's pieces
     auto next_offsets = [&]() {
         const unsigned c0b = 2u * (unsigned)(lc * P_KC);
@@ -142,15 +128,15 @@ __global__ __launch_bounds__(512, 1) void bconv3_kernel(const BConv3Params p) {
         }
         if (++lc == p.nchunks) { lc = 0; ++lj; load_unit(); }
     };
-    auto load_x = [&](auto S_, int it) { constexpr int S = decltype(S_)::value; if (ABL & 2) xr[S][it] = bp_u32x4{0u, 0u, 0u, 0u}; else xr[S][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)xo[it], 0, 0); };
-    auto load_w = [&](auto S_, int it) { constexpr int S = decltype(S_)::value; if (ABL & 2) wr[S][it] = bp_u32x4{0u, 0u, 0u, 0u}; else wr[S][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (int)wo[it], 0, 0); };
+    auto load_x = [&](auto S_, int it) { constexpr int S = decltype(S_)::value; if (ABL & 2) xr[S][it] = u32x4{0u, 0u, 0u, 0u}; else xr[S][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)xo[it], 0, 0); };
+    auto load_w = [&](auto S_, int it) { constexpr int S = decltype(S_)::value; if (ABL & 2) wr[S][it] = u32x4{0u, 0u, 0u, 0u}; else wr[S][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (int)wo[it], 0, 0); };
     auto store_x = [&](auto S_, __bf16* xs, int it) {
         constexpr int S = decltype(S_)::value;
-        if (x_yx[it] >= 0 && !(ABL & 4)) *reinterpret_cast<bp_u32x4*>(xs + x_lds[it]) = xr[S][it];
+        if (x_yx[it] >= 0 && !(ABL & 4)) *reinterpret_cast<u32x4*>(xs + x_lds[it]) = xr[S][it];
     };
     auto store_w = [&](auto S_, __bf16* ws, int it) {
         constexpr int S = decltype(S_)::value;
-        if (w_co[it] >= 0 && !(ABL & 4)) *reinterpret_cast<bp_u32x4*>(ws + w_lds[it]) = wr[S][it];
+        if (w_co[it] >= 0 && !(ABL & 4)) *reinterpret_cast<u32x4*>(ws + w_lds[it]) = wr[S][it];
     };
 
     f32x16 acc[WC];
@@ -180,23 +166,23 @@ __global__ __launch_bounds__(512, 1) void bconv3_kernel(const BConv3Params p) {
     int mj = 0, mc = 0;
     auto iteration = [&](auto P_) {
         constexpr int P = decltype(P_)::value;
-        const __bf16* wa = lds + p_opaque(P * WS + a_base);
-        const __bf16* xb = lds + p_opaque(2 * WS + P * P_XS + b_base);
+        const __bf16* wa = lds + mrdis_opaque(P * WS + a_base);
+        const __bf16* xb = lds + mrdis_opaque(2 * WS + P * P_XS + b_base);
         __bf16* wn = lds + (P ^ 1) * WS;              // item i + 1 goes here (from register set P ^ 1)
         __bf16* xn = lds + 2 * WS + (P ^ 1) * P_XS;
         next_offsets();                               // item i + 2: loaded into register set P in the first XR + WR steps
-        bp_bf16x8 af[2][WC], bf[2];
+        bf16x8 af[2][WC], bf[2];
 #pragma unroll
-        for (int j = 0; j < WC; ++j) af[0][j] = *reinterpret_cast<const bp_bf16x8*>(wa + 32 * j * P_PITCH);
-        bf[0] = *reinterpret_cast<const bp_bf16x8*>(xb + toff[0]);
+        for (int j = 0; j < WC; ++j) af[0][j] = *reinterpret_cast<const bf16x8*>(wa + 32 * j * P_PITCH);
+        bf[0] = *reinterpret_cast<const bf16x8*>(xb + toff[0]);
 #pragma unroll
         for (int s_ = 0; s_ < 18; ++s_) {
             const int t = s_ >> 1, ks = s_ & 1, c_ = s_ & 1;
             if (s_ + 1 < 18 && !(ABL & 8)) {
                 const int t1 = (s_ + 1) >> 1, ks1 = (s_ + 1) & 1;
 #pragma unroll
-                for (int j = 0; j < WC; ++j) af[c_ ^ 1][j] = *reinterpret_cast<const bp_bf16x8*>(wa + (t1 * BN + 32 * j) * P_PITCH + 16 * ks1);
-                bf[c_ ^ 1] = *reinterpret_cast<const bp_bf16x8*>(xb + toff[t1] + 16 * ks1);
+                for (int j = 0; j < WC; ++j) af[c_ ^ 1][j] = *reinterpret_cast<const bf16x8*>(wa + (t1 * BN + 32 * j) * P_PITCH + 16 * ks1);
+                bf[c_ ^ 1] = *reinterpret_cast<const bf16x8*>(xb + toff[t1] + 16 * ks1);
             }
             // staging slice of this step: loads of item i + 2 first, then the LDS stores of item i + 1
             if (s_ < XR) load_x(PIC<P>{}, s_);
@@ -220,18 +206,18 @@ __global__ __launch_bounds__(512, 1) void bconv3_kernel(const BConv3Params p) {
                 const int c0 = co0 / 2;                          // the workgroup's first channel
                 const long long pix = (long long)(n * p.H + a) * p.W + b;
                 const __bf16* zp = reinterpret_cast<const __bf16*>(p.z) + pix * p.ldz;
-                bp_bf16x4 zq[4]; float4 mu[4], rs[4];
+                bf16x4 zq[4]; float4 mu[4], rs[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {                  // loads first
                     const int ch = c0 + 8 * q + 4 * half;
                     const bool ok = pos_ok && ch < p.C;
-                    zq[q] = ok ? *reinterpret_cast<const bp_bf16x4*>(zp + ch) : bp_bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+                    zq[q] = ok ? *reinterpret_cast<const bf16x4*>(zp + ch) : bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
                     mu[q] = ch < p.C ? *reinterpret_cast<const float4*>(p.mean + (long long)n * p.C + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
                     rs[q] = ch < p.C ? *reinterpret_cast<const float4*>(p.rstd + (long long)n * p.C + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
                 }
                 __bf16* mixp = reinterpret_cast<__bf16*>(p.out) + pix * p.ldout;
                 __bf16* gamp = reinterpret_cast<__bf16*>(p.gamma_out) + pix * p.ldg;
-                bp_u32x2 pko[4], pkg[4];
+                u32x2 pko[4], pkg[4];
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const int ch = c0 + 8 * q + 4 * half;
@@ -240,7 +226,7 @@ __global__ __launch_bounds__(512, 1) void bconv3_kernel(const BConv3Params p) {
                     const float g[4] = {acc[0][4 * q] + bg.x, acc[0][4 * q + 1] + bg.y, acc[0][4 * q + 2] + bg.z, acc[0][4 * q + 3] + bg.w};
                     const float bt[4] = {acc[WC - 1][4 * q] + bb.x, acc[WC - 1][4 * q + 1] + bb.y, acc[WC - 1][4 * q + 2] + bb.z, acc[WC - 1][4 * q + 3] + bb.w};
                     const float m_[4] = {mu[q].x, mu[q].y, mu[q].z, mu[q].w}, r_[4] = {rs[q].x, rs[q].y, rs[q].z, rs[q].w};
-                    bp_bf16x4 o, og;
+                    bf16x4 o, og;
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         // gamma and beta reach the modulation kernel of the two-step path as bf16: round them the same way
@@ -248,15 +234,15 @@ __global__ __launch_bounds__(512, 1) void bconv3_kernel(const BConv3Params p) {
                         og[k] = (__bf16)g[k];
                         o[k] = (__bf16)(((float)zq[q][k] - m_[k]) * r_[k] * (1.f + gr) + br);
                     }
-                    if (p.wide) { pko[q] = __builtin_bit_cast(bp_u32x2, o); pkg[q] = __builtin_bit_cast(bp_u32x2, og); }
-                    else if (pos_ok && ch < p.C) { *reinterpret_cast<bp_bf16x4*>(mixp + ch) = o; *reinterpret_cast<bp_bf16x4*>(gamp + ch) = og; }
+                    if (p.wide) { pko[q] = __builtin_bit_cast(u32x2, o); pkg[q] = __builtin_bit_cast(u32x2, og); }
+                    else if (pos_ok && ch < p.C) { *reinterpret_cast<bf16x4*>(mixp + ch) = o; *reinterpret_cast<bf16x4*>(gamp + ch) = og; }
                 }
                 if (p.wide) {
 #pragma unroll
                     for (int q = 0; q < 4; q += 2) {
-                        const bp_u32x4 wo = bp_pair8(pko[q], pko[q + 1]), wg = bp_pair8(pkg[q], pkg[q + 1]);
+                        const u32x4 wo = mrdis_pair8(pko[q], pko[q + 1]), wg = mrdis_pair8(pkg[q], pkg[q + 1]);
                         const int ch = c0 + 8 * (q + half);
-                        if (pos_ok && ch < p.C) { *reinterpret_cast<bp_u32x4*>(mixp + ch) = wo; *reinterpret_cast<bp_u32x4*>(gamp + ch) = wg; }
+                        if (pos_ok && ch < p.C) { *reinterpret_cast<u32x4*>(mixp + ch) = wo; *reinterpret_cast<u32x4*>(gamp + ch) = wg; }
                     }
                 }
 #pragma unroll
@@ -269,7 +255,7 @@ __global__ __launch_bounds__(512, 1) void bconv3_kernel(const BConv3Params p) {
             if (p.wide && !(ABL & 16)) {
 #pragma unroll
                 for (int j = 0; j < WC; ++j) {
-                    bp_u32x2 pk[4];
+                    u32x2 pk[4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int co = co0 + 32 * j + 8 * q + 4 * half;
@@ -279,14 +265,14 @@ __global__ __launch_bounds__(512, 1) void bconv3_kernel(const BConv3Params p) {
 #pragma unroll
                             for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.f ? v[k] : 0.2f * v[k];
                         }
-                        bp_bf16x4 o; o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
-                        pk[q] = __builtin_bit_cast(bp_u32x2, o);
+                        bf16x4 o; o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
+                        pk[q] = __builtin_bit_cast(u32x2, o);
                     }
 #pragma unroll
                     for (int q = 0; q < 4; q += 2) {
-                        const bp_u32x4 w8 = bp_pair8(pk[q], pk[q + 1]);
+                        const u32x4 w8 = mrdis_pair8(pk[q], pk[q + 1]);
                         const int co = co0 + 32 * j + 8 * (q + half);          // this lane's eight consecutive couts
-                        if (pos_ok && co < p.Cout) *reinterpret_cast<bp_u32x4*>(dst + co) = w8;
+                        if (pos_ok && co < p.Cout) *reinterpret_cast<u32x4*>(dst + co) = w8;
                     }
 #pragma unroll
                     for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
@@ -304,8 +290,8 @@ __global__ __launch_bounds__(512, 1) void bconv3_kernel(const BConv3Params p) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.f ? v[k] : 0.2f * v[k];
                     }
-                    bp_bf16x4 o; o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
-                    if (pos_ok && co < p.Cout && (!(ABL & 16) || v[0] == 1.2345f)) *reinterpret_cast<bp_bf16x4*>(dst + co) = o;
+                    bf16x4 o; o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
+                    if (pos_ok && co < p.Cout && (!(ABL & 16) || v[0] == 1.2345f)) *reinterpret_cast<bf16x4*>(dst + co) = o;
                 }
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;

@@ -19,10 +19,6 @@
 // order): results are bit-identical to theirs.
 #include "mrdis_tapconv.h"
 
-typedef __bf16 bq_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bq_bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned bq_u32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned bq_u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 constexpr int Q_TW = 32, Q_INW = Q_TW + 2;
@@ -44,13 +40,6 @@ template <int NW, int KC, int RPW = 2, int DMAW = NW> struct QGeo {
 constexpr int Q_BIAS = 1024;
 constexpr unsigned Q_OOB = 0xfffffff0u;
 template <int V_> struct QIC { static constexpr int value = V_; };
-__device__ __forceinline__ int q_opaque(int idx) { asm volatile("" : "+v"(idx)); return idx; }
-// see bp_pair8 (mrdis_bf16p.hip): the two half-waves of a position swap one 4-cout piece so that every lane holds 8 consecutive couts (one 16-byte store)
-__device__ __forceinline__ bq_u32x4 bq_pair8(bq_u32x2 gq, bq_u32x2 gq1) {
-    const auto s0 = __builtin_amdgcn_permlane32_swap(gq[0], gq1[0], false, false);
-    const auto s1 = __builtin_amdgcn_permlane32_swap(gq[1], gq1[1], false, false);
-    return bq_u32x4{s0[0], s1[0], s0[1], s1[1]};
-}
 }  // namespace
 
 struct BConv4Params {
@@ -123,8 +112,8 @@ __global__ __launch_bounds__(64 * NW, 1) void bconv4_kernel(const BConv4Params p
         const int co_g = SPADE ? ((co >> 5) ? p.C : 0) + (co & 31) : co;
         w_rel[i] = 2u * (unsigned)((p.widx[t < 9 ? t : 0] * p.Cout + co_g) * p.Cin + 8 * pc);
     }
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = mrdis_buffer_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = mrdis_buffer_rsrc(p.w, p.w_bytes);
     for (int c = tid; c < Q_BIAS; c += NT) Bs[c] = (p.bias != nullptr && c < p.Cout) ? p.bias[c] : 0.f;
     const unsigned lds_raw = (unsigned)(size_t)(__attribute__((address_space(3))) void*)smem_q;
 
@@ -171,9 +160,7 @@ __global__ __launch_bounds__(64 * NW, 1) void bconv4_kernel(const BConv4Params p
     // before the barrier below is explicit) nor orders LDS reads behind them.
     auto dma = [&](const __amdgpu_buffer_rsrc_t& rs, unsigned off, unsigned lds_byte) {
         const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_raw + lds_byte);
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(off), "s"(m0v), "s"(rs) : "memory");
+        mrdis_buffer_lds_dma16(m0v, off, rs);
     };
     auto dma_x = [&](int stage, int i) { if (wave < DMAW && wave + DMAW * i < Q_XP && !((ABL & 2) && stage >= 0 && lj > 1)) dma(rs_in, x_off(i), (unsigned)(XBASE + stage * Q_XBYTES + 1024 * (wave + DMAW * i))); };
     auto dma_w = [&](int stage, int i) { if (wave < DMAW && wave + DMAW * i < WP && !((ABL & 2) && lj > 1)) dma(rs_w, w_off(i), (unsigned)(stage * WBYTES + 1024 * (wave + DMAW * i))); };
@@ -211,20 +198,20 @@ __global__ __launch_bounds__(64 * NW, 1) void bconv4_kernel(const BConv4Params p
     auto iteration = [&](auto P_) {
         constexpr int P = decltype(P_)::value;
         stamp(1);
-        const unsigned char* wa0 = smem_q + q_opaque(P * WBYTES + aaddr);
-        const unsigned char* wa1 = smem_q + q_opaque(P * WBYTES + (aaddr ^ 32));
+        const unsigned char* wa0 = smem_q + mrdis_opaque(P * WBYTES + aaddr);
+        const unsigned char* wa1 = smem_q + mrdis_opaque(P * WBYTES + (aaddr ^ 32));
         const unsigned char* xs = smem_q + P * Q_XBYTES;                // + xbase[dw] (^ 32) + the tap row: stage and row offsets stay in the instruction's immediate
         next_offsets();                                // item i + 1: its DMA goes out in the first steps below, into stage P ^ 1
         // operand registers in a ring of three: the reads of step s + 2 are issued in step s (a full step of MFMAs -- this wave's and its SIMD partner's --
         // covers their LDS latency; one step ahead left the matrix pipe waiting: 68 us of MFMA + operand reads + barriers against 37 us of MFMAs on 128 -> 256 at 64x64)
-        bq_bf16x8 af[3][WC], bf[3][RPW];
+        bf16x8 af[3][WC], bf[3][RPW];
         constexpr int NSTEP = 9 * G::KS;
         auto ld_ops = [&](int slot, int s1) {
             const int t1 = s1 / G::KS, ks1 = s1 % G::KS;
 #pragma unroll
-            for (int j = 0; j < WC; ++j) af[slot][j] = *reinterpret_cast<const bq_bf16x8*>((ks1 ? wa1 : wa0) + (t1 * BN + 32 * j) * RB);
+            for (int j = 0; j < WC; ++j) af[slot][j] = *reinterpret_cast<const bf16x8*>((ks1 ? wa1 : wa0) + (t1 * BN + 32 * j) * RB);
 #pragma unroll
-            for (int r = 0; r < RPW; ++r) bf[slot][r] = *reinterpret_cast<const bq_bf16x8*>(xs + (xbase[tap_dw(t1) + 1] ^ (ks1 << 5)) + (r + 1 + tap_dh(t1)) * (Q_INW * RB));
+            for (int r = 0; r < RPW; ++r) bf[slot][r] = *reinterpret_cast<const bf16x8*>(xs + (xbase[tap_dw(t1) + 1] ^ (ks1 << 5)) + (r + 1 + tap_dh(t1)) * (Q_INW * RB));
         };
         ld_ops(0, 0); ld_ops(1, 1);
         static_assert(Q_NXI <= NSTEP && NWI <= NSTEP, "at most one pixel and one filter piece per step");
@@ -265,12 +252,12 @@ __global__ __launch_bounds__(64 * NW, 1) void bconv4_kernel(const BConv4Params p
                     if (SPADE) {
                         const int c0 = co0 / 2;
                         const __bf16* zp = reinterpret_cast<const __bf16*>(p.z) + pix * p.ldz + c0 + 4 * half;
-                        bq_bf16x4 zq[4];
+                        bf16x4 zq[4];
 #pragma unroll
-                        for (int q = 0; q < 4; ++q) zq[q] = *reinterpret_cast<const bq_bf16x4*>(zp + 8 * q);
+                        for (int q = 0; q < 4; ++q) zq[q] = *reinterpret_cast<const bf16x4*>(zp + 8 * q);
                         __bf16* mixp = reinterpret_cast<__bf16*>(p.out) + pix * p.ldout + c0;
                         __bf16* gamp = reinterpret_cast<__bf16*>(p.gamma_out) + pix * p.ldg + c0;
-                        bq_u32x2 pko[4], pkg[4];
+                        u32x2 pko[4], pkg[4];
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const int ch = c0 + 8 * q + 4 * half;
@@ -281,36 +268,36 @@ __global__ __launch_bounds__(64 * NW, 1) void bconv4_kernel(const BConv4Params p
                             const float g[4] = {acc[r][0][4 * q] + bg.x, acc[r][0][4 * q + 1] + bg.y, acc[r][0][4 * q + 2] + bg.z, acc[r][0][4 * q + 3] + bg.w};
                             const float bt[4] = {acc[r][WC - 1][4 * q] + bb.x, acc[r][WC - 1][4 * q + 1] + bb.y, acc[r][WC - 1][4 * q + 2] + bb.z, acc[r][WC - 1][4 * q + 3] + bb.w};
                             const float m_[4] = {mu.x, mu.y, mu.z, mu.w}, r_[4] = {rs.x, rs.y, rs.z, rs.w};
-                            bq_bf16x4 o, og;
+                            bf16x4 o, og;
 #pragma unroll
                             for (int k = 0; k < 4; ++k) {
                                 const float gr = (float)(__bf16)g[k], br = (float)(__bf16)bt[k];
                                 og[k] = (__bf16)g[k];
                                 o[k] = (__bf16)(((float)zq[q][k] - m_[k]) * r_[k] * (1.f + gr) + br);
                             }
-                            pko[q] = __builtin_bit_cast(bq_u32x2, o); pkg[q] = __builtin_bit_cast(bq_u32x2, og);
+                            pko[q] = __builtin_bit_cast(u32x2, o); pkg[q] = __builtin_bit_cast(u32x2, og);
                         }
 #pragma unroll
                         for (int q = 0; q < 4; q += 2) {
-                            const bq_u32x4 wo_ = bq_pair8(pko[q], pko[q + 1]), wg = bq_pair8(pkg[q], pkg[q + 1]);
-                            *reinterpret_cast<bq_u32x4*>(mixp + 8 * (q + half)) = wo_; *reinterpret_cast<bq_u32x4*>(gamp + 8 * (q + half)) = wg;
+                            const u32x4 wo_ = mrdis_pair8(pko[q], pko[q + 1]), wg = mrdis_pair8(pkg[q], pkg[q + 1]);
+                            *reinterpret_cast<u32x4*>(mixp + 8 * (q + half)) = wo_; *reinterpret_cast<u32x4*>(gamp + 8 * (q + half)) = wg;
                         }
                     } else {
                         __bf16* dst = reinterpret_cast<__bf16*>(p.out) + pix * p.ldout + co0;
 #pragma unroll
                         for (int j = 0; j < WC; ++j) {
-                            bq_u32x2 pk[4];
+                            u32x2 pk[4];
 #pragma unroll
                             for (int q = 0; q < 4; ++q) {
                                 const float4 bb = *reinterpret_cast<const float4*>(Bs + co0 + 32 * j + 8 * q + 4 * half);
                                 float v[4] = {acc[r][j][4 * q] + bb.x, acc[r][j][4 * q + 1] + bb.y, acc[r][j][4 * q + 2] + bb.z, acc[r][j][4 * q + 3] + bb.w};
 #pragma unroll
                                 for (int k = 0; k < 4; ++k) v[k] = fmaxf(v[k], slope * v[k]);      // LeakyReLU(0.2), or the identity (slope 1): same values as the select
-                                bq_bf16x4 o; o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
-                                pk[q] = __builtin_bit_cast(bq_u32x2, o);
+                                bf16x4 o; o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
+                                pk[q] = __builtin_bit_cast(u32x2, o);
                             }
 #pragma unroll
-                            for (int q = 0; q < 4; q += 2) *reinterpret_cast<bq_u32x4*>(dst + 32 * j + 8 * (q + half)) = bq_pair8(pk[q], pk[q + 1]);
+                            for (int q = 0; q < 4; q += 2) *reinterpret_cast<u32x4*>(dst + 32 * j + 8 * (q + half)) = mrdis_pair8(pk[q], pk[q + 1]);
                         }
                     }
 #pragma unroll
@@ -327,18 +314,18 @@ __global__ __launch_bounds__(64 * NW, 1) void bconv4_kernel(const BConv4Params p
                 if (SPADE) {
                     const int c0 = co0 / 2;                          // the workgroup's first channel
                     const __bf16* zp = reinterpret_cast<const __bf16*>(p.z) + pix * p.ldz;
-                    bq_bf16x4 zq[4]; float4 mu[4], rs[4];
+                    bf16x4 zq[4]; float4 mu[4], rs[4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {                  // loads first
                         const int ch = c0 + 8 * q + 4 * half;
                         const bool ok = pos_ok && ch < p.C;
-                        zq[q] = ok ? *reinterpret_cast<const bq_bf16x4*>(zp + ch) : bq_bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+                        zq[q] = ok ? *reinterpret_cast<const bf16x4*>(zp + ch) : bf16x4{(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
                         mu[q] = ch < p.C ? *reinterpret_cast<const float4*>(p.mean + (long long)n * p.C + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
                         rs[q] = ch < p.C ? *reinterpret_cast<const float4*>(p.rstd + (long long)n * p.C + ch) : make_float4(0.f, 0.f, 0.f, 0.f);
                     }
                     __bf16* mixp = reinterpret_cast<__bf16*>(p.out) + pix * p.ldout;
                     __bf16* gamp = reinterpret_cast<__bf16*>(p.gamma_out) + pix * p.ldg;
-                    bq_u32x2 pko[4], pkg[4];
+                    u32x2 pko[4], pkg[4];
 #pragma unroll
                     for (int q = 0; q < 4; ++q) {
                         const int ch = c0 + 8 * q + 4 * half;
@@ -347,7 +334,7 @@ __global__ __launch_bounds__(64 * NW, 1) void bconv4_kernel(const BConv4Params p
                         const float g[4] = {acc[r][0][4 * q] + bg.x, acc[r][0][4 * q + 1] + bg.y, acc[r][0][4 * q + 2] + bg.z, acc[r][0][4 * q + 3] + bg.w};
                         const float bt[4] = {acc[r][WC - 1][4 * q] + bb.x, acc[r][WC - 1][4 * q + 1] + bb.y, acc[r][WC - 1][4 * q + 2] + bb.z, acc[r][WC - 1][4 * q + 3] + bb.w};
                         const float m_[4] = {mu[q].x, mu[q].y, mu[q].z, mu[q].w}, r_[4] = {rs[q].x, rs[q].y, rs[q].z, rs[q].w};
-                        bq_bf16x4 o, og;
+                        bf16x4 o, og;
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             // gamma and beta reach the modulation kernel of the two-step path as bf16: round them the same way
@@ -355,22 +342,22 @@ __global__ __launch_bounds__(64 * NW, 1) void bconv4_kernel(const BConv4Params p
                             og[k] = (__bf16)g[k];
                             o[k] = (__bf16)(((float)zq[q][k] - m_[k]) * r_[k] * (1.f + gr) + br);
                         }
-                        if (p.wide) { pko[q] = __builtin_bit_cast(bq_u32x2, o); pkg[q] = __builtin_bit_cast(bq_u32x2, og); }
-                        else if (pos_ok && ch < p.C) { *reinterpret_cast<bq_bf16x4*>(mixp + ch) = o; *reinterpret_cast<bq_bf16x4*>(gamp + ch) = og; }
+                        if (p.wide) { pko[q] = __builtin_bit_cast(u32x2, o); pkg[q] = __builtin_bit_cast(u32x2, og); }
+                        else if (pos_ok && ch < p.C) { *reinterpret_cast<bf16x4*>(mixp + ch) = o; *reinterpret_cast<bf16x4*>(gamp + ch) = og; }
                     }
                     if (p.wide) {
 #pragma unroll
                         for (int q = 0; q < 4; q += 2) {
-                            const bq_u32x4 wo_ = bq_pair8(pko[q], pko[q + 1]), wg = bq_pair8(pkg[q], pkg[q + 1]);
+                            const u32x4 wo_ = mrdis_pair8(pko[q], pko[q + 1]), wg = mrdis_pair8(pkg[q], pkg[q + 1]);
                             const int ch = c0 + 8 * (q + half);
-                            if (pos_ok && ch < p.C) { *reinterpret_cast<bq_u32x4*>(mixp + ch) = wo_; *reinterpret_cast<bq_u32x4*>(gamp + ch) = wg; }
+                            if (pos_ok && ch < p.C) { *reinterpret_cast<u32x4*>(mixp + ch) = wo_; *reinterpret_cast<u32x4*>(gamp + ch) = wg; }
                         }
                     }
                 } else {
                     __bf16* dst = reinterpret_cast<__bf16*>(p.out) + pix * p.ldout;
 #pragma unroll
                     for (int j = 0; j < WC; ++j) {
-                        bq_u32x2 pk[4];
+                        u32x2 pk[4];
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
                             const int co = co0 + 32 * j + 8 * q + 4 * half;
@@ -380,16 +367,16 @@ __global__ __launch_bounds__(64 * NW, 1) void bconv4_kernel(const BConv4Params p
 #pragma unroll
                                 for (int k = 0; k < 4; ++k) v[k] = v[k] > 0.f ? v[k] : 0.2f * v[k];
                             }
-                            bq_bf16x4 o; o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
-                            if (p.wide) pk[q] = __builtin_bit_cast(bq_u32x2, o);
-                            else if (pos_ok && co < p.Cout) *reinterpret_cast<bq_bf16x4*>(dst + co) = o;
+                            bf16x4 o; o[0] = (__bf16)v[0]; o[1] = (__bf16)v[1]; o[2] = (__bf16)v[2]; o[3] = (__bf16)v[3];
+                            if (p.wide) pk[q] = __builtin_bit_cast(u32x2, o);
+                            else if (pos_ok && co < p.Cout) *reinterpret_cast<bf16x4*>(dst + co) = o;
                         }
                         if (p.wide) {
 #pragma unroll
                             for (int q = 0; q < 4; q += 2) {
-                                const bq_u32x4 w8 = bq_pair8(pk[q], pk[q + 1]);
+                                const u32x4 w8 = mrdis_pair8(pk[q], pk[q + 1]);
                                 const int co = co0 + 32 * j + 8 * (q + half);          // this lane's eight consecutive couts
-                                if (pos_ok && co < p.Cout) *reinterpret_cast<bq_u32x4*>(dst + co) = w8;
+                                if (pos_ok && co < p.Cout) *reinterpret_cast<u32x4*>(dst + co) = w8;
                             }
                         }
                     }

@@ -23,7 +23,6 @@ struct C16Params {
 namespace {
 constexpr int C16_TH = 8, C16_TW = 32, C16_RW = C16_TW + 2, C16_NPX = (C16_TH + 2) * C16_RW;     // 340 pixels of input per tile
 constexpr unsigned C16_OOB = 0xfffffff0u;
-typedef unsigned c16_u32x4 __attribute__((ext_vector_type(4)));
 }
 
 template <int HALVES>
@@ -44,7 +43,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_kernel(const C16Params p) 
                               : make_float4(0.f, 0.f, 0.f, 0.f);
 
     // staging roles: item = (pixel of the 10 x 34 block, float4 piece)
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, p.x_bytes);
     int s_l[XR], s_ry[XR], s_rx[XR], s_q[XR];
 #pragma unroll
     for (int it = 0; it < XR; ++it) {
@@ -53,7 +52,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_kernel(const C16Params p) 
         s_ry[it] = pi / C16_RW; s_rx[it] = pi - s_ry[it] * C16_RW;
         s_l[it] = idx < C16_NPX * Q ? pi * PP + s_q[it] : -1;
     }
-    c16_u32x4 xr[XR];
+    u32x4 xr[XR];
     auto load_tile = [&](int tile) {                  // tile >= ntiles: every offset out of range -> zeros, no branch around a load
         const bool on = tile < p.ntiles;
         int t = tile;
@@ -70,7 +69,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_kernel(const C16Params p) 
     auto store_tile = [&]() {
 #pragma unroll
         for (int it = 0; it < XR; ++it)
-            if (s_l[it] >= 0) *reinterpret_cast<c16_u32x4*>(smem + s_l[it]) = xr[it];
+            if (s_l[it] >= 0) *reinterpret_cast<u32x4*>(smem + s_l[it]) = xr[it];
     };
 
     // MFMA role: tiles t = 0..3 of the wave = (row 2 wave + (t >> 1), columns 16 (t & 1) ..)
@@ -138,8 +137,6 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_kernel(const C16Params p) 
 // 16 cycles instead of 8 of 32.  The split of x happens once per input pixel, on its way from the staging registers into LDS: a pixel is three 64-byte runs
 // [hi | mid | lo] of 32 bf16 (+ 16 bytes: pitch 208 B = 52 words, the 16 pixels of a tile land on 16 distinct 4-bank groups), and a lane's B operand of
 // (tap, term) is one ds_read_b128.  The filter's three terms stay in registers (108 VGPRs).
-typedef __bf16 c16_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 c16_bf16x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256, 2) void conv3x3_c16_split6_kernel(const C16Params p) {
     constexpr int CI = 32, Q = CI / 4, PB = 208;                     // float4 pieces per pixel, LDS pixel pitch in BYTES
     constexpr int XR = (C16_NPX * Q + 255) / 256;                    // staging items per thread (11)
@@ -147,18 +144,17 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_split6_kernel(const C16Par
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, kq = lane >> 4;
 
     // the filter: A operand of tap g, term: row l16 = cout, k-slot j <-> channel 8 kq + j
-    c16_bf16x8 a[9][3];
+    bf16x8 a[9][3];
 #pragma unroll
     for (int g = 0; g < 9; ++g)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const float v = p.w[(g * CI + 8 * kq + j) * 16 + l16];
-            const __bf16 hi = (__bf16)v; const float r1 = v - (float)hi; const __bf16 mid = (__bf16)r1;
-            a[g][0][j] = hi; a[g][1][j] = mid; a[g][2][j] = (__bf16)(r1 - (float)mid);
+            mrdis_split3(v, a[g][0], a[g][1], a[g][2], j);
         }
     const float4 bv = p.bias ? make_float4(p.bias[4 * kq], p.bias[4 * kq + 1], p.bias[4 * kq + 2], p.bias[4 * kq + 3]) : make_float4(0.f, 0.f, 0.f, 0.f);
 
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, p.x_bytes);
     int s_l[XR], s_ry[XR], s_rx[XR], s_q[XR];                        // s_l: LDS byte offset of the item's hi quad, or -1
 #pragma unroll
     for (int it = 0; it < XR; ++it) {
@@ -167,7 +163,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_split6_kernel(const C16Par
         s_ry[it] = pi / C16_RW; s_rx[it] = pi - s_ry[it] * C16_RW;
         s_l[it] = idx < C16_NPX * Q ? pi * PB + 2 * s_q[it] : -1;
     }
-    c16_u32x4 xr[XR];
+    u32x4 xr[XR];
     auto load_tile = [&](int tile) {                  // tile >= ntiles: every offset out of range -> zeros, no branch around a load
         const bool on = tile < p.ntiles;
         int t = tile;
@@ -186,15 +182,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_split6_kernel(const C16Par
         for (int it = 0; it < XR; ++it) {
             if (s_l[it] < 0) continue;
             const float xv[4] = {__uint_as_float(xr[it].x), __uint_as_float(xr[it].y), __uint_as_float(xr[it].z), __uint_as_float(xr[it].w)};
-            c16_bf16x4 hi, mid, lo;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const __bf16 h_ = (__bf16)xv[c]; const float r1 = xv[c] - (float)h_; const __bf16 m_ = (__bf16)r1;
-                hi[c] = h_; mid[c] = m_; lo[c] = (__bf16)(r1 - (float)m_);
-            }
-            *reinterpret_cast<c16_bf16x4*>(smem_b + s_l[it]) = hi;
-            *reinterpret_cast<c16_bf16x4*>(smem_b + s_l[it] + 64) = mid;
-            *reinterpret_cast<c16_bf16x4*>(smem_b + s_l[it] + 128) = lo;
+            bf16x4 hi, mid, lo; mrdis_split3(xv, hi, mid, lo);
+            *reinterpret_cast<bf16x4*>(smem_b + s_l[it]) = hi;
+            *reinterpret_cast<bf16x4*>(smem_b + s_l[it] + 64) = mid;
+            *reinterpret_cast<bf16x4*>(smem_b + s_l[it] + 128) = lo;
         }
     };
 
@@ -215,12 +206,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16_split6_kernel(const C16Par
 #pragma unroll
         for (int g = 0; g < 9; ++g) {
             const int go = ((g / 3) * C16_RW + (g % 3)) * PB;
-            c16_bf16x8 xh[4], xm[4], xl[4];
+            bf16x8 xh[4], xm[4], xl[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                xh[t] = *reinterpret_cast<const c16_bf16x8*>(smem_b + boff[t] + go);
-                xm[t] = *reinterpret_cast<const c16_bf16x8*>(smem_b + boff[t] + go + 64);
-                xl[t] = *reinterpret_cast<const c16_bf16x8*>(smem_b + boff[t] + go + 128);
+                xh[t] = *reinterpret_cast<const bf16x8*>(smem_b + boff[t] + go);
+                xm[t] = *reinterpret_cast<const bf16x8*>(smem_b + boff[t] + go + 64);
+                xl[t] = *reinterpret_cast<const bf16x8*>(smem_b + boff[t] + go + 128);
             }
             // smallest products first; the four tiles of a wave share every A register
 #pragma unroll
@@ -267,17 +258,16 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16t_split6_kernel(const C16Pa
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, e = lane & 31, half = lane >> 5;
 
     // the filter: A operand of tap g, term: row e = cout (of 32), k-slot j <-> channel 8 half + j.  p.lrelu carries the tap flip (1: data gradient)
-    c16_bf16x8 a[9][3];
+    bf16x8 a[9][3];
 #pragma unroll
     for (int g = 0; g < 9; ++g)
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
             const int gf = p.lrelu ? 8 - g : g;
             const float v = p.w[(gf * CI + 8 * half + j) * 32 + e];
-            const __bf16 hi = (__bf16)v; const float r1 = v - (float)hi; const __bf16 mid = (__bf16)r1;
-            a[g][0][j] = hi; a[g][1][j] = mid; a[g][2][j] = (__bf16)(r1 - (float)mid);
+            mrdis_split3(v, a[g][0], a[g][1], a[g][2], j);
         }
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, p.x_bytes);
     int s_l[XR], s_ry[XR], s_rx[XR], s_q[XR];
 #pragma unroll
     for (int it = 0; it < XR; ++it) {
@@ -286,7 +276,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16t_split6_kernel(const C16Pa
         s_ry[it] = pi / C16_RW; s_rx[it] = pi - s_ry[it] * C16_RW;
         s_l[it] = idx < C16_NPX * Q ? pi * PB + 2 * s_q[it] : -1;
     }
-    c16_u32x4 xr[XR];
+    u32x4 xr[XR];
     auto load_tile = [&](int tile) {
         const bool on = tile < p.ntiles;
         int t = tile;
@@ -305,15 +295,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16t_split6_kernel(const C16Pa
         for (int it = 0; it < XR; ++it) {
             if (s_l[it] < 0) continue;
             const float xv[4] = {__uint_as_float(xr[it].x), __uint_as_float(xr[it].y), __uint_as_float(xr[it].z), __uint_as_float(xr[it].w)};
-            c16_bf16x4 hi, mid, lo;
-#pragma unroll
-            for (int c = 0; c < 4; ++c) {
-                const __bf16 h_ = (__bf16)xv[c]; const float r1 = xv[c] - (float)h_; const __bf16 m_ = (__bf16)r1;
-                hi[c] = h_; mid[c] = m_; lo[c] = (__bf16)(r1 - (float)m_);
-            }
-            *reinterpret_cast<c16_bf16x4*>(smem_t + s_l[it]) = hi;
-            *reinterpret_cast<c16_bf16x4*>(smem_t + s_l[it] + 32) = mid;
-            *reinterpret_cast<c16_bf16x4*>(smem_t + s_l[it] + 64) = lo;
+            bf16x4 hi, mid, lo; mrdis_split3(xv, hi, mid, lo);
+            *reinterpret_cast<bf16x4*>(smem_t + s_l[it]) = hi;
+            *reinterpret_cast<bf16x4*>(smem_t + s_l[it] + 32) = mid;
+            *reinterpret_cast<bf16x4*>(smem_t + s_l[it] + 64) = lo;
         }
     };
     // MFMA role: tiles t = 0, 1 of the wave = rows 2 wave + t, all 32 columns; B operand: pixel e of the row, channels 8 half .. + 7
@@ -335,12 +320,12 @@ __global__ __launch_bounds__(256, 2) void conv3x3_c16t_split6_kernel(const C16Pa
 #pragma unroll
         for (int g = 0; g < 9; ++g) {
             const int go = ((g / 3) * C16_RW + (g % 3)) * PB;
-            c16_bf16x8 xh[2], xm[2], xl[2];
+            bf16x8 xh[2], xm[2], xl[2];
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
-                xh[t] = *reinterpret_cast<const c16_bf16x8*>(smem_t + boff[t] + go);
-                xm[t] = *reinterpret_cast<const c16_bf16x8*>(smem_t + boff[t] + go + 32);
-                xl[t] = *reinterpret_cast<const c16_bf16x8*>(smem_t + boff[t] + go + 64);
+                xh[t] = *reinterpret_cast<const bf16x8*>(smem_t + boff[t] + go);
+                xm[t] = *reinterpret_cast<const bf16x8*>(smem_t + boff[t] + go + 32);
+                xl[t] = *reinterpret_cast<const bf16x8*>(smem_t + boff[t] + go + 64);
             }
 #pragma unroll
             for (int t = 0; t < 2; ++t) acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[g][1], xm[t], acc[t], 0, 0, 0);

@@ -24,8 +24,6 @@ struct Co4Params {
 
 namespace {
 constexpr unsigned CO4_OOB = 0xfffffff0u;
-typedef unsigned co4_u32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 co4_bf16x8 __attribute__((ext_vector_type(8)));
 }
 
 // HALVES = Ci / 16 (2 | 4), TPW = 16-pixel tiles per wave and row = W / 64 (1 | 2 | 4).  XB: the input is a bf16 view -- a lane's 16-byte
@@ -53,7 +51,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_co4_kernel(const Co4Params p) 
     // of the fp32 sum differs -- 9 bf16 MFMAs per 32 channels and tile (144 cycles) against 24 fp32 ones (768).
     constexpr int NG = XB ? NLD : HALVES / 2;          // 32-channel groups
     float a[(XB || SPLIT) ? 1 : KS][3];
-    co4_bf16x8 ab[(XB || SPLIT) ? NG : 1][3][3];       // [32-channel group][row tile][term]
+    bf16x8 ab[(XB || SPLIT) ? NG : 1][3][3];       // [32-channel group][row tile][term]
     {
         const int co = l16 >> 2, tl = l16 & 3;
 #pragma unroll
@@ -67,8 +65,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_co4_kernel(const Co4Params p) 
                     for (int j = 0; j < 8; ++j) {
                         const int ch = XB ? 32 * h + 8 * kq + j : 32 * h + 16 * (j >> 2) + 4 * kq + (j & 3);
                         const float wv = tap < 9 ? p.w[(tf * CI + ch) * p.wld + co] : 0.f;
-                        const __bf16 hi = (__bf16)wv; const float r1 = wv - (float)hi;
-                        const __bf16 mid = (__bf16)r1; const __bf16 lo = (__bf16)(r1 - (float)mid);
+                        __bf16 hi, mid, lo; mrdis_split3(wv, hi, mid, lo);        // (scalar form: all three terms before they are placed, the order of this loop's schedule)
                         ab[h][rt][0][j] = hi; ab[h][rt][1][j] = mid; ab[h][rt][2][j] = lo;
                     }
             } else {
@@ -81,9 +78,9 @@ __global__ __launch_bounds__(256, 2) void conv3x3_co4_kernel(const Co4Params p) 
         }
     }
     for (int i = tid; i < 9 * WP * 4; i += 256) zs[i] = 0.f;       // the halo columns stay zero
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, p.x_bytes);
 
-    co4_u32x4 xr[TPW][NLD];
+    u32x4 xr[TPW][NLD];
     auto load_tile = [&](int t, int r) {              // tile t of the wave (pixels 16 (wave + 4 t) ..) of input row r; outside -> zeros
         const int px = 16 * (wave + 4 * t) + l16;
         const bool ok = (unsigned)r < (unsigned)p.H && r >= r0 - 1 && r <= r1;
@@ -111,13 +108,11 @@ __global__ __launch_bounds__(256, 2) void conv3x3_co4_kernel(const Co4Params p) 
 #pragma unroll
                 for (int g = 0; g < NG; ++g) {
                     const unsigned u[8] = {xr[t][2 * g].x, xr[t][2 * g].y, xr[t][2 * g].z, xr[t][2 * g].w, xr[t][2 * g + 1].x, xr[t][2 * g + 1].y, xr[t][2 * g + 1].z, xr[t][2 * g + 1].w};
-                    co4_bf16x8 xh, xm, xl;
+                    bf16x8 xh, xm, xl;
 #pragma unroll
                     for (int j = 0; j < 8; ++j) {
                         const float v = __uint_as_float(u[j]);
-                        const __bf16 hi = (__bf16)v; const float r1 = v - (float)hi;
-                        const __bf16 mid = (__bf16)r1;
-                        xh[j] = hi; xm[j] = mid; xl[j] = (__bf16)(r1 - (float)mid);
+                        mrdis_split3(v, xh, xm, xl, j);
                     }
 #pragma unroll
                     for (int rt = 0; rt < 3; ++rt) {   // smallest products first
@@ -136,7 +131,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_co4_kernel(const Co4Params p) 
 #pragma unroll
             for (int h = 0; h < NLD; ++h) {
                 if (XB) {
-                    const co4_bf16x8 xb = __builtin_bit_cast(co4_bf16x8, xr[t][h]);
+                    const bf16x8 xb = __builtin_bit_cast(bf16x8, xr[t][h]);
 #pragma unroll
                     for (int term = 2; term >= 0; --term)      // smallest terms first
 #pragma unroll

@@ -873,8 +873,6 @@ struct C4Params {
     int wrows;                   // channel rows per tap of the filter in memory: 4, or 16 for the zero-padded [9][16][Co] layout the mixing
                                  // launch writes under bf16 storage (rows 4..15 are zero and never read)
 };
-typedef unsigned u32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 #define C4_OOB 0x40000000u       // any offset >= this is outside every descriptor this kernel builds
 
 // OBF16: the output is a bf16 view (MRDIS_DT_XF32_YBF16: the si_layers under `compute_dtype: bf16` read the fp32 anatomy map and open a
@@ -907,30 +905,27 @@ __device__ __forceinline__ void c4conv_body(const C4Params& p) {
     // loads FIVE taps of 16 bytes (its four + tap 8) instead of nine of 8, and the x side of the seven k-steps is the same expression of those five
     // loads in both half-waves: (L0h L0m) (L0h L1h) (L1m L1h) (L2h L2m) (L2h L3h) (L3m L3h) (L4h L4m); the filter side, set up once, is
     // (wh wh) (wm wh) (wh wm) ... and for tap 8 (wh wh) in the lower, (wm 0) in the upper half-wave.
-    typedef __bf16 c4_bf16x8 __attribute__((ext_vector_type(8)));
-    typedef __bf16 c4_bf16x4 __attribute__((ext_vector_type(4)));
     constexpr int NTAPL = BFP ? 5 : 9;                 // tap loads per strip
     constexpr int NKS = SPLIT6 ? 14 : (OBF16 ? 7 : 9); // pipeline slots (k-steps | taps) per strip
     float b[BFP ? 1 : 9][2][NS];
-    c4_bf16x8 bw[BFP ? NKS : 1][NS];
+    bf16x8 bw[BFP ? NKS : 1][NS];
     if (SPLIT6) {
 #pragma unroll
         for (int ns = 0; ns < NS; ++ns) {
             const int co = (cot * NS + ns) * 32 + m;
             const int coc = co < p.Co ? co : p.Co - 1;
-            c4_bf16x4 wh[5], wm[5], wl[5];             // local tap l: tap 4 half + l (l < 4), tap 8 (l = 4)
+            bf16x4 wh[5], wm[5], wl[5];             // local tap l: tap 4 half + l (l < 4), tap 8 (l = 4)
 #pragma unroll
             for (int l = 0; l < 5; ++l) {
                 const int tap = l < 4 ? 4 * half + l : 8;
 #pragma unroll
                 for (int c = 0; c < 4; ++c) {
                     const float v = co < p.Co ? p.w[((p.flip ? 8 - tap : tap) * p.wrows + c) * p.Co + coc] : 0.f;
-                    const __bf16 h = (__bf16)v; const float r1 = v - (float)h; const __bf16 mi = (__bf16)r1;
-                    wh[l][c] = h; wm[l][c] = mi; wl[l][c] = (__bf16)(r1 - (float)mi);
+                    mrdis_split3(v, wh[l], wm[l], wl[l], c);
                 }
             }
-            const c4_bf16x4 z4 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
-            c4_bf16x4 seq[28];
+            const bf16x4 z4 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+            bf16x4 seq[28];
 #pragma unroll
             for (int l = 0; l < 4; ++l) { seq[6 * l] = wh[l]; seq[6 * l + 1] = wh[l]; seq[6 * l + 2] = wm[l]; seq[6 * l + 3] = wh[l]; seq[6 * l + 4] = wl[l]; seq[6 * l + 5] = wm[l]; }
             seq[24] = half ? wl[4] : wh[4]; seq[25] = half ? wm[4] : wh[4]; seq[26] = half ? z4 : wm[4]; seq[27] = half ? z4 : wh[4];
@@ -945,7 +940,7 @@ __device__ __forceinline__ void c4conv_body(const C4Params& p) {
         for (int ns = 0; ns < NS; ++ns) {
             const int co = (cot * NS + ns) * 32 + m;
             const int coc = co < p.Co ? co : p.Co - 1;
-            c4_bf16x4 wh[5], wm[5];                    // local tap l: tap 4 half + l (l < 4), tap 8 (l = 4)
+            bf16x4 wh[5], wm[5];                    // local tap l: tap 4 half + l (l < 4), tap 8 (l = 4)
 #pragma unroll
             for (int l = 0; l < 5; ++l) {
                 const int tap = l < 4 ? 4 * half + l : 8;
@@ -956,9 +951,9 @@ __device__ __forceinline__ void c4conv_body(const C4Params& p) {
                     wh[l][c] = h; wm[l][c] = (__bf16)(v - (float)h);
                 }
             }
-            const c4_bf16x4 z4 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
+            const bf16x4 z4 = {(__bf16)0.f, (__bf16)0.f, (__bf16)0.f, (__bf16)0.f};
             // group sequence of the filter side: per local tap l < 4: wh wh wm (against x: h m h); tap 8: lower half wh wh, upper half wm 0
-            c4_bf16x4 seq[14];
+            bf16x4 seq[14];
 #pragma unroll
             for (int l = 0; l < 4; ++l) { seq[3 * l] = wh[l]; seq[3 * l + 1] = wh[l]; seq[3 * l + 2] = wm[l]; }
             seq[12] = half ? wm[4] : wh[4]; seq[13] = half ? z4 : wh[4];
@@ -1036,11 +1031,11 @@ __device__ __forceinline__ void c4conv_body(const C4Params& p) {
     };
     auto x_desc = [&](int n) {
         const unsigned long long a = uni64((unsigned long long)(uintptr_t)(p.x + (size_t)n * (imgbytes / 4)));
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)a, 0, __builtin_amdgcn_readfirstlane((int)xrec), 0x00020000);
+        return mrdis_buffer_rsrc((const void*)(uintptr_t)a, (unsigned)__builtin_amdgcn_readfirstlane((int)xrec));
     };
     auto y_desc = [&](int n) {
         const unsigned long long a = uni64((unsigned long long)(uintptr_t)((char*)p.y + (size_t)n * oimgbytes));
-        return __builtin_amdgcn_make_buffer_rsrc((void*)(uintptr_t)a, 0, __builtin_amdgcn_readfirstlane((int)yrec), 0x00020000);
+        return mrdis_buffer_rsrc((const void*)(uintptr_t)a, (unsigned)__builtin_amdgcn_readfirstlane((int)yrec));
     };
     // 9 tap byte offsets of a strip: 3 row bases x 3 column offsets, each either valid or C4_OOB.
     auto strip_offsets = [&](int th, int tw, unsigned (&voff)[NTAPL]) {
@@ -1076,34 +1071,29 @@ __device__ __forceinline__ void c4conv_body(const C4Params& p) {
     };
     auto load_tap = [&](__amdgpu_buffer_rsrc_t rs, unsigned voff, auto& dst) {
         if constexpr (BFP) {
-            const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0);
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)voff, 0, 0);
             dst = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
         } else {
-            const u32x2_t v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)voff, 0, 0);
+            const u32x2 v = __builtin_amdgcn_raw_buffer_load_b64(rs, (int)voff, 0, 0);
             dst = make_float2(__uint_as_float(v.x), __uint_as_float(v.y));
         }
     };
     // a loaded tap as two bf16 terms: hi = bf16(x) (round to nearest even), mid = bf16(x - hi)
-    auto split_tap = [&](const float4& x, c4_bf16x4& hi, c4_bf16x4& mid) {
+    auto split_tap = [&](const float4& x, bf16x4& hi, bf16x4& mid) {
         const float xv[4] = {x.x, x.y, x.z, x.w};
 #pragma unroll
         for (int c = 0; c < 4; ++c) { const __bf16 h = (__bf16)xv[c]; hi[c] = h; mid[c] = (__bf16)(xv[c] - (float)h); }
     };
-    auto split_tap3 = [&](const float4& x, c4_bf16x4& hi, c4_bf16x4& mid, c4_bf16x4& lo) {
+    auto split_tap3 = [&](const float4& x, bf16x4& hi, bf16x4& mid, bf16x4& lo) {
         const float xv[4] = {x.x, x.y, x.z, x.w};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const __bf16 h = (__bf16)xv[c]; const float r1 = xv[c] - (float)h; const __bf16 mi = (__bf16)r1;
-            hi[c] = h; mid[c] = mi; lo[c] = (__bf16)(r1 - (float)mi);
-        }
+        mrdis_split3(xv, hi, mid, lo);
     };
-    auto cat8 = [](const c4_bf16x4& lo, const c4_bf16x4& hi) -> c4_bf16x8 { return c4_bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; };
+    auto cat8 = [](const bf16x4& lo, const bf16x4& hi) -> bf16x8 { return bf16x8{lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]}; };
     unsigned lane_ok_off[NS];                          // C4_OOB for lanes whose cout does not exist
 #pragma unroll
     for (int ns = 0; ns < NS; ++ns) lane_ok_off[ns] = ((cot * NS + ns) * 32 + m < p.Co) ? 0u : C4_OOB;
     auto store_group = [&](const f32x16 (&acc)[NS], __amdgpu_buffer_rsrc_t rs, unsigned so, int th, int tw, int g) {
         if (OBF16) {
-            typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
             const bool odd = (m & 1) != 0;
 #pragma unroll
             for (int k = 0; k < 4; k += 2) {
@@ -1122,7 +1112,7 @@ __device__ __forceinline__ void c4conv_body(const C4Params& p) {
                     if (LRELU) { a0 = fmaxf(a0, 0.2f * a0); a1 = fmaxf(a1, 0.2f * a1); }
                     const float send = odd ? a0 : a1;                                  // what the neighbour's store needs from this lane
                     const float recv = __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(send), 0xB1, 0xF, 0xF, true));
-                    bf16x2_t pk;
+                    bf16x2 pk;
                     pk[0] = (__bf16)(odd ? recv : a0);                                 // the lower cout of the pair
                     pk[1] = (__bf16)(odd ? a1 : recv);
                     __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, pk), rs, (int)((vo | lane_ok_off[ns]) + 64u * ns), (int)soff, C4_STORE_NT);
@@ -1178,14 +1168,14 @@ __device__ __forceinline__ void c4conv_body(const C4Params& p) {
         if constexpr (SPLIT6) {
             // a tap is split when its first k-step comes up and its raw registers are refilled (strip i + 2) behind its last one: one tap's three terms live at a
             // time (all five up front: 192 VGPRs, two waves per SIMD)
-            c4_bf16x4 xh, xm, xl;
+            bf16x4 xh, xm, xl;
             const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int t = 0; t < 14; ++t) {
                 const int l = t / 3;                   // k-steps 3 l .. 3 l + 2 belong to local tap l (12, 13: tap 8)
                 if (!PRO) {
                     if (t % 3 == 0) split_tap3(X[l], xh, xm, xl);
-                    const c4_bf16x8 a8 = (t % 3 == 1) ? cat8(xh, xl) : cat8(xh, xm);
+                    const bf16x8 a8 = (t % 3 == 1) ? cat8(xh, xl) : cat8(xh, xm);
 #pragma unroll
                     for (int ns = 0; ns < NS; ++ns) acc[ns] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a8, bw[t][ns], t == 0 ? zero16 : acc[ns], 0, 0, 0);
                 }
@@ -1196,7 +1186,7 @@ __device__ __forceinline__ void c4conv_body(const C4Params& p) {
             }
         } else
         if constexpr (OBF16) {
-            c4_bf16x4 xh[5], xm[5];
+            bf16x4 xh[5], xm[5];
             if (!PRO) {
 #pragma unroll
                 for (int l = 0; l < 5; ++l) split_tap(X[l], xh[l], xm[l]);
@@ -1205,7 +1195,7 @@ __device__ __forceinline__ void c4conv_body(const C4Params& p) {
             for (int t = 0; t < 7; ++t) {
                 if (!PRO) {
                     // x side of k-step t (see the top of the kernel)
-                    const c4_bf16x8 a8 = t == 0 ? cat8(xh[0], xm[0]) : t == 1 ? cat8(xh[0], xh[1]) : t == 2 ? cat8(xm[1], xh[1]) : t == 3 ? cat8(xh[2], xm[2])
+                    const bf16x8 a8 = t == 0 ? cat8(xh[0], xm[0]) : t == 1 ? cat8(xh[0], xh[1]) : t == 2 ? cat8(xm[1], xh[1]) : t == 3 ? cat8(xh[2], xm[2])
                                        : t == 4 ? cat8(xh[2], xh[3]) : t == 5 ? cat8(xm[3], xh[3]) : cat8(xh[4], xm[4]);
 #pragma unroll
                     for (int ns = 0; ns < NS; ++ns) acc[ns] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a8, bw[t][ns], t == 0 ? f32x16{0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f} : acc[ns], 0, 0, 0);
@@ -1967,8 +1957,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(const WgradParams p, 
                     if (n < p.N && (unsigned)h < (unsigned)gHin && (unsigned)w_ < (unsigned)gWin)
                         src = xg + (long long)n * p.x_img + (long long)h * p.x_row + (long long)w_ * p.x_pix + c_lo + c4;
                 }
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(xs + q * 256), 16, 0, 0);
+                mrdis_lds_copy16(src, xs + q * 256);
             }
         }
 #pragma unroll
@@ -1980,8 +1969,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_dma_kernel(const WgradParams p, 
                 if (n < p.N && a < p.A && bb < p.B && co_lo + c4 < p.Co)      // couts beyond Co (Co % 4 == 0) read zeros
                     src = p.dy + ((long long)(n * p.A + a) * p.B + bb) * p.lddy + co_lo + c4;
             }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(dys + q * 256), 16, 0, 0);
+            mrdis_lds_copy16(src, dys + q * 256);
         }
     };
 
@@ -2171,8 +2159,7 @@ __global__ __launch_bounds__(256) void wgrad_thin_dma_kernel(const WgradParams p
                     if (n < p.N && (unsigned)h < (unsigned)gHin && (unsigned)w_ < (unsigned)gWin)
                         src = xg + (long long)n * p.x_img + (long long)h * p.x_row + (long long)w_ * p.x_pix + (NARROW_X ? 0 : c_lo + xc4);
                 }
-                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                                 (__attribute__((address_space(3))) void*)(xs + q * 256), 16, 0, 0);
+                mrdis_lds_copy16(src, xs + q * 256);
             }
         }
 #pragma unroll
@@ -2185,8 +2172,7 @@ __global__ __launch_bounds__(256) void wgrad_thin_dma_kernel(const WgradParams p
                 if (n < p.N && a < p.A && bb < p.B && co_lo + c4 < p.Co)
                     src = p.dy + ((long long)(n * p.A + a) * p.B + bb) * p.lddy + co_lo + c4;
             }
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
-                                             (__attribute__((address_space(3))) void*)(dys + q * 256), 16, 0, 0);
+            mrdis_lds_copy16(src, dys + q * 256);
         }
     };
 

@@ -21,8 +21,6 @@
 #include "mrdis_conv3d.h"
 
 namespace {
-typedef __bf16 s6_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 s6_bf16x4 __attribute__((ext_vector_type(4)));
 constexpr int S6_TD = 4, S6_TH = 8, S6_TW = 16;
 constexpr int S6_ID = S6_TD + 2, S6_IH = S6_TH + 2, S6_IW = S6_TW + 2;
 constexpr int S6_NPX = S6_ID * S6_IH * S6_IW;          // 1080 pixels
@@ -32,9 +30,6 @@ constexpr int S6_XR = (S6_NPX * 4 + 255) / 256;        // float4 staging items p
 constexpr size_t S6_LDS = (size_t)27 * S6_FT + (size_t)S6_NPX * S6_PB;     // 41,472 + 103,680 B
 
 template <int V_> struct S6IC { static constexpr int value = V_; };
-__device__ __forceinline__ void s6_split(float v, __bf16& h, __bf16& m, __bf16& l) {
-    h = (__bf16)v; const float r1 = v - (float)h; m = (__bf16)r1; l = (__bf16)(r1 - (float)m);
-}
 }  // namespace
 
 __global__ __launch_bounds__(256) void conv3d16_s6_kernel(const Conv3dParams p, int nboxes) {
@@ -49,7 +44,7 @@ __global__ __launch_bounds__(256) void conv3d16_s6_kernel(const Conv3dParams p, 
         const int t = idx >> 8, k = (idx >> 4) & 15, j = idx & 15;
         const int c = ((p.dd[t] - p.dd_min) * 3 + (p.dh[t] - p.dh_min)) * 3 + (p.dw[t] - p.dw_min);
         __bf16 h, m, l;
-        s6_split(p.w[((long long)p.widx[t] * 16 + k) * 16 + j], h, m, l);
+        mrdis_split3(p.w[((long long)p.widx[t] * 16 + k) * 16 + j], h, m, l);
         __bf16* d = reinterpret_cast<__bf16*>(fs + c * S6_FT + (k >> 3) * 256 + j * 16) + (k & 7);
         d[0] = h; d[2 * 128] = m; d[4 * 128] = l;             // pieces (term, half) = term * 2 + half, 256 B = 128 bf16 each
     }
@@ -91,12 +86,12 @@ __global__ __launch_bounds__(256) void conv3d16_s6_kernel(const Conv3dParams p, 
         for (int it = 0; it < S6_XR; ++it) {
             if (s_l[it] < 0) continue;
             const float xv[4] = {xr[it].x, xr[it].y, xr[it].z, xr[it].w};
-            s6_bf16x4 hi, mid, lo;
+            bf16x4 hi, mid, lo;                                // (the scalar split3, not its bf16x4 form: all three terms before they are placed, the order this kernel is scheduled with)
 #pragma unroll
-            for (int c = 0; c < 4; ++c) { __bf16 h, m, l; s6_split(xv[c], h, m, l); hi[c] = h; mid[c] = m; lo[c] = l; }
-            *reinterpret_cast<s6_bf16x4*>(xs + s_l[it]) = hi;
-            *reinterpret_cast<s6_bf16x4*>(xs + s_l[it] + 32) = mid;
-            *reinterpret_cast<s6_bf16x4*>(xs + s_l[it] + 64) = lo;
+            for (int c = 0; c < 4; ++c) { __bf16 h, m, l; mrdis_split3(xv[c], h, m, l); hi[c] = h; mid[c] = m; lo[c] = l; }
+            *reinterpret_cast<bf16x4*>(xs + s_l[it]) = hi;
+            *reinterpret_cast<bf16x4*>(xs + s_l[it] + 32) = mid;
+            *reinterpret_cast<bf16x4*>(xs + s_l[it] + 64) = lo;
         }
     };
 
@@ -120,18 +115,18 @@ __global__ __launch_bounds__(256) void conv3d16_s6_kernel(const Conv3dParams p, 
         for (int g = 0; g < S6_TH; ++g) acc[g] = f32x4{0.f, 0.f, 0.f, 0.f};
         // software pipeline over the 27 cube positions: the 19 operand reads of position c + 1 are issued BETWEEN the 24 MFMAs of position c (one wave per SIMD:
         // nothing else hides the LDS latency -- without the interleave a position cost its read phase plus its MFMA phase, 25.7k cycles per box against 10.4k of MFMAs)
-        s6_bf16x8 A[2][3], Bx[2][2][S6_TH];
+        bf16x8 A[2][3], Bx[2][2][S6_TH];
         auto load_ops = [&](int c, auto SET_) {
             constexpr int set = decltype(SET_)::value;
             const int dz = c / 9, dy = (c / 3) % 3, dx = c % 3;
             const int po = ((dz * S6_IH + dy) * S6_IW + dx) * S6_PB;
-            A[set][0] = *reinterpret_cast<const s6_bf16x8*>(fs + c * S6_FT + a1);
-            A[set][1] = *reinterpret_cast<const s6_bf16x8*>(fs + c * S6_FT + a2);
-            A[set][2] = *reinterpret_cast<const s6_bf16x8*>(fs + c * S6_FT + a3);
+            A[set][0] = *reinterpret_cast<const bf16x8*>(fs + c * S6_FT + a1);
+            A[set][1] = *reinterpret_cast<const bf16x8*>(fs + c * S6_FT + a2);
+            A[set][2] = *reinterpret_cast<const bf16x8*>(fs + c * S6_FT + a3);
 #pragma unroll
             for (int g = 0; g < S6_TH; ++g) {
-                Bx[set][0][g] = *reinterpret_cast<const s6_bf16x8*>(xs + b1 + po + g * (S6_IW * S6_PB));
-                Bx[set][1][g] = *reinterpret_cast<const s6_bf16x8*>(xs + b3 + po + g * (S6_IW * S6_PB));
+                Bx[set][0][g] = *reinterpret_cast<const bf16x8*>(xs + b1 + po + g * (S6_IW * S6_PB));
+                Bx[set][1][g] = *reinterpret_cast<const bf16x8*>(xs + b3 + po + g * (S6_IW * S6_PB));
             }
         };
         auto mfmas = [&](auto SET_) {
@@ -230,7 +225,6 @@ int mrdis_run_conv3d16_s6(const Conv3dParams& p_in, long long ptiles_hint, hipSt
 // A wave owns one depth slice (four k-steps) and keeps the 16 x 16 accumulators of all 27 taps (108 registers); per k-step 6 + 27 x 6 transposing reads for
 // 162 MFMAs, the dy reads of tap t + 1 between the MFMAs of tap t.  Slabs per workgroup (split-K over boxes) + the fp32 kernel's ordered reduction launch.
 namespace {
-typedef short s6_s16x4 __attribute__((ext_vector_type(4)));
 constexpr int W6D_XROWP = 18 * 32;                         // bytes per x row (16 pixels + 2 of padding)
 constexpr int W6D_XPLANE = S6_TD * S6_TH * W6D_XROWP;      // 18,432
 constexpr int W6D_YPLANE = S6_NPX * 32;                    // 34,560
@@ -293,18 +287,18 @@ __global__ __launch_bounds__(256) void wgrad3d16_s6_kernel(const Wgrad3dS6Params
                 yr[it] = *reinterpret_cast<const float4*>(yn + ((long long)(d * p.H + h) * p.W + w_) * p.lddy);
         }
     };
-    auto split4 = [](const float4& v, s6_bf16x4& hi, s6_bf16x4& mid, s6_bf16x4& lo) {
+    auto split4 = [](const float4& v, bf16x4& hi, bf16x4& mid, bf16x4& lo) {
         const float f[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
-        for (int c = 0; c < 4; ++c) { __bf16 h, m, l; s6_split(f[c], h, m, l); hi[c] = h; mid[c] = m; lo[c] = l; }
+        for (int c = 0; c < 4; ++c) { __bf16 h, m, l; mrdis_split3(f[c], h, m, l); hi[c] = h; mid[c] = m; lo[c] = l; }
     };
     auto store_box = [&]() {
 #pragma unroll
         for (int it = 0; it < W6D_XR; ++it) {
             const int idx = tid + 256 * it, px = idx >> 2, q = idx & 3;
-            s6_bf16x4 hi, mid, lo; split4(xr[it], hi, mid, lo);
+            bf16x4 hi, mid, lo; split4(xr[it], hi, mid, lo);
             unsigned char* d = xs + ((px >> 4) * 18 + (px & 15)) * 32 + 8 * q;
-            *reinterpret_cast<s6_bf16x4*>(d) = hi; *reinterpret_cast<s6_bf16x4*>(d + W6D_XPLANE) = mid; *reinterpret_cast<s6_bf16x4*>(d + 2 * W6D_XPLANE) = lo;
+            *reinterpret_cast<bf16x4*>(d) = hi; *reinterpret_cast<bf16x4*>(d + W6D_XPLANE) = mid; *reinterpret_cast<bf16x4*>(d + 2 * W6D_XPLANE) = lo;
         }
 #pragma unroll
         for (int it = 0; it < W6D_YR; ++it) {
@@ -314,15 +308,15 @@ __global__ __launch_bounds__(256) void wgrad3d16_s6_kernel(const Wgrad3dS6Params
             if (iz >= 1 && iz <= S6_TD && iy >= 1 && iy <= S6_TH && ix >= 1 && ix <= S6_TW) {      // the box's own positions: the bias gradient (fp32, before the split)
                 bs4[0] += yr[it].x; bs4[1] += yr[it].y; bs4[2] += yr[it].z; bs4[3] += yr[it].w;
             }
-            s6_bf16x4 hi, mid, lo; split4(yr[it], hi, mid, lo);
+            bf16x4 hi, mid, lo; split4(yr[it], hi, mid, lo);
             unsigned char* d = ys + px * 32 + 8 * q;
-            *reinterpret_cast<s6_bf16x4*>(d) = hi; *reinterpret_cast<s6_bf16x4*>(d + W6D_YPLANE) = mid; *reinterpret_cast<s6_bf16x4*>(d + 2 * W6D_YPLANE) = lo;
+            *reinterpret_cast<bf16x4*>(d) = hi; *reinterpret_cast<bf16x4*>(d + W6D_YPLANE) = mid; *reinterpret_cast<bf16x4*>(d + 2 * W6D_YPLANE) = lo;
         }
     };
-    auto tr_read = [](const unsigned char* a) -> s6_bf16x8 {
-        union { s6_bf16x8 v; s6_s16x4 h[2]; } u;
-        u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s6_s16x4 __attribute__((address_space(3)))*)(a));
-        u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s6_s16x4 __attribute__((address_space(3)))*)(a + 4 * 32));
+    auto tr_read = [](const unsigned char* a) -> bf16x8 {
+        union { bf16x8 v; s16x4 h[2]; } u;
+        u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(a));
+        u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(a + 4 * 32));
         return u.v;
     };
 
@@ -335,7 +329,7 @@ __global__ __launch_bounds__(256) void wgrad3d16_s6_kernel(const Wgrad3dS6Params
 #pragma unroll
         for (int ks = 0; ks < 4; ++ks) {
             const int ya = (ks >> 1) * 4 + (ks & 1);                  // row pairs (0, 2), (1, 3), (4, 6), (5, 7) of the wave's depth slice
-            s6_bf16x8 ax[3], by[2][3];
+            bf16x8 ax[3], by[2][3];
 #pragma unroll
             for (int term = 0; term < 3; ++term) ax[term] = tr_read(xs + term * W6D_XPLANE + xbase + ya * W6D_XROWP);
             auto load_by = [&](int t, auto SET_) {

@@ -5,16 +5,12 @@
 // Reductions are two-level with a fixed summation order (partials in fp32 over
 // short runs, combination in fp64) so every result is bit-reproducible.
 #include "mrdis_common.h"
-#include <mutex>
 #include <type_traits>
 #include <stdlib.h>
-#include <string.h>
-#include <stdio.h>
 
 // ------------------------------------------------------------------ small vector helper
 // Activations are stored as fp32 or bf16 (MRDIS_DT_BF16: BASELINE.json configs[2]); the arithmetic is fp32 either way:
 // a kernel is templated on the storage type T and converts on load / store (bf16 stores round to nearest even).
-typedef __bf16 bf16x4_t __attribute__((ext_vector_type(4)));
 template <int V> struct Vec;
 template <> struct Vec<1> {
     float v[1];
@@ -30,20 +26,13 @@ template <> struct Vec<4> {
     }
     __device__ __forceinline__ void store(float* p) const { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
     __device__ __forceinline__ void load(const __bf16* p) {
-        const bf16x4_t t = *reinterpret_cast<const bf16x4_t*>(p); v[0] = (float)t[0]; v[1] = (float)t[1]; v[2] = (float)t[2]; v[3] = (float)t[3];
+        const bf16x4 t = *reinterpret_cast<const bf16x4*>(p); v[0] = (float)t[0]; v[1] = (float)t[1]; v[2] = (float)t[2]; v[3] = (float)t[3];
     }
     __device__ __forceinline__ void store(__bf16* p) const {
-        bf16x4_t t; t[0] = (__bf16)v[0]; t[1] = (__bf16)v[1]; t[2] = (__bf16)v[2]; t[3] = (__bf16)v[3];
-        *reinterpret_cast<bf16x4_t*>(p) = t;
+        bf16x4 t; t[0] = (__bf16)v[0]; t[1] = (__bf16)v[1]; t[2] = (__bf16)v[2]; t[3] = (__bf16)v[3];
+        *reinterpret_cast<bf16x4*>(p) = t;
     }
 };
-__device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 ld4(const __bf16* p) {
-    const bf16x4_t t = *reinterpret_cast<const bf16x4_t*>(p);
-    return make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
-}
-__device__ __forceinline__ float ld1(const float* p) { return *p; }
-__device__ __forceinline__ float ld1(const __bf16* p) { return (float)*p; }
 
 template <typename T>
 static inline bool vec4_ok(const T* p, int ld, int C) { return (C % 4 == 0) && (ld % 4 == 0) && (((uintptr_t)p & (4 * sizeof(T) - 1)) == 0); }
@@ -65,8 +54,8 @@ __device__ __forceinline__ void up2_value(const T* __restrict__ x, int ldx, int 
     else { r0 = i > 0 ? i - 1 : 0; r1 = i; A0 = i > 0 ? 0.25f : 0.f; A1 = i > 0 ? 0.75f : 1.f; }
     if (w & 1) { c0 = j; c1 = j < Wi - 1 ? j + 1 : Wi - 1; B0 = 0.75f; B1 = 0.25f; }
     else { c0 = j > 0 ? j - 1 : 0; c1 = j; B0 = j > 0 ? 0.25f : 0.f; B1 = j > 0 ? 0.75f : 1.f; }
-    const float4 p00 = ld4(x + ((long long)r0 * Wi + c0) * ldx), p01 = ld4(x + ((long long)r0 * Wi + c1) * ldx);
-    const float4 p10 = ld4(x + ((long long)r1 * Wi + c0) * ldx), p11 = ld4(x + ((long long)r1 * Wi + c1) * ldx);
+    const float4 p00 = mrdis_ld4(x + ((long long)r0 * Wi + c0) * ldx), p01 = mrdis_ld4(x + ((long long)r0 * Wi + c1) * ldx);
+    const float4 p10 = mrdis_ld4(x + ((long long)r1 * Wi + c0) * ldx), p11 = mrdis_ld4(x + ((long long)r1 * Wi + c1) * ldx);
     const float* a = &p00.x; const float* b = &p01.x; const float* c = &p10.x; const float* d = &p11.x;
 #pragma unroll
     for (int k = 0; k < 4; ++k) out[k] = (float)(T)(A0 * (B0 * a[k] + B1 * b[k]) + A1 * (B0 * c[k] + B1 * d[k]));
@@ -112,9 +101,9 @@ __global__ void stat_partial_kernel(const T* __restrict__ a, int lda, const T* _
             if (MODE != 0) { const int si = stat_per_group ? grp * C + c : c; mu = mean[si]; rs = rstd[si]; }
             for (long long r = r0 + threadIdx.y * rpx + sub; r < r1; r += 4 * rpx) {
                 const long long row = gbase + r;
-                if (MODE == 0) { const float x = ld1(a + row * lda + c); s0 += x; s1 += x * x; }
-                else if (MODE == 1) { const float d = ld1(a + row * lda + c); const float xh = (ld1(b + row * ldb + c) - mu) * rs; s0 += d; s1 += d * xh; }
-                else { const float d = ld1(a + row * lda + c) * (1.f + ld1(g + row * ldg + c)); const float zh = (ld1(b + row * ldb + c) - mu) * rs; s0 += d; s1 += d * zh; }
+                if (MODE == 0) { const float x = mrdis_ld1(a + row * lda + c); s0 += x; s1 += x * x; }
+                else if (MODE == 1) { const float d = mrdis_ld1(a + row * lda + c); const float xh = (mrdis_ld1(b + row * ldb + c) - mu) * rs; s0 += d; s1 += d * xh; }
+                else { const float d = mrdis_ld1(a + row * lda + c) * (1.f + mrdis_ld1(g + row * ldg + c)); const float zh = (mrdis_ld1(b + row * ldb + c) - mu) * rs; s0 += d; s1 += d * zh; }
             }
         }
         red[0][threadIdx.y][threadIdx.x] = s0; red[1][threadIdx.y][threadIdx.x] = s1;
@@ -164,7 +153,7 @@ __global__ __launch_bounds__(256) void stat_partial_vec_kernel(const T* __restri
             }
             auto one = [&](long long r) {
                 const long long row = gbase + r;
-                const float4 av = ld4(a + row * lda + c);
+                const float4 av = mrdis_ld4(a + row * lda + c);
                 const float aa[4] = {av.x, av.y, av.z, av.w};
                 if (MODE == 0) {
 #pragma unroll
@@ -175,11 +164,11 @@ __global__ __launch_bounds__(256) void stat_partial_vec_kernel(const T* __restri
                         const int Wo_ = 2 * Wlo, h_ = (int)(r / Wo_), w_ = (int)(r - (long long)h_ * Wo_);
                         up2_value<T>(xlo + (long long)grp * (P >> 2) * ldxlo + c, ldxlo, (int)(P / (4LL * Wlo)), Wlo, h_, w_, bb);
                     } else {
-                        const float4 bv = ld4(b + row * ldb + c);
+                        const float4 bv = mrdis_ld4(b + row * ldb + c);
                         bb[0] = bv.x; bb[1] = bv.y; bb[2] = bv.z; bb[3] = bv.w;
                     }
                     float gg[4] = {0.f, 0.f, 0.f, 0.f};
-                    if (MODE == 2) { const float4 gv = ld4(g + row * ldg + c); gg[0] = gv.x; gg[1] = gv.y; gg[2] = gv.z; gg[3] = gv.w; }
+                    if (MODE == 2) { const float4 gv = mrdis_ld4(g + row * ldg + c); gg[0] = gv.x; gg[1] = gv.y; gg[2] = gv.z; gg[3] = gv.w; }
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
                         const float d = (MODE == 2) ? aa[k] * (1.f + gg[k]) : aa[k];
@@ -632,7 +621,7 @@ __global__ __launch_bounds__(NT) void spade_bwd_up2_kernel(const T* __restrict__
             const int ly = px / (UB_T + 2), lx = px - ly * (UB_T + 2);
             int i = i0 - 1 + ly, j = j0 - 1 + lx;
             i = i < 0 ? 0 : (i > Hi - 1 ? Hi - 1 : i); j = j < 0 ? 0 : (j > Wi - 1 ? Wi - 1 : j);
-            *reinterpret_cast<float4*>(xt + (px * (UB_CC / 4) + q1) * 4) = ld4(xlo + (((long long)n * Hi + i) * Wi + j) * ldxlo + c0 + 4 * q1);
+            *reinterpret_cast<float4*>(xt + (px * (UB_CC / 4) + q1) * 4) = mrdis_ld4(xlo + (((long long)n * Hi + i) * Wi + j) * ldxlo + c0 + 4 * q1);
         }
         __syncthreads();
     }
@@ -768,7 +757,7 @@ __global__ void spade_bwd_up2_final_kernel(T* __restrict__ dx, int lddx, const T
             float rowv[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int b = 0; b < 3; ++b) {
-                const float4 v = ld4(xlo + (((long long)n * Hi + ir[a]) * Wi + ic[b]) * ldxlo + c);
+                const float4 v = mrdis_ld4(xlo + (((long long)n * Hi + ir[a]) * Wi + ic[b]) * ldxlo + c);
                 rowv[0] += cc[b] * v.x; rowv[1] += cc[b] * v.y; rowv[2] += cc[b] * v.z; rowv[3] += cc[b] * v.w;
             }
 #pragma unroll
@@ -1378,7 +1367,7 @@ __global__ void cast_view_kernel(const TS* __restrict__ src, int lds_, int Cs, T
         if (c + V <= Cs) a.load(src + r * lds_ + c);
         else {
 #pragma unroll
-            for (int k = 0; k < V; ++k) a.v[k] = (c + k < Cs) ? ld1(src + r * lds_ + c + k) : 0.f;
+            for (int k = 0; k < V; ++k) a.v[k] = (c + k < Cs) ? mrdis_ld1(src + r * lds_ + c + k) : 0.f;
         }
         a.store(dst + r * ldd + c);
     }
@@ -1925,183 +1914,3 @@ extern "C" int mrdis_stream_fill(float* dst, long long n_floats, float value, vo
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }
-
-// ------------------------------------------------------------------ misc
-// ---------------------------------------------------------------------------------------------- process-wide switches
-namespace {
-struct OptDef { const char* name; const char* env; int is_flag; long long dflt; };
-const OptDef OPT_DEFS[MRDIS_OPT_COUNT] = {
-    {"wino", "MRDIS_WINO", 0, 1},            // 0 direct kernels only | 1 measured policy | 2 Winograd wherever it applies
-    {"nt_mb", "MRDIS_NT_MB", 0, 128},        // outputs of at least this many MB leave the Winograd kernel with non-temporal stores
-    {"wino_pipe", "MRDIS_WINO_PIPE", 0, 1},  // 1: the software-pipelined Winograd kernel (mrdis_wino2.hip) where it applies | 0: the phase-by-phase one
-    {"wino_u", "MRDIS_WINO_U", 0, 1},        // 1: the pipelined kernel reads a pre-transformed filter image when the caller passes one | 0: always transforms the taps itself
-    {"wino4", "MRDIS_WINO4", 0, 1},          // 1: F(4x4, 3x3) (mrdis_wino4.hip) for the filters mrdis_wino_u_format() names, where the grid fills the chip | 0: never | 2: wherever the kernel applies
-    {"wino4r", "MRDIS_WINO4R", 0, 1},        // <= 32 couts: 1: the register-fed F(4x4, 3x3) form (mrdis_wino4r.hip) for <= 64 reduction channels and inputs beyond the Infinity Cache | 0: the shared-transform form | 2 / 3: always its 64-tile / channel-split form
-    {"bconv4", "MRDIS_BCONV4", 0, 1},        // bf16 3x3 stride-1 layers: 1: the LDS-DMA kernel (mrdis_bf16q.hip) where the launch fills the chip | 0: bconv3_kernel (mrdis_bf16p.hip) | 2: wherever it applies
-    {"split6", "MRDIS_SPLIT6", 0, 1},        // thin fp32 3x3 stride-1 layers on the bf16 matrix pipe: both fp32 operands as three bf16 terms, the six products of order <= 2 summed in fp32 (2^-23 relative per product).  1: the 4 -> C kernel for <= 32 couts, the C -> 4 kernel, sp6.out forward + weight gradient (32 -> 16) | 0: fp32 MFMA | 2 .. 7: one 2-D kernel at a time, see run_c4conv | 8 / 9: only the 3-D 16 -> 16 forward + data gradient / weight gradient kernel (mrdis_conv3d_s6.hip; both also under 1) | 10: only the tap-table kernel for launches that bring a filter image (mrdis_s6conv.hip; also under 1)
-    {"debug_no16", "MRDIS_DEBUG_NO16", 1, 0}, {"debug_nothin", "MRDIS_DEBUG_NOTHIN", 1, 0}, {"debug_noc4", "MRDIS_DEBUG_NOC4", 1, 0},
-    {"debug_nodma", "MRDIS_DEBUG_NODMA", 1, 0}, {"debug_no16_3d", "MRDIS_DEBUG_NO16_3D", 1, 0},
-    {"debug_bilgen", "MRDIS_DEBUG_BILGEN", 1, 0}, {"debug_now16", "MRDIS_DEBUG_NOW16", 1, 0},
-    {"debug_nopack", "MRDIS_DEBUG_NOPACK", 1, 0},   // 1: the four parity classes of a stride-2 data gradient as four launches
-    {"debug_mode", "MRDIS_DEBUG_MODE", 0, -1}, {"debug_bn", "MRDIS_DEBUG_BN", 0, -1}, {"debug_kc", "MRDIS_DEBUG_KC", 0, -1},
-    {"debug_bm", "MRDIS_DEBUG_BM", 0, -1}, {"debug_c4_tw", "MRDIS_DEBUG_C4_TW", 0, -1}, {"debug_wgsplit", "MRDIS_DEBUG_WGSPLIT", 0, -1},
-    {"debug_bn3", "MRDIS_DEBUG_BN3", 0, -1}, {"debug_kc3", "MRDIS_DEBUG_KC3", 0, -1},
-    {"c4_grid", "MRDIS_C4_GRID", 0, 0},      // persistent grid of the Cin = 4 kernels (run_c4conv): 0 = workgroups per CU from the occupancy query of the launched instantiation | k > 0: k workgroups per CU
-    {"debug_c4_blocks", "MRDIS_DEBUG_C4_BLOCKS", 0, -1},      // read-only diagnostic: grid.x of the last run_c4conv launch
-    {"zsearch_grid", "MRDIS_ZSEARCH_GRID", 0, 0},   // workgroups of mrdis_cosine_top1 (mrdis_zsearch.hip): 0 = min(tiles, 1024) | k > 0: min(k, tiles, 2048)
-    {"debug_volgen", "MRDIS_DEBUG_VOLGEN", 1, 0},   // 1: mrdis_volume_gather always runs its element kernel (mrdis_volgather.hip), never the LDS-tile form
-};
-long long* opt_table() {
-    static long long* table = [] {
-        static long long v[MRDIS_OPT_COUNT];
-        for (int i = 0; i < MRDIS_OPT_COUNT; ++i) {
-            const char* e = getenv(OPT_DEFS[i].env);
-            v[i] = !e ? OPT_DEFS[i].dflt : (OPT_DEFS[i].is_flag ? 1 : atoll(e));
-        }
-        return v;
-    }();
-    return table;
-}
-int opt_index(const char* name) {
-    if (!name) return -1;
-    for (int i = 0; i < MRDIS_OPT_COUNT; ++i)
-        if (!strcmp(name, OPT_DEFS[i].name)) return i;
-    return -1;
-}
-}  // namespace
-// relaxed atomics: launchers on any thread read the table while mrdis_set_option / mrdis_opt_note write it
-long long mrdis_opt(int id) { return __atomic_load_n(&opt_table()[id], __ATOMIC_RELAXED); }
-void mrdis_opt_note(int id, long long value) { __atomic_store_n(&opt_table()[id], value, __ATOMIC_RELAXED); }
-extern "C" int mrdis_set_option(const char* name, long long value) {
-    const int i = opt_index(name);
-    if (i < 0) return MRDIS_EINVAL;
-    mrdis_opt_note(i, value);
-    return MRDIS_OK;
-}
-extern "C" long long mrdis_get_option(const char* name) {
-    const int i = opt_index(name);
-    return i < 0 ? (long long)MRDIS_EINVAL : mrdis_opt(i);
-}
-
-namespace {
-const char* const CNT_NAMES[MRDIS_CNT_COUNT] = {"wino", "wino_spade", "wino2", "wino2_spade", "wino4", "wino4_spade", "wino4n", "wino4r",
-                                                "wino_wgrad", "wino_wgrad2", "wino4_wgrad", "bconv3", "bconv3_spade", "bconv4", "bconv4_spade",
-                                                "split6_c4", "split6_c16", "split6_wgrad16", "split6_co4", "split6_c3d", "split6_w3d", "split6_tap", "zsearch",
-                                                "conv2src", "ana_act", "kl", "avgpool", "chatt", "symdiff", "rgate",
-                                                "direct3d", "c3d16", "wgrad3d", "wgrad3d16", "wino_wgrad3d", "volgather", "loss3d", "segcounts", "all"};
-long long g_counts[MRDIS_CNT_COUNT];
-}  // namespace
-void mrdis_count(int id) { __atomic_fetch_add(&g_counts[id], 1LL, __ATOMIC_RELAXED); }
-extern "C" long long mrdis_launch_count(const char* family) {
-    if (!family) return MRDIS_EINVAL;
-    for (int i = 0; i < MRDIS_CNT_COUNT; ++i)
-        if (!strcmp(family, CNT_NAMES[i])) return __atomic_load_n(&g_counts[i], __ATOMIC_RELAXED);
-    return MRDIS_EINVAL;
-}
-extern "C" void mrdis_launch_count_reset(void) {
-    for (int i = 0; i < MRDIS_CNT_COUNT; ++i) __atomic_store_n(&g_counts[i], 0LL, __ATOMIC_RELAXED);
-}
-
-namespace {
-struct LdsNote { const char* expr; size_t bytes; };
-LdsNote g_lds[128]; int g_nlds = 0;
-std::mutex g_lds_mu;        // forward (main thread) and backward (autograd thread) both launch
-}  // namespace
-void mrdis_note_lds(const char* kernel_expr, size_t bytes) {       // host, launch path: a pointer compare per known kernel (string literals are unique per call site)
-    const int n = __atomic_load_n(&g_nlds, __ATOMIC_ACQUIRE);
-    for (int i = 0; i < n; ++i)        // known kernel at a size already seen: no lock (entries are only ever appended, bytes only ever grow)
-        if (g_lds[i].expr == kernel_expr && bytes <= g_lds[i].bytes) return;
-    std::lock_guard<std::mutex> lk(g_lds_mu);
-    for (int i = 0; i < g_nlds; ++i)
-        if (g_lds[i].expr == kernel_expr) { if (bytes > g_lds[i].bytes) g_lds[i].bytes = bytes; return; }
-    if (g_nlds < 128) { g_lds[g_nlds].expr = kernel_expr; g_lds[g_nlds].bytes = bytes; __atomic_store_n(&g_nlds, g_nlds + 1, __ATOMIC_RELEASE); }
-}
-// "kernel expression=bytes" lines, at most cap - 1 characters, only whole lines; returns the number of entries written
-extern "C" int mrdis_dynamic_lds_table(char* buf, int cap) {
-    int pos = 0, written = 0;
-    if (!buf || cap < 1) return MRDIS_EINVAL;
-    buf[0] = 0;
-    std::lock_guard<std::mutex> lk(g_lds_mu);
-    for (int i = 0; i < g_nlds; ++i) {
-        const int n = snprintf(buf + pos, (size_t)(cap - pos), "%s=%zu\n", g_lds[i].expr, g_lds[i].bytes);
-        if (n < 0 || pos + n >= cap) { buf[pos] = 0; break; }      // the entry did not fit: drop its truncated text
-        pos += n; ++written;
-    }
-    return written;
-}
-
-// ---------------------------------------------------------------------------------------------- launch setup (mrdis_common.h)
-int mrdis_cu_count() {
-    static const int ncu = [] {
-        int dev = 0, n = 0;
-        (void)hipGetDevice(&dev);
-        return hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && n > 0 ? n : 256;
-    }();
-    return ncu;
-}
-
-namespace {
-// Open-addressed tables keyed by kernel address.  Slots are only ever filled, under g_setup_mu, and a slot's key is stored last (release), so a
-// reader that sees the key also sees the rest; an opt-in size only grows and is read atomically.
-constexpr unsigned SETUP_SLOTS = 512;         // power of two, well above the kernels the library can launch
-struct OptinSlot { const void* fn; int bytes; };
-struct OccSlot { const void* fn; int block; size_t lds; int n; };
-OptinSlot g_optin[SETUP_SLOTS];
-OccSlot g_occ[SETUP_SLOTS];
-std::mutex g_setup_mu;
-unsigned setup_hash(const void* fn) { return (unsigned)(((uintptr_t)fn * 0x9E3779B97F4A7C15ull) >> 40); }
-}  // namespace
-
-bool mrdis_lds_optin(const void* kernel, int bytes) {
-    const unsigned h = setup_hash(kernel);
-    for (unsigned i = 0; i < SETUP_SLOTS; ++i) {
-        OptinSlot& e = g_optin[(h + i) % SETUP_SLOTS];
-        const void* fn = __atomic_load_n(&e.fn, __ATOMIC_ACQUIRE);
-        if (fn == kernel && __atomic_load_n(&e.bytes, __ATOMIC_RELAXED) >= bytes) return true;
-        if (!fn || fn == kernel) break;
-    }
-    std::lock_guard<std::mutex> lk(g_setup_mu);
-    OptinSlot* slot = nullptr;             // this kernel's slot or the first free one; none when the table is full (then nothing is cached)
-    for (unsigned i = 0; i < SETUP_SLOTS && !slot; ++i) {
-        OptinSlot& e = g_optin[(h + i) % SETUP_SLOTS];
-        if (!e.fn || e.fn == kernel) slot = &e;
-    }
-    if (slot && slot->fn == kernel && slot->bytes >= bytes) return true;       // another thread opted it in meanwhile
-    if (hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes) != hipSuccess) return false;
-    if (slot) { __atomic_store_n(&slot->bytes, bytes, __ATOMIC_RELAXED); __atomic_store_n(&slot->fn, kernel, __ATOMIC_RELEASE); }
-    return true;
-}
-
-int mrdis_occupancy(const void* kernel, int block, size_t lds) {
-    const unsigned h = setup_hash(kernel);
-    for (unsigned i = 0; i < SETUP_SLOTS; ++i) {
-        const OccSlot& e = g_occ[(h + i) % SETUP_SLOTS];
-        const void* fn = __atomic_load_n(&e.fn, __ATOMIC_ACQUIRE);
-        if (!fn) break;
-        if (fn == kernel && e.block == block && e.lds == lds) return e.n;
-    }
-    std::lock_guard<std::mutex> lk(g_setup_mu);
-    OccSlot* slot = nullptr;
-    for (unsigned i = 0; i < SETUP_SLOTS && !slot; ++i) {
-        OccSlot& e = g_occ[(h + i) % SETUP_SLOTS];
-        if (!e.fn || (e.fn == kernel && e.block == block && e.lds == lds)) slot = &e;
-    }
-    if (slot && slot->fn) return slot->n;
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kernel, block, lds) != hipSuccess || n < 1) return 0;
-    if (slot) { slot->block = block; slot->lds = lds; slot->n = n; __atomic_store_n(&slot->fn, kernel, __ATOMIC_RELEASE); }
-    return n;
-}
-
-extern "C" const char* mrdis_strerror(int code) {
-    switch (code) {
-        case MRDIS_OK: return "ok";
-        case MRDIS_EINVAL: return "invalid argument";
-        case MRDIS_EUNSUPPORTED: return "unsupported geometry";
-        case MRDIS_EWORKSPACE: return "workspace too small";
-        case MRDIS_ELAUNCH: return "kernel launch failed";
-        case MRDIS_EALIGN: return "misaligned pointer or leading dimension";
-        default: return "unknown error";
-    }
-}
-extern "C" int mrdis_version(void) { return 110; }

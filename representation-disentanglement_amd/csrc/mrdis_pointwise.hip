@@ -15,18 +15,6 @@
 namespace {
 constexpr int PW_CI = 16, PW_MAXCO = 8;
 
-typedef __bf16 pw_bf16x4 __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 pw_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-__device__ __forceinline__ float4 pw_ld4(const __bf16* p) {
-    const pw_bf16x4 t = *reinterpret_cast<const pw_bf16x4*>(p);
-    return make_float4((float)t[0], (float)t[1], (float)t[2], (float)t[3]);
-}
-__device__ __forceinline__ void pw_st4(float* p, float4 v) { *reinterpret_cast<float4*>(p) = v; }
-__device__ __forceinline__ void pw_st4(__bf16* p, float4 v) {
-    pw_bf16x4 t; t[0] = (__bf16)v.x; t[1] = (__bf16)v.y; t[2] = (__bf16)v.z; t[3] = (__bf16)v.w;      // round to nearest even
-    *reinterpret_cast<pw_bf16x4*>(p) = t;
-}
-
 __device__ __forceinline__ float pw_quad_sum(float v) {
     // v + quad_perm(1,0,3,2)(v), then + quad_perm(2,3,0,1): every lane of the quad ends with the sum of the four
     int t = __builtin_amdgcn_update_dpp(0, __float_as_int(v), 0xB1, 0xF, 0xF, true);
@@ -53,7 +41,7 @@ __global__ __launch_bounds__(256) void pw_fwd_kernel(const T16* __restrict__ x, 
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
             const long long it = it0 + u * gsz;
-            xv[u] = it < nitems ? pw_ld4(x + (it >> 2) * ldx + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+            xv[u] = it < nitems ? mrdis_ld4(x + (it >> 2) * ldx + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -100,7 +88,7 @@ __global__ __launch_bounds__(256) void pw_dgrad_kernel(const float* __restrict__
             float4 o = make_float4(0.f, 0.f, 0.f, 0.f);
 #pragma unroll
             for (int c = 0; c < CO; ++c) { o.x += g[u][c] * wq[c][0]; o.y += g[u][c] * wq[c][1]; o.z += g[u][c] * wq[c][2]; o.w += g[u][c] * wq[c][3]; }
-            if (it < nitems) pw_st4(dx + (it >> 2) * lddx + 4 * q, o);
+            if (it < nitems) mrdis_st4(dx + (it >> 2) * lddx + 4 * q, o);
         }
     }
 }
@@ -121,7 +109,7 @@ __global__ __launch_bounds__(256) void pw_wgrad_kernel(const T16* __restrict__ x
         for (int u = 0; u < 2; ++u) {
             const long long it = it0 + u * gsz;
             const bool ok = it < nitems;
-            xv[u] = ok ? pw_ld4(x + (it >> 2) * ldx + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
+            xv[u] = ok ? mrdis_ld4(x + (it >> 2) * ldx + 4 * q) : make_float4(0.f, 0.f, 0.f, 0.f);
             const float* s = dy + (it >> 2) * lddy;
 #pragma unroll
             for (int c = 0; c < CO; ++c) g[u][c] = ok ? s[c] : 0.f;

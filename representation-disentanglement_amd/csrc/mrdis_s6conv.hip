@@ -27,27 +27,9 @@
 #include "mrdis_s6conv.h"
 
 namespace {
-typedef __bf16 s6t_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 s6t_bf16x2 __attribute__((ext_vector_type(2)));
-typedef float s6t_f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned s6t_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int S6T_ROW = 48, S6T_PLANE = 32 * S6T_ROW;      // bytes per filter row (8 channels x 3 terms) / per (q, g, tap)
 
 __host__ __device__ constexpr int s6t_pitch(int kc) { return ((kc / 8) * 3) % 2 ? (kc / 8) * 48 : (kc / 8) * 48 + 16; }
-
-// v -> (h, m, l) for 8 values, conversions in pairs (v_cvt_pk_bf16_f32 rounds two values per instruction)
-__device__ __forceinline__ void s6t_split8(const float* v, s6t_u32x4& h, s6t_u32x4& m, s6t_u32x4& l) {
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const s6t_f32x2 a = {v[2 * k], v[2 * k + 1]};
-        const s6t_bf16x2 hh = __builtin_convertvector(a, s6t_bf16x2);
-        const s6t_f32x2 r1 = a - __builtin_convertvector(hh, s6t_f32x2);
-        const s6t_bf16x2 mm = __builtin_convertvector(r1, s6t_bf16x2);
-        const s6t_f32x2 r2 = r1 - __builtin_convertvector(mm, s6t_f32x2);
-        const s6t_bf16x2 ll = __builtin_convertvector(r2, s6t_bf16x2);
-        h[k] = __builtin_bit_cast(unsigned, hh); m[k] = __builtin_bit_cast(unsigned, mm); l[k] = __builtin_bit_cast(unsigned, ll);
-    }
-}
 
 template <int V_> struct S6TIC { static constexpr int value = V_; };
 
@@ -113,7 +95,7 @@ __device__ __forceinline__ void s6conv_body(const TapConvParams& p, const S6Conv
     const unsigned char* const wimg = reinterpret_cast<const unsigned char*>(p.w_bf16);
     const long long w_chunk = (long long)QX * G * T * S6T_PLANE;      // bytes per channel chunk of the image
     float4 xr[XR][2];
-    s6t_u32x4 wr[WR];
+    u32x4 wr[WR];
     unsigned x_ok = 0;                             // bit it: piece it holds image data (else zeros: padding, past the tile)
     auto tile_origin = [&](int tile, int& n0, int& a0, int& b0) {
         const int tb = tile % p.tilesB; tile /= p.tilesB;
@@ -137,7 +119,7 @@ __device__ __forceinline__ void s6conv_body(const TapConvParams& p, const S6Conv
         if (want_w) {
             const unsigned char* src = wimg + (long long)chunk * w_chunk;
 #pragma unroll
-            for (int it = 0; it < WR; ++it) wr[it] = *reinterpret_cast<const s6t_u32x4*>(src + (w_src[it] < 0 ? 0 : w_src[it]));
+            for (int it = 0; it < WR; ++it) wr[it] = *reinterpret_cast<const u32x4*>(src + (w_src[it] < 0 ? 0 : w_src[it]));
         }
     };
     auto store_item = [&](bool have_w) {
@@ -148,16 +130,16 @@ __device__ __forceinline__ void s6conv_body(const TapConvParams& p, const S6Conv
                 float v[8];
 #pragma unroll
                 for (int k = 0; k < 8; ++k) v[k] = live ? (&xr[it][0].x)[k] : 0.f;
-                s6t_u32x4 h, m, l;
-                s6t_split8(v, h, m, l);
+                u32x4 h, m, l;
+                mrdis_split3x8(v, h, m, l);
                 unsigned char* d = xs + x_dst[it];
-                *reinterpret_cast<s6t_u32x4*>(d) = h; *reinterpret_cast<s6t_u32x4*>(d + 16) = m; *reinterpret_cast<s6t_u32x4*>(d + 32) = l;
+                *reinterpret_cast<u32x4*>(d) = h; *reinterpret_cast<u32x4*>(d + 16) = m; *reinterpret_cast<u32x4*>(d + 32) = l;
             }
         }
         if (have_w) {
 #pragma unroll
             for (int it = 0; it < WR; ++it)
-                if (tid + it * 256 < nw) *reinterpret_cast<s6t_u32x4*>(ws + 16 * (tid + it * 256)) = w_src[it] < 0 ? s6t_u32x4{0u, 0u, 0u, 0u} : wr[it];
+                if (tid + it * 256 < nw) *reinterpret_cast<u32x4*>(ws + 16 * (tid + it * 256)) = w_src[it] < 0 ? u32x4{0u, 0u, 0u, 0u} : wr[it];
         }
     };
 
@@ -188,7 +170,7 @@ __device__ __forceinline__ void s6conv_body(const TapConvParams& p, const S6Conv
     // software pipeline over the k-steps: with one or two waves per SIMD nothing else hides the LDS latency (un-pipelined, a step cost its offset read + its
     // operand reads + its MFMAs one after the other, 3 x the MFMA time)
     constexpr int NRD = 2 * WP + 3 * WC, NMF = 3 * WP * WC;
-    s6t_bf16x8 Bq[2][2][WP], Aq[2][3][WC];
+    bf16x8 Bq[2][2][WP], Aq[2][3][WC];
     auto load_ops = [&](int s_, int xo, auto SET_) {
         constexpr int set = decltype(SET_)::value;
         const int t = s_ / QX, ks = s_ - t * QX;
@@ -196,14 +178,14 @@ __device__ __forceinline__ void s6conv_body(const TapConvParams& p, const S6Conv
 #pragma unroll
         for (int i = 0; i < WP; ++i) {
             const unsigned char* px = xs + abase[i] + xo;
-            Bq[set][0][i] = *reinterpret_cast<const s6t_bf16x8*>(px + ob1);
-            Bq[set][1][i] = *reinterpret_cast<const s6t_bf16x8*>(px + ob2);
+            Bq[set][0][i] = *reinterpret_cast<const bf16x8*>(px + ob1);
+            Bq[set][1][i] = *reinterpret_cast<const bf16x8*>(px + ob2);
         }
 #pragma unroll
         for (int j = 0; j < WC; ++j) {
-            Aq[set][0][j] = *reinterpret_cast<const s6t_bf16x8*>(wrow + j * jstride + oa1);
-            Aq[set][1][j] = *reinterpret_cast<const s6t_bf16x8*>(wrow + j * jstride + 16);
-            Aq[set][2][j] = *reinterpret_cast<const s6t_bf16x8*>(wrow + j * jstride);
+            Aq[set][0][j] = *reinterpret_cast<const bf16x8*>(wrow + j * jstride + oa1);
+            Aq[set][1][j] = *reinterpret_cast<const bf16x8*>(wrow + j * jstride + 16);
+            Aq[set][2][j] = *reinterpret_cast<const bf16x8*>(wrow + j * jstride);
         }
     };
     auto mfmas = [&](auto SET_) {
@@ -341,10 +323,10 @@ __global__ void s6_filter_image_kernel(const float* __restrict__ w, int taps, in
         float v[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = co < Cout ? w[((long long)t * Cred + 8 * q + k) * Cout + co] : 0.f;
-        s6t_u32x4 h, m, l;
-        s6t_split8(v, h, m, l);
+        u32x4 h, m, l;
+        mrdis_split3x8(v, h, m, l);
         unsigned char* d = img + r * S6T_ROW;
-        *reinterpret_cast<s6t_u32x4*>(d) = h; *reinterpret_cast<s6t_u32x4*>(d + 16) = m; *reinterpret_cast<s6t_u32x4*>(d + 32) = l;
+        *reinterpret_cast<u32x4*>(d) = h; *reinterpret_cast<u32x4*>(d + 16) = m; *reinterpret_cast<u32x4*>(d + 32) = l;
     }
 }
 }  // namespace

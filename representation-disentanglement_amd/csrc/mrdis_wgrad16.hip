@@ -153,10 +153,6 @@ __global__ __launch_bounds__(256, 2) void wgrad16_kernel(const Wgrad16Params p) 
 // the 32-byte dy rows (halo'd 10 x 34 box, [pixel][16 co] planes) are re-read per tap: 66 LDS reads per 108 MFMAs of a row.  A wave keeps all 9 x 2
 // accumulators (72 VGPRs); the four waves of a workgroup take rows r, r + 4 of an 8 x 32 box; boxes are walked with a grid stride with the next box in flight
 // in registers.  Slab layout, in-block wave reduction and the slab reduction launch are wgrad16_kernel's (a workgroup writes both 16-channel slices).
-typedef __bf16 w16_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 w16_bf16x4 __attribute__((ext_vector_type(4)));
-typedef short w16_s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned w16_u32x4 __attribute__((ext_vector_type(4)));
 struct Wgrad16SParams {
     const float* x; const float* dy; float* slab; float* bias_slab;
     int N, H, W, ldx, lddy;
@@ -177,8 +173,8 @@ __global__ __launch_bounds__(256, 2) void wgrad16_split6_kernel(const Wgrad16SPa
     unsigned char* ys = smem6 + 3 * XPLANE;            // [3 terms][340 px][16 co] bf16
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, kq = lane >> 4;
     const int split = mrdis_xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.dy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_y = mrdis_buffer_rsrc(p.dy, p.dy_bytes);
 
     // transposing reads: lane (q4, p4) of a 16-lane group supplies the address of pixel-row q4, columns 4 p4 .. + 3 of the group's 4 x 16 block and
     // receives column l16 (a channel / a cout) of the four pixel rows; group kq covers positions 8 kq .. 8 kq + 7 of the k-step in two reads
@@ -191,7 +187,7 @@ __global__ __launch_bounds__(256, 2) void wgrad16_split6_kernel(const Wgrad16SPa
     for (int t = 0; t < 9; ++t) { acc[t][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[t][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     float bs4[4] = {0.f, 0.f, 0.f, 0.f};              // this thread's share of the bias gradient: couts 4 (tid & 3) .. + 3
 
-    w16_u32x4 xr[XR], yr[YR];
+    u32x4 xr[XR], yr[YR];
     auto load_box = [&](int box) {                    // box >= numTiles: every offset out of range -> zeros
         const bool on = box < p.numTiles;
         int tt = box;
@@ -215,21 +211,17 @@ __global__ __launch_bounds__(256, 2) void wgrad16_split6_kernel(const Wgrad16SPa
             yr[it] = __builtin_amdgcn_raw_buffer_load_b128(rs_y, (int)(ok ? 4u * (unsigned)(((n * p.H + h) * p.W + w_) * p.lddy + 4 * q) : OOB), 0, 0);
         }
     };
-    auto split4 = [](const w16_u32x4& v, w16_bf16x4& hi, w16_bf16x4& mid, w16_bf16x4& lo) {
+    auto split4 = [](const u32x4& v, bf16x4& hi, bf16x4& mid, bf16x4& lo) {
         const float f[4] = {__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            const __bf16 h_ = (__bf16)f[c]; const float r1 = f[c] - (float)h_; const __bf16 m_ = (__bf16)r1;
-            hi[c] = h_; mid[c] = m_; lo[c] = (__bf16)(r1 - (float)m_);
-        }
+        mrdis_split3(f, hi, mid, lo);
     };
     auto store_box = [&]() {
 #pragma unroll
         for (int it = 0; it < XR; ++it) {
             const int idx = tid + 256 * it, px = idx >> 3, q = idx & 7;
-            w16_bf16x4 hi, mid, lo; split4(xr[it], hi, mid, lo);
+            bf16x4 hi, mid, lo; split4(xr[it], hi, mid, lo);
             unsigned char* d = xs + px * 64 + 8 * q;
-            *reinterpret_cast<w16_bf16x4*>(d) = hi; *reinterpret_cast<w16_bf16x4*>(d + XPLANE) = mid; *reinterpret_cast<w16_bf16x4*>(d + 2 * XPLANE) = lo;
+            *reinterpret_cast<bf16x4*>(d) = hi; *reinterpret_cast<bf16x4*>(d + XPLANE) = mid; *reinterpret_cast<bf16x4*>(d + 2 * XPLANE) = lo;
         }
 #pragma unroll
         for (int it = 0; it < YR; ++it) {
@@ -239,9 +231,9 @@ __global__ __launch_bounds__(256, 2) void wgrad16_split6_kernel(const Wgrad16SPa
             if (ly >= 1 && ly <= W6_TH && lx >= 1 && lx <= W6_TW) {      // the box's own positions: the bias gradient (fp32, before the split)
                 bs4[0] += __uint_as_float(yr[it].x); bs4[1] += __uint_as_float(yr[it].y); bs4[2] += __uint_as_float(yr[it].z); bs4[3] += __uint_as_float(yr[it].w);
             }
-            w16_bf16x4 hi, mid, lo; split4(yr[it], hi, mid, lo);
+            bf16x4 hi, mid, lo; split4(yr[it], hi, mid, lo);
             unsigned char* d = ys + px * 32 + 8 * q;
-            *reinterpret_cast<w16_bf16x4*>(d) = hi; *reinterpret_cast<w16_bf16x4*>(d + YPLANE) = mid; *reinterpret_cast<w16_bf16x4*>(d + 2 * YPLANE) = lo;
+            *reinterpret_cast<bf16x4*>(d) = hi; *reinterpret_cast<bf16x4*>(d + YPLANE) = mid; *reinterpret_cast<bf16x4*>(d + 2 * YPLANE) = lo;
         }
     };
     int box = split;
@@ -254,27 +246,27 @@ __global__ __launch_bounds__(256, 2) void wgrad16_split6_kernel(const Wgrad16SPa
         for (int rr = 0; rr < 2; ++rr) {
             const int row = wave + 4 * rr;
             // x operand of the row: [ci tile mt][term], read once for the nine taps
-            w16_bf16x8 ax[2][3];
+            bf16x8 ax[2][3];
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
                 for (int term = 0; term < 3; ++term) {
                     const unsigned char* a = xs + term * XPLANE + row * (32 * 64) + xoff + 32 * mt;
-                    union { w16_bf16x8 v; w16_s16x4 h[2]; } u;
-                    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w16_s16x4 __attribute__((address_space(3)))*)(a));
-                    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w16_s16x4 __attribute__((address_space(3)))*)(a + 4 * 64));
+                    union { bf16x8 v; s16x4 h[2]; } u;
+                    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(a));
+                    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(a + 4 * 64));
                     ax[mt][term] = u.v;
                 }
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int ty = t / 3, tx = t % 3;
-                w16_bf16x8 by[3];
+                bf16x8 by[3];
 #pragma unroll
                 for (int term = 0; term < 3; ++term) {
                     const unsigned char* b = ys + term * YPLANE + ((row - ty + 2) * W6_YW + 2 - tx) * 32 + yoff;
-                    union { w16_bf16x8 v; w16_s16x4 h[2]; } u;
-                    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w16_s16x4 __attribute__((address_space(3)))*)(b));
-                    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w16_s16x4 __attribute__((address_space(3)))*)(b + 4 * 32));
+                    union { bf16x8 v; s16x4 h[2]; } u;
+                    u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(b));
+                    u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(b + 4 * 32));
                     by[term] = u.v;
                 }
                 // six products of order <= 2 (terms 0 = hi, 1 = mid, 2 = lo), smallest first
@@ -337,8 +329,8 @@ __global__ __launch_bounds__(256, 2) void wgrad16_bf16_kernel(const Wgrad16SPara
     unsigned char* ys = smem7 + XPX * 64;              // [340 px][16 co] bf16
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l16 = lane & 15, kq = lane >> 4;
     const int split = mrdis_xcd_remap((int)blockIdx.x, (int)gridDim.x);
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.dy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_y = mrdis_buffer_rsrc(p.dy, p.dy_bytes);
     const int q4 = l16 >> 2, p4 = l16 & 3;
     const int xoff = (8 * kq + q4) * 64 + 8 * p4;
     const int yoff = (8 * kq + q4) * 32 + 8 * p4;
@@ -348,7 +340,7 @@ __global__ __launch_bounds__(256, 2) void wgrad16_bf16_kernel(const Wgrad16SPara
     for (int t = 0; t < 9; ++t) { acc[t][0] = f32x4{0.f, 0.f, 0.f, 0.f}; acc[t][1] = f32x4{0.f, 0.f, 0.f, 0.f}; }
     float bs8[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};      // this thread's share of the bias gradient: couts 8 (tid & 1) .. + 7
 
-    w16_u32x4 xr[XR], yr[YR];
+    u32x4 xr[XR], yr[YR];
     auto load_box = [&](int box) {
         const bool on = box < p.numTiles;
         int tt = box;
@@ -376,7 +368,7 @@ __global__ __launch_bounds__(256, 2) void wgrad16_bf16_kernel(const Wgrad16SPara
 #pragma unroll
         for (int it = 0; it < XR; ++it) {
             const int idx = tid + 256 * it, px = idx >> 2, q = idx & 3;
-            *reinterpret_cast<w16_u32x4*>(xs + px * 64 + 16 * q) = xr[it];
+            *reinterpret_cast<u32x4*>(xs + px * 64 + 16 * q) = xr[it];
         }
 #pragma unroll
         for (int it = 0; it < YR; ++it) {
@@ -388,7 +380,7 @@ __global__ __launch_bounds__(256, 2) void wgrad16_bf16_kernel(const Wgrad16SPara
 #pragma unroll
                 for (int k = 0; k < 4; ++k) { bs8[2 * k] += __uint_as_float(u[k] << 16); bs8[2 * k + 1] += __uint_as_float(u[k] & 0xffff0000u); }
             }
-            *reinterpret_cast<w16_u32x4*>(ys + px * 32 + 16 * q) = yr[it];
+            *reinterpret_cast<u32x4*>(ys + px * 32 + 16 * q) = yr[it];
         }
     };
 
@@ -401,22 +393,22 @@ __global__ __launch_bounds__(256, 2) void wgrad16_bf16_kernel(const Wgrad16SPara
 #pragma unroll
         for (int rr = 0; rr < 2; ++rr) {
             const int row = wave + 4 * rr;
-            w16_bf16x8 ax[2];
+            bf16x8 ax[2];
 #pragma unroll
             for (int mt = 0; mt < 2; ++mt) {
                 const unsigned char* a = xs + row * (32 * 64) + xoff + 32 * mt;
-                union { w16_bf16x8 v; w16_s16x4 h[2]; } u;
-                u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w16_s16x4 __attribute__((address_space(3)))*)(a));
-                u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w16_s16x4 __attribute__((address_space(3)))*)(a + 4 * 64));
+                union { bf16x8 v; s16x4 h[2]; } u;
+                u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(a));
+                u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(a + 4 * 64));
                 ax[mt] = u.v;
             }
 #pragma unroll
             for (int t = 0; t < 9; ++t) {
                 const int ty = t / 3, tx = t % 3;
                 const unsigned char* b = ys + ((row - ty + 2) * W6_YW + 2 - tx) * 32 + yoff;
-                union { w16_bf16x8 v; w16_s16x4 h[2]; } u;
-                u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w16_s16x4 __attribute__((address_space(3)))*)(b));
-                u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((w16_s16x4 __attribute__((address_space(3)))*)(b + 4 * 32));
+                union { bf16x8 v; s16x4 h[2]; } u;
+                u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(b));
+                u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(b + 4 * 32));
                 acc[t][0] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ax[0], u.v, acc[t][0], 0, 0, 0);
                 acc[t][1] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ax[1], u.v, acc[t][1], 0, 0, 0);
             }

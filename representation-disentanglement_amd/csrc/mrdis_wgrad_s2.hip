@@ -24,7 +24,6 @@ struct WgradS2Params {
     unsigned x_bytes, dy_bytes;
 };
 
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 namespace {
 constexpr unsigned S2_OOB = 0xfffffff0u;
 constexpr int S2_XJ = 7;      // x items per thread and input row: W * Ci <= 1792
@@ -59,8 +58,8 @@ __global__ __launch_bounds__(256) void wgrad_s2_kernel(const WgradS2Params p) {
     const int boff = kq * DYP + l16;
 
     // staging roles
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.dy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_y = mrdis_buffer_rsrc(p.dy, p.dy_bytes);
     unsigned xg[S2_XJ]; int xl[S2_XJ];
 #pragma unroll
     for (int j = 0; j < S2_XJ; ++j) {
@@ -286,7 +285,7 @@ __global__ __launch_bounds__(256) void conv_s2_fwd_kernel(const ConvS2Params p) 
         bv[nt] = p.bias ? make_float4(p.bias[16 * nt + 4 * kq], p.bias[16 * nt + 4 * kq + 1], p.bias[16 * nt + 4 * kq + 2], p.bias[16 * nt + 4 * kq + 3])
                         : make_float4(0.f, 0.f, 0.f, 0.f);
 
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, p.x_bytes);
     unsigned xg[S2_XJ]; int xl[S2_XJ];
 #pragma unroll
     for (int j = 0; j < S2_XJ; ++j) {
@@ -400,8 +399,8 @@ __global__ __launch_bounds__(256) void wgrad_c4_kernel(const WgradC4Params p) {
         acol[mt] = (tap % 3) * 4 + ci + 4 * kq;
     }
     const int boff = kq * DYP + l16;
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.dy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_y = mrdis_buffer_rsrc(p.dy, p.dy_bytes);
     for (int i = tid; i < 4 * p.rowp; i += 256) xs[i] = 0.f;
 
     f32x4 acc[MT][NT];
@@ -549,8 +548,6 @@ __global__ __launch_bounds__(256) void wgrad_c4_kernel(const WgradC4Params p) {
 //     order of the fp32 sum differs;
 //   * patch row 36 (unused in the third 16-row tile) is a row of ones: its D row is the column sum of dy, the bias gradient, for free.
 // 9 NT bf16 MFMAs of 16 cycles per 32 pixels; slab format, row split across the four waves, final cross-wave sum and the slab reduction are wgrad_c4_kernel's.
-typedef __bf16 wc_bf16x8 __attribute__((ext_vector_type(8)));
-typedef short wc_s16x4 __attribute__((ext_vector_type(4)));
 
 // SWAP: the C -> 4 layer (ana_dec.output, MRDIS_DT_XBF16_YF32: x a bf16 view of C channels, dy fp32 with 4) is the same sum with the roles exchanged,
 //   dW[tap][ci][co] = sum_p x[p + off(tap)][ci] dy[p][co] = sum_p' dy[p' + off(8 - tap)][co] x[p'][ci]:
@@ -583,8 +580,8 @@ __global__ __launch_bounds__(256) void wgrad_c4b_kernel(const WgradC4Params p) {
     const bool ones_row = l16 == 4;                    // (in row tile 2)
     const int q4 = l16 >> 2, p4 = l16 & 3;
     const int boff = (8 * kq + q4) * DYPB + 8 * p4;    // transposing read: this lane supplies row q4, columns 4 p4 .. + 3 of its group's block
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, p.x_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.dy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, p.x_bytes);
+    const __amdgpu_buffer_rsrc_t rs_y = mrdis_buffer_rsrc(p.dy, p.dy_bytes);
     for (int i = tid; i < 48 * PL / 2; i += 256) reinterpret_cast<unsigned*>(xs)[i] = 0u;
 
     f32x4 acc[MT][NT];
@@ -616,8 +613,7 @@ __global__ __launch_bounds__(256) void wgrad_c4b_kernel(const WgradC4Params p) {
             if (SWAP && iy >= oy0 && iy < oy1) { bs4[0] += xv[0]; bs4[1] += xv[1]; bs4[2] += xv[2]; bs4[3] += xv[3]; }
 #pragma unroll
             for (int ci = 0; ci < 4; ++ci) {
-                const __bf16 hi = (__bf16)xv[ci]; const float r1 = xv[ci] - (float)hi;
-                const __bf16 mid = (__bf16)r1; const __bf16 lo = (__bf16)(r1 - (float)mid);
+                __bf16 hi, mid, lo; mrdis_split3(xv[ci], hi, mid, lo);
                 dst[ci * PL] = hi; dst[(4 + ci) * PL] = mid; dst[(8 + ci) * PL] = lo;
             }
         }
@@ -637,13 +633,13 @@ __global__ __launch_bounds__(256) void wgrad_c4b_kernel(const WgradC4Params p) {
         for (int mt = 0; mt < MT; ++mt) arow[mt] = xs + (size_t)((oy + aty[mt]) & 3) * 12 * PL + aoff[mt];     // input row oy - 1 + ty -> slot (oy + ty) & 3
         for (int i = wave; i < nsteps; i += 4) {
             const int b0 = 32 * i;
-            wc_bf16x8 bq[NT];
+            bf16x8 bq[NT];
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) {
-                union { wc_bf16x8 v; wc_s16x4 h[2]; } u;
+                union { bf16x8 v; s16x4 h[2]; } u;
                 const unsigned char* src = dys + b0 * DYPB + boff + 32 * nt;
-                u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wc_s16x4 __attribute__((address_space(3)))*)(src));
-                u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((wc_s16x4 __attribute__((address_space(3)))*)(src + 4 * DYPB));
+                u.h[0] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(src));
+                u.h[1] = __builtin_amdgcn_ds_read_tr16_b64_v4i16((s16x4 __attribute__((address_space(3)))*)(src + 4 * DYPB));
                 bq[nt] = u.v;
             }
 #pragma unroll
@@ -663,7 +659,7 @@ __global__ __launch_bounds__(256) void wgrad_c4b_kernel(const WgradC4Params p) {
                         const unsigned r = __builtin_amdgcn_alignbit(dd[j + 1], dd[j], sh);
                         o[j] = atx[mt] == 2 ? dd[j + 1] : r;
                     }
-                    wc_bf16x8 a = __builtin_bit_cast(wc_bf16x8, o);
+                    bf16x8 a = __builtin_bit_cast(bf16x8, o);
                     if (!aok[mt]) {
                         const __bf16 fill = (mt == 2 && ones_row && term == 0) ? (__bf16)1.f : (__bf16)0.f;
 #pragma unroll
@@ -762,7 +758,7 @@ __global__ __launch_bounds__(256, 2) void dgrad_s2_kernel(const DgradS2Params p)
         for (int ks = 0; ks < KSTEPS; ++ks) a[ks][mt] = ok ? p.w[(tap * CO + 16 * (ks >> 2) + 4 * kq + (ks & 3)) * Ci + ci] : 0.f;
     }
     for (int i = tid; i < (p.Wout + 2) * MP; i += 256) zs[i] = 0.f;    // rows q = -1 and q = Wout stay zero
-    const __amdgpu_buffer_rsrc_t rs_y = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, p.dy_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_y = mrdis_buffer_rsrc(p.dy, p.dy_bytes);
     const int tpw = p.Wout >> 6;                      // 16-pixel tiles per wave and row (host: Wout % 64 == 0, <= 2)
     u32x4 yr[2][HALVES];
     auto load_tile = [&](int t, int r) {

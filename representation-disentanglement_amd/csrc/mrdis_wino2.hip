@@ -46,11 +46,9 @@ constexpr int UVBUF = 16 * XI, RAWBUF = KC * PIXP;
 constexpr int BIASBUF = 1024;                          // the bias vector, staged once (a global load in the epilogue costs its full latency)
 constexpr size_t WINO2_LDS = sizeof(float) * (4 * UVBUF + 2 * RAWBUF + BIASBUF);
 template <int V_> struct IC { static constexpr int value = V_; };
-typedef unsigned u32x4_t __attribute__((ext_vector_type(4)));
 // An LDS pointer the compiler may not fold constants into: accesses at ptr[k * XI] then use the instruction's 16-bit offset
 // field; left alone, hipcc builds one address register per 2 KB plane beyond the first 64 KB (27 spilled registers in wgrad2).
 // (The laundering is done on the element INDEX: a laundered pointer would lose its LDS address space and turn into flat loads.)
-__device__ __forceinline__ int w2_opaque(int idx) { asm volatile("" : "+v"(idx)); return idx; }
 constexpr unsigned W2_OOB = 0xfffffff0u;               // byte offset past every record count: the buffer load returns zeros
 }  // namespace
 
@@ -103,9 +101,9 @@ __global__ __launch_bounds__(512, 1) void wino2_kernel(const Wino2Params p) {
     // ---- raw-block cursor (two iterations ahead of the MFMAs)
     // All global loads are buffer loads whose offset is W2_OOB where there is nothing to read (zeros come back): no branch
     // around a load, so the compiler's vmcnt bookkeeping stays exact and a wait covers only the loads it must.
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_w = UIMG ? __builtin_amdgcn_make_buffer_rsrc((void*)p.u_img, 0, p.u_bytes, 0x00020000)
-                                             : __builtin_amdgcn_make_buffer_rsrc((void*)p.w, 0, p.w_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = mrdis_buffer_rsrc(p.in, p.in_bytes);
+    const __amdgpu_buffer_rsrc_t rs_w = UIMG ? mrdis_buffer_rsrc(p.u_img, p.u_bytes)
+                                             : mrdis_buffer_rsrc(p.w, p.w_bytes);
     unsigned xg[2] = {W2_OOB, W2_OOB};
     int rj = 0, rc = 0;
     auto raw_block = [&]() {
@@ -133,7 +131,7 @@ __global__ __launch_bounds__(512, 1) void wino2_kernel(const Wino2Params p) {
     auto load_raw1 = [&](auto S_, int it) {
         constexpr int S = decltype(S_)::value;
         if (ABL & 32) { xr[S][it] = make_float4(0.f, 0.f, 0.f, 0.f); return; }
-        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)xo[it], 0, 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)xo[it], 0, 0);
         xr[S][it] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     };
     auto load_raw = [&](auto S_) { raw_next(); load_raw1(S_, 0); load_raw1(S_, 1); };
@@ -171,7 +169,7 @@ __global__ __launch_bounds__(512, 1) void wino2_kernel(const Wino2Params p) {
     };
     float4 ur[4];                                     // UIMG: points 4 a .. 4 a + 3 of this thread's (channel, cout) pair, a = 0..3
     auto load_u = [&](int a) {
-        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (int)(f_wo != W2_OOB ? f_wo + 1024u * (unsigned)a : W2_OOB), 0, 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (int)(f_wo != W2_OOB ? f_wo + 1024u * (unsigned)a : W2_OOB), 0, 0);
         ur[a] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     };
     auto u_put = [&](float* Un, int a) {
@@ -254,10 +252,10 @@ __global__ __launch_bounds__(512, 1) void wino2_kernel(const Wino2Params p) {
     // one iteration; P = its parity = the U / V / raw buffers and the register set it LOADS into
     auto iteration = [&](auto P_) {
         constexpr int P = decltype(P_)::value;
-        const float* Ua0 = smem + w2_opaque(P * UVBUF + a0_off); const float* Ua1 = smem + w2_opaque(P * UVBUF + a1_off);
-        const float* Vbv = smem + w2_opaque((2 + P) * UVBUF + b_off);
-        float* Un = smem + w2_opaque((P ^ 1) * UVBUF + t_dst); float* Vn = smem + w2_opaque((2 + (P ^ 1)) * UVBUF + t_dst);
-        const float* Rr = smem + w2_opaque(4 * UVBUF + (P ^ 1) * RAWBUF + v_src);      // raw block of chunk i + 1
+        const float* Ua0 = smem + mrdis_opaque(P * UVBUF + a0_off); const float* Ua1 = smem + mrdis_opaque(P * UVBUF + a1_off);
+        const float* Vbv = smem + mrdis_opaque((2 + P) * UVBUF + b_off);
+        float* Un = smem + mrdis_opaque((P ^ 1) * UVBUF + t_dst); float* Vn = smem + mrdis_opaque((2 + (P ^ 1)) * UVBUF + t_dst);
+        const float* Rr = smem + mrdis_opaque(4 * UVBUF + (P ^ 1) * RAWBUF + v_src);      // raw block of chunk i + 1
         float* Rw = Rb + P * RAWBUF;                  // raw block of chunk i + 2 goes where chunk i's was
         // Global loads go out ONE OR TWO PER STEP: a burst of 11 vector-memory instructions per wave fills the CU's memory
         // queue, the in-order waves stall on their loads and the matrix pipe idles behind them (measured: 65 us of a 375 us
@@ -630,8 +628,8 @@ __global__ __launch_bounds__(512, 1) void wino_wgrad2_kernel(const WinoWgradPara
     }
     const int q4 = 4 * (tid & 15);
 
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (unsigned)(4LL * ((long long)(p.N * p.H) * p.W - 1) * p.ldx + 4LL * p.Ci), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, (unsigned)(4LL * ((long long)(p.N * p.H) * p.W - 1) * p.lddy + 4LL * p.Co), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, mrdis_nhwc_bytes(p.N, p.H, p.W, p.ldx, p.Ci, 4));
+    const __amdgpu_buffer_rsrc_t rs_dy = mrdis_buffer_rsrc(p.dy, mrdis_nhwc_bytes(p.N, p.H, p.W, p.lddy, p.Co, 4));
 
     // block cursors: (n, by, bx) advance by `splits` blocks per iteration = (s_n, s_by, s_bx) with carries (wave-uniform, scalar)
     struct Cur { int n, by, bx; };
@@ -650,7 +648,7 @@ __global__ __launch_bounds__(512, 1) void wino_wgrad2_kernel(const WinoWgradPara
         const int h = 4 * rcur.by - 1 + (s_rc[it] >> 8), w_ = 8 * rcur.bx - 1 + (s_rc[it] & 255);
         const bool ok = s_l[it] >= 0 && rcur.n < p.N && (unsigned)h < (unsigned)p.H && (unsigned)w_ < (unsigned)p.W;
         const unsigned o = ok ? 4u * (unsigned)(((rcur.n * p.H + h) * p.W + w_) * p.ldx + ci0 + q4) : W2_OOB;
-        const u32x4_t v = __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)o, 0, 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_x, (int)o, 0, 0);
         xr[S][it] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
         if (it == 1) advance(rcur);
     };
@@ -725,10 +723,10 @@ __global__ __launch_bounds__(512, 1) void wino_wgrad2_kernel(const WinoWgradPara
     const int niter = (p.nblocks - split + p.splits - 1) / p.splits;
     auto iteration = [&](auto P_) {
         constexpr int P = decltype(P_)::value;
-        const float* Va = smem + w2_opaque(P * UVBUF + a_off);
-        const float* Zb0 = smem + w2_opaque((2 + P) * UVBUF + b0_off); const float* Zb1 = smem + w2_opaque((2 + P) * UVBUF + b1_off);
-        float* Vn = smem + w2_opaque((P ^ 1) * UVBUF + t_dst); float* Zn = smem + w2_opaque((2 + (P ^ 1)) * UVBUF + t_dst);
-        const float* Rr = smem + w2_opaque(4 * UVBUF + (P ^ 1) * G_RAW + v_src);     // raw block of iteration i + 1
+        const float* Va = smem + mrdis_opaque(P * UVBUF + a_off);
+        const float* Zb0 = smem + mrdis_opaque((2 + P) * UVBUF + b0_off); const float* Zb1 = smem + mrdis_opaque((2 + P) * UVBUF + b1_off);
+        float* Vn = smem + mrdis_opaque((P ^ 1) * UVBUF + t_dst); float* Zn = smem + mrdis_opaque((2 + (P ^ 1)) * UVBUF + t_dst);
+        const float* Rr = smem + mrdis_opaque(4 * UVBUF + (P ^ 1) * G_RAW + v_src);     // raw block of iteration i + 1
         float* Rw = Rb + P * G_RAW;                   // raw block of iteration i + 2
         // raw(i + 3) is loaded in steps 1 and 5, dy(i + 2) in steps 11-14, once Z(i + 1) has left `dr`
         float2 av[3], b0[3], b1[3];

@@ -54,14 +54,11 @@ constexpr int BIAS4 = 512;
 constexpr int W4_SINK = 8 * 64;                                // floats: a 256-byte landing strip per wave for the z prefetch (SPADE form; never read)
 constexpr size_t W4_LDS = sizeof(float) * (2 * UBUF + 2 * VBUF + 2 * RAWBUF + BIAS4 + W4_SINK);
 template <int V_> struct IC4 { static constexpr int value = V_; };
-typedef unsigned u32x4_w4 __attribute__((ext_vector_type(4)));
-typedef float f32x2_w4 __attribute__((ext_vector_type(2)));
 // 8-byte LDS accesses that stay 8-byte accesses: volatile keeps hipcc from pairing neighbours into ds_read2_b64 / ds_write2st64_b64 (half the
 // rate of two ds_read_b64, banked by 32 where these images are laid out for the 64-bank rule of the 8-byte forms: 0.5 conflict cycles per LDS
 // instruction measured); the explicit LDS address space keeps a volatile access from becoming a flat one
-__device__ __forceinline__ f32x2_w4 w4_ld2(const float* p) { return *(const volatile __attribute__((address_space(3))) f32x2_w4*)p; }
-__device__ __forceinline__ void w4_st2(float* p, f32x2_w4 v) { *(volatile __attribute__((address_space(3))) f32x2_w4*)p = v; }
-__device__ __forceinline__ int w4_opaque(int idx) { asm volatile("" : "+v"(idx)); return idx; }
+__device__ __forceinline__ f32x2 w4_ld2(const float* p) { return *(const volatile __attribute__((address_space(3))) f32x2*)p; }
+__device__ __forceinline__ void w4_st2(float* p, f32x2 v) { *(volatile __attribute__((address_space(3))) f32x2*)p = v; }
 constexpr unsigned W4_OOB = 0xfffffff0u;
 __device__ __forceinline__ int w4_skew(int g) { return 2 * ((g >> 1) & 1); }
 }  // namespace
@@ -134,7 +131,7 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(const Wino4Params p) {
     };
 
     // ---- S: raw-block cursor.  Every global load is a buffer load whose offset is W4_OOB where there is nothing to read
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = mrdis_buffer_rsrc(p.in, p.in_bytes);
     int rj = 0, rc = 0;
     auto raw_block = [&]() {
 #pragma unroll
@@ -153,7 +150,7 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(const Wino4Params p) {
     auto load_raw1 = [&](int it, unsigned c0b) {      // c0b: byte offset of the double chunk's first channel
         if (ABL & 32) { W4_XR(it, 0) = 0.f; W4_XR(it, 1) = 0.f; W4_XR(it, 2) = 0.f; W4_XR(it, 3) = 0.f; return; }
         const unsigned xg = (unsigned)W4_XG(it);
-        const u32x4_w4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)(xg != W4_OOB ? xg + c0b : W4_OOB), 0, 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)(xg != W4_OOB ? xg + c0b : W4_OOB), 0, 0);
         W4_XR(it, 0) = __uint_as_float(v.x); W4_XR(it, 1) = __uint_as_float(v.y); W4_XR(it, 2) = __uint_as_float(v.z); W4_XR(it, 3) = __uint_as_float(v.w);
     };
     auto raw_advance = [&]() { if (++rc == nch / 2) { rc = 0; ++rj; raw_block(); } };
@@ -183,15 +180,14 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(const Wino4Params p) {
         if (ABL & 8) return;
         const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_u + 4u * (unsigned)(buf * UBUF) + 1024u * (unsigned)((wave & 3) + 4 * k));
         const float* src = f_chunk + 1024 * k;        // + 4 KiB per round of the four S waves
-        unsigned keep;                                 // M0 is the compiler's: written and restored inside the one statement that reads it
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "s"(m0v), "v"(f_voff), "s"(src) : "memory");
+        mrdis_lds_dma16(m0v, f_voff, src);
     };
 
     // ---- T: input transform pieces
     auto v_row = [&](const float* Rr, int ii, auto RH_) {           // patch row i = RH + ii (Rr: the chunk's channel planes of the raw block)
         const int row = decltype(RH_)::value + ii;                  // compile-time after unrolling
         const float* src = Rr + (row < 4 ? W4_VLO : W4_VHI) + row * RWP;
-        const f32x2_w4 a = w4_ld2(src), b = w4_ld2(src + 2), c = w4_ld2(src + 4);
+        const f32x2 a = w4_ld2(src), b = w4_ld2(src + 2), c = w4_ld2(src + 4);
         W4_D(ii, 0) = a.x; W4_D(ii, 1) = a.y; W4_D(ii, 2) = b.x; W4_D(ii, 3) = b.y; W4_D(ii, 4) = c.x; W4_D(ii, 5) = c.y;
     };
     auto v_col = [&](int j, auto RH_) {               // three rows of B^T d in column j: B^T rows 0-2 on patch rows 0-4, rows 3-5 on patch rows 1-5
@@ -213,9 +209,9 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(const Wino4Params p) {
     auto v_put = [&](float* Vn, int a, auto RH_) {    // row 3 RH + a of V: point pairs 3 (3 RH + a) + 0..2
         constexpr int RH = decltype(RH_)::value;
         float* vp = Vn + (3 * (3 * RH + a)) * VPP;
-        w4_st2(vp, f32x2_w4{W4_VO(0), W4_VO(1)});
-        w4_st2(vp + VPP, f32x2_w4{W4_VO(2), W4_VO(3)});
-        w4_st2(vp + 2 * VPP, f32x2_w4{W4_VO(4), W4_VO(5)});
+        w4_st2(vp, f32x2{W4_VO(0), W4_VO(1)});
+        w4_st2(vp + VPP, f32x2{W4_VO(2), W4_VO(3)});
+        w4_st2(vp + 2 * VPP, f32x2{W4_VO(4), W4_VO(5)});
     };
 
     f32x4 acc[36];
@@ -278,11 +274,11 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(const Wino4Params p) {
     // one iteration g of parity P = g & 1 in role ROLE (0 / 1: T wave, rows 0-2 / 3-5 of V; 2: S wave)
     auto iteration = [&](auto P_, auto ROLE_, int g) {
         constexpr int P = decltype(P_)::value, ROLE = decltype(ROLE_)::value;
-        const float* Ua = smem + w4_opaque(P * UBUF + a_off);
-        const float* Va = smem + w4_opaque(2 * UBUF + P * VBUF + b_off);
+        const float* Ua = smem + mrdis_opaque(P * UBUF + a_off);
+        const float* Va = smem + mrdis_opaque(2 * UBUF + P * VBUF + b_off);
         // T: V(g + 1) from channels 4 (P ^ 1) .. + 3 of raw double chunk (g + 1) / 2
-        const float* Rr = smem + w4_opaque(2 * UBUF + 2 * VBUF + (((g + 1) >> 1) & 1) * RAWBUF + (P ^ 1) * 4 * PL);
-        float* Vn = smem + w4_opaque(2 * UBUF + (P ^ 1) * VBUF + W4_TDST);
+        const float* Rr = smem + mrdis_opaque(2 * UBUF + 2 * VBUF + (((g + 1) >> 1) & 1) * RAWBUF + (P ^ 1) * 4 * PL);
+        float* Vn = smem + mrdis_opaque(2 * UBUF + (P ^ 1) * VBUF + W4_TDST);
         // S: U(g + 1) by DMA; even g: loads of raw double chunk g / 2 + 2 (registers); odd g: their LDS stores, into the buffer whose block
         // (double chunk (g - 1) / 2) the T waves finished with in iteration g - 1.  A block ends after an odd iteration: nothing staged is live
         // in registers across the epilogue
@@ -294,7 +290,7 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(const Wino4Params p) {
         }
 
         stamp(1);
-        f32x2_w4 av[3], bv[3];
+        f32x2 av[3], bv[3];
 #pragma unroll
         for (int s_ = 0; s_ < 2; ++s_) {
             av[s_] = w4_ld2(Ua + s_ * UPP);
@@ -360,7 +356,7 @@ __global__ __launch_bounds__(512, 2) void wino4_kernel(const Wino4Params p) {
                 int n_, oy0_, ox0_, cot_; decode(mj, n_, oy0_, ox0_, cot_);
                 const int tile_ = 16 * tg + l16, oy_ = oy0_ + 4 * (tile_ >> 3), ox_ = ox0_ + 4 * (tile_ & 7);
                 const int ch_ = 32 * cot_ + 8 * cg + 4 * (kq & 1);
-                const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc((void*)p.z, 0, p.z_bytes, 0x00020000);
+                const __amdgpu_buffer_rsrc_t rs_z = mrdis_buffer_rsrc(p.z, p.z_bytes);
                 const unsigned m0s = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)(Bs + BIAS4) + 256u * (unsigned)wave);
 #pragma unroll
                 for (int ip = 0; ip < 2; ++ip) {
@@ -537,7 +533,7 @@ __global__ __launch_bounds__(512, 2) void wino4n_kernel(const Wino4Params p) {
         const int by = b % p.nby;
         n = b / p.nby; oy0 = 32 * by; ox0 = 32 * bx;
     };
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = mrdis_buffer_rsrc(p.in, p.in_bytes);
     int rj = 0, rc = 0;
     auto raw_block = [&]() {
 #pragma unroll
@@ -556,7 +552,7 @@ __global__ __launch_bounds__(512, 2) void wino4n_kernel(const Wino4Params p) {
     float4 xr[N_NIT];
     auto load_raw1 = [&](int it, unsigned c0b) {
         if (ABL & 32) { xr[it] = make_float4(0.f, 0.f, 0.f, 0.f); return; }
-        const u32x4_w4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)(xg[it] != W4_OOB ? xg[it] + c0b : W4_OOB), 0, 0);
+        const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_in, (int)(xg[it] != W4_OOB ? xg[it] + c0b : W4_OOB), 0, 0);
         xr[it] = make_float4(__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w));
     };
     auto raw_advance = [&]() { if (++rc == nch) { rc = 0; ++rj; raw_block(); } };
@@ -580,15 +576,14 @@ __global__ __launch_bounds__(512, 2) void wino4n_kernel(const Wino4Params p) {
         if ((ABL & 8) || wave + 8 * k >= 18) return;
         const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_u + 4u * (unsigned)(buf * N_UBUF) + 1024u * (unsigned)(wave + 8 * k));
         const float* src = f_chunk + 2048 * k;
-        unsigned keep;                                 // M0 is the compiler's: written and restored inside the one statement that reads it
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0" : "=&s"(keep) : "s"(m0v), "v"(f_voff), "s"(src) : "memory");
+        mrdis_lds_dma16(m0v, f_voff, src);
     };
 
     float d[5][6], r[3][6], vo[6];
     auto v_row = [&](const float* Rr, int ii, auto RH_) {
         const int row = decltype(RH_)::value + ii;
         const float* src = Rr + (row < 4 ? v_lo : v_hi) + row * RWP;
-        const f32x2_w4 a = w4_ld2(src), b = w4_ld2(src + 2), c = w4_ld2(src + 4);
+        const f32x2 a = w4_ld2(src), b = w4_ld2(src + 2), c = w4_ld2(src + 4);
         d[ii][0] = a.x; d[ii][1] = a.y; d[ii][2] = b.x; d[ii][3] = b.y; d[ii][4] = c.x; d[ii][5] = c.y;
     };
     auto v_col = [&](int j, auto RH_) {
@@ -610,7 +605,7 @@ __global__ __launch_bounds__(512, 2) void wino4n_kernel(const Wino4Params p) {
     auto v_put = [&](float* Vn, int a, auto RH_) {
         constexpr int RH = decltype(RH_)::value;
         float* vp = Vn + (3 * (3 * RH + a)) * N_VPP;
-        w4_st2(vp, f32x2_w4{vo[0], vo[1]}); w4_st2(vp + N_VPP, f32x2_w4{vo[2], vo[3]}); w4_st2(vp + 2 * N_VPP, f32x2_w4{vo[4], vo[5]});
+        w4_st2(vp, f32x2{vo[0], vo[1]}); w4_st2(vp + N_VPP, f32x2{vo[2], vo[3]}); w4_st2(vp + 2 * N_VPP, f32x2{vo[4], vo[5]});
     };
 
     f32x4 acc[36];
@@ -660,14 +655,14 @@ __global__ __launch_bounds__(512, 2) void wino4n_kernel(const Wino4Params p) {
 
     auto iteration = [&](auto P_, auto RH_) {
         constexpr int P = decltype(P_)::value;
-        const float* Ua = smem + w4_opaque(P * N_UBUF + a_off);
-        const float* Va = smem + w4_opaque(2 * N_UBUF + P * N_VBUF + b_off);
-        const float* Rr = smem + w4_opaque(2 * N_UBUF + 2 * N_VBUF + (P ^ 1) * N_RAWBUF);        // raw chunk g + 1
-        float* Vn = smem + w4_opaque(2 * N_UBUF + (P ^ 1) * N_VBUF + t_dst);
+        const float* Ua = smem + mrdis_opaque(P * N_UBUF + a_off);
+        const float* Va = smem + mrdis_opaque(2 * N_UBUF + P * N_VBUF + b_off);
+        const float* Rr = smem + mrdis_opaque(2 * N_UBUF + 2 * N_VBUF + (P ^ 1) * N_RAWBUF);        // raw chunk g + 1
+        float* Vn = smem + mrdis_opaque(2 * N_UBUF + (P ^ 1) * N_VBUF + t_dst);
         float* Rw = Rb + P * N_RAWBUF;                 // raw chunk g + 2 (in registers since iteration g - 1) goes where chunk g was
         filt_next();
         const unsigned c0b = 16u * (unsigned)rc;       // raw chunk g + 3
-        f32x2_w4 av[3], bv[3];
+        f32x2 av[3], bv[3];
 #pragma unroll
         for (int s_ = 0; s_ < 2; ++s_) { av[s_] = w4_ld2(Ua + s_ * N_UPP); bv[s_] = w4_ld2(Va + s_ * N_VPP); }
 #pragma unroll

@@ -36,7 +36,6 @@ constexpr int NTR = 512;
 constexpr int R_RWP = 40;                       // pixel slots per raw row (34 + skew 3, rounded to a multiple of 4)
 constexpr int R_UCH = MRDIS_W4N_UCHUNK;         // floats per (32-cout tile, chunk) of the format-5 image
 constexpr unsigned R_OOB = 0xfffffff0u;
-typedef float f32x2_r __attribute__((ext_vector_type(2)));
 template <int V_> struct ICR { static constexpr int value = V_; };
 template <int NKH> struct RGeo {
     static constexpr int TGY = NKH == 2 ? 1 : 2;            // tile groups down the block (two across)
@@ -53,7 +52,7 @@ template <int NKH> struct RGeo {
     static constexpr int BSTRIDE = SBUF + EXTRA;
     static constexpr size_t LDS = sizeof(float) * (2 * SBUF + EXTRA);
 };
-__device__ __forceinline__ f32x2_r r_ld2(const float* p) { return *(const volatile __attribute__((address_space(3))) f32x2_r*)p; }
+__device__ __forceinline__ f32x2 r_ld2(const float* p) { return *(const volatile __attribute__((address_space(3))) f32x2*)p; }
 // (volatile: one ds_read_b32 each -- hipcc otherwise pairs neighbours into ds_read2_b32, which the LDS serves by the 32-bank rule: two tiles per bank here)
 __device__ __forceinline__ float r_ld1(const float* p) { return *(const volatile __attribute__((address_space(3))) float*)p; }
 }  // namespace
@@ -100,7 +99,7 @@ __global__ __launch_bounds__(512, 2) void wino4r_kernel(const Wino4rParams p) {
     //      pieces w + 8 k and raw pieces w + 8 i, one or two per row step of its chunk(s) so that they queue behind the MFMAs instead of in front of them
     //      (issued in one burst at the top of the stage they held every wave for 1000-2000 cycles: the texture addresser takes 16 cycles per piece).
     //      An index past the last piece repeats the last piece (same bytes to the same place) rather than branching around the copy.
-    const __amdgpu_buffer_rsrc_t rs_in = __builtin_amdgcn_make_buffer_rsrc((void*)p.in, 0, p.in_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_in = mrdis_buffer_rsrc(p.in, p.in_bytes);
     int s_yx[G::NRP]; unsigned s_off[G::NRP];
     auto raw_piece = [&](int i, int& start) {
         int r = wave + 8 * i;
@@ -143,15 +142,13 @@ __global__ __launch_bounds__(512, 2) void wino4r_kernel(const Wino4rParams p) {
             if (q > 35) q = 35;
             const unsigned m0v = __builtin_amdgcn_readfirstlane(base + 1024u * (unsigned)q);
             const float* src = f_blk + (long long)ds * (2 * R_UCH) + 256 * q;
-            unsigned keep;                                         // M0 is the compiler's: written and restored inside the one statement that reads it
-            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %2, %3\n\ts_mov_b32 m0, %0"
-                         : "=&s"(keep) : "s"(m0v), "v"(f_voff), "s"(src) : "memory");
+            mrdis_lds_dma16(m0v, f_voff, src);
         } else {
             if (ABL & 32) return;
             int start; raw_piece(i - 5, start);
             const unsigned soff = __builtin_amdgcn_readfirstlane(32u * (unsigned)ds);
             const unsigned m0v = __builtin_amdgcn_readfirstlane(base + 4u * (unsigned)(2 * R_UCH) + 16u * (unsigned)start);
-            unsigned keep;
+            unsigned keep;                                         // M0 is the compiler's: written and restored inside the one statement that reads it (as mrdis_buffer_lds_dma16, + a scalar offset)
             asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, %4 offen lds\n\ts_mov_b32 m0, %0"
                          : "=&s"(keep) : "v"(s_off[i - 5]), "s"(m0v), "s"(rs_in), "s"(soff) : "memory");
         }
@@ -187,7 +184,7 @@ __global__ __launch_bounds__(512, 2) void wino4r_kernel(const Wino4rParams p) {
     auto chunk = [&](const float* Uc, const float* Rg, auto CI_, int nbuf) {
         constexpr int CI = decltype(CI_)::value;
         float ca[6], cb[6], tr[6], v[2][6];
-        f32x2_r u[4][3];
+        f32x2 u[4][3];
         const float* Ua = Uc + a_off;
         // 64-tile form: the second chunk's patch is read during the first chunk's MFMAs (rows 0, 2, 4 in step 3, rows 1, 3, 5 in step 5: into the registers
         // the first patch has vacated by then), so only one patch read per stage stands in front of the MFMAs
@@ -195,7 +192,7 @@ __global__ __launch_bounds__(512, 2) void wino4r_kernel(const Wino4rParams p) {
 #pragma unroll
         for (int a_ = 0; a_ < 3; ++a_)
 #pragma unroll
-            for (int b2 = 0; b2 < 3; ++b2) u[a_][b2] = (ABL & 2) ? f32x2_r{1.f, 1.f} : r_ld2(Ua + (3 * a_ + b2) * 256);
+            for (int b2 = 0; b2 < 3; ++b2) u[a_][b2] = (ABL & 2) ? f32x2{1.f, 1.f} : r_ld2(Ua + (3 * a_ + b2) * 256);
         auto col_row = [&](int a_) {                               // row a_ of B^T d into tr[]
 #pragma unroll
             for (int c = 0; c < 6; ++c) {
@@ -226,7 +223,7 @@ __global__ __launch_bounds__(512, 2) void wino4r_kernel(const Wino4rParams p) {
             for (int i = 0; i < G::NP; ++i) if (i >= p0 && i < p1) stage_piece(nbuf, i);
             if (a_ + 3 < 6) {
 #pragma unroll
-                for (int b2 = 0; b2 < 3; ++b2) u[(a_ + 3) & 3][b2] = (ABL & 2) ? f32x2_r{1.f, 1.f} : r_ld2(Ua + (3 * (a_ + 3) + b2) * 256);
+                for (int b2 = 0; b2 < 3; ++b2) u[(a_ + 3) & 3][b2] = (ABL & 2) ? f32x2{1.f, 1.f} : r_ld2(Ua + (3 * (a_ + 3) + b2) * 256);
             }
             if (a_ + 1 < 6) { col_row(a_ + 1); row_op(v[(a_ + 1) & 1]); }
             if (NKH == 1 && CI == 0 && a_ == 3) patch_rows(Rg, 1, 0);
@@ -234,7 +231,7 @@ __global__ __launch_bounds__(512, 2) void wino4r_kernel(const Wino4rParams p) {
 #pragma unroll
             for (int b2 = 0; b2 < 3; ++b2) {
                 const int pp = 3 * a_ + b2;
-                const f32x2_r uu = u[a_ & 3][b2];
+                const f32x2 uu = u[a_ & 3][b2];
                 if (!(ABL & 4)) {
                     acc[2 * pp] = __builtin_amdgcn_mfma_f32_16x16x4f32(uu.x, v[a_ & 1][2 * b2], acc[2 * pp], 0, 0, 0);
                     acc[2 * pp + 1] = __builtin_amdgcn_mfma_f32_16x16x4f32(uu.y, v[a_ & 1][2 * b2 + 1], acc[2 * pp + 1], 0, 0, 0);

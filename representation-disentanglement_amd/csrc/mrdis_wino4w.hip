@@ -30,11 +30,8 @@ constexpr int W_PIX = 32, W_RAW = 128 * W_PIX;
 constexpr int W_NXI = 4;                               // DMA pieces per V wave and iteration
 constexpr size_t W4W_LDS = sizeof(float) * (2 * W_VBUF + 2 * W_ZBUF + 3 * W_RAW);
 template <int V_> struct WIC { static constexpr int value = V_; };
-typedef unsigned u32x4_ww __attribute__((ext_vector_type(4)));
-typedef float f32x2_ww __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ f32x2_ww ww_ld2(const float* p) { return *(const volatile __attribute__((address_space(3))) f32x2_ww*)p; }
-__device__ __forceinline__ void ww_st2(float* p, f32x2_ww v) { *(volatile __attribute__((address_space(3))) f32x2_ww*)p = v; }
-__device__ __forceinline__ int ww_opaque(int idx) { asm volatile("" : "+v"(idx)); return idx; }
+__device__ __forceinline__ f32x2 ww_ld2(const float* p) { return *(const volatile __attribute__((address_space(3))) f32x2*)p; }
+__device__ __forceinline__ void ww_st2(float* p, f32x2 v) { *(volatile __attribute__((address_space(3))) f32x2*)p = v; }
 constexpr unsigned WW_OOB = 0xfffffff0u;
 }  // namespace
 
@@ -84,8 +81,8 @@ __global__ __launch_bounds__(512, 2) void wino4_wgrad_kernel(const Wino4WgradPar
     };
     Cur xcur, dcur;
     { int t = split; xcur.gx = t % p.ngx; t /= p.ngx; xcur.gy = t % p.ngy; xcur.n = t / p.ngy; dcur = xcur; }
-    const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)p.x, 0, (unsigned)(4LL * ((long long)(p.N * p.H) * p.W - 1) * p.ldx + 4LL * p.Ci), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc((void*)p.dy, 0, (unsigned)(4LL * ((long long)(p.N * p.H) * p.W - 1) * p.lddy + 4LL * p.Co), 0x00020000);
+    const __amdgpu_buffer_rsrc_t rs_x = mrdis_buffer_rsrc(p.x, mrdis_nhwc_bytes(p.N, p.H, p.W, p.ldx, p.Ci, 4));
+    const __amdgpu_buffer_rsrc_t rs_dy = mrdis_buffer_rsrc(p.dy, mrdis_nhwc_bytes(p.N, p.H, p.W, p.lddy, p.Co, 4));
 
     // role state shared in registers: sc[] = V waves: two patch columns (10) + B^T d (18) + one V row (6);
     //                                        Z waves: two sets of 16 dy values (32) + G dY (24) + one Z row (6)
@@ -118,9 +115,7 @@ __global__ __launch_bounds__(512, 2) void wino4_wgrad_kernel(const Wino4WgradPar
         const unsigned gb = 4u * (unsigned)(((xcur.n * p.H + 8 * xcur.gy - 1) * p.W + 8 * xcur.gx - 1) * p.ldx);     // wraps for halo origins; added mod 2^32
         const unsigned vo = ok ? gb + x_rel[j] : WW_OOB;
         const unsigned m0v = __builtin_amdgcn_readfirstlane(lds_raw + 4u * (unsigned)(buf * W_RAW) + 1024u * (unsigned)((wave & 3) + 4 * j));
-        unsigned keep;
-        asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tbuffer_load_dwordx4 %1, %3, 0 offen lds\n\ts_mov_b32 m0, %0"
-                     : "=&s"(keep) : "v"(vo), "s"(m0v), "s"(rs_x) : "memory");
+        mrdis_buffer_lds_dma16(m0v, vo, rs_x);
         if (j == W_NXI - 1) advance(xcur);
     };
     // ---- V waves: B^T d B (the forward kernel's input transform: B^T = [4 0 -5 0 1 0; 0 -4 -4 1 1 0; 0 4 -4 -1 1 0; 0 -2 -1 2 1 0; 0 2 -1 -2 1 0; 0 4 0 -5 0 1])
@@ -146,7 +141,7 @@ __global__ __launch_bounds__(512, 2) void wino4_wgrad_kernel(const Wino4WgradPar
     };
     auto v_put = [&](float* Vn, int a, auto RH_) {
         float* vp = Vn + (3 * (3 * decltype(RH_)::value + a)) * W_VPP;
-        ww_st2(vp, f32x2_ww{WW_VO(0), WW_VO(1)}); ww_st2(vp + W_VPP, f32x2_ww{WW_VO(2), WW_VO(3)}); ww_st2(vp + 2 * W_VPP, f32x2_ww{WW_VO(4), WW_VO(5)});
+        ww_st2(vp, f32x2{WW_VO(0), WW_VO(1)}); ww_st2(vp + W_VPP, f32x2{WW_VO(2), WW_VO(3)}); ww_st2(vp + 2 * W_VPP, f32x2{WW_VO(4), WW_VO(5)});
     };
     // ---- Z waves: dy loads and the unscaled G dY G^T: rows of 24 G = [6 0 0 0; -4 -4 -4 -4; -4 4 -4 4; 1 2 4 8; 1 -2 4 -8; 0 0 0 24] with the row factors
     //      (6, -4, -4, 1, 1, 24) / 24 left out: w = (d0, e + o, e - o, p + q, p - q, d3), e = d0 + d2, o = d1 + d3, p = d0 + 4 d2, q = 2 d1 + 8 d3
@@ -179,7 +174,7 @@ __global__ __launch_bounds__(512, 2) void wino4_wgrad_kernel(const Wino4WgradPar
     };
     auto z_put = [&](float* Zn, int i) {
         float* zp = Zn + (3 * i) * W_ZPP;
-        ww_st2(zp, f32x2_ww{WW_ZO(0), WW_ZO(1)}); ww_st2(zp + W_ZPP, f32x2_ww{WW_ZO(2), WW_ZO(3)}); ww_st2(zp + 2 * W_ZPP, f32x2_ww{WW_ZO(4), WW_ZO(5)});
+        ww_st2(zp, f32x2{WW_ZO(0), WW_ZO(1)}); ww_st2(zp + W_ZPP, f32x2{WW_ZO(2), WW_ZO(3)}); ww_st2(zp + 2 * W_ZPP, f32x2{WW_ZO(4), WW_ZO(5)});
     };
 
     f32x4 acc[36];
@@ -234,13 +229,13 @@ __global__ __launch_bounds__(512, 2) void wino4_wgrad_kernel(const Wino4WgradPar
     // one iteration of parity P in role ROLE (0 / 1: V wave, rows 0-2 / 3-5 of V; 2: Z wave)
     auto iteration = [&](auto P_, auto ROLE_) {
         constexpr int P = decltype(P_)::value, ROLE = decltype(ROLE_)::value;
-        const float* Va = smem + ww_opaque(P * W_VBUF + a_off);
-        const float* Za = smem + ww_opaque(2 * W_VBUF + P * W_ZBUF + b_off);
-        const float* Rr = smem + ww_opaque(2 * W_VBUF + 2 * W_ZBUF + ring1 * W_RAW);         // raw x block of group i + 1 (ring1 = (i + 1) % 3)
-        float* Vn = smem + ww_opaque((P ^ 1) * W_VBUF + v_dst);
-        float* Zn = smem + ww_opaque(2 * W_VBUF + (P ^ 1) * W_ZBUF + z_dst);
+        const float* Va = smem + mrdis_opaque(P * W_VBUF + a_off);
+        const float* Za = smem + mrdis_opaque(2 * W_VBUF + P * W_ZBUF + b_off);
+        const float* Rr = smem + mrdis_opaque(2 * W_VBUF + 2 * W_ZBUF + ring1 * W_RAW);         // raw x block of group i + 1 (ring1 = (i + 1) % 3)
+        float* Vn = smem + mrdis_opaque((P ^ 1) * W_VBUF + v_dst);
+        float* Zn = smem + mrdis_opaque(2 * W_VBUF + (P ^ 1) * W_ZBUF + z_dst);
         stamp(1);
-        f32x2_ww av[3], bv[3];
+        f32x2 av[3], bv[3];
 #pragma unroll
         for (int s_ = 0; s_ < 2; ++s_) { av[s_] = ww_ld2(Va + s_ * W_VPP); bv[s_] = ww_ld2(Za + s_ * W_ZPP); }
 #pragma unroll

@@ -97,6 +97,33 @@ def test_option_and_counter_tables_match_the_library(mrdis):
     assert lib.mrdis_dynamic_lds_table(tiny, 4) >= 0 and b'=' not in tiny.value.replace(b'\n', b'')[:0]
 
 
+OPTION_DEFAULTS = {
+    'wino': 1, 'nt_mb': 128, 'wino_pipe': 1, 'wino_u': 1, 'wino4': 1, 'wino4r': 1, 'bconv4': 1, 'split6': 1,
+    'debug_no16': 0, 'debug_nothin': 0, 'debug_noc4': 0, 'debug_nodma': 0, 'debug_no16_3d': 0, 'debug_bilgen': 0, 'debug_now16': 0, 'debug_nopack': 0,
+    'debug_mode': -1, 'debug_bn': -1, 'debug_kc': -1, 'debug_bm': -1, 'debug_c4_tw': -1, 'debug_wgsplit': -1, 'debug_bn3': -1, 'debug_kc3': -1,
+    'c4_grid': 0, 'debug_c4_blocks': -1, 'zsearch_grid': 0, 'debug_volgen': 0}
+
+
+def test_options_read_their_environment_once_at_load(mrdis):
+    """one environment variable per option kind, set before a FRESH process loads the library: a value switch with a default (MRDIS_WINO=0), a flag
+    (MRDIS_DEBUG_NO16 present, empty = 1) and a value switch that is unset by default (MRDIS_DEBUG_KC=16); every other option reads its default
+    (host-only calls, no kernel launch)"""
+    import json
+    import sys
+    assert set(OPTION_DEFAULTS) == set(mrdis.hip.OPTION_NAMES)
+    child = ('import ctypes, json, sys\n'
+             'lib = ctypes.CDLL(sys.argv[1])\n'
+             'lib.mrdis_get_option.restype, lib.mrdis_get_option.argtypes = ctypes.c_longlong, [ctypes.c_char_p]\n'
+             'print(json.dumps({n: lib.mrdis_get_option(n.encode()) for n in sys.argv[2:]}))\n')
+    env = {k: v for k, v in os.environ.items() if not k.startswith('MRDIS_')}
+    env.update(MRDIS_WINO='0', MRDIS_DEBUG_NO16='', MRDIS_DEBUG_KC='16')
+    out = subprocess.run([sys.executable, '-c', child, mrdis.LIB_PATH] + list(mrdis.hip.OPTION_NAMES), env=env, check=True,
+                         capture_output=True, text=True, timeout=120).stdout
+    got = json.loads(out.strip().splitlines()[-1])
+    want = dict(OPTION_DEFAULTS, wino=0, debug_no16=1, debug_kc=16)
+    assert got == want, {n: (got.get(n), want[n]) for n in want if got.get(n) != want[n]}
+
+
 def test_library_issues_no_memset_or_memcpy_calls():
     """the training step is recorded into HIP graphs (trainer.GraphedTrainStep): a hipMemsetAsync node did not run again on later replays (round 6, max_pool
     backward), so device buffers are cleared / copied by kernels only"""
@@ -113,7 +140,7 @@ def test_library_issues_no_memset_or_memcpy_calls():
 
 
 def test_launch_setup_lives_in_one_place():
-    """LDS opt-ins, CU counts and occupancy queries go through mrdis_lds_optin / mrdis_cu_count / mrdis_occupancy (mrdis_elem.hip), which cache per
+    """LDS opt-ins, CU counts and occupancy queries go through mrdis_lds_optin / mrdis_cu_count / mrdis_occupancy (mrdis_runtime.hip), which cache per
     kernel address and are safe from any thread: forward launches run on the main thread, backward ones on autograd's.  No launcher keeps a
     function-local cache of its own (a mutable host static)"""
     import glob
@@ -123,7 +150,7 @@ def test_launch_setup_lives_in_one_place():
     local_static = re.compile(r'^\s+static\s+(?!(const|constexpr|inline|__device__|__shared__)\b)')
     bad = []
     for f in sorted(glob.glob(os.path.join(root, '*.hip')) + glob.glob(os.path.join(root, '*.h'))):
-        if os.path.basename(f) == 'mrdis_elem.hip':
+        if os.path.basename(f) == 'mrdis_runtime.hip':
             continue
         for n, line in enumerate(open(f), 1):
             code = line.split('//')[0]
