@@ -440,6 +440,24 @@ int mrdis_nvnet_loss_bwd(const float* uout, const long long* stride_u, const flo
  * apply_sigmoid != 0: pred holds logits, the kernel compares sigmoid(pred).  C <= 4, P C < 2^31.  One launch, counted as "segcounts". */
 int mrdis_seg_counts(const float* pred, const float* target, int* out, int B, long long P, int C, int apply_sigmoid, void* stream);
 
+/* ---- whole-volume sliding-window prediction of the 3-D nets (csrc/mrdis_segvol.hip).  The overlap rule and the label rule are this
+ * package's own convention, like the objective: the reference ships no 3-D inference.
+ * mrdis_seg_accum: logits (B, H, W, Dz, C) fp32 (channels-last-3d view of the net's (B, C, H, W, Dz) output), acc (B, H, W, D, C) fp32,
+ *   16-byte aligned: acc[b][h][w][z0 + k][c] += sigmoid(logits[b][h'][w][k][c]), h' = H - 1 - h if flip_h (the prediction of an H-flipped
+ *   input, un-flipped), else h.  The sigmoid is the one of mrdis_seg_counts (accurate expf, IEEE division).  One thread owns an acc element
+ *   within a launch and there are no atomics: windows add in launch order, bit-identical from run to run.  1 <= C <= 4, any H, W, Dz >= 1,
+ *   0 <= z0 <= D - Dz (else MRDIS_EINVAL); B H W (Dz C + 6) / 4 < 2^31.  One launch, counted as "segaccum".
+ * mrdis_seg_label_volume: acc as above; cover (D) int32, device: how many accumulations touched each depth (windows times flips);
+ *   targets: B 64-bit device pointers (device memory) to raw (H, W, D) fp32 label volumes, 0 = none, or NULL = none for any sample.
+ *   Per voxel pbar_c = acc_c / (float)cover[z] (IEEE fp32 division; cover 1: the sigmoid itself; cover 0: nothing is predicted there);
+ *   counts (B, C, 3) int32 += { |pbar_c > 0.5 and t == c + 1|, |pbar_c > 0.5|, |t == c + 1| } (strictly above, t relabelled 4 -> 3 if
+ *   `relabel`: the semantics of mrdis_seg_counts); the caller zeroes `counts`.  labels (B, H, W, D) uint8, 4-byte aligned: 0 if
+ *   max_c pbar_c <= 0.5, else 1 + argmax_c pbar_c (lowest c on a tie), a 3 written as 4 if `relabel` (BraTS labels 0 / 1 / 2 / 4).
+ *   1 <= C <= 4, H W D < 2^31.  One launch, counted as "seglabels".                                                                 */
+int mrdis_seg_accum(const float* logits, float* acc, int B, int H, int W, int Dz, int D, int C, int z0, int flip_h, void* stream);
+int mrdis_seg_label_volume(const float* acc, const int* cover, const void* targets, unsigned char* labels, int* counts, int B, int H,
+                           int W, int D, int C, int relabel, void* stream);
+
 /* ---- max_pool2d(kernel k x k, stride k): model.py:3448-3451 ---------------- */
 int mrdis_maxpool_fwd(const float* x, int ldx, float* y, int32_t* argmax, int N, int H, int W, int C,
                       int k, void* stream);

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Entry point of the 3-D nets (NVNet3D / UNet3D), the counterpart of `main_missing.py`: reads `config3d.yaml` (or the file named first on
-the command line, then key=value overrides), trains with a validation pass per epoch or scores the test set on the MI355X hot path.
+the command line, then key=value overrides), trains with a validation pass per epoch, scores the test set, or writes whole-volume label maps (phase=predict) on the MI355X hot path.
 
     python main_3d.py                            # config3d.yaml in the working directory, else the built-in defaults
     python main_3d.py cfg3d.yaml epochs=2 batch_size=2 ckpt_path=/tmp/ckpt3d
     python main_3d.py cfg3d.yaml phase=test
+    python main_3d.py cfg3d.yaml phase=predict   # <ckpt_path>/result_test/<subj_id>_seg.npy + predict.csv
 """
 import os
 import sys

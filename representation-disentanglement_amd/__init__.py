@@ -23,7 +23,7 @@ from .trainer import (TrainStep, GraphedTrainStep, make_train_step, regular_mask
                       derive_config, build_model, synthetic_batch, fit_to_model, forward_losses,
                       save_checkpoint, load_checkpoint_model, LOSS_KEYS)
 
-from .model3d import BasicBlock, VAEBranch, UNet3D, NVNet3D, HipConv3d, nvnet_loss, nvnet_loss_hip, seg_metrics   # noqa: F401
+from .model3d import BasicBlock, VAEBranch, UNet3D, NVNet3D, HipConv3d, nvnet_loss, nvnet_loss_hip, seg_metrics, seg_metrics_from_counts, window_offsets, predict_volumes   # noqa: F401
 from .data import VolumeStore, SliceDataset, BatchLoader, load_idx_list   # noqa: F401
 from .data3d import VolumeStore3D, VolumeDataset3D, VolumeLoader3D, VolumeData3D, load_subj_list   # noqa: F401
 from . import train   # noqa: F401,E402

@@ -61,6 +61,7 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
     X(DIRECT3D, "direct3d") X(C3D16, "c3d16") X(WGRAD3D, "wgrad3d") X(WGRAD3D16, "wgrad3d16") X(WINO_WGRAD3D, "wino_wgrad3d") /* mrdis_conv3d.hip / mrdis_wino.hip: the 3-D kernels */ \
     X(VOLGATHER, "volgather") /* mrdis_volgather.hip: the 3-D batch gather, one count per mrdis_volume_gather call */ \
     X(LOSS3D, "loss3d") X(SEGCOUNTS, "segcounts") /* mrdis_loss3d.hip: one count per mrdis_nvnet_loss_fwd / _bwd call; one per mrdis_seg_counts call */ \
+    X(SEGACCUM, "segaccum") X(SEGLABELS, "seglabels") /* mrdis_segvol.hip: one count per mrdis_seg_accum / mrdis_seg_label_volume call */ \
     X(ALL, "all") /* every launch of the library */
 #define MRDIS_X_CNT_ID(id, name) MRDIS_CNT_##id,
 enum { MRDIS_COUNTERS(MRDIS_X_CNT_ID) MRDIS_CNT_COUNT };

@@ -1,5 +1,5 @@
 // Device-side primitives shared by the kernels of libmrdis_hip (gfx950 only), each defined ONCE: vector types, buffer descriptors, LDS-DMA copies,
-// the half-wave pairing of bf16 stores, bf16 <-> fp32 loads / stores and the three-term bf16 split.  A new kernel uses these instead of a copy under
+// the half-wave pairing of bf16 stores, bf16 <-> fp32 loads / stores, the sigmoid and the three-term bf16 split.  A new kernel uses these instead of a copy under
 // a prefix of its own; what is local to one kernel (tile constants, its body) stays in that kernel's file.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -75,6 +75,10 @@ __device__ __forceinline__ void mrdis_st4(__bf16* p, float4 v) {
 }
 __device__ __forceinline__ float mrdis_ld1(const float* p) { return *p; }
 __device__ __forceinline__ float mrdis_ld1(const __bf16* p) { return (float)*p; }
+
+// the fp32 sigmoid torch computes: accurate expf and an IEEE division.  The objective, the segmentation counts and the sliding-window accumulation
+// (mrdis_loss3d.hip, mrdis_segvol.hip) must agree on which side of 0.5 a probability falls, so they share this one.
+__device__ __forceinline__ float mrdis_sigmoid(float u) { return 1.f / (1.f + expf(-u)); }
 
 // ------------------------------------------------------------------ three-term bf16 split
 // v = h + m + l, each term the bf16 rounding (to nearest even) of what the terms before it left: 3 x 8 mantissa bits.  With both operands of a

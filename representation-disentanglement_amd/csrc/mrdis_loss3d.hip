@@ -31,15 +31,13 @@ constexpr int L3_THREADS = 256;
 constexpr int L3_MAX_BLOCKS = 2048;          // 256 CUs x 8 workgroups: the grid of a memory-bound pass (cdna_hip_programming.md Guideline 11)
 constexpr int L3_UNROLL = 4;
 
-__device__ __forceinline__ float l3_sigmoid(float u) { return 1.f / (1.f + expf(-u)); }
-
 struct L3Sums { double a, p2, t2, se; };
 struct L3Coef { double c1, c2, cv; };
 
 // per-element operations: two that add to the running sums, two that give a gradient
 struct L3AccUT {
     __device__ __forceinline__ void operator()(float u, float t, L3Sums& s) const {
-        const double p = (double)l3_sigmoid(u), td = (double)t;
+        const double p = (double)mrdis_sigmoid(u), td = (double)t;
         s.a = fma(p, td, s.a); s.p2 = fma(p, p, s.p2); s.t2 = fma(td, td, s.t2);
     }
 };
@@ -52,7 +50,7 @@ struct L3AccVX {
 struct L3GradU {
     L3Coef c;
     __device__ __forceinline__ float operator()(float u, float t) const {
-        const double p = (double)l3_sigmoid(u);
+        const double p = (double)mrdis_sigmoid(u);
         return (float)(fma(c.c2, p, c.c1 * (double)t) * (p * (1.0 - p)));
     }
 };
@@ -194,7 +192,7 @@ __global__ __launch_bounds__(L3_THREADS) void seg_counts_kernel(const float* __r
         }
 #pragma unroll
         for (int j = 0; j < 4 * C; ++j) {
-            const float q = apply_sigmoid ? l3_sigmoid(pv[j]) : pv[j];
+            const float q = apply_sigmoid ? mrdis_sigmoid(pv[j]) : pv[j];
             const bool pp = q > 0.5f, tt = tv[j] == 1.f;   // strictly above 0.5, util.py:986-987
             cnt[j % C][0] += (pp && tt) ? 1 : 0; cnt[j % C][1] += pp ? 1 : 0; cnt[j % C][2] += tt ? 1 : 0;
         }

@@ -89,15 +89,18 @@ class VolumeDataset3D:
             raise ValueError(f'volumes of depth {self.store.shape[2]} leave nothing inside the crop')
         return Z0, Dz
 
-    def meta(self, idx, rng=None):
+    def meta(self, idx, rng=None, plain=False):
         """-> (subj_id, slice_idx = 0, volume pointers, dropped contrast or -1, target pointer, flip, scale, shift).  rng: None = the global np.random (the
-        reference's own stream, draw for draw) or the loader's own np.random.RandomState (data-parallel runs, see BatchLoader)."""
+        reference's own stream, draw for draw) or the loader's own np.random.RandomState (data-parallel runs, see BatchLoader).  `plain`: the item as
+        stored -- nothing dropped, not augmented -- and no draw from any stream (the windowed reads of VolumeLoader3D.batches(z0=...))."""
         rng = np.random if rng is None else rng
         subj_id = str(self.subj_list[idx])
         ptrs = [self.store.ptr(subj_id + '/' + c) for c in self.contrast_list]
         mask = np.array([1 if p else 0 for p in ptrs])
         tkey = self.TARGET_KEYS.get(self.dataset_name)
         tptr = self.store.ptr(subj_id + tkey) if tkey else 0
+        if plain:
+            return subj_id, 0, ptrs, -1, tptr, False, 1.0, 0.0
         drop = -1
         if self.dropoff and mask.sum() > 1:                           # :791-795, same RNG call order
             if rng.rand() > 0.8:
@@ -123,11 +126,13 @@ class VolumeLoader3D(BatchLoader):
         super().__init__(dataset, batch_size, shuffle, rank, world, equal_steps, generator)
         self.region_channels = int(region_channels)
 
-    def table(self, metas):
-        """the per-batch table of mrdis_volume_gather (include/mrdis.h), on the host, and the host twin of `mask`."""
+    def table(self, metas, plain=False):
+        """the per-batch table of mrdis_volume_gather (include/mrdis.h), on the host, and the host twin of `mask`.  `plain`: the augment bit stays
+        clear whatever the dataset says, and no crop minima are looked up (only the augmentation reads them; they belong to the crop's own z0)."""
         ds, st = self.dataset, self.dataset.store
         M = len(ds.contrast_list)
         z0, Dz = ds.crop()
+        aug = ds.aug and not plain
         B = len(metas)
         tab = np.zeros((B, 2 * M + 3), dtype=np.int64)
         mask_host = np.zeros((B, M), dtype=np.float32)                 # host twin of `mask`: a loss may branch on it without a sync
@@ -135,31 +140,82 @@ class VolumeLoader3D(BatchLoader):
             for m, p in enumerate(ptrs):
                 if p and m != drop:
                     tab[r, m] = p
-                    tab[r, M + m] = st.crop_min_ptr(subj_id + '/' + ds.contrast_list[m], z0, Dz)
+                    tab[r, M + m] = st.crop_min_ptr(subj_id + '/' + ds.contrast_list[m], z0, Dz) if not plain else 0
                     mask_host[r, m] = 1.0
             tab[r, 2 * M] = tptr
-            tab[r, 2 * M + 1] = (1 if flip else 0) | (2 if ds.aug else 0)
+            tab[r, 2 * M + 1] = (1 if flip else 0) | (2 if aug else 0)
             bits = np.array([scale, shift], dtype=np.float32).view(np.uint32).astype(np.uint64)
             tab[r, 2 * M + 2] = (bits[0] | (bits[1] << np.uint64(32))).view(np.int64)
         return tab, mask_host
 
-    def batches(self, limit=None):
+    def plain_plan(self, limit=None):
+        """host half of the windowed reads: yields (batch index, dataset indices, item metas) of this rank's batches with every item as stored
+        (VolumeDataset3D.meta(plain=True): nothing dropped, nothing augmented).  The batches follow the DATASET order whether or not the loader
+        shuffles, and every subject is served (no equal_steps tail is dropped): the plan draws from no random stream, so every call gives the
+        same batches -- all depth windows of a prediction see the same subjects in the same rows -- and a training loader's shuffle stream
+        is left where it was.  For a loader that does not shuffle (the evaluation loaders) these are the batches of `batch_plan`."""
+        n, bs = len(self.dataset), self.batch_size
+        g = (n + bs - 1) // bs
+        for k in range(g if limit is None else min(g, limit)):
+            if k % self.world == self.rank:
+                idxs = list(range(k * bs, min((k + 1) * bs, n)))
+                yield k, idxs, [self.dataset.meta(i, plain=True) for i in idxs]
+
+    @staticmethod
+    def target_ptrs(batch):
+        """(B,) int64 on the device: the addresses of a windowed batch's raw (H, W, D) label volumes, 0 = none -- word [2M] of its gather table
+        (what hip.seg_label_volume scores a whole-volume prediction against).  Only the batches of `window` / `batches(z0=...)` carry the table."""
+        table = batch['table']
+        return table[:, (table.shape[1] - 3)].contiguous()
+
+    def _gather(self, k, metas, z0, plain):
         ds, st = self.dataset, self.dataset.store
         H, W, D = st.shape
         M = len(ds.contrast_list)
-        z0, Dz = ds.crop()
+        Dz = ds.crop()[1]
         dev = st.device
-        for k, _, metas in self.batch_plan(limit):
-            tab, mask_host = self.table(metas)
-            host = torch.from_numpy(tab)
-            if dev.type == 'cuda':
-                host = host.pin_memory()
-            d = host.to(dev, non_blocking=True)                       # one small H2D copy per batch
-            inputs, mask = hip.volume_gather(d, M, H, W, D, z0, Dz)
-            targets = hip.volume_gather(d, M, H, W, D, z0, Dz, targets=True, K=self.region_channels, relabel=ds.dataset_name == 'BraTS')
-            yield {'inputs': inputs, 'targets': targets, 'subj_id': [m[0] for m in metas],
-                   'slice_idx': torch.zeros(len(metas), dtype=torch.int64, device=dev), 'mask': mask, 'mask_host': mask_host,
-                   'batch_index': k}
+        tab, mask_host = self.table(metas, plain=plain)
+        host = torch.from_numpy(tab)
+        if dev.type == 'cuda':
+            host = host.pin_memory()
+        d = host.to(dev, non_blocking=True)                           # one small H2D copy per batch
+        inputs, mask = hip.volume_gather(d, M, H, W, D, z0, Dz)
+        targets = hip.volume_gather(d, M, H, W, D, z0, Dz, targets=True, K=self.region_channels, relabel=ds.dataset_name == 'BraTS')
+        batch = {'inputs': inputs, 'targets': targets, 'subj_id': [m[0] for m in metas],
+                 'slice_idx': torch.zeros(len(metas), dtype=torch.int64, device=dev), 'mask': mask, 'mask_host': mask_host,
+                 'batch_index': k}
+        if plain:
+            batch['table'] = d                                        # windowed reads only: `target_ptrs` reads the label-volume addresses from it
+        return batch
+
+    def window(self, k, metas, z0, flip=False):
+        """one batch of `plain_plan` at depth offset z0 (same Dz as the crop), every item as stored, H-flipped by the gather itself if `flip`:
+        the sample dict of `batches` plus 'table', the device gather table (`target_ptrs`)."""
+        D = self.dataset.store.shape[2]
+        Dz = self.dataset.crop()[1]
+        if not 0 <= int(z0) <= D - Dz:
+            raise ValueError(f'z0 {z0} outside [0, {D - Dz}] (D {D}, Dz {Dz})')
+        if flip:
+            metas = [m[:5] + (True,) + m[6:] for m in metas]
+        return self._gather(k, metas, int(z0), plain=True)
+
+    def batches(self, limit=None, z0=None, flip=False):
+        """`z0=None`: the reference's batches (crop [45:-46], drop-off, augmentation).  An integer serves the batches of `plain_plan` with that
+        depth offset and the same Dz, every item as stored (no drop-off redraws, no augmentation, no shuffle): the windowed reads for
+        whole-volume prediction (model3d.predict_volumes).  `flip` (with z0 only): every item H-flipped by the gather itself."""
+        if z0 is None:
+            if flip:
+                raise ValueError('flip belongs to the windowed reads: give z0')
+            crop_z0 = self.dataset.crop()[0]
+            for k, _, metas in self.batch_plan(limit):
+                yield self._gather(k, metas, crop_z0, plain=False)
+        else:
+            D = self.dataset.store.shape[2]
+            Dz = self.dataset.crop()[1]
+            if not 0 <= int(z0) <= D - Dz:
+                raise ValueError(f'z0 {z0} outside [0, {D - Dz}] (D {D}, Dz {Dz})')
+            for k, _, metas in self.plain_plan(limit):
+                yield self.window(k, metas, z0, flip)
 
 
 class VolumeData3D:

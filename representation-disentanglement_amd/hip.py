@@ -94,6 +94,8 @@ _SIGS = {
     'mrdis_nvnet_loss_fwd': (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_double, _P, _P, _P, _Z, _P]),
     'mrdis_nvnet_loss_bwd': (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_double, _P, _P, _P, _P, _P]),
     'mrdis_seg_counts': (_I, [_P, _P, _P, _I, _L, _I, _I, _P]),
+    'mrdis_seg_accum': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'mrdis_seg_label_volume': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_bwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_sumsq_workspace': (_Z, []),
@@ -207,6 +209,9 @@ DATA_FAMILIES = ('volgather',)
 # the fused objective of the 3-D nets and the segmentation counts (csrc/mrdis_loss3d.hip): 'loss3d' counts one per mrdis_nvnet_loss_fwd and one per
 # mrdis_nvnet_loss_bwd call, 'segcounts' one per mrdis_seg_counts call.
 LOSS3D_FAMILIES = ('loss3d', 'segcounts')
+# whole-volume sliding-window prediction (csrc/mrdis_segvol.hip): 'segaccum' counts one per mrdis_seg_accum call (one per window and flip),
+# 'seglabels' one per mrdis_seg_label_volume call (one per batch).
+SEGVOL_FAMILIES = ('segaccum', 'seglabels')
 
 
 def stream_fill(t, value=0.0):
@@ -234,7 +239,7 @@ def dynamic_lds():
 def launch_counts(reset=False):
     """{family: launches since load / the last reset} of the Winograd, bf16 LDS-DMA and six-product (split6) kernel families (include/mrdis.h mrdis_launch_count)"""
     lib = load()
-    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES}
+    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES}
     if reset:
         lib.mrdis_launch_count_reset()
     return out
@@ -1200,6 +1205,45 @@ def seg_counts(pred, target, logits=False):
     out = torch.zeros((B, C, 3), dtype=torch.int32, device=pred.device)
     _chk(lib.mrdis_seg_counts(_ptr(pred), _ptr(target), _ptr(out), B, P, C, int(bool(logits)), _stream()), 'seg_counts')
     return out
+
+
+def seg_accum(logits, acc, z0, flip_h=False):
+    """acc[:, :, :, z0:z0 + Dz, :] += sigmoid(logits), un-flipped along H if `flip_h` (include/mrdis.h mrdis_seg_accum), in place; returns acc.
+    logits (B, C, H, W, Dz) fp32 dense channels-last-3d (the net's output), acc (B, H, W, D, C) fp32 contiguous.  Any other layout raises
+    MrdisError: nothing is copied."""
+    lib = load()
+    if logits.dtype != torch.float32 or acc.dtype != torch.float32 or logits.dim() != 5 or acc.dim() != 5:
+        raise MrdisError(f'seg_accum: fp32 5-d tensors only, got {logits.dtype} {tuple(logits.shape)} and {acc.dtype} {tuple(acc.shape)}')
+    B, C, H, W, Dz = logits.shape
+    D = acc.shape[3]
+    if tuple(acc.shape) != (B, H, W, D, C):
+        raise MrdisError(f'seg_accum: acc {tuple(acc.shape)} does not belong to logits {tuple(logits.shape)}: (B, H, W, D, C) wanted')
+    if not logits.permute(0, 2, 3, 4, 1).is_contiguous():
+        raise MrdisError(f'seg_accum: logits with strides {logits.stride()} are not dense channels-last-3d')
+    if not acc.is_contiguous():
+        raise MrdisError(f'seg_accum: acc with strides {acc.stride()} is not contiguous')
+    _chk(lib.mrdis_seg_accum(_ptr(logits), _ptr(acc), B, H, W, Dz, D, C, int(z0), int(bool(flip_h)), _stream()), 'seg_accum')
+    return acc
+
+
+def seg_label_volume(acc, cover, target_ptrs=None, relabel=False):
+    """-> (labels (B, H, W, D) uint8, counts (B, C, 3) int32), both on the device (include/mrdis.h mrdis_seg_label_volume).  acc (B, H, W, D, C)
+    fp32 contiguous as `seg_accum` leaves it, cover (D,) int32 on the device, target_ptrs (B,) int64 on the device: addresses of raw (H, W, D)
+    fp32 label volumes, 0 = none (None: none for any sample).  A tensor that is not dense in that layout raises MrdisError; nothing is copied."""
+    lib = load()
+    if acc.dtype != torch.float32 or acc.dim() != 5 or not acc.is_contiguous():
+        raise MrdisError(f'seg_label_volume: acc must be a contiguous fp32 (B, H, W, D, C) tensor, got {acc.dtype} {tuple(acc.shape)} strides {acc.stride()}')
+    B, H, W, D, C = acc.shape
+    if cover.dtype != torch.int32 or tuple(cover.shape) != (D,) or not cover.is_contiguous() or cover.device != acc.device:
+        raise MrdisError(f'seg_label_volume: cover must be a contiguous int32 ({D},) tensor on {acc.device}, got {cover.dtype} {tuple(cover.shape)}')
+    if target_ptrs is not None and (target_ptrs.dtype != torch.int64 or tuple(target_ptrs.shape) != (B,) or not target_ptrs.is_contiguous()
+                                    or target_ptrs.device != acc.device):
+        raise MrdisError(f'seg_label_volume: target_ptrs must be a contiguous int64 ({B},) tensor on {acc.device}')
+    labels = torch.empty((B, H, W, D), dtype=torch.uint8, device=acc.device)
+    counts = torch.zeros((B, C, 3), dtype=torch.int32, device=acc.device)
+    _chk(lib.mrdis_seg_label_volume(_ptr(acc), _ptr(cover), _ptr(target_ptrs), _ptr(labels), _ptr(counts), B, H, W, D, C, int(bool(relabel)),
+                                    _stream()), 'seg_label_volume')
+    return labels, counts
 
 
 def recon_err_bwd(gt, x, w, p):

@@ -339,3 +339,74 @@ def seg_metrics(pred_or_logits, target, logits=True):
     formed in float64 on the host (one small D2H copy).  Inputs that are not channels-last-3d are copied into that layout first (hip.seg_counts).
     -> {'dice': (B,), 'iou': (B,)} float64 CPU tensors."""
     return seg_metrics_from_counts(hip.seg_counts(pred_or_logits, target, logits=logits).cpu().numpy())
+
+
+# --------------------------------------------------------------------------- whole-volume sliding-window prediction (csrc/mrdis_segvol.hip)
+def window_offsets(D, Dz, stride):
+    """depth offsets of the windows [z0, z0 + Dz) that slide along D: 0, stride, 2 stride, ... below D - Dz, then D - Dz itself (no duplicate);
+    [0] when D == Dz.  A stride above Dz leaves depths no window covers (they are predicted as label 0)."""
+    D, Dz, stride = int(D), int(Dz), int(stride)
+    if D < Dz or Dz < 1:
+        raise ValueError(f'a window of {Dz} slices does not fit a depth of {D}')
+    if stride < 1:
+        raise ValueError(f'stride {stride}: at least 1')
+    return list(range(0, D - Dz, stride)) + [D - Dz]
+
+
+def window_cover(D, Dz, offsets, flips=1):
+    """(D,) int32: how many accumulations touch each depth -- windows that hold it times `flips`"""
+    cover = np.zeros(D, dtype=np.int32)
+    for z0 in offsets:
+        cover[z0:z0 + Dz] += flips
+    return cover
+
+
+def predict_volumes(model, loader, stride=None, flip=False, limit=None):
+    """Label volumes over the FULL depth of every subject a VolumeLoader3D serves, as a generator over its batches:
+        {'subj_id': list, 'labels': (B, H, W, D) uint8 on the device, 'counts': (B, 3, 3) int32 on the device, 'acc': (B, H, W, D, C) fp32}
+    The trained depth window (Dz = the loader's crop depth) slides along D at `window_offsets(D, Dz, stride)` (stride None: Dz // 2); the sigmoid
+    probabilities of overlapping windows -- and, with `flip`, of the H-flipped input, un-flipped -- are averaged; a voxel's label is 0 if no
+    region's mean probability is above 0.5, else 1 + the most probable region (lowest on a tie), region 3 written as 4 for BraTS: the store's
+    own labels 0 / 1 / 2 / 4 in its own (H, W, D) geometry.  `counts` are the reference's Dice / IoU counts (`seg_metrics_from_counts`) of the
+    mean probabilities against the subject's full label volume; `acc` holds the summed probabilities.  Overlap rule and label rule are this
+    package's own convention, like `nvnet_loss`: the reference ships no 3-D inference.
+
+    Eval mode, no_grad.  An `NVNet3D` runs its `unet` only: the VAE branch is training-time regularisation and is bound to the crop shape.
+    Per batch: one `hip.seg_accum` launch per window (and per flip), then one `hip.seg_label_volume`; nothing syncs with the host.  The loader
+    must serve the items as stored (aug and dropoff off), otherwise ValueError.  The batches are those of `loader.plain_plan`: dataset order
+    even for a loader that shuffles, drawn ONCE and shared by all windows, and no random stream is touched.  `limit`: stop after that many
+    batches.  `acc` stays alive as long as the caller holds the yielded dict (57 MB per BraTS subject): drop it if it is not wanted."""
+    ds = loader.dataset
+    if ds.aug or ds.dropoff:
+        raise ValueError('predict_volumes reads the volumes as stored: the loader must have aug=False and dropoff=False')
+    H, W, D = ds.store.shape
+    _, Dz = ds.crop()
+    offsets = window_offsets(D, Dz, Dz // 2 if stride is None else stride)
+    flips = (False, True) if flip else (False,)
+    net = model.unet if isinstance(model, NVNet3D) else model
+    C = net.out_channels
+    dev = ds.store.device
+    cover = torch.from_numpy(window_cover(D, Dz, offsets, len(flips))).to(dev)
+    relabel = ds.dataset_name == 'BraTS'
+    was_training = net.training
+    net.eval()
+    try:
+        with torch.no_grad():
+            # ONE plan for all windows: every window and flip of a batch gathers the same subjects into the same rows
+            for k, _, metas in loader.plain_plan(limit):
+                subj_id = [m[0] for m in metas]
+                acc = torch.zeros((len(metas), H, W, D, C), dtype=torch.float32, device=dev)
+                ptrs = None
+                for z0 in offsets:
+                    for f in flips:
+                        batch = loader.window(k, metas, z0, flip=f)
+                        if batch['subj_id'] != subj_id:
+                            raise RuntimeError(f'window {z0} of batch {k} serves {batch["subj_id"]}, not {subj_id}')
+                        if ptrs is None:
+                            ptrs = loader.target_ptrs(batch)
+                        hip.seg_accum(net(batch['inputs'])[0], acc, z0, flip_h=f)
+                        del batch
+                labels, counts = hip.seg_label_volume(acc, cover, ptrs, relabel=relabel)
+                yield {'subj_id': subj_id, 'labels': labels, 'counts': counts, 'acc': acc}
+    finally:
+        net.train(was_training)

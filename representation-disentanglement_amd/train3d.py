@@ -7,7 +7,8 @@ here is the package's own: the objective is `nvnet_loss` (Myronenko 2018) -- thr
 csrc/mrdis_loss3d.hip) unless `fused_loss: false` -- the optimizer is `ArenaAdam` with the fused clip, the validation metric is the reference's
 Dice / IoU (`compute_segmentation_metrics`, util.py:946-992) from the integer counts of `mrdis_seg_counts`, and stat.csv / `epochNNN.pth.tar` /
 `model_best.pth.tar` are written by the same `save_result_stat` / `save_checkpoint` as the 2-D entry.  The best checkpoint is the epoch with the
-highest validation Dice.
+highest validation Dice.  `phase: predict` loads it and writes one label volume per subject over the FULL depth (sliding window,
+model3d.predict_volumes) with its Dice / IoU.
 
 A checkpoint also carries the host and device RNG states (np.random, torch default, the torch device generator, the loaders' own generator
 if any), written after the epoch's validation pass: `continue_train` then continues exactly where the run stopped -- the shuffles, augmentation
@@ -27,12 +28,12 @@ import yaml
 
 from . import hip
 from .data3d import VolumeData3D
-from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, seg_metrics_from_counts
+from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, predict_volumes, seg_metrics_from_counts
 from .train import parse_overrides, save_config_file, save_result_stat
 from .trainer import ArenaAdam, load_checkpoint_model, save_checkpoint
 
 DEFAULT_CONFIG_3D = {
-    'phase': 'train',                  # train | test (test: load model_best.pth.tar, print the test-set stat)
+    'phase': 'train',                  # train | test (load model_best.pth.tar, print the test-set stat) | predict (load it, write whole-volume label maps)
     'dataset_name': 'BraTS', 'data_path': '../data/', 'norm_type': 'z-score', 'fold': 0,
     'contrast_list': ['T1', 'T1c', 'T2', 'T2_FLAIR'], 'batch_size': 4,
     'model_name': 'NVNet3D',           # NVNet3D | UNet3D (Dice-only objective)
@@ -45,7 +46,11 @@ DEFAULT_CONFIG_3D = {
     'ckpt_name': None,                 # checkpoint file to load; None: the last epochNNN.pth.tar (continue_train) / model_best.pth.tar (test)
     'seed': 10, 'device': 'cuda:0',
     'max_batches': None,               # cap on the batches of every train / validation / test pass (tests)
+    'predict_set': 'test',             # phase predict: the loader whose subjects are predicted (train | val | test; it must serve them as stored)
+    'predict_stride': None,            # depth stride of the sliding window; None: half the trained depth
+    'predict_flip': False,             # also average the prediction of the H-flipped input
 }
+PHASES = ('train', 'test', 'predict')
 MODEL_NAMES = ('NVNet3D', 'UNet3D')
 LR_SCHEDULES = ('none', 'poly')
 STAT_KEYS = ('loss', 'loss_dice', 'loss_l2', 'loss_kl')
@@ -68,8 +73,14 @@ def load_config3d(path=None, overrides=None):
         raise ValueError(f'model_name {cfg["model_name"]!r}: one of {MODEL_NAMES}')
     if cfg['lr_schedule'] not in LR_SCHEDULES:
         raise ValueError(f'lr_schedule {cfg["lr_schedule"]!r}: one of {LR_SCHEDULES}')
-    if cfg['phase'] not in ('train', 'test'):
-        raise ValueError(f'phase {cfg["phase"]!r}: train or test')
+    if cfg['phase'] not in PHASES:
+        raise ValueError(f'phase {cfg["phase"]!r}: one of {PHASES}')
+    if cfg['predict_set'] not in ('train', 'val', 'test'):
+        raise ValueError(f'predict_set {cfg["predict_set"]!r}: train, val or test')
+    if cfg['predict_stride'] is not None:
+        cfg['predict_stride'] = int(cfg['predict_stride'])
+        if cfg['predict_stride'] < 1:
+            raise ValueError(f'predict_stride {cfg["predict_stride"]}: at least 1 (or null: half the trained depth)')
     return cfg
 
 
@@ -137,7 +148,7 @@ class Run3D:
         self.optimizer = ArenaAdam(self.model.parameters(), lr=cfg['lr'], weight_decay=cfg['weight_decay'], used=list(self.model.parameters()))
         self.start_epoch = -1
         self.best_dice = -1.0
-        if cfg['continue_train'] or cfg['phase'] == 'test':
+        if cfg['continue_train'] or cfg['phase'] in ('test', 'predict'):
             self._load(cfg['ckpt_name'] or (last_epoch_checkpoint(cfg['ckpt_path']) if cfg['phase'] == 'train' else 'model_best.pth.tar'))
         if cfg['phase'] == 'train':
             os.makedirs(cfg['ckpt_path'], exist_ok=True)
@@ -266,6 +277,34 @@ class Run3D:
         stat['dice'], stat['iou'] = float(met['dice'].mean()), float(met['iou'].mean())
         return stat
 
+    def predict(self, set_=None):
+        """whole-volume sliding-window prediction (model3d.predict_volumes) of every subject the `set_` loader serves (None: `predict_set`):
+        writes <ckpt_path>/result_<set>/<subj_id>_seg.npy -- uint8 (H, W, D), the store's own geometry and labels (BraTS: 0 / 1 / 2 / 4) -- and
+        result_<set>/predict.csv with a header and one `subj_id,dice,iou` row per subject (the reference's Dice / IoU over the FULL depth);
+        returns their means.  One D2H copy of the labels per batch, one of all counts at the end; no window syncs with the host."""
+        cfg = self.config
+        set_ = cfg['predict_set'] if set_ is None else set_
+        out_dir = os.path.join(cfg['ckpt_path'], f'result_{set_}')
+        os.makedirs(out_dir, exist_ok=True)
+        subj, counts = [], []
+        for res in predict_volumes(self.model, self.loaders[set_], stride=cfg['predict_stride'], flip=cfg['predict_flip'],
+                                   limit=cfg['max_batches'] or None):
+            labels = res['labels'].cpu().numpy()
+            for i, sid in enumerate(res['subj_id']):
+                np.save(os.path.join(out_dir, f'{sid}_seg.npy'), labels[i])
+            subj += res['subj_id']
+            counts.append(res['counts'])
+        if not subj:
+            raise RuntimeError(f'predict({set_!r}): the loader yielded no batch')
+        met = seg_metrics_from_counts(torch.cat(counts).cpu().numpy())
+        with open(os.path.join(out_dir, 'predict.csv'), 'w') as f:
+            f.write('subj_id,dice,iou\n')
+            for sid, d, i in zip(subj, met['dice'].tolist(), met['iou'].tolist()):
+                f.write(f'{sid},{d!r},{i!r}\n')
+        stat = {'dice': float(met['dice'].mean()), 'iou': float(met['iou'].mean()), 'n': len(subj)}
+        self.log(f'predict {set_}: {len(subj)} volumes under {out_dir}, dice {stat["dice"]:.4f}, iou {stat["iou"]:.4f}')
+        return stat
+
 
 def main(argv=None):
     path, overrides = parse_argv(sys.argv[1:] if argv is None else argv)
@@ -274,6 +313,8 @@ def main(argv=None):
     run = Run3D(load_config3d(path, overrides))
     if run.config['phase'] == 'train':
         run.train()
+    elif run.config['phase'] == 'predict':
+        print(run.predict())
     else:
         print(run.evaluate('test'))
     return run

@@ -6,13 +6,17 @@ net (forward / data gradient / weight gradient, TFLOP/s against the 157 TFLOP/s 
     python tools/bench3d.py --loader [--batch 4] [--vol 160 192 155]      # the HBM-resident 3-D loader (data3d.py) in front of that step
     python tools/bench3d.py --loss-only                                   # the objective alone, forward + backward: torch composition vs fused HIP kernels
     python tools/bench3d.py --fused-loss                                  # the step with the torch objective and with the fused one, alternating windows
+    python tools/bench3d.py --predict [--batch 4] [--vol 160 192 155]     # whole-volume sliding-window prediction: the two kernels, the torch composition, a batch end to end
 
 --loader builds a synthetic BraTS-shaped store, times the one-launch batch gather (mrdis_volume_gather) beside a store-only probe over the same
 buffer and beside the obvious torch composition of the same batch (stack, slice, flip, mul / add, where, permute().contiguous()), then times
 the configs[4]-shaped step fed by a fixed batch and fed by the loader.  --loss-only times `nvnet_loss` + autograd against `nvnet_loss_hip`
 (csrc/mrdis_loss3d.hip) on the net's own output shapes, the two kernels alone (achieved bytes/s from the bytes the algorithm needs) beside the
 store-only probe, and prints both objectives' error against a float64 evaluation.  --fused-loss times the whole step with either objective in
-alternating windows; the torch windows repeat, which gives the box's run-to-run spread.  One JSON line per measurement.
+alternating windows; the torch windows repeat, which gives the box's run-to-run spread.  --predict times mrdis_seg_accum (at an aligned and at
+BraTS's unaligned last offset) and mrdis_seg_label_volume (csrc/mrdis_segvol.hip) beside the store-only probe over the same bytes and beside the
+torch composition of the same batch, in alternating windows, then predict_volumes of one batch at stride 32 with and without the flip.  One JSON
+line per measurement.
 """
 import argparse
 import json
@@ -272,6 +276,104 @@ def step_bench(a):
                       'config': f'{B}x4x{S}^3 fp32, init_channels {a.channels}, dropout 0.2', 'loss': float(loss.detach())}), flush=True)
 
 
+def predict_bench(a):
+    """the kernels of csrc/mrdis_segvol.hip at B x 3 x H x W, Dz = 64, D from --vol: achieved bytes/s from the bytes the algorithm needs"""
+    dev = torch.device('cuda:0')
+    H, W, D = a.vol
+    B, C, Dz = a.batch, 3, 64
+    hip = mrdis.hip
+    g = torch.Generator().manual_seed(4)
+    logits = (3 * torch.randn(B, H, W, Dz, C, generator=g)).to(dev).permute(0, 4, 1, 2, 3)
+    acc = torch.zeros(B, H, W, D, C, device=dev)
+    win = 4.0 * logits.numel()
+    cfgs = f'{B} x {C} x {H} x {W}, Dz {Dz}, D {D}'
+    z_al, z_un = 32, D - Dz
+
+    def torch_accum(z0, flip=False):
+        p = torch.sigmoid(logits.permute(0, 2, 3, 4, 1))
+        acc[:, :, :, z0:z0 + Dz] += p.flip(1) if flip else p
+
+    buf = torch.empty(int(3 * win / 4) // 4 * 4, device=dev)
+    rows = {'kernel_z%d' % z_al: [], 'kernel_z%d' % z_un: [], 'kernel_z%d_flip' % z_un: [], 'torch_z%d' % z_un: [], 'store_only': []}
+    for _ in range(3):                                          # alternating windows: the repeats give the spread
+        rows['kernel_z%d' % z_al].append(round(timeit(lambda: hip.seg_accum(logits, acc, z_al), a.reps), 1))
+        rows['kernel_z%d' % z_un].append(round(timeit(lambda: hip.seg_accum(logits, acc, z_un), a.reps), 1))
+        rows['kernel_z%d_flip' % z_un].append(round(timeit(lambda: hip.seg_accum(logits, acc, z_un, flip_h=True), a.reps), 1))
+        rows['torch_z%d' % z_un].append(round(timeit(lambda: torch_accum(z_un), a.reps), 1))
+        rows['store_only'].append(round(timeit(lambda: hip.stream_fill(buf), a.reps), 1))
+    best = {k: min(v) for k, v in rows.items()}
+    print(json.dumps({'metric': 'mrdis_seg_accum, us per call (three alternating windows)', 'config': cfgs, **rows,
+                      'moved_mb': round(3 * win / 1e6, 1), 'note': 'moved = logits read + acc window read + acc window write',
+                      'tb_per_s': {k: round(3 * win / t / 1e6, 2) for k, t in best.items() if k.startswith('kernel')},
+                      'store_only_tb_per_s': round(4.0 * buf.numel() / best['store_only'] / 1e6, 2),
+                      'torch_over_kernel': round(best['torch_z%d' % z_un] / best['kernel_z%d' % z_un], 2)}), flush=True)
+    # labels + counts
+    acc.zero_()
+    offs = mrdis.window_offsets(D, Dz, 32)
+    for z0 in offs:
+        hip.seg_accum(logits, acc, z0)
+    cover = torch.from_numpy(mrdis.model3d.window_cover(D, Dz, offs)).to(dev)
+    vols = [torch.randint(0, 5, (H, W, D), generator=g).float().to(dev) for _ in range(B)]
+    ptrs = torch.tensor([v.data_ptr() for v in vols], dtype=torch.int64).to(dev)
+    tvol = torch.stack(vols)
+
+    def torch_labels():
+        pbar = acc / cover.float().view(1, 1, 1, D, 1)
+        pred = pbar > 0.5
+        t = torch.where(tvol == 4, torch.full_like(tvol, 3.0), tvol)
+        lab = torch.stack([t == c + 1 for c in range(C)], dim=-1)
+        mx, arg = pbar.max(dim=-1)
+        labels = torch.where(mx > 0.5, arg + 1, torch.zeros_like(arg))
+        labels = torch.where(labels == 3, torch.full_like(labels, 4), labels).to(torch.uint8)
+        counts = torch.stack([(pred & lab).flatten(1, 3).sum(1), pred.flatten(1, 3).sum(1), lab.flatten(1, 3).sum(1)], dim=-1)
+        return labels, counts
+
+    lk, ck = hip.seg_label_volume(acc, cover, ptrs, relabel=True)
+    lt, ct = torch_labels()
+    moved = 4.0 * acc.numel() + 4.0 * tvol.numel() + 1.0 * tvol.numel()
+    buf2 = torch.empty(int(moved / 4) // 4 * 4, device=dev)
+    rows = {'kernel': [], 'torch': [], 'store_only': []}
+    for _ in range(3):
+        rows['kernel'].append(round(timeit(lambda: hip.seg_label_volume(acc, cover, ptrs, relabel=True), a.reps), 1))
+        rows['torch'].append(round(timeit(torch_labels, a.reps), 1))
+        rows['store_only'].append(round(timeit(lambda: hip.stream_fill(buf2), a.reps), 1))
+    best = {k: min(v) for k, v in rows.items()}
+    print(json.dumps({'metric': 'mrdis_seg_label_volume (incl. zeroing the counts), us per call (three alternating windows)', 'config': cfgs, **rows,
+                      'moved_mb': round(moved / 1e6, 1), 'note': 'moved = acc read + ground truth read + labels written',
+                      'tb_per_s': round(moved / best['kernel'] / 1e6, 2), 'store_only_tb_per_s': round(4.0 * buf2.numel() / best['store_only'] / 1e6, 2),
+                      'torch_over_kernel': round(best['torch'] / best['kernel'], 2),
+                      'labels_differ_from_torch': int((lk != lt).sum()), 'counts_equal_torch': bool(torch.equal(ck.long(), ct.long()))}), flush=True)
+    del buf, buf2, acc, logits, tvol, vols
+    # one batch end to end: gather, the net's unet and the accumulation per window (and flip), then the label volume
+    contrasts = ['T1', 'T1c', 'T2', 'T2_FLAIR']
+    store = mrdis.VolumeStore3D(dev)
+    for s_ in range(B):
+        for c in contrasts:
+            store.add(f's{s_:02d}/{c}', torch.randn(H, W, D, generator=g).numpy())
+        store.add(f's{s_:02d}/seg', torch.randint(0, 5, (H, W, D), generator=g).float().numpy())
+    ds = mrdis.VolumeDataset3D('BraTS', store, [f's{s_:02d}' for s_ in range(B)], contrasts)
+    loader = mrdis.VolumeLoader3D(ds, B, region_channels=3)
+    torch.manual_seed(10)
+    model = mrdis.NVNet3D((H, W, ds.crop()[1]), 4, 3, a.channels, p=0.2).to(dev)
+
+    def whole(flip):
+        for r in mrdis.predict_volumes(model, loader, stride=32, flip=flip):
+            last = r['labels']
+        torch.cuda.synchronize()
+        return last
+
+    whole(False); whole(True)
+    rows = {'no_flip_ms': [], 'flip_ms': []}
+    for _ in range(3):
+        for key, f in (('no_flip_ms', False), ('flip_ms', True)):
+            t0 = time.perf_counter()
+            for _ in range(a.steps):
+                whole(f)
+            rows[key].append(round((time.perf_counter() - t0) / a.steps * 1e3, 1))
+    print(json.dumps({'metric': 'predict_volumes, ms per batch (three alternating windows)', 'config': cfgs + f', stride 32, init_channels {a.channels}',
+                      'windows': len(offs), **rows}), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--size', type=int, default=128)
@@ -284,6 +386,7 @@ def main():
     ap.add_argument('--loader', action='store_true')
     ap.add_argument('--loss-only', action='store_true', help='time the objective (forward + backward): torch composition vs fused HIP kernels')
     ap.add_argument('--fused-loss', action='store_true', help='time the step with the torch objective and with the fused one')
+    ap.add_argument('--predict', action='store_true', help='time whole-volume sliding-window prediction (csrc/mrdis_segvol.hip)')
     ap.add_argument('--vol', type=int, nargs=3, default=[160, 192, 155], help='--loader: H W D of the stored volumes')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs an MI355X (no CPU fallback)'
@@ -300,6 +403,9 @@ def main():
         return
     if a.fused_loss:
         step_bench(a)
+        return
+    if a.predict:
+        predict_bench(a)
         return
     S, B = a.size, a.batch
     torch.manual_seed(10)
