@@ -84,7 +84,7 @@ long long mrdis_get_option(const char* name);
  * "split6_c4" | "split6_c16" | "split6_wgrad16" | "split6_co4" | "split6_c3d" | "split6_w3d" | "split6_tap" (option split6: the 4 -> C kernel, the 32 -> 16 forward, its weight gradient, the
  * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "zsearch" (mrdis_cosine_top1); "conv2src" | "ana_act" (the others variants); "kl" | "avgpool" (the latent-code options); "chatt" | "symdiff" | "rgate" (the attention output decoders);
  * "direct3d" | "c3d16" | "wgrad3d" | "wgrad3d16" | "wino_wgrad3d" (the 3-D tap-table, 16-cout, generic and narrow weight-gradient kernels and the hybrid
- * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "volgather"; "loss3d" | "segcounts" (the fused 3-D objective, one count per forward and per backward call, and the segmentation counts); "all" (every kernel launch of the library).  MRDIS_EINVAL for an unknown name.  Diagnostics: the parity tests
+ * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "volgather"; "loss3d" | "segcounts" (the fused 3-D objective, one count per forward and per backward call, and the segmentation counts); "segaccum" | "seglabels" (whole-volume prediction of the 3-D nets); "synthaccum" | "synthfinish" (whole-subject synthesis of the 2-D model, one count per call); "all" (every kernel launch of the library).  MRDIS_EINVAL for an unknown name.  Diagnostics: the parity tests
  * use it to prove that the form under test is the one that ran. */
 long long mrdis_launch_count(const char* family);
 void mrdis_launch_count_reset(void);
@@ -457,6 +457,25 @@ int mrdis_seg_counts(const float* pred, const float* target, int* out, int B, lo
 int mrdis_seg_accum(const float* logits, float* acc, int B, int H, int W, int Dz, int D, int C, int z0, int flip_h, void* stream);
 int mrdis_seg_label_volume(const float* acc, const int* cover, const void* targets, unsigned char* labels, int* counts, int B, int H,
                            int W, int D, int C, int relabel, void* stream);
+
+/* ---- whole-subject synthesis of missing contrasts by the 2-D model (csrc/mrdis_synth.hip): slice blocks -> volume.  The block rule is this
+ * package's own convention: the reference ships no such path.
+ * mrdis_synth_accum: srcs: HOST array of n_src (1 .. MRDIS_SYNTH_MAX_SRC) device pointers, handed to the kernel by value; each a dense
+ *   channels-last (B, C, H, W) fp32 reconstruction (memory [B][H][W][C]) of B samples with CONSECUTIVE centres s0, s0 + 1, ... (the caller
+ *   checks that), C = 2b + 1.  Channel c of sample r predicts plane k = s0 + r + c - b.  For every plane k the batch predicts with a channel in
+ *   [c_lo, c_hi] (b..b: the centre slice only; 0..2b: every prediction) and 0 <= k < D:
+ *     acc[k][h][w] += the values src_j[r][c][h][w], added one by one in the order (r ascending -- c = k - s0 - r + b follows --, j ascending);
+ *     cnt[k] += their number.
+ *   acc (D, H, W) fp32, cnt (D) int32, both read and written.  A gather: one thread owns an acc element within a launch and there are no atomics,
+ *   so batches add in launch order, bit-identical from run to run.  C odd, 0 <= c_lo <= c_hi < C (else MRDIS_EINVAL); H W < 2^31.  acc planes are
+ *   accessed 16 bytes per lane when H W % 4 == 0 and acc is 16-byte aligned, else 4.  One launch, counted as "synthaccum".
+ * mrdis_synth_finish: acc[d][h][w] = cnt[d] > 0 ? acc[d][h][w] / (float)cnt[d] : fill (IEEE fp32 division), in place, and the same values in the
+ *   volume store's (H, W, D) layout: out[h][w][d].  The transpose goes through LDS (both sides coalesced for any D).  One launch, counted as
+ *   "synthfinish".                                                                                                                          */
+#define MRDIS_SYNTH_MAX_SRC 8
+int mrdis_synth_accum(const float* const* srcs, int n_src, float* acc, int* cnt, int B, int C, int H, int W, int D, int s0, int c_lo, int c_hi,
+                      void* stream);
+int mrdis_synth_finish(float* acc, const int* cnt, float* out, int D, int H, int W, float fill, void* stream);
 
 /* ---- max_pool2d(kernel k x k, stride k): model.py:3448-3451 ---------------- */
 int mrdis_maxpool_fwd(const float* x, int ldx, float* y, int32_t* argmax, int N, int H, int W, int C,

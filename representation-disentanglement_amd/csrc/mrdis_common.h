@@ -62,6 +62,7 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
     X(VOLGATHER, "volgather") /* mrdis_volgather.hip: the 3-D batch gather, one count per mrdis_volume_gather call */ \
     X(LOSS3D, "loss3d") X(SEGCOUNTS, "segcounts") /* mrdis_loss3d.hip: one count per mrdis_nvnet_loss_fwd / _bwd call; one per mrdis_seg_counts call */ \
     X(SEGACCUM, "segaccum") X(SEGLABELS, "seglabels") /* mrdis_segvol.hip: one count per mrdis_seg_accum / mrdis_seg_label_volume call */ \
+    X(SYNTHACCUM, "synthaccum") X(SYNTHFINISH, "synthfinish") /* mrdis_synth.hip: one count per mrdis_synth_accum / mrdis_synth_finish call */ \
     X(ALL, "all") /* every launch of the library */
 #define MRDIS_X_CNT_ID(id, name) MRDIS_CNT_##id,
 enum { MRDIS_COUNTERS(MRDIS_X_CNT_ID) MRDIS_CNT_COUNT };

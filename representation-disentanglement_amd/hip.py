@@ -96,6 +96,8 @@ _SIGS = {
     'mrdis_seg_counts': (_I, [_P, _P, _P, _I, _L, _I, _I, _P]),
     'mrdis_seg_accum': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_seg_label_volume': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'mrdis_synth_accum': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'mrdis_synth_finish': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     'mrdis_maxpool_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_bwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_sumsq_workspace': (_Z, []),
@@ -212,6 +214,10 @@ LOSS3D_FAMILIES = ('loss3d', 'segcounts')
 # whole-volume sliding-window prediction (csrc/mrdis_segvol.hip): 'segaccum' counts one per mrdis_seg_accum call (one per window and flip),
 # 'seglabels' one per mrdis_seg_label_volume call (one per batch).
 SEGVOL_FAMILIES = ('segaccum', 'seglabels')
+# whole-subject synthesis of missing contrasts by the 2-D model (csrc/mrdis_synth.hip): 'synthaccum' counts one per mrdis_synth_accum call (one per
+# batch and target), 'synthfinish' one per mrdis_synth_finish call (one per target).
+SYNTH_FAMILIES = ('synthaccum', 'synthfinish')
+SYNTH_MAX_SRC = 8                   # include/mrdis.h MRDIS_SYNTH_MAX_SRC
 
 
 def stream_fill(t, value=0.0):
@@ -239,7 +245,7 @@ def dynamic_lds():
 def launch_counts(reset=False):
     """{family: launches since load / the last reset} of the Winograd, bf16 LDS-DMA and six-product (split6) kernel families (include/mrdis.h mrdis_launch_count)"""
     lib = load()
-    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES}
+    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES}
     if reset:
         lib.mrdis_launch_count_reset()
     return out
@@ -1244,6 +1250,50 @@ def seg_label_volume(acc, cover, target_ptrs=None, relabel=False):
     _chk(lib.mrdis_seg_label_volume(_ptr(acc), _ptr(cover), _ptr(target_ptrs), _ptr(labels), _ptr(counts), B, H, W, D, C, int(bool(relabel)),
                                     _stream()), 'seg_label_volume')
     return labels, counts
+
+
+def synth_accum(recons, centres, acc, cnt, c_lo, c_hi):
+    """acc[k] += every prediction of plane k the batch holds in channels c_lo .. c_hi, cnt[k] += their number (include/mrdis.h mrdis_synth_accum),
+    in place; returns acc.  recons: 1 .. 8 fp32 (B, C, H, W) dense channels-last reconstructions of one target, one per source, in the order they
+    add; centres: the B centre slices of the samples (host integers), which must be consecutive; acc (D, H, W) fp32 and cnt (D,) int32
+    contiguous on the same device.  Any other layout raises MrdisError: nothing is copied."""
+    lib = load()
+    recons = list(recons)
+    if not 1 <= len(recons) <= SYNTH_MAX_SRC:
+        raise MrdisError(f'synth_accum: 1 to {SYNTH_MAX_SRC} sources, got {len(recons)}')
+    x0 = recons[0]
+    if x0.dim() != 4:
+        raise MrdisError(f'synth_accum: (B, C, H, W) reconstructions wanted, got {tuple(x0.shape)}')
+    B, C, H, W = x0.shape
+    for x in recons:
+        if x.dtype != torch.float32 or tuple(x.shape) != (B, C, H, W) or x.device != acc.device or not x.permute(0, 2, 3, 1).is_contiguous():
+            raise MrdisError(f'synth_accum: every source must be a dense channels-last fp32 {(B, C, H, W)} tensor on {acc.device}, got {x.dtype} '
+                             f'{tuple(x.shape)} strides {x.stride()} on {x.device}')
+    centres = [int(c) for c in centres]
+    if len(centres) != B or any(centres[r] != centres[0] + r for r in range(B)):
+        raise MrdisError(f'synth_accum: the {B} samples need consecutive centre slices, got {centres}')
+    if acc.dtype != torch.float32 or acc.dim() != 3 or tuple(acc.shape[1:]) != (H, W) or not acc.is_contiguous():
+        raise MrdisError(f'synth_accum: acc must be a contiguous fp32 (D, {H}, {W}) tensor, got {acc.dtype} {tuple(acc.shape)} strides {acc.stride()}')
+    D = acc.shape[0]
+    if cnt.dtype != torch.int32 or tuple(cnt.shape) != (D,) or not cnt.is_contiguous() or cnt.device != acc.device:
+        raise MrdisError(f'synth_accum: cnt must be a contiguous int32 ({D},) tensor on {acc.device}, got {cnt.dtype} {tuple(cnt.shape)}')
+    ptrs = (_c.c_void_p * len(recons))(*[x.data_ptr() for x in recons])
+    _chk(lib.mrdis_synth_accum(ptrs, len(recons), _ptr(acc), _ptr(cnt), B, C, H, W, D, centres[0], int(c_lo), int(c_hi), _stream()), 'synth_accum')
+    return acc
+
+
+def synth_finish(acc, cnt, fill=0.0):
+    """acc (D, H, W) becomes acc / cnt[d] in place (`fill` where cnt[d] == 0; include/mrdis.h mrdis_synth_finish) -> (acc, the same volume as a new
+    contiguous (H, W, D) tensor, the volume store's layout).  acc fp32 and cnt (D,) int32 contiguous on one device, else MrdisError."""
+    lib = load()
+    if acc.dtype != torch.float32 or acc.dim() != 3 or not acc.is_contiguous():
+        raise MrdisError(f'synth_finish: acc must be a contiguous fp32 (D, H, W) tensor, got {acc.dtype} {tuple(acc.shape)} strides {acc.stride()}')
+    D, H, W = acc.shape
+    if cnt.dtype != torch.int32 or tuple(cnt.shape) != (D,) or not cnt.is_contiguous() or cnt.device != acc.device:
+        raise MrdisError(f'synth_finish: cnt must be a contiguous int32 ({D},) tensor on {acc.device}, got {cnt.dtype} {tuple(cnt.shape)}')
+    out = torch.empty((H, W, D), dtype=torch.float32, device=acc.device)
+    _chk(lib.mrdis_synth_finish(_ptr(acc), _ptr(cnt), _ptr(out), D, H, W, float(fill), _stream()), 'synth_finish')
+    return acc, out
 
 
 def recon_err_bwd(gt, x, w, p):

@@ -14,7 +14,8 @@ What is kept from the reference, statement by statement:
     `scheduler.step(monitor)` with monitor = val recon_x_mix (or recon_y_fused), `epochNNN.pth.tar` every epoch and
     `model_best.pth.tar` when the monitor improves (util.py:148-153, 854-866)
   * evaluate() (:337-609): eval-mode pass over a loader, loss means + mean MSE / PSNR / SSIM of the mix
-    reconstructions, capped at 502 batches (:562-563).  Result dumping to h5 (:565-606) is out of scope.
+    reconstructions, capped at 502 batches (:562-563).  Result dumping to h5 (:565-606) is out of scope (SURVEY 8);
+    `phase: synthesize` (Run.synthesize, synth.py) writes whole-subject volumes instead, by this package's own rules.
 Data parallel (north_star; BASELINE configs[2] / [3]: the entry point as the 8-GPU job).  Launched as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 main_missing.py ...` (or with the
 reserved config key `ddp: true` under such a launcher) every rank runs this file on `cuda:LOCAL_RANK`: one RCCL process group
@@ -41,7 +42,10 @@ from .data import BatchLoader, SliceDataset, VolumeStore, load_idx_list
 from .trainer import (DEFAULT_CONFIG, LOSS_KEYS, EVAL_INFOS, EvalStep, ZGallery, build_z_gallery, TrainStep, make_train_step, build_model, derive_config, load_checkpoint_model,
                       load_config_yaml, save_checkpoint)
 
+from .synth import check_synth_options, synthesize_volumes
+
 SEED = 10                                                                   # main_missing.py:18
+SYNTH_KEYS = ('synth_info', 'synth_drop', 'synth_block', 'synth_set')
 
 
 # --------------------------------------------------------------------------- data-parallel launch (replaces main_missing.py:28)
@@ -138,7 +142,7 @@ def setup_config(config_path='config.yaml', overrides=None, ckpt_root='../ckpt/'
         device = torch.device('cuda:' + str(config['gpu']))
     config = derive_config(config, device)
     rank, world = dist_info()
-    if config['ckpt_timelabel'] and (config['phase'] == 'test' or config['continue_train'] is True):
+    if config['ckpt_timelabel'] and (config['phase'] in ('test', 'synthesize') or config['continue_train'] is True):
         label = config['ckpt_timelabel']
     else:
         label = _bcast_object(time_label_now())                             # one directory per job: rank 0's clock names it
@@ -163,7 +167,7 @@ def setup_config(config_path='config.yaml', overrides=None, ckpt_root='../ckpt/'
         flag, saved = load_config_yaml(os.path.join(config['ckpt_path'], 'config.yaml'))
         if flag:
             for k, v in saved.items():                                      # :45-51
-                if k in ('phase', 'continue_train', 'eval_info') or k not in config:    # eval_info: per invocation, like phase
+                if k in ('phase', 'continue_train', 'eval_info') + SYNTH_KEYS or k not in config:    # eval_info, synth_*: per invocation, like phase
                     continue
                 config[k] = v
             config = derive_config(config, device)
@@ -285,7 +289,7 @@ class Run:
         self.optimizer, self.optimizer_d_s = self.step.optimizer, self.step.optimizer_d_s
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode='min', factor=0.1, patience=5, min_lr=1e-5)   # :119
         self.start_epoch = -1
-        if config['continue_train'] or config['phase'] == 'test':           # :125-135
+        if config['continue_train'] or config['phase'] in ('test', 'synthesize'):    # :125-135
             _, self.start_epoch, loaded = load_checkpoint_by_key([self.optimizer, self.scheduler, self.model], config['ckpt_path'],
                                                                  ['optimizer', 'scheduler', 'model'], config['device'], config['ckpt_name'])
             log(f'loaded {loaded} from {config["ckpt_name"]} (epoch {self.start_epoch})')
@@ -422,6 +426,50 @@ class Run:
             stat[k] = float(vec[nk + 1 + 2 * j] / vec[nk + 2 + 2 * j]) if vec[nk + 2 + 2 * j] > 0 else float('nan')
         return stat
 
+    def synthesize(self, set_=None, info=None, drop=None, block=None, batch_size=None):
+        """whole-subject synthesis (synth.synthesize_volumes) of the distinct subjects of `set_`'s slice list, in order of first appearance (None:
+        the config's synth_set / synth_info / synth_drop / synth_block).  Writes <ckpt_path>/result_<set>/synth/<subj_id>_<contrast>.npy -- float32
+        (H, W, D), the store's own geometry -- for every synthesised contrast and result_<set>/synth.csv with one
+        `subj_id,contrast,present,dropped,n_sources,mse,psnr,ssim` row per subject and contrast (n_sources 0: not synthesised; NaN: nothing to score
+        against); returns the mean metrics over the scored volumes.  With an `info` the z gallery of `set_` is loaded or built (Run.z_gallery).
+        World size 1 only."""
+        cfg = self.config
+        if getattr(self, 'world', 1) > 1 or (dist.is_available() and dist.is_initialized()):
+            raise NotImplementedError('synthesize under a process group: the subjects and the z gallery are not sharded; synthesize on one process')
+        set_ = cfg.get('synth_set', 'test') if set_ is None else set_
+        info = (cfg.get('synth_info') or '') if info is None else info
+        drop = (cfg.get('synth_drop') or []) if drop is None else drop
+        block = cfg.get('synth_block', 'centre') if block is None else block
+        names = [str(c) for c in cfg['contrast_list']]
+        check_synth_options(names, info, drop, block)
+        if set_ not in ('train', 'val', 'test'):
+            raise ValueError(f'synth_set {set_!r}: train, val or test')
+        ds = self.loaders[set_].dataset
+        subjects = list(dict.fromkeys(str(x) for x in ds.subj_list))
+        gallery = self.z_gallery(set_) if info else None
+        out_dir = os.path.join(cfg['ckpt_path'], 'result_' + set_)
+        os.makedirs(os.path.join(out_dir, 'synth'), exist_ok=True)
+        rows, scored = [], []
+        for res in synthesize_volumes(self.model, cfg, ds.store, subjects, info=info, gallery=gallery, drop=drop, block=block, batch_size=batch_size):
+            sid = res['subj_id']
+            for i, c in enumerate(names):
+                done = i in res['targets']
+                if done:
+                    np.save(os.path.join(out_dir, 'synth', f'{sid}_{c}.npy'), res['volumes'][c].cpu().numpy())
+                met = res['metrics'][c] if done else (float('nan'),) * 3
+                if done and not np.isnan(met[0]):
+                    scored.append(met)
+                rows.append(f'{sid},{c},{int(res["present"][i])},{int(res["dropped"][i])},{res["n_sources"][c] if done else 0},'
+                            f'{met[0]!r},{met[1]!r},{met[2]!r}')
+        with open(os.path.join(out_dir, 'synth.csv'), 'w') as f:
+            f.write('subj_id,contrast,present,dropped,n_sources,mse,psnr,ssim\n')
+            f.write(''.join(r + '\n' for r in rows))
+        mean = np.mean(np.array(scored, dtype=np.float64), 0) if scored else np.full(3, np.nan)
+        stat = {'rmse': float(mean[0]), 'psnr': float(mean[1]), 'ssim': float(mean[2]), 'subjects': len(subjects), 'scored': len(scored)}
+        self.log(f'synthesize {set_}: {len(subjects)} subjects under {out_dir}/synth, {len(scored)} volumes scored, '
+                 f'mse {stat["rmse"]:.5f}, psnr {stat["psnr"]:.3f}, ssim {stat["ssim"]:.4f}')
+        return stat
+
 
 def parse_overrides(args):
     out = {}
@@ -444,6 +492,10 @@ def main(argv=None):
     try:
         if config['phase'] == 'train':                                      # :611-614
             run.train()
+        elif config['phase'] == 'synthesize':
+            stat = run.synthesize()
+            if run.rank == 0:
+                print(stat)
         else:
             stat = run.evaluate(phase='test', set_='test', info=config.get('eval_info') or '')
             if run.rank == 0:

@@ -38,6 +38,11 @@ DEFAULT_CONFIG = {
     'graph': None,                     # true: steady-state iterations as HIP-graph replays (trainer.GraphedTrainStep); None: MRDIS_GRAPH decides (default off)
     'compute_dtype': 'f32',            # BASELINE configs[2]: 'bf16' = bf16 activations + bf16 MFMA operands + fp32 accumulate; 'bf16m' = bf16 MFMA operands only
     'eval_info': '',                   # phase: test -- '' | 'nearest_neighbour' | 'mean': decode with a searched / mean modality code (main_missing.py:409-426; EvalStep)
+    # phase: synthesize -- whole-subject volumes of every contrast the model can produce (synth.synthesize_volumes, Run.synthesize)
+    'synth_info': '',                  # '' | 'nearest_neighbour' | 'mean': the modality code of a contrast the subject lacks ('': such a contrast is skipped)
+    'synth_drop': [],                  # contrast names hidden on purpose, so that their synthesis is scored against the stored volume
+    'synth_block': 'centre',           # 'centre': a plane is the centre slice of its own sample | 'mean': the mean of every prediction of it
+    'synth_set': 'test',               # train | val | test: the slice list whose distinct subjects are synthesised
 }
 
 
