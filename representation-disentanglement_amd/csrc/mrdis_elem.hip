@@ -253,6 +253,7 @@ static int launch_stats(const T* a, int lda, const T* b, int ldb, const T* g, in
     const bool vec = vec4_ok(a, lda, C) && (MODE == 0 || (xlo ? vec4_ok(xlo, ldxlo, C) : vec4_ok(b, ldb, C))) && (MODE != 2 || vec4_ok(g, ldg, C)) &&
                      ((C >> 2) >= 256 ? (C >> 2) % 256 == 0 : 256 % (C >> 2) == 0);
     if (xlo && !vec) return MRDIS_EUNSUPPORTED;
+    mrdis_count(vec ? (xlo ? MRDIS_CNT_STAT_INTERP : MRDIS_CNT_STAT_VEC) : MRDIS_CNT_STAT_SCALAR);
     if (vec && xlo) {
         if constexpr (MODE == 2)                          // (its own instantiation: the interpolation's registers do not ride on the plain statistics passes)
             MRDIS_LAUNCH((stat_partial_vec_kernel<2, T, true>), dim3(sp.chunks, groups), dim3(256), 0, s, a, lda, b, ldb, g, ldg, mean, rstd,
@@ -350,8 +351,10 @@ static int bn_train_fwd_impl(const T* x, int ldx, T* y, int ldy, const float* ga
     const long long rows = P * G;
     if (vec4_ok(x, ldx, C) && vec4_ok(y, ldy, C))
         MRDIS_LAUNCH((bn_apply_kernel<4, T>), dim3(ew_blocks(rows * C / 4)), dim3(256), 0, s, x, ldx, y, ldy, gamma, beta, save_mean, save_rstd, rows, C, P);
-    else
+    else {
+        mrdis_count(MRDIS_CNT_ELEM_V1);
         MRDIS_LAUNCH((bn_apply_kernel<1, T>), dim3(ew_blocks(rows * C)), dim3(256), 0, s, x, ldx, y, ldy, gamma, beta, save_mean, save_rstd, rows, C, P);
+    }
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }
@@ -380,8 +383,10 @@ static int bn_eval_fwd_impl(const T* x, int ldx, T* y, int ldy, const float* gam
     hipStream_t s = (hipStream_t)stream;
     if (vec4_ok(x, ldx, C) && vec4_ok(y, ldy, C))
         MRDIS_LAUNCH((bn_eval_kernel<4, T>), dim3(ew_blocks(P * C / 4)), dim3(256), 0, s, x, ldx, y, ldy, gamma, beta, running_mean, running_var, eps, P, C);
-    else
+    else {
+        mrdis_count(MRDIS_CNT_ELEM_V1);
         MRDIS_LAUNCH((bn_eval_kernel<1, T>), dim3(ew_blocks(P * C)), dim3(256), 0, s, x, ldx, y, ldy, gamma, beta, running_mean, running_var, eps, P, C);
+    }
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }
@@ -432,8 +437,10 @@ static int bn_train_bwd_impl(const T* dy, int lddy, const T* x, int ldx, const f
     const long long rows = P * G;
     if (vec4_ok(dy, lddy, C) && vec4_ok(x, ldx, C) && vec4_ok(dx, lddx, C))
         MRDIS_LAUNCH((bn_bwd_apply_kernel<4, T>), dim3(ew_blocks(rows * C / 4)), dim3(256), 0, s, dy, lddy, x, ldx, gamma, save_mean, save_rstd, dbeta, dgamma, dx, lddx, rows, C, acc_dgamma, acc_dbeta, P, G);
-    else
+    else {
+        mrdis_count(MRDIS_CNT_ELEM_V1);
         MRDIS_LAUNCH((bn_bwd_apply_kernel<1, T>), dim3(ew_blocks(rows * C)), dim3(256), 0, s, dy, lddy, x, ldx, gamma, save_mean, save_rstd, dbeta, dgamma, dx, lddx, rows, C, acc_dgamma, acc_dbeta, P, G);
+    }
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }
@@ -477,8 +484,10 @@ static int instnorm_spade_fwd_impl(const T* z, int ldz, const T* gamma, int ldg,
     const long long rows = (long long)N * HW;
     if (vec4_ok(z, ldz, C) && vec4_ok(gamma, ldg, C) && vec4_ok(beta, ldb, C) && vec4_ok(out, ldo, C))
         MRDIS_LAUNCH((spade_fwd_kernel<4, T>), dim3(ew_blocks(rows * C / 4)), dim3(256), 0, s, z, ldz, gamma, ldg, beta, ldb, out, ldo, save_mean, save_rstd, HW, rows, C);
-    else
+    else {
+        mrdis_count(MRDIS_CNT_ELEM_V1);
         MRDIS_LAUNCH((spade_fwd_kernel<1, T>), dim3(ew_blocks(rows * C)), dim3(256), 0, s, z, ldz, gamma, ldg, beta, ldb, out, ldo, save_mean, save_rstd, HW, rows, C);
+    }
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }
@@ -533,8 +542,10 @@ static int instnorm_spade_bwd_impl(const T* dout, int lddo, const T* z, int ldz,
                    vec4_ok(dgamma, lddg, C) && (!dbeta || vec4_ok(dbeta, lddb, C));
     if (v)
         MRDIS_LAUNCH((spade_bwd_kernel<4, T>), dim3(ew_blocks(rows * C / 4)), dim3(256), 0, s, dout, lddo, z, ldz, gamma, ldg, save_mean, save_rstd, s0, s1, dz, lddz, dgamma, lddg, dbeta, lddb, HW, rows, C);
-    else
+    else {
+        mrdis_count(MRDIS_CNT_ELEM_V1);
         MRDIS_LAUNCH((spade_bwd_kernel<1, T>), dim3(ew_blocks(rows * C)), dim3(256), 0, s, dout, lddo, z, ldz, gamma, ldg, save_mean, save_rstd, s0, s1, dz, lddz, dgamma, lddg, dbeta, lddb, HW, rows, C);
+    }
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }
@@ -812,6 +823,7 @@ static int instnorm_spade_bwd_up2_impl(const T* dout, int lddo, const T* z, int 
             float* t0 = reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + p1bytes);
             float* t1 = t0 + (size_t)N * C;
             float* abuf = f32 ? nullptr : t1 + (size_t)N * C;
+            mrdis_count(MRDIS_CNT_SPADE_UP2_ONEPASS);
             if (NW == 8)       // (reading a stored z instead of interpolating it from xlo was measured level to slower: the kernel is not bound by the interpolation)
                 MRDIS_LAUNCH((spade_bwd_up2_kernel<T, true, 512, true>), dim3(tiles_x * tiles_y, N, mrdis_cdiv(C, UB_CC)), dim3(512), 0, s, dout, lddo, z, ldz, gamma, ldg,
                                    save_mean, save_rstd, nullptr, nullptr, dx, lddx, dgamma, lddg, dbeta, lddb, Hi, Wi, C, tiles_x, xlo, ldxlo, part1, abuf,
@@ -833,6 +845,7 @@ static int instnorm_spade_bwd_up2_impl(const T* dout, int lddo, const T* z, int 
     float* s1 = s0 + (size_t)N * C;
     int rc = launch_stats<2, T>(dout, lddo, z, ldz, gamma, ldg, save_mean, save_rstd, 1, N, HW, C, part, s, 0, xlo, ldxlo, Wi);
     if (rc) return rc;
+    mrdis_count(MRDIS_CNT_SPADE_UP2_TWOPASS);
     const StatPlan sp = stat_plan(N, HW);
     MRDIS_LAUNCH((stat_final_kernel<1>), dim3(mrdis_cdiv(N * C, 64)), dim3(64, stat_final_lanes(sp.chunks)), 0, s, part, sp.chunks, C, N, HW, 0.f, 0.f, s0, s1, nullptr, nullptr);
     MRDIS_CHECK_LAUNCH();
@@ -875,8 +888,10 @@ static int lrelu_bwd_impl(const T* dy, int lddy, const T* y, int ldy, T* dx, int
     hipStream_t s = (hipStream_t)stream;
     if (vec4_ok(dy, lddy, C) && vec4_ok(y, ldy, C) && vec4_ok(dx, lddx, C))
         MRDIS_LAUNCH((lrelu_bwd_kernel<4, T>), dim3(ew_blocks(P * C / 4)), dim3(256), 0, s, dy, lddy, y, ldy, dx, lddx, P, C, slope);
-    else
+    else {
+        mrdis_count(MRDIS_CNT_ELEM_V1);
         MRDIS_LAUNCH((lrelu_bwd_kernel<1, T>), dim3(ew_blocks(P * C)), dim3(256), 0, s, dy, lddy, y, ldy, dx, lddx, P, C, slope);
+    }
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }
@@ -1203,14 +1218,18 @@ static int bilinear_fwd_impl(const T* x, int ldx, T* y, int ldy, int N, int Hi, 
     const float sh = bil_scale(Hi, Ho, align_corners), sw = bil_scale(Wi, Wo, align_corners);
     hipStream_t s = (hipStream_t)stream;
     if (!align_corners && Ho == 2 * Hi && Wo == 2 * Wi && vec4_ok(x, ldx, C) && vec4_ok(y, ldy, C) && !mrdis_opt(MRDIS_OPT_BILGEN)) {
+        mrdis_count(MRDIS_CNT_BIL_FWD_X2);
         MRDIS_LAUNCH((bilinear_up2_fwd_kernel<T>), dim3(Hi, N), dim3(bil_threads((long long)Wi * (C / 4))), 0, s, x, ldx, y, ldy, Hi, Wi, C);
         MRDIS_CHECK_LAUNCH();
         return MRDIS_OK;
     }
+    mrdis_count(MRDIS_CNT_BIL_FWD_GENERAL);
     if (vec4_ok(x, ldx, C) && vec4_ok(y, ldy, C))
         MRDIS_LAUNCH((bilinear_fwd_kernel<4, T>), dim3(Ho, N), dim3(bil_threads((long long)Wo * (C / 4))), 0, s, x, ldx, y, ldy, N, Hi, Wi, Ho, Wo, C, align_corners, sh, sw);
-    else
+    else {
+        mrdis_count(MRDIS_CNT_ELEM_V1);
         MRDIS_LAUNCH((bilinear_fwd_kernel<1, T>), dim3(Ho, N), dim3(bil_threads((long long)Wo * C)), 0, s, x, ldx, y, ldy, N, Hi, Wi, Ho, Wo, C, align_corners, sh, sw);
+    }
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }
@@ -1225,19 +1244,25 @@ static int bilinear_bwd_impl(const T* dy, int lddy, T* dx, int lddx, int N, int 
     const float smin = sh < sw ? sh : sw;
     const bool big = (long long)N * Hi * Wi * C >= 6000000LL;          // measured: 108 vs 129 us at 16 M elements, a wash below 6 M
     if (!align_corners && Ho == 2 * Hi && Wo == 2 * Wi && vec4_ok(dy, lddy, C) && vec4_ok(dx, lddx, C) && !mrdis_opt(MRDIS_OPT_BILGEN)) {
+        mrdis_count(MRDIS_CNT_BIL_BWD_X2);
         MRDIS_LAUNCH((bilinear_up2_bwd_kernel<T>), dim3(Hi, N), dim3(bil_threads((long long)Wi * (C / 4))), 0, s, dy, lddy, dx, lddx, Hi, Wi, C);
         MRDIS_CHECK_LAUNCH();
         return MRDIS_OK;
     }
     const bool tight3 = big && sh >= 1.f && sw >= 1.f, tight5 = big && smin > 0.4975f && !mrdis_opt(MRDIS_OPT_BILGEN);
-    if (vec4_ok(dy, lddy, C) && vec4_ok(dx, lddx, C) && tight3 && !mrdis_opt(MRDIS_OPT_BILGEN))
+    if (vec4_ok(dy, lddy, C) && vec4_ok(dx, lddx, C) && tight3 && !mrdis_opt(MRDIS_OPT_BILGEN)) {
+        mrdis_count(MRDIS_CNT_BIL_BWD_TIGHT3);
         MRDIS_LAUNCH((bilinear_bwd_tight_kernel<4, 3, 3, T>), dim3(Hi, N), dim3(bil_threads((long long)Wi * (C / 4))), 0, s, dy, lddy, dx, lddx, N, Hi, Wi, Ho, Wo, C, align_corners, sh, sw);
-    else if (vec4_ok(dy, lddy, C) && vec4_ok(dx, lddx, C) && tight5)
+    } else if (vec4_ok(dy, lddy, C) && vec4_ok(dx, lddx, C) && tight5) {
+        mrdis_count(MRDIS_CNT_BIL_BWD_TIGHT5);
         MRDIS_LAUNCH((bilinear_bwd_tight_kernel<4, 5, 5, T>), dim3(Hi, N), dim3(bil_threads((long long)Wi * (C / 4))), 0, s, dy, lddy, dx, lddx, N, Hi, Wi, Ho, Wo, C, align_corners, sh, sw);
-    else if (vec4_ok(dy, lddy, C) && vec4_ok(dx, lddx, C))
+    } else if (vec4_ok(dy, lddy, C) && vec4_ok(dx, lddx, C)) {
+        mrdis_count(MRDIS_CNT_BIL_BWD_GENERAL);
         MRDIS_LAUNCH((bilinear_bwd_kernel<4, T>), dim3(Hi, N), dim3(bil_threads((long long)Wi * (C / 4))), 0, s, dy, lddy, dx, lddx, N, Hi, Wi, Ho, Wo, C, align_corners, sh, sw);
-    else
+    } else {
+        mrdis_count(MRDIS_CNT_BIL_BWD_GENERAL); mrdis_count(MRDIS_CNT_ELEM_V1);
         MRDIS_LAUNCH((bilinear_bwd_kernel<1, T>), dim3(Hi, N), dim3(bil_threads((long long)Wi * C)), 0, s, dy, lddy, dx, lddx, N, Hi, Wi, Ho, Wo, C, align_corners, sh, sw);
+    }
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }
@@ -1377,8 +1402,10 @@ static int cast_view_impl(const TS* src, int lds_, int Cs, TD* dst, int ldd, int
     if (!src || !dst || P < 1 || Cs < 1 || Cd < 1 || lds_ < Cs || ldd < Cd) return MRDIS_EINVAL;
     if (vec4_ok(dst, ldd, Cd) && (Cs >= Cd ? vec4_ok(src, lds_, Cd) : (lds_ % 4 == 0 && Cs % 4 == 0 && (((uintptr_t)src & (4 * sizeof(TS) - 1)) == 0))))
         MRDIS_LAUNCH((cast_view_kernel<4, TS, TD>), dim3(ew_blocks(P * Cd / 4)), dim3(256), 0, (hipStream_t)stream, src, lds_, Cs, dst, ldd, Cd, P);
-    else
+    else {
+        mrdis_count(MRDIS_CNT_ELEM_V1);
         MRDIS_LAUNCH((cast_view_kernel<1, TS, TD>), dim3(ew_blocks(P * Cd)), dim3(256), 0, (hipStream_t)stream, src, lds_, Cs, dst, ldd, Cd, P);
+    }
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
 }

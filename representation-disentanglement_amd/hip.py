@@ -217,7 +217,13 @@ SEGVOL_FAMILIES = ('segaccum', 'seglabels')
 # whole-subject synthesis of missing contrasts by the 2-D model (csrc/mrdis_synth.hip): 'synthaccum' counts one per mrdis_synth_accum call (one per
 # batch and target), 'synthfinish' one per mrdis_synth_finish call (one per target).
 SYNTH_FAMILIES = ('synthaccum', 'synthfinish')
-SYNTH_MAX_SRC = 8                   # include/mrdis.h MRDIS_SYNTH_MAX_SRC
+# the dispatch choices of the statistics, norm and resize entry points (csrc/mrdis_elem.hip), host-side counts only: which partial-sum kernel a
+# statistics pass took ('stat_vec' | 'stat_scalar' | 'stat_interp': one per pass), the route of mrdis_instnorm_spade_bwd_up2 (one per call), the
+# kernel of mrdis_bilinear_fwd / _bwd (one per call), and 'elem_v1': an element-wise pass that took its one-channel-per-thread instantiation.
+# Outside KERNEL_FAMILIES for the same reason as the tables above (tests/test_gpu_elem_paths.py covers them).
+ELEM_FAMILIES = ('stat_vec', 'stat_scalar', 'stat_interp', 'spade_up2_onepass', 'spade_up2_twopass', 'bil_fwd_x2', 'bil_fwd_general',
+                 'bil_bwd_x2', 'bil_bwd_tight3', 'bil_bwd_tight5', 'bil_bwd_general', 'elem_v1')
+SYNTH_MAX_SRC = 8                 # include/mrdis.h MRDIS_SYNTH_MAX_SRC
 
 
 def stream_fill(t, value=0.0):
@@ -242,10 +248,13 @@ def dynamic_lds():
     return out
 
 
-def launch_counts(reset=False):
-    """{family: launches since load / the last reset} of the Winograd, bf16 LDS-DMA and six-product (split6) kernel families (include/mrdis.h mrdis_launch_count)"""
+def launch_counts(reset=False, elem=False):
+    """{family: launches since load / the last reset} of the Winograd, bf16 LDS-DMA and six-product (split6) kernel families (include/mrdis.h mrdis_launch_count).
+    elem=True adds ELEM_FAMILIES: they count dispatch choices of passes that run beside almost every counted kernel (the statistics in front of a fused
+    SPADE convolution, say), so callers that assert "this family and no other" over the whole dictionary only see them when they ask."""
     lib = load()
-    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES}
+    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES
+    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in fams + (ELEM_FAMILIES if elem else ())}
     if reset:
         lib.mrdis_launch_count_reset()
     return out

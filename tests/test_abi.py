@@ -90,6 +90,10 @@ def test_option_and_counter_tables_match_the_library(mrdis):
         assert lib.mrdis_launch_count(fam.encode()) >= 0, fam
     assert not set(hip.CONV3D_FAMILIES) & set(hip.KERNEL_FAMILIES + hip.VARIANT_FAMILIES + hip.LATENT_FAMILIES)
     assert set(hip.CONV3D_FAMILIES) <= set(hip.launch_counts())
+    for fam in hip.ELEM_FAMILIES:          # handed out by launch_counts(elem=True) only
+        assert lib.mrdis_launch_count(fam.encode()) >= 0, fam
+    assert not set(hip.ELEM_FAMILIES) & set(hip.launch_counts()) and set(hip.ELEM_FAMILIES) <= set(hip.launch_counts(elem=True))
+    assert len(set(hip.ELEM_FAMILIES)) == len(hip.ELEM_FAMILIES) == 12
     assert lib.mrdis_launch_count(b'no_such_family') == -1
     assert isinstance(hip.dynamic_lds(), dict)
     import ctypes
