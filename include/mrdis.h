@@ -84,7 +84,7 @@ long long mrdis_get_option(const char* name);
  * "split6_c4" | "split6_c16" | "split6_wgrad16" | "split6_co4" | "split6_c3d" | "split6_w3d" | "split6_tap" (option split6: the 4 -> C kernel, the 32 -> 16 forward, its weight gradient, the
  * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "zsearch" (mrdis_cosine_top1); "conv2src" | "ana_act" (the others variants); "kl" | "avgpool" (the latent-code options); "chatt" | "symdiff" | "rgate" (the attention output decoders);
  * "direct3d" | "c3d16" | "wgrad3d" | "wgrad3d16" | "wino_wgrad3d" (the 3-D tap-table, 16-cout, generic and narrow weight-gradient kernels and the hybrid
- * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "volgather"; "loss3d" | "segcounts" (the fused 3-D objective, one count per forward and per backward call, and the segmentation counts); "segaccum" | "seglabels" (whole-volume prediction of the 3-D nets); "synthaccum" | "synthfinish" (whole-subject synthesis of the 2-D model, one count per call);
+ * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "volgather"; "loss3d" | "segcounts" (the fused 3-D objective, one count per forward and per backward call, and the segmentation counts); "segaccum" | "seglabels" (whole-volume prediction of the 3-D nets); "synthaccum" | "synthfinish" (whole-subject synthesis of the 2-D model, one count per call); "fuse" (mrdis_fuse_present_fwd / _bwd, one count per call);
  * "stat_vec" | "stat_scalar" | "stat_interp" (the partial-sum kernel of a statistics pass), "spade_up2_onepass" | "spade_up2_twopass" (the route of
  * mrdis_instnorm_spade_bwd_up2, one per call), "bil_fwd_x2" | "bil_fwd_general", "bil_bwd_x2" | "bil_bwd_tight3" | "bil_bwd_tight5" | "bil_bwd_general"
  * (mrdis_bilinear_fwd / _bwd, one per call), "elem_v1" (an element-wise pass in its one-channel-per-thread form): dispatch choices, not launches;
@@ -480,6 +480,28 @@ int mrdis_seg_label_volume(const float* acc, const int* cover, const void* targe
 int mrdis_synth_accum(const float* const* srcs, int n_src, float* acc, int* cnt, int B, int C, int H, int W, int D, int s0, int c_lo, int c_hi,
                       void* stream);
 int mrdis_synth_finish(float* acc, const int* cnt, float* out, int D, int H, int W, float fill, void* stream);
+
+/* ---- fusion of the anatomy maps over the contrasts a sample has (csrc/mrdis_fuse.hip; lambda_recon_y_fused).  The rule is this package's own
+ * convention: the reference's `si_cat[mask == 1]` (model.py:3239-3258) never fuses and fails for M > 1.
+ * srcs / ld_srcs: HOST arrays of K (1 .. MRDIS_FUSE_MAX_SRC) device pointers and pixel strides (floats), handed to the kernel by value; each
+ *   source a (B, H, W, C) fp32 NHWC view.  mask: (B, K) fp32 contiguous ON THE DEVICE, present = 1.0f exactly; the kernels derive the present
+ *   set and its size n_b from it, nothing per step is baked into the launch.  method: MRDIS_FUSE_MEAN | _MAX | _MEAN_MAX_MIN.
+ * mrdis_fuse_present_fwd: out (B, H, W, F C) with pixel stride ldo >= F C, F = 3 for MRDIS_FUSE_MEAN_MAX_MIN ([mean | max | min]) else 1.  Over
+ *   the present contrasts of sample b: mean = (the sum in increasing k) / (float)n_b (IEEE fp32 division), max, min.  One launch, every output
+ *   element written once.  K = 1: the identity.
+ * mrdis_fuse_present_bwd: dout as out; dsrcs / ld_dsrcs: K gradient views like the sources.  Every element of all K gradients is written once:
+ *   0 for an absent contrast; mean: g / (float)n_b for every present k; max / min: g for the LOWEST present k that attains the extremum (recomputed
+ *   from the maps, no saved index), 0 for the others; mean-max-min: the three contributions added in the order mean, max, min.  One launch.
+ * A row of the mask without any present contrast gets zeros both ways (callers refuse it from the host mask).  16 bytes per lane when C % 4 == 0
+ * and every pointer and stride allows it, else 4.  B <= 65535, H W < 2^31.  Each call counts once as "fuse".                              */
+#define MRDIS_FUSE_MAX_SRC 8
+#define MRDIS_FUSE_MEAN 0
+#define MRDIS_FUSE_MAX 1
+#define MRDIS_FUSE_MEAN_MAX_MIN 2
+int mrdis_fuse_present_fwd(const float* const* srcs, const int* ld_srcs, int K, const float* mask, int method, float* out, int ldo, int B,
+                           long long HW, int C, void* stream);
+int mrdis_fuse_present_bwd(const float* dout, int lddo, const float* const* srcs, const int* ld_srcs, int K, const float* mask, int method,
+                           float* const* dsrcs, const int* ld_dsrcs, int B, long long HW, int C, void* stream);
 
 /* ---- max_pool2d(kernel k x k, stride k): model.py:3448-3451 ---------------- */
 int mrdis_maxpool_fwd(const float* x, int ldx, float* y, int32_t* argmax, int N, int H, int W, int C,

@@ -63,6 +63,7 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
     X(LOSS3D, "loss3d") X(SEGCOUNTS, "segcounts") /* mrdis_loss3d.hip: one count per mrdis_nvnet_loss_fwd / _bwd call; one per mrdis_seg_counts call */ \
     X(SEGACCUM, "segaccum") X(SEGLABELS, "seglabels") /* mrdis_segvol.hip: one count per mrdis_seg_accum / mrdis_seg_label_volume call */ \
     X(SYNTHACCUM, "synthaccum") X(SYNTHFINISH, "synthfinish") /* mrdis_synth.hip: one count per mrdis_synth_accum / mrdis_synth_finish call */ \
+    X(FUSE, "fuse") /* mrdis_fuse.hip: one count per mrdis_fuse_present_fwd / _bwd call */ \
     X(STAT_VEC, "stat_vec") X(STAT_SCALAR, "stat_scalar") X(STAT_INTERP, "stat_interp") /* mrdis_elem.hip launch_stats: which partial-sum kernel took the pass */ \
     X(SPADE_UP2_ONEPASS, "spade_up2_onepass") X(SPADE_UP2_TWOPASS, "spade_up2_twopass") /* mrdis_instnorm_spade_bwd_up2: one count per call, by route */ \
     X(BIL_FWD_X2, "bil_fwd_x2") X(BIL_FWD_GENERAL, "bil_fwd_general") /* mrdis_bilinear_fwd */ \

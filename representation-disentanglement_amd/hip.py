@@ -98,6 +98,8 @@ _SIGS = {
     'mrdis_seg_label_volume': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_synth_accum': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_synth_finish': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
+    'mrdis_fuse_present_fwd': (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _L, _I, _P]),
+    'mrdis_fuse_present_bwd': (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _L, _I, _P]),
     'mrdis_maxpool_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_bwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_sumsq_workspace': (_Z, []),
@@ -217,6 +219,9 @@ SEGVOL_FAMILIES = ('segaccum', 'seglabels')
 # whole-subject synthesis of missing contrasts by the 2-D model (csrc/mrdis_synth.hip): 'synthaccum' counts one per mrdis_synth_accum call (one per
 # batch and target), 'synthfinish' one per mrdis_synth_finish call (one per target).
 SYNTH_FAMILIES = ('synthaccum', 'synthfinish')
+# the fusion of the anatomy maps over the contrasts a sample has (csrc/mrdis_fuse.hip; lambda_recon_y_fused): 'fuse' counts one per
+# mrdis_fuse_present_fwd and one per mrdis_fuse_present_bwd call.  Outside KERNEL_FAMILIES for the same reason as the tables above.
+FUSE_FAMILIES = ('fuse',)
 # the dispatch choices of the statistics, norm and resize entry points (csrc/mrdis_elem.hip), host-side counts only: which partial-sum kernel a
 # statistics pass took ('stat_vec' | 'stat_scalar' | 'stat_interp': one per pass), the route of mrdis_instnorm_spade_bwd_up2 (one per call), the
 # kernel of mrdis_bilinear_fwd / _bwd (one per call), and 'elem_v1': an element-wise pass that took its one-channel-per-thread instantiation.
@@ -224,6 +229,8 @@ SYNTH_FAMILIES = ('synthaccum', 'synthfinish')
 ELEM_FAMILIES = ('stat_vec', 'stat_scalar', 'stat_interp', 'spade_up2_onepass', 'spade_up2_twopass', 'bil_fwd_x2', 'bil_fwd_general',
                  'bil_bwd_x2', 'bil_bwd_tight3', 'bil_bwd_tight5', 'bil_bwd_general', 'elem_v1')
 SYNTH_MAX_SRC = 8                 # include/mrdis.h MRDIS_SYNTH_MAX_SRC
+FUSE_MAX_SRC = 8                  # include/mrdis.h MRDIS_FUSE_MAX_SRC
+FUSE_METHODS = ('mean', 'max', 'mean-max-min')      # MRDIS_FUSE_MEAN | _MAX | _MEAN_MAX_MIN, in this order
 
 
 def stream_fill(t, value=0.0):
@@ -253,7 +260,7 @@ def launch_counts(reset=False, elem=False):
     elem=True adds ELEM_FAMILIES: they count dispatch choices of passes that run beside almost every counted kernel (the statistics in front of a fused
     SPADE convolution, say), so callers that assert "this family and no other" over the whole dictionary only see them when they ask."""
     lib = load()
-    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES
+    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + FUSE_FAMILIES
     out = {f: int(lib.mrdis_launch_count(f.encode())) for f in fams + (ELEM_FAMILIES if elem else ())}
     if reset:
         lib.mrdis_launch_count_reset()
@@ -1303,6 +1310,68 @@ def synth_finish(acc, cnt, fill=0.0):
     out = torch.empty((H, W, D), dtype=torch.float32, device=acc.device)
     _chk(lib.mrdis_synth_finish(_ptr(acc), _ptr(cnt), _ptr(out), D, H, W, float(fill), _stream()), 'synth_finish')
     return acc, out
+
+
+def _fuse_args(what, srcs, mask, method):
+    """the checks mrdis_fuse_present_fwd / _bwd share: -> (views, pixel strides, mask, method code, B, C, H, W).  Raises before the library is touched."""
+    srcs = list(srcs)
+    if method not in FUSE_METHODS:
+        raise MrdisError(f'{what}: method {method!r} is not one of {FUSE_METHODS}')
+    if not 1 <= len(srcs) <= FUSE_MAX_SRC:
+        raise MrdisError(f'{what}: 1 to {FUSE_MAX_SRC} maps, got {len(srcs)}')
+    x0 = srcs[0]
+    if x0.dim() != 4:
+        raise MrdisError(f'{what}: (B, C, H, W) maps wanted, got {tuple(x0.shape)}')
+    B, C, H, W = x0.shape
+    views = []
+    for x in srcs:
+        if x.dtype is not torch.float32 or tuple(x.shape) != (B, C, H, W) or x.device != x0.device:
+            raise MrdisError(f'{what}: every map must be an fp32 {(B, C, H, W)} tensor on {x0.device}, got {x.dtype} {tuple(x.shape)} on {x.device}')
+        views.append(nhwc(x))
+    if mask.dtype is not torch.float32 or tuple(mask.shape) != (B, len(srcs)) or not mask.is_contiguous() or mask.device != x0.device:
+        raise MrdisError(f'{what}: mask must be a contiguous fp32 ({B}, {len(srcs)}) tensor on {x0.device}, got {mask.dtype} {tuple(mask.shape)} on {mask.device}')
+    return [v for v, _ in views], [ld for _, ld in views], mask, FUSE_METHODS.index(method), B, C, H, W
+
+
+def _view_table(ts, lds):
+    return (_c.c_void_p * len(ts))(*[t.data_ptr() for t in ts]), (_c.c_int * len(ts))(*lds)
+
+
+def fuse_present_fwd(srcs, mask, method, out=None):
+    """the K fp32 NHWC maps `srcs` (B, C, H, W) fused per sample over the contrasts with mask[b, k] == 1 (include/mrdis.h mrdis_fuse_present_fwd):
+    'mean' | 'max' -> (B, C, H, W); 'mean-max-min' -> (B, 3 C, H, W) = [mean | max | min].  mask: (B, K) fp32 on the device; the kernel reads it
+    there.  out: an NHWC view to write into (a channel slice of a wider buffer qualifies); default a new channels-last tensor.  One launch."""
+    xs, lds, mask, code, B, C, H, W = _fuse_args('fuse_present_fwd', srcs, mask, method)
+    F = 3 if code == 2 else 1
+    y, ldy = _out_view(empty_nhwc(B, F * C, H, W, xs[0].device) if out is None else out)
+    if y.dtype is not torch.float32 or tuple(y.shape) != (B, F * C, H, W):
+        raise MrdisError(f'fuse_present_fwd: out must be an fp32 {(B, F * C, H, W)} view, got {y.dtype} {tuple(y.shape)}')
+    ptrs, ldarr = _view_table(xs, lds)
+    _chk(load().mrdis_fuse_present_fwd(ptrs, ldarr, len(xs), _ptr(mask), code, _ptr(y), ldy, B, H * W, C, _stream()), 'fuse_present_fwd')
+    return y
+
+
+def fuse_present_bwd(dout, srcs, mask, method, outs=None):
+    """-> the K gradients of fuse_present_fwd's maps (include/mrdis.h mrdis_fuse_present_bwd): zeros for an absent contrast, g / n_b for the mean,
+    g to the lowest present index that attains the max / the min (recomputed from the maps).  outs: K NHWC views to write into.  One launch."""
+    xs, lds, mask, code, B, C, H, W = _fuse_args('fuse_present_bwd', srcs, mask, method)
+    F = 3 if code == 2 else 1
+    if dout.dtype is not torch.float32 or tuple(dout.shape) != (B, F * C, H, W):
+        raise MrdisError(f'fuse_present_bwd: dout must be an fp32 {(B, F * C, H, W)} tensor, got {dout.dtype} {tuple(dout.shape)}')
+    dout, lddo = nhwc(dout)
+    if outs is None:
+        outs = [empty_nhwc(B, C, H, W, dout.device) for _ in xs]
+    if len(outs) != len(xs):
+        raise MrdisError(f'fuse_present_bwd: {len(xs)} maps, {len(outs)} gradient views')
+    dviews = [_out_view(t) for t in outs]
+    for d, _ in dviews:
+        if d.dtype is not torch.float32 or tuple(d.shape) != (B, C, H, W):
+            raise MrdisError(f'fuse_present_bwd: every gradient view must be fp32 {(B, C, H, W)}, got {d.dtype} {tuple(d.shape)}')
+    ptrs, ldarr = _view_table(xs, lds)
+    dptrs, dldarr = _view_table([d for d, _ in dviews], [ld for _, ld in dviews])
+    _chk(load().mrdis_fuse_present_bwd(_ptr(dout), lddo, ptrs, ldarr, len(xs), _ptr(mask), code, dptrs, dldarr, B, H * W, C, _stream()),
+         'fuse_present_bwd')
+    return [d for d, _ in dviews]
 
 
 def recon_err_bwd(gt, x, w, p):

@@ -1354,6 +1354,14 @@ class MultimodalModel(nn.Module):
         ones = np.ones((B, 1), dtype=np.float32)
         return [self.reconstruct_output_si_fused([si_list[i]], None, ones) for i in range(self.modality_num)]
 
+    # ---- the fusion the reference's reconstruct_output_si_fused evidently intends (THIS PACKAGE'S CONVENTION, see the quirk above): per sample b
+    # the anatomy maps of the contrasts with mask[b, k] == 1 are reduced by fuse_method ('mean': the sum in increasing k over the count; 'max';
+    # 'mean-max-min': [mean | max | min] along the channels) and the output decoder runs on all B rows.  One HIP launch each way
+    # (ops.fuse_present); a sample without any present contrast raises ValueError from the host mask, before any launch.  M = 1: the identity.
+    def reconstruct_output_fused(self, si_list, mask, mask_host=None):
+        fused = ops.fuse_present(si_list, mask, _host_mask(mask, mask_host), self.fuse_method)
+        return self.output_decoder(fused)[0]
+
     def compute_recon_loss_y_list(self, gt, y_list, mask, p=2, mask_host=None):                 # :3268-3278
         mh = _host_mask(mask, mask_host)
         errs = []
@@ -1364,9 +1372,15 @@ class MultimodalModel(nn.Module):
             return torch.zeros((), device=self.device)
         return (torch.stack(errs) * self._weights(lambda m: [m[:, i] / float(m[:, i].sum()) for i in terms], mh)).sum() / len(errs)
 
+    def compute_recon_loss_y(self, gt, y, p=2):                                                  # :3280-3285
+        return self.compute_recon_loss(gt, y, p).mean()
+
     def compute_segmentation_loss_y(self, gt, y, weight=(1., 5., 5., 5.)):                      # :3287-3297
-        w = torch.tensor(weight, dtype=torch.float32, device=y.device)
-        loss_seg = F.cross_entropy(y, gt.squeeze(1).long(), weight=w)
+        w = ops.to_device(torch.tensor(weight, dtype=torch.float32), y.device)      # (a constant of the step under graph capture: no pageable copy inside a recording)
+        # the weighted mean as the sum of the per-pixel terms over the sum of their weights: torch's own 'mean' reduction adds one partial sum per
+        # block with a float atomic, so from four samples up its last bit depends on the order the blocks finish in (eager and replayed steps differ)
+        t = gt.squeeze(1).long()
+        loss_seg = F.cross_entropy(y, t, weight=w, reduction='none').sum() / w[t].sum()
         y_act = F.softmax(y, dim=1)                                       # F.softmax(y) on a 4-D tensor: dim 1
         dice = 0
         for i in range(1, 4):

@@ -1563,6 +1563,63 @@ def residual_gate(x, alpha):
     return _ResidualGate.apply(x, alpha.float())
 
 
+# --------------------------------------------------------------------------- fusion over the present contrasts (csrc/mrdis_fuse.hip)
+FUSE_METHODS = hip.FUSE_METHODS
+
+
+def check_fuse_mask(mask_host, K=None):
+    """the (B, K) host mask of a fusion: every sample needs a present contrast.  ValueError otherwise (host only: no launch, no library call)."""
+    mh = _np.asarray(mask_host.numpy() if isinstance(mask_host, torch.Tensor) else mask_host, dtype=_np.float32)
+    if mh.ndim != 2 or (K is not None and mh.shape[1] != K):
+        raise ValueError(f'fuse_present: a (B, {K}) host mask wanted, got shape {mh.shape}')
+    empty = _np.flatnonzero((mh == 1).sum(1) == 0)
+    if len(empty):
+        raise ValueError(f'fuse_present: sample(s) {empty.tolist()} have no present contrast: nothing to fuse (the loader drops a contrast only '
+                         f'when more than one is present)')
+    return mh
+
+
+class _FusePresent(Function):
+    """one launch forward, one backward; the mask is read on the device, the arg of max / min is recomputed from the saved maps"""
+
+    @staticmethod
+    def forward(ctx, mask, method, *maps):
+        ctx.method = method
+        ctx.save_for_backward(mask, *maps)
+        return hip.fuse_present_fwd(maps, mask, method)
+
+    @staticmethod
+    def backward(ctx, dout):
+        mask, *maps = ctx.saved_tensors
+        return (None, None) + tuple(hip.fuse_present_bwd(dout, maps, mask, ctx.method))
+
+
+def fuse_present(si_list, mask, mask_host, method):
+    """the anatomy maps si_list (K fp32 (B, C, H, W) NHWC maps, K <= 8) fused per sample over the contrasts with mask[b, k] == 1: 'mean' (the sum
+    in increasing k over the count), 'max', or 'mean-max-min' (the channel concatenation [mean | max | min]).  This package's own convention:
+    the reference's `si_cat[mask == 1]` (model.py:3239-3258) never fuses.  mask: the (B, K) fp32 device mask the kernels read (None: made from
+    mask_host); mask_host: its host copy, from which a sample without any present contrast is refused (ValueError) before any launch.
+    Gradients: an absent contrast gets zeros, the mean g / n_b, the max / min g at the LOWEST present index that attains it (ties are common:
+    the background of the softmax maps is 0 in every contrast)."""
+    si_list = list(si_list)
+    if method not in FUSE_METHODS:
+        raise ValueError(f'fuse_present: method {method!r} is not one of {FUSE_METHODS}')
+    K = len(si_list)
+    if not 1 <= K <= hip.FUSE_MAX_SRC:
+        raise ValueError(f'fuse_present: 1 to {hip.FUSE_MAX_SRC} maps, got {K}')
+    if mask_host is None:
+        if mask is None:
+            raise ValueError('fuse_present: needs the mask or its host copy')
+        mask_host = mask.cpu()
+    mh = check_fuse_mask(mask_host, K)
+    for s in si_list:
+        if s.dtype != torch.float32:
+            raise NotImplementedError(f"the fusion runs on fp32 anatomy maps (got {s.dtype}): compute_dtype 'f32' or 'bf16m'")
+    if mask is None:
+        mask = to_device(torch.from_numpy(_np.ascontiguousarray(mh)), si_list[0].device)
+    return _FusePresent.apply(mask.float().contiguous(), method, *si_list)
+
+
 # --------------------------------------------------------------------------- mixed-kernel cache
 # The reference re-mixes the experts on every CondConv2d call.  Inside one training step the same
 # (layer, modality type) pair recurs (encoder passes 1 and 2, SPADEShared for every s_i), so the

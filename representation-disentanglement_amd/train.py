@@ -39,7 +39,7 @@ import torch.distributed as dist
 import yaml
 
 from .data import BatchLoader, SliceDataset, VolumeStore, load_idx_list
-from .trainer import (DEFAULT_CONFIG, LOSS_KEYS, EVAL_INFOS, EvalStep, ZGallery, build_z_gallery, TrainStep, make_train_step, build_model, derive_config, load_checkpoint_model,
+from .trainer import (DEFAULT_CONFIG, LOSS_KEYS, EVAL_INFOS, EvalStep, eval_metric_keys, ZGallery, build_z_gallery, TrainStep, make_train_step, build_model, derive_config, load_checkpoint_model,
                       load_config_yaml, save_checkpoint)
 
 from .synth import check_synth_options, synthesize_volumes
@@ -167,7 +167,7 @@ def setup_config(config_path='config.yaml', overrides=None, ckpt_root='../ckpt/'
         flag, saved = load_config_yaml(os.path.join(config['ckpt_path'], 'config.yaml'))
         if flag:
             for k, v in saved.items():                                      # :45-51
-                if k in ('phase', 'continue_train', 'eval_info') + SYNTH_KEYS or k not in config:    # eval_info, synth_*: per invocation, like phase
+                if k in ('phase', 'continue_train', 'eval_info', 'eval_drop') + SYNTH_KEYS or k not in config:    # eval_info, eval_drop, synth_*: per invocation, like phase
                     continue
                 config[k] = v
             config = derive_config(config, device)
@@ -315,7 +315,7 @@ class Run:
             acc, n_iter = None, 0
             for it, sample in enumerate(self.loaders['train']):
                 self.global_iter += 1
-                targets = sample['targets'] if cfg['lambda_recon_y'] > 0 else None
+                targets = sample['targets'] if (cfg['lambda_recon_y'] > 0 or cfg['lambda_recon_y_fused'] > 0) else None
                 loss, parts, _ = self.step(sample['inputs'], sample['mask'], sample['mask_img'], sample.get('mask_host'), targets=targets, it=it)
                 vec = torch.stack([parts[k].float().reshape(()) for k in LOSS_KEYS])
                 acc = vec if acc is None else acc + vec                     # :253-263 without the 11 .item() syncs
@@ -393,7 +393,7 @@ class Run:
             if self.world > 1 or (dist.is_available() and dist.is_initialized()):
                 raise NotImplementedError(f'evaluate(info={info!r}) under a process group: the z gallery is not sharded; evaluate on one process')
             step = EvalStep(self.model, cfg, info=info, gallery=self.z_gallery(set_, max_batches))
-        acc, n_iter, met = None, 0, {'rmse': [], 'psnr': [], 'ssim': []}
+        acc, n_iter, met = None, 0, {k: [] for k in eval_metric_keys(cfg)}      # the names are the configuration's, so every rank sums the same vector
         # the reference stops after global batch 501 (:562-563).  The cap is applied by the loader, on the GLOBAL batch index and before any meta of a later
         # batch is drawn, so every rank walks the same `max_batches` batches and leaves the host generators in the same state (a cap tested per rank after
         # the step let world = 8 evaluate up to batch 508 and end the ranks' np.random streams apart)
@@ -401,11 +401,13 @@ class Run:
         for it, sample in enumerate(batches):
             if sample.get('batch_index', it) >= max_batches:
                 break
-            targets = sample['targets'] if cfg['lambda_recon_y'] > 0 else None
+            targets = sample['targets'] if (cfg['lambda_recon_y'] > 0 or cfg['lambda_recon_y_fused'] > 0) else None
             kw = dict(subj_id=sample['subj_id']) if info else {}
             loss, parts, metrics, _ = step(sample['inputs'], sample['mask'], sample['mask_img'], sample.get('mask_host'), targets=targets, **kw)
             vec = torch.stack([parts[k].float().reshape(()) for k in LOSS_KEYS])
             acc = vec if acc is None else acc + vec
+            if set(metrics) != set(met):
+                raise RuntimeError(f'evaluate: the step returned the metrics {sorted(metrics)}, the configuration names {sorted(met)}')
             for k in met:
                 met[k].append(metrics[k])
             n_iter += 1

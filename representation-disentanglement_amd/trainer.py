@@ -43,6 +43,7 @@ DEFAULT_CONFIG = {
     'synth_drop': [],                  # contrast names hidden on purpose, so that their synthesis is scored against the stored volume
     'synth_block': 'centre',           # 'centre': a plane is the centre slice of its own sample | 'mean': the mean of every prediction of it
     'synth_set': 'test',               # train | val | test: the slice list whose distinct subjects are synthesised
+    'eval_drop': [],                   # contrast names hidden during evaluation (EvalStep): their input channels become the store's absent value (0), their mask column 0
 }
 
 
@@ -614,11 +615,7 @@ def forward_losses(model, config, inputs, mask, mask_img, mask_host, phase='trai
     xi_fake_mix_list = model.reconstruct_input_si_zj(si_list, z_dec)                             # :178
     parts = {k: zero for k in LOSS_KEYS}
     loss = zero
-    if config['lambda_recon_y_fused'] > 0:
-        # main_missing.py:201-208: reconstruct_output_si_fused returns sum(mask) rows (boolean-index quirk), so the
-        # loss against B targets raises in the reference for every M > 1
-        raise NotImplementedError('lambda_recon_y_fused: the reference path raises a shape error for M > 1')
-    y_list = None
+    y_list = y_fused = None
     if config['lambda_recon_y'] > 0:                                                             # :187-198
         if targets is None:
             raise ValueError('lambda_recon_y > 0 needs targets')
@@ -628,6 +625,17 @@ def forward_losses(model, config, inputs, mask, mask_img, mask_host, phase='trai
         else:
             parts['recon_y'] = model.compute_recon_loss_y_list(targets, y_list, mask, p, mask_host)
         loss = loss + config['lambda_recon_y'] * parts['recon_y']
+    if config['lambda_recon_y_fused'] > 0:                                                       # :201-206
+        # the reference's reconstruct_output_si_fused returns sum(mask) rows (boolean-index quirk) and raises against B targets for every
+        # M > 1; here the maps are fused per sample over its present contrasts (model.reconstruct_output_fused: this package's convention)
+        if targets is None:
+            raise ValueError('lambda_recon_y_fused > 0 needs targets')
+        y_fused = model.reconstruct_output_fused(si_list, mask, mask_host)
+        if config['dataset_name'] == 'BraTS':
+            parts['recon_y_fused'] = model.compute_segmentation_loss_y(targets, y_fused)
+        else:
+            parts['recon_y_fused'] = model.compute_recon_loss_y(targets, y_fused, p)
+        loss = loss + config['lambda_recon_y_fused'] * parts['recon_y_fused']
     if config['lambda_recon_x'] > 0:
         parts['recon_x'] = model.compute_recon_loss_x_list(inputs_list, xi_fake_list, mask, p, mask_host)
         loss = loss + config['lambda_recon_x'] * parts['recon_x']
@@ -660,7 +668,7 @@ def forward_losses(model, config, inputs, mask, mask_img, mask_host, phase='trai
         loss = loss + config['lambda_adv_s'] * parts['adv_s']
     parts['all'] = loss
     aux = dict(si_list=si_list, zi_list=zi_list, mu_list=mu_list, lv_list=lv_list, xi_fake_list=xi_fake_list,
-               xi_fake_mix_list=xi_fake_mix_list, y_list=y_list)
+               xi_fake_mix_list=xi_fake_mix_list, y_list=y_list, y_fused=y_fused)
     if z_recon is not None:
         aux['z_find'] = z_dec
     return loss, parts, aux
@@ -910,6 +918,8 @@ class GraphedTrainStep:
             self.stats['eager'] += 1
             return self._eager(x, m, mi, mask_host, tg, do_step)
         ent = group[pairs.get('adv_s')]
+        if ts.config['lambda_recon_y_fused'] > 0:
+            ops.check_fuse_mask(mask_host)          # the recorded fusion reads the device mask: a sample without a present contrast is refused here, as in the eager step
         ops.set_step_mask_host(mask_host)
         ent['hv'].refill()                       # eps and the mask weights of THIS step (the closures draw from the global torch generator in the recorded order)
         self.stats['replays'] += 1
@@ -1032,6 +1042,47 @@ def make_train_step(model, config, **kw):
 
 
 EVAL_INFOS = ('', 'nearest_neighbour', 'mean')
+
+
+def eval_metric_keys(config):
+    """the metric names EvalStep returns for a configuration (main_missing.py:520-533): the segmentation metrics of the fused output for BraTS
+    with lambda_recon_y_fused > 0, the reconstruction metrics otherwise (of the fused output with lambda_recon_y_fused > 0, else of the mix
+    reconstructions)"""
+    if config.get('lambda_recon_y_fused', 0) > 0 and config['dataset_name'] == 'BraTS':
+        return ('dice', 'iou')
+    return ('rmse', 'psnr', 'ssim')
+
+
+def eval_drop_indices(config):
+    """indices of the contrasts `eval_drop` names; ValueError for a name outside contrast_list or a list that hides every contrast"""
+    names = [str(c) for c in config['contrast_list']]
+    drop = config.get('eval_drop') or []
+    if isinstance(drop, str):
+        drop = [drop]
+    bad = [d for d in drop if str(d) not in names]
+    if bad:
+        raise ValueError(f'eval_drop {bad}: not in contrast_list {names}')
+    idx = sorted({names.index(str(d)) for d in drop})
+    if idx and len(idx) == len(names):
+        raise ValueError(f'eval_drop {list(drop)} hides every contrast')
+    return idx
+
+
+def segmentation_metrics(targets, y):
+    """{'dice', 'iou'}: (B,) float64 device tensors, util.py:980-992 per sample with that function's quirks kept: output channel i (i = 0, 1, 2) of
+    the RAW decoder output y (no softmax, no argmax) is thresholded at 0.5 and scored against label i + 1 -- so channel 0, the background logit
+    of the training objective, is scored against label 1 and channel 3 never --; dice = (2 |A and B| + 1) / (|A| + |B| + 1),
+    iou = (|A and B| + 1) / (|A or B| + 1); the mean over the three classes.  Counts by torch ops on the device (not a hot path)."""
+    t = targets[:, 0] if targets.dim() == 4 else targets
+    dice, iou = [], []
+    for i in range(3):
+        a = (t == i + 1).flatten(1)
+        b = (y[:, i] > 0.5).flatten(1)
+        inter = (a & b).sum(1).double()
+        union = (a | b).sum(1).double()
+        dice.append((2. * inter + 1) / (a.sum(1).double() + b.sum(1).double() + 1))
+        iou.append((inter + 1) / (union + 1))
+    return {'dice': (dice[0] + dice[1] + dice[2]) / 3, 'iou': (iou[0] + iou[1] + iou[2]) / 3}
 
 
 def nn_source_contrast(i):
@@ -1179,7 +1230,13 @@ class EvalStep:
     decode with z_find instead of the slice's own modality code; z_find[i] is the z[:, i] of the gallery row whose compact s of contrast
     nn_source_contrast(i) is nearest (cosine) to the query's, rows of the query's own subject excluded -- one mrdis_cosine_top1 launch per
     distinct source contrast -- or, for 'mean', the mean z[:, i] over every other subject's rows.  Losses and metrics follow unchanged
-    (sim_z and latent_z still see the slice's own codes, as in the reference).  aux['z_find'] holds the codes used.  World size 1 only."""
+    (sim_z and latent_z still see the slice's own codes, as in the reference).  aux['z_find'] holds the codes used.  World size 1 only.
+
+    lambda_recon_y_fused > 0 (:529-533): the metrics are those of y_fused -- the output decoder on the anatomy maps fused over each sample's present
+    contrasts (aux['y_fused']) -- against `targets`: BraTS {'dice', 'iou'} (segmentation_metrics, (B,) float64), other datasets 'rmse' / 'psnr' /
+    'ssim' from hip.recon_metrics(targets, y_fused).  With lambda_recon_y_fused == 0 nothing changes.
+    Config key `eval_drop` (default []): contrasts hidden for the evaluation -- their input channels become the store's absent value (0) and their
+    mask column 0 before anything runs (mask_img is left as the loader made it) --, so Dice can be reported per missing-contrast pattern."""
 
     def __init__(self, model, config, info='', gallery=None):
         if info not in EVAL_INFOS:
@@ -1191,6 +1248,7 @@ class EvalStep:
         if info == 'nearest_neighbour':
             gallery.check_compact_method(model)
         self.model, self.config, self.info, self.gallery = model, config, info, gallery
+        self.drop = eval_drop_indices(config)
 
     def _z_find(self, si_list, zi_list, codes):
         M = len(si_list)
@@ -1207,6 +1265,14 @@ class EvalStep:
         model, cfg = self.model, self.config
         if mask_host is None:
             mask_host = mask.cpu()
+        if self.drop:
+            c = 2 * cfg['block_size'] + 1
+            inputs, mask = inputs.clone(), mask.clone()
+            mask_host = np.array(mask_host.numpy() if isinstance(mask_host, torch.Tensor) else mask_host, dtype=np.float32)
+            for j in self.drop:
+                inputs[:, j * c:(j + 1) * c] = 0
+                mask[:, j] = 0
+                mask_host[:, j] = 0
         z_recon = None
         if self.info:
             if subj_id is None or len(subj_id) != inputs.shape[0]:
@@ -1221,15 +1287,21 @@ class EvalStep:
                 loss, parts, aux = forward_losses(model, cfg, inputs, mask, mask_img, mask_host, phase='test', targets=targets, z_recon=z_recon)
                 M = len(cfg['contrast_list'])
                 c = 2 * cfg['block_size'] + 1
-                rows, k = [], 0
-                for i in range(M):                                                   # main_missing.py:520-528
-                    for j in range(M):
-                        if i == j:
-                            continue
-                        rows.append(hip.recon_metrics(inputs[:, j * c:(j + 1) * c], aux['xi_fake_mix_list'][k]))
-                        k += 1
-                rows = torch.cat(rows, 0)                                            # (M(M-1)B, 3), reference order
-                metrics = {'rmse': rows[:, 0], 'psnr': rows[:, 1], 'ssim': rows[:, 2]}
+                if cfg['lambda_recon_y_fused'] > 0 and cfg['dataset_name'] == 'BraTS':   # main_missing.py:529-531
+                    metrics = segmentation_metrics(targets, aux['y_fused'])
+                else:
+                    if cfg['lambda_recon_y_fused'] > 0:                              # :532-533
+                        rows = hip.recon_metrics(targets.float(), aux['y_fused'])
+                    else:
+                        rows, k = [], 0
+                        for i in range(M):                                           # :520-528
+                            for j in range(M):
+                                if i == j:
+                                    continue
+                                rows.append(hip.recon_metrics(inputs[:, j * c:(j + 1) * c], aux['xi_fake_mix_list'][k]))
+                                k += 1
+                        rows = torch.cat(rows, 0)                                    # (M(M-1)B, 3), reference order
+                    metrics = {'rmse': rows[:, 0], 'psnr': rows[:, 1], 'ssim': rows[:, 2]}
         finally:
             model.train(was)
         return loss, parts, metrics, aux
