@@ -503,6 +503,47 @@ int mrdis_fuse_present_fwd(const float* const* srcs, const int* ld_srcs, int K, 
 int mrdis_fuse_present_bwd(const float* dout, int lddo, const float* const* srcs, const int* ld_srcs, int K, const float* mask, int method,
                            float* const* dsrcs, const int* ld_dsrcs, int B, long long HW, int C, void* stream);
 
+/* ---- region scoring of label volumes (csrc/mrdis_surfdist.hip): region surfaces, the exact squared Euclidean distance transform and the
+ * histogram of surface distances behind the 95th-percentile Hausdorff distance (HD95).  Integer arithmetic throughout: exact, and the same
+ * bits from run to run.  Volumes are (B, H, W, D), D contiguous; voxel spacing is isotropic, squared distances are integers in voxel units.
+ * mrdis_region_surfaces: labels (B, H, W, D) uint8 as mrdis_seg_label_volume writes them, 4-byte aligned; targets: B 64-bit device pointers
+ *   (device memory) to raw (H, W, D) fp32 label volumes, 0 = none, or NULL = none for any sample (the convention of mrdis_seg_label_volume);
+ *   region_masks: HOST array of R (1 .. MRDIS_SURF_MAX_REGIONS) integers in 0 .. 255: a label value l in 0 .. 7 belongs to region r iff bit l
+ *   of region_masks[r] is set; a value above 7, negative, or non-integral after the cast belongs to no region.  flags (B, H, W, D) uint8,
+ *   4-byte aligned, every byte written: bit r = the voxel is a surface voxel of predicted region r, bit 4 + r = of ground-truth region r.  A
+ *   surface voxel lies in the region and has at least one of its six face neighbours outside it; the volume border counts as outside.
+ *   counts (B, R, 5) int32 += { |P and T|, |P|, |T|, surface voxels of P, surface voxels of T }; the caller zeroes `counts`.  A sample without
+ *   ground truth keeps its ground-truth bits and T counts at 0.  H W D < 2^31, B <= 65535.  One launch, counted as "regsurf".
+ * mrdis_edt_sq: src (B, H, W, D) uint8; src_masks: HOST array of S (1 .. MRDIS_EDT_MAX_SRC) bytes: a voxel is a feature of source s iff
+ *   (src & src_masks[s]) != 0 (0xFF: a plain mask; 1 << k: bit k of the flags above).  out (S, B, H, W, D) int32, 16-byte aligned: the squared
+ *   Euclidean distance to the nearest feature of the same source and batch item, 0 on a feature, MRDIS_EDT_FAR everywhere in an item without
+ *   one.  Separable: a nearest-feature scan along D, then min_j (g[j] + (i - j)^2) along W and along H, brute force over an LDS-resident line.
+ *   Each of H, W, D in 1 .. 1024 and (H-1)^2 + (W-1)^2 + (D-1)^2 < MRDIS_EDT_FAR, B <= 65535: anything else returns MRDIS_EINVAL.
+ *   workspace: mrdis_edt_workspace bytes (0: unsupported geometry), 16-byte aligned.  Three launches whatever B and S, each counted as "edt".
+ * mrdis_surface_hist: flags as mrdis_region_surfaces wrote them for R regions.  For region r, at every surface voxel of T adds 1 into
+ *   hist[b][r][0][d2], d2 = the squared distance to the nearest surface voxel of P, and at every surface voxel of P into hist[b][r][1][d2],
+ *   d2 to the nearest surface voxel of T; a direction whose source surface is empty adds nothing.  hist (B, R, 2, bins) int32,
+ *   bins = (H-1)^2 + (W-1)^2 + (D-1)^2 + 1 (anything else: MRDIS_EINVAL); the caller zeroes it.  The distances are never stored: the histogram
+ *   is the last pass of the transform of the 2 R surfaces.  workspace: mrdis_edt_workspace(2 R, ...) bytes.  Geometry as mrdis_edt_sq.  Three
+ *   launches: two counted as "edt", the last as "surfhist".
+ * The scores formed from counts and histograms on the host (surfdist.region_scores) follow THIS PACKAGE'S CONVENTION -- BraTS's region
+ * definitions (WT = {1, 2, 4}, TC = {1, 4}, ET = {4}) are standard, the empty-region and percentile rules vary between toolkits.  N = H W D,
+ * TN = N - P - T + I:  dice = 2 I / (P + T);  sensitivity = I / T, or 1 if T = 0;  specificity = TN / (N - T), or 1 if N = T.  The directed 95 %
+ * distance from A to B is spacing * sqrt(k), k the smallest squared distance with 20 * cum[k] >= 19 * n_A (n_A surface voxels of A, cum the
+ * running sum of its histogram row): the nearest rank, decided in integers, no interpolation; hd95 is the larger of the two directed distances.
+ * Both regions empty: dice 1, hd95 0.  Exactly one empty: dice 0, hd95 = spacing * sqrt(H^2 + W^2 + D^2) (373.13 for BraTS geometry, the
+ * challenge's penalty).  No ground truth for the sample: NaN in all four.                                                             */
+#define MRDIS_EDT_FAR (1 << 30)
+#define MRDIS_EDT_MAX_SRC 8
+#define MRDIS_SURF_MAX_REGIONS 4
+int mrdis_region_surfaces(const unsigned char* labels, const void* targets, const int* region_masks, int R, unsigned char* flags, int* counts,
+                          int B, int H, int W, int D, void* stream);
+size_t mrdis_edt_workspace(int S, int B, int H, int W, int D);
+int mrdis_edt_sq(const unsigned char* src, const unsigned char* src_masks, int S, int* out, void* workspace, size_t workspace_bytes, int B,
+                 int H, int W, int D, void* stream);
+int mrdis_surface_hist(const unsigned char* flags, int R, int* hist, long long bins, void* workspace, size_t workspace_bytes, int B, int H,
+                       int W, int D, void* stream);
+
 /* ---- max_pool2d(kernel k x k, stride k): model.py:3448-3451 ---------------- */
 int mrdis_maxpool_fwd(const float* x, int ldx, float* y, int32_t* argmax, int N, int H, int W, int C,
                       int k, void* stream);

@@ -6,6 +6,8 @@ the command line, then key=value overrides), trains with a validation pass per e
     python main_3d.py cfg3d.yaml epochs=2 batch_size=2 ckpt_path=/tmp/ckpt3d
     python main_3d.py cfg3d.yaml phase=test
     python main_3d.py cfg3d.yaml phase=predict   # <ckpt_path>/result_test/<subj_id>_seg.npy + predict.csv
+    python main_3d.py cfg3d.yaml phase=predict predict_regions=true     # + predict_regions.csv: Dice, sensitivity, specificity, HD95 of WT / TC / ET
+    python main_3d.py cfg3d.yaml phase=score     # the same csv for label volumes already under result_test/ (no model is built or loaded)
 """
 import os
 import sys

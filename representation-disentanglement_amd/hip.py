@@ -100,6 +100,10 @@ _SIGS = {
     'mrdis_synth_finish': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     'mrdis_fuse_present_fwd': (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _L, _I, _P]),
     'mrdis_fuse_present_bwd': (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _L, _I, _P]),
+    'mrdis_region_surfaces': (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
+    'mrdis_edt_workspace': (_Z, [_I, _I, _I, _I, _I]),
+    'mrdis_edt_sq': (_I, [_P, _c.c_char_p, _I, _P, _P, _Z, _I, _I, _I, _I, _P]),
+    'mrdis_surface_hist': (_I, [_P, _I, _P, _L, _P, _Z, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_bwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_sumsq_workspace': (_Z, []),
@@ -222,6 +226,10 @@ SYNTH_FAMILIES = ('synthaccum', 'synthfinish')
 # the fusion of the anatomy maps over the contrasts a sample has (csrc/mrdis_fuse.hip; lambda_recon_y_fused): 'fuse' counts one per
 # mrdis_fuse_present_fwd and one per mrdis_fuse_present_bwd call.  Outside KERNEL_FAMILIES for the same reason as the tables above.
 FUSE_FAMILIES = ('fuse',)
+# region scoring of label volumes (csrc/mrdis_surfdist.hip): 'regsurf' counts one per mrdis_region_surfaces call, 'edt' one per LAUNCH of a
+# distance-transform pass (three per mrdis_edt_sq call, two per mrdis_surface_hist call), 'surfhist' one per mrdis_surface_hist call (its last
+# pass, which adds into the histogram instead of storing distances).  None depends on the batch size.
+SURFDIST_FAMILIES = ('regsurf', 'edt', 'surfhist')
 # the dispatch choices of the statistics, norm and resize entry points (csrc/mrdis_elem.hip), host-side counts only: which partial-sum kernel a
 # statistics pass took ('stat_vec' | 'stat_scalar' | 'stat_interp': one per pass), the route of mrdis_instnorm_spade_bwd_up2 (one per call), the
 # kernel of mrdis_bilinear_fwd / _bwd (one per call), and 'elem_v1': an element-wise pass that took its one-channel-per-thread instantiation.
@@ -231,6 +239,10 @@ ELEM_FAMILIES = ('stat_vec', 'stat_scalar', 'stat_interp', 'spade_up2_onepass', 
 SYNTH_MAX_SRC = 8                 # include/mrdis.h MRDIS_SYNTH_MAX_SRC
 FUSE_MAX_SRC = 8                  # include/mrdis.h MRDIS_FUSE_MAX_SRC
 FUSE_METHODS = ('mean', 'max', 'mean-max-min')      # MRDIS_FUSE_MEAN | _MAX | _MEAN_MAX_MIN, in this order
+EDT_FAR = 1 << 30                 # include/mrdis.h MRDIS_EDT_FAR
+EDT_MAX_SRC = 8                   # include/mrdis.h MRDIS_EDT_MAX_SRC
+EDT_MAX_EXTENT = 1024             # each of H, W, D of a distance transform
+SURF_MAX_REGIONS = 4              # include/mrdis.h MRDIS_SURF_MAX_REGIONS
 
 
 def stream_fill(t, value=0.0):
@@ -260,7 +272,7 @@ def launch_counts(reset=False, elem=False):
     elem=True adds ELEM_FAMILIES: they count dispatch choices of passes that run beside almost every counted kernel (the statistics in front of a fused
     SPADE convolution, say), so callers that assert "this family and no other" over the whole dictionary only see them when they ask."""
     lib = load()
-    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + FUSE_FAMILIES
+    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES
     out = {f: int(lib.mrdis_launch_count(f.encode())) for f in fams + (ELEM_FAMILIES if elem else ())}
     if reset:
         lib.mrdis_launch_count_reset()
@@ -1266,6 +1278,83 @@ def seg_label_volume(acc, cover, target_ptrs=None, relabel=False):
     _chk(lib.mrdis_seg_label_volume(_ptr(acc), _ptr(cover), _ptr(target_ptrs), _ptr(labels), _ptr(counts), B, H, W, D, C, int(bool(relabel)),
                                     _stream()), 'seg_label_volume')
     return labels, counts
+
+
+def _volume_u8(t, what):
+    """(B, H, W, D) of a contiguous uint8 device volume, else MrdisError; nothing is copied"""
+    if t.dtype != torch.uint8 or t.dim() != 4 or not t.is_contiguous():
+        raise MrdisError(f'{what} must be a contiguous uint8 (B, H, W, D) tensor, got {t.dtype} {tuple(t.shape)} strides {t.stride()}')
+    return tuple(t.shape)
+
+
+def edt_bins(H, W, D):
+    """bins of a surface-distance histogram: every squared distance inside an (H, W, D) volume, 0 included"""
+    return (H - 1) ** 2 + (W - 1) ** 2 + (D - 1) ** 2 + 1
+
+
+def _edt_geometry(B, H, W, D, what):
+    if not (1 <= B <= 65535 and all(1 <= n <= EDT_MAX_EXTENT for n in (H, W, D)) and edt_bins(H, W, D) - 1 < EDT_FAR):
+        raise MrdisError(f'{what}: unsupported geometry {(B, H, W, D)}: each of H, W, D in 1 .. {EDT_MAX_EXTENT}')
+
+
+def region_surfaces(labels, target_ptrs, region_masks):
+    """-> (flags (B, H, W, D) uint8, counts (B, R, 5) int32), both on the device (include/mrdis.h mrdis_region_surfaces).  labels (B, H, W, D)
+    uint8 contiguous; target_ptrs (B,) int64 on the device: addresses of raw (H, W, D) fp32 label volumes, 0 = none (None: none for any
+    sample); region_masks: R <= 4 host integers, bit l of region_masks[r] set = label l belongs to region r.  flags bit r: surface voxel of
+    predicted region r, bit 4 + r: of ground-truth region r; counts = [|P and T|, |P|, |T|, surface voxels of P, surface voxels of T]."""
+    lib = load()
+    B, H, W, D = _volume_u8(labels, 'region_surfaces: labels')
+    masks = [int(m) for m in region_masks]
+    R = len(masks)
+    if not 1 <= R <= SURF_MAX_REGIONS or any(not 0 <= m <= 255 for m in masks):
+        raise MrdisError(f'region_surfaces: 1 .. {SURF_MAX_REGIONS} region masks in 0 .. 255, got {masks}')
+    if B < 1 or H < 1 or W < 1 or D < 1:
+        raise MrdisError(f'region_surfaces: unsupported geometry {(B, H, W, D)}')
+    if target_ptrs is not None and (target_ptrs.dtype != torch.int64 or tuple(target_ptrs.shape) != (B,) or not target_ptrs.is_contiguous()
+                                    or target_ptrs.device != labels.device):
+        raise MrdisError(f'region_surfaces: target_ptrs must be a contiguous int64 ({B},) tensor on {labels.device}')
+    flags = torch.empty((B, H, W, D), dtype=torch.uint8, device=labels.device)
+    counts = torch.zeros((B, R, 5), dtype=torch.int32, device=labels.device)
+    _chk(lib.mrdis_region_surfaces(_ptr(labels), _ptr(target_ptrs), (_I * R)(*masks), R, _ptr(flags), _ptr(counts), B, H, W, D, _stream()),
+         'region_surfaces')
+    return flags, counts
+
+
+def edt_sq(src, src_masks=(0xFF,)):
+    """-> (S, B, H, W, D) int32 on the device: the exact squared Euclidean distance of every voxel to the nearest voxel of the same batch item
+    with (src & src_masks[s]) != 0; 0 on such a voxel, EDT_FAR everywhere in an item without one (include/mrdis.h mrdis_edt_sq).  src
+    (B, H, W, D) uint8 contiguous; each of H, W, D in 1 .. 1024, else MrdisError('... unsupported geometry ...')."""
+    lib = load()
+    B, H, W, D = _volume_u8(src, 'edt_sq: src')
+    _edt_geometry(B, H, W, D, 'edt_sq')
+    vals = [int(m) for m in src_masks]
+    S = len(vals)
+    if not 1 <= S <= EDT_MAX_SRC or any(not 0 <= m <= 255 for m in vals):
+        raise MrdisError(f'edt_sq: 1 .. {EDT_MAX_SRC} source masks in 0 .. 255, got {vals}')
+    masks = bytes(vals)
+    out = torch.empty((S, B, H, W, D), dtype=torch.int32, device=src.device)
+    nws = _ws_bytes(lib.mrdis_edt_workspace, S, B, H, W, D)
+    ws = torch.empty(nws, dtype=torch.uint8, device=src.device)      # 6 bytes per voxel and source: its own allocation, returned after the call
+    _chk(lib.mrdis_edt_sq(_ptr(src), masks, S, _ptr(out), _ptr(ws), nws, B, H, W, D, _stream()), 'edt_sq')
+    return out
+
+
+def surface_hist(flags, R):
+    """-> hist (B, R, 2, bins) int32 on the device, bins = edt_bins(H, W, D) (include/mrdis.h mrdis_surface_hist): hist[b, r, 0, d2] = surface
+    voxels of ground-truth region r at squared distance d2 from the nearest surface voxel of predicted region r, hist[b, r, 1, d2] the other
+    way round; a direction whose source surface is empty stays 0.  flags as `region_surfaces` wrote them for R regions.  The distance volumes
+    are never stored."""
+    lib = load()
+    B, H, W, D = _volume_u8(flags, 'surface_hist: flags')
+    _edt_geometry(B, H, W, D, 'surface_hist')
+    if not 1 <= int(R) <= SURF_MAX_REGIONS:
+        raise MrdisError(f'surface_hist: 1 .. {SURF_MAX_REGIONS} regions, got {R}')
+    bins = edt_bins(H, W, D)
+    hist = torch.zeros((B, int(R), 2, bins), dtype=torch.int32, device=flags.device)
+    nws = _ws_bytes(lib.mrdis_edt_workspace, 2 * int(R), B, H, W, D)
+    ws = torch.empty(nws, dtype=torch.uint8, device=flags.device)    # (1.29 GB for four BraTS subjects: not kept in the binding's grow-only scratch)
+    _chk(lib.mrdis_surface_hist(_ptr(flags), int(R), _ptr(hist), bins, _ptr(ws), nws, B, H, W, D, _stream()), 'surface_hist')
+    return hist
 
 
 def synth_accum(recons, centres, acc, cnt, c_lo, c_hi):

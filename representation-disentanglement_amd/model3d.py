@@ -363,7 +363,8 @@ def window_cover(D, Dz, offsets, flips=1):
 
 def predict_volumes(model, loader, stride=None, flip=False, limit=None):
     """Label volumes over the FULL depth of every subject a VolumeLoader3D serves, as a generator over its batches:
-        {'subj_id': list, 'labels': (B, H, W, D) uint8 on the device, 'counts': (B, 3, 3) int32 on the device, 'acc': (B, H, W, D, C) fp32}
+        {'subj_id': list, 'labels': (B, H, W, D) uint8 on the device, 'counts': (B, 3, 3) int32 on the device, 'acc': (B, H, W, D, C) fp32,
+         'target_ptrs': (B,) int64 on the device, the addresses of the subjects' full label volumes (0 = none; `surfdist.region_scores`)}
     The trained depth window (Dz = the loader's crop depth) slides along D at `window_offsets(D, Dz, stride)` (stride None: Dz // 2); the sigmoid
     probabilities of overlapping windows -- and, with `flip`, of the H-flipped input, un-flipped -- are averaged; a voxel's label is 0 if no
     region's mean probability is above 0.5, else 1 + the most probable region (lowest on a tie), region 3 written as 4 for BraTS: the store's
@@ -407,6 +408,6 @@ def predict_volumes(model, loader, stride=None, flip=False, limit=None):
                         hip.seg_accum(net(batch['inputs'])[0], acc, z0, flip_h=f)
                         del batch
                 labels, counts = hip.seg_label_volume(acc, cover, ptrs, relabel=relabel)
-                yield {'subj_id': subj_id, 'labels': labels, 'counts': counts, 'acc': acc}
+                yield {'subj_id': subj_id, 'labels': labels, 'counts': counts, 'acc': acc, 'target_ptrs': ptrs}
     finally:
         net.train(was_training)

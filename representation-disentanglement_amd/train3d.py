@@ -8,7 +8,9 @@ csrc/mrdis_loss3d.hip) unless `fused_loss: false` -- the optimizer is `ArenaAdam
 Dice / IoU (`compute_segmentation_metrics`, util.py:946-992) from the integer counts of `mrdis_seg_counts`, and stat.csv / `epochNNN.pth.tar` /
 `model_best.pth.tar` are written by the same `save_result_stat` / `save_checkpoint` as the 2-D entry.  The best checkpoint is the epoch with the
 highest validation Dice.  `phase: predict` loads it and writes one label volume per subject over the FULL depth (sliding window,
-model3d.predict_volumes) with its Dice / IoU.
+model3d.predict_volumes) with its Dice / IoU; with `predict_regions: true` also the BraTS region scores (Dice, sensitivity, specificity, HD95
+of WT / TC / ET: surfdist.region_scores) in predict_regions.csv.  `phase: score` writes that file for label volumes that already lie under
+result_<predict_set>/ -- predicted earlier or post-processed elsewhere -- without building or loading a model.
 
 A checkpoint also carries the host and device RNG states (np.random, torch default, the torch device generator, the loaders' own generator
 if any), written after the epoch's validation pass: `continue_train` then continues exactly where the run stopped -- the shuffles, augmentation
@@ -29,11 +31,13 @@ import yaml
 from . import hip
 from .data3d import VolumeData3D
 from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, predict_volumes, seg_metrics_from_counts
+from .surfdist import BRATS_REGIONS, SCORE_KEYS, region_scores
 from .train import parse_overrides, save_config_file, save_result_stat
 from .trainer import ArenaAdam, load_checkpoint_model, save_checkpoint
 
 DEFAULT_CONFIG_3D = {
     'phase': 'train',                  # train | test (load model_best.pth.tar, print the test-set stat) | predict (load it, write whole-volume label maps)
+                                       # | score (region scores of the label maps already under result_<predict_set>/: no model)
     'dataset_name': 'BraTS', 'data_path': '../data/', 'norm_type': 'z-score', 'fold': 0,
     'contrast_list': ['T1', 'T1c', 'T2', 'T2_FLAIR'], 'batch_size': 4,
     'model_name': 'NVNet3D',           # NVNet3D | UNet3D (Dice-only objective)
@@ -49,8 +53,10 @@ DEFAULT_CONFIG_3D = {
     'predict_set': 'test',             # phase predict: the loader whose subjects are predicted (train | val | test; it must serve them as stored)
     'predict_stride': None,            # depth stride of the sliding window; None: half the trained depth
     'predict_flip': False,             # also average the prediction of the H-flipped input
+    'predict_regions': False,          # phase predict: also write predict_regions.csv (Dice, sensitivity, specificity, HD95 of WT / TC / ET; BraTS only)
 }
-PHASES = ('train', 'test', 'predict')
+PHASES = ('train', 'test', 'predict', 'score')
+REGION_CSV_KEYS = (('dice', 'dice'), ('sens', 'sensitivity'), ('spec', 'specificity'), ('hd95', 'hd95'))      # csv column prefix, region_scores key
 MODEL_NAMES = ('NVNet3D', 'UNet3D')
 LR_SCHEDULES = ('none', 'poly')
 STAT_KEYS = ('loss', 'loss_dice', 'loss_l2', 'loss_kl')
@@ -81,7 +87,31 @@ def load_config3d(path=None, overrides=None):
         cfg['predict_stride'] = int(cfg['predict_stride'])
         if cfg['predict_stride'] < 1:
             raise ValueError(f'predict_stride {cfg["predict_stride"]}: at least 1 (or null: half the trained depth)')
+    if not isinstance(cfg['predict_regions'], bool):
+        raise ValueError(f'predict_regions {cfg["predict_regions"]!r}: true or false')
+    if (cfg['predict_regions'] or cfg['phase'] == 'score') and cfg['dataset_name'] != 'BraTS':
+        raise ValueError(f'region scores (predict_regions, phase score) are defined for dataset_name BraTS only, not {cfg["dataset_name"]!r}')
     return cfg
+
+
+def region_csv_header():
+    return 'subj_id,' + ','.join(f'{col}_{name}' for col, _ in REGION_CSV_KEYS for name, _ in BRATS_REGIONS)
+
+
+def write_region_csv(path, subj, scores):
+    """predict_regions.csv: `subj_id,dice_wt,dice_tc,dice_et,sens_wt,...,spec_et,hd95_wt,hd95_tc,hd95_et`, one row per subject, floats written
+    with repr; scores: {key: (n, 3) float64} of `region_scores`.  -> the per-region means {'dice_wt': ..., ...} over the subjects that have a
+    value (NaN = no ground truth; NaN if none has one)."""
+    cols = [(f'{col}_{name}', scores[key][:, r].tolist()) for col, key in REGION_CSV_KEYS for r, (name, _) in enumerate(BRATS_REGIONS)]
+    with open(path, 'w') as f:
+        f.write(region_csv_header() + '\n')
+        for i, sid in enumerate(subj):
+            f.write(sid + ',' + ','.join(repr(v[i]) for _, v in cols) + '\n')
+    means = {}
+    for name, v in cols:
+        have = [x for x in v if x == x]
+        means[name] = float(np.mean(have)) if have else float('nan')
+    return means
 
 
 def parse_argv(argv):
@@ -142,12 +172,15 @@ class Run3D:
         ds = data.trainLoader.dataset
         H, W, _ = ds.store.shape
         self.input_shape = (H, W, ds.crop()[1])
+        self.start_epoch = -1
+        self.best_dice = -1.0
+        if cfg['phase'] == 'score':            # scores label volumes that are already written: no model, no optimizer, no checkpoint
+            self.model = self.optimizer = None
+            return
         M = len(cfg['contrast_list'])
         net = NVNet3D if cfg['model_name'] == 'NVNet3D' else UNet3D
         self.model = net(self.input_shape, M, 3, cfg['init_channels'], p=cfg['p']).to(dev)
         self.optimizer = ArenaAdam(self.model.parameters(), lr=cfg['lr'], weight_decay=cfg['weight_decay'], used=list(self.model.parameters()))
-        self.start_epoch = -1
-        self.best_dice = -1.0
         if cfg['continue_train'] or cfg['phase'] in ('test', 'predict'):
             self._load(cfg['ckpt_name'] or (last_epoch_checkpoint(cfg['ckpt_path']) if cfg['phase'] == 'train' else 'model_best.pth.tar'))
         if cfg['phase'] == 'train':
@@ -281,14 +314,18 @@ class Run3D:
         """whole-volume sliding-window prediction (model3d.predict_volumes) of every subject the `set_` loader serves (None: `predict_set`):
         writes <ckpt_path>/result_<set>/<subj_id>_seg.npy -- uint8 (H, W, D), the store's own geometry and labels (BraTS: 0 / 1 / 2 / 4) -- and
         result_<set>/predict.csv with a header and one `subj_id,dice,iou` row per subject (the reference's Dice / IoU over the FULL depth);
-        returns their means.  One D2H copy of the labels per batch, one of all counts at the end; no window syncs with the host."""
+        returns their means.  One D2H copy of the labels per batch, one of all counts at the end; no window syncs with the host.
+        `predict_regions: true` also scores every batch by BraTS region on the labels it holds on the device (surfdist.region_scores; one more small
+        D2H copy per batch), writes result_<set>/predict_regions.csv (`write_region_csv`) and adds the per-region means to the returned stat."""
         cfg = self.config
         set_ = cfg['predict_set'] if set_ is None else set_
         out_dir = os.path.join(cfg['ckpt_path'], f'result_{set_}')
         os.makedirs(out_dir, exist_ok=True)
-        subj, counts = [], []
+        subj, counts, regions = [], [], []
         for res in predict_volumes(self.model, self.loaders[set_], stride=cfg['predict_stride'], flip=cfg['predict_flip'],
                                    limit=cfg['max_batches'] or None):
+            if cfg['predict_regions']:
+                regions.append(region_scores(res['labels'], res['target_ptrs']))
             labels = res['labels'].cpu().numpy()
             for i, sid in enumerate(res['subj_id']):
                 np.save(os.path.join(out_dir, f'{sid}_seg.npy'), labels[i])
@@ -302,7 +339,44 @@ class Run3D:
             for sid, d, i in zip(subj, met['dice'].tolist(), met['iou'].tolist()):
                 f.write(f'{sid},{d!r},{i!r}\n')
         stat = {'dice': float(met['dice'].mean()), 'iou': float(met['iou'].mean()), 'n': len(subj)}
+        if cfg['predict_regions']:
+            stat.update(write_region_csv(os.path.join(out_dir, 'predict_regions.csv'), subj,
+                                         {k: torch.cat([r[k] for r in regions]) for k in SCORE_KEYS}))
         self.log(f'predict {set_}: {len(subj)} volumes under {out_dir}, dice {stat["dice"]:.4f}, iou {stat["iou"]:.4f}')
+        return stat
+
+    def score(self, set_=None):
+        """region scores of the label volumes ALREADY under <ckpt_path>/result_<set>/ (`<subj_id>_seg.npy`, uint8 (H, W, D) in the store's geometry,
+        as `predict` writes them) against the store's ground truth: writes result_<set>/predict_regions.csv and returns the per-region means.
+        Every subject the `set_` loader serves must have its file; a missing file, a wrong shape or a wrong dtype raises ValueError naming it."""
+        cfg = self.config
+        set_ = cfg['predict_set'] if set_ is None else set_
+        out_dir = os.path.join(cfg['ckpt_path'], f'result_{set_}')
+        loader = self.loaders[set_]
+        shape = tuple(loader.dataset.store.shape)
+        subj, regions = [], []
+        for _, _, metas in loader.plain_plan(cfg['max_batches'] or None):
+            vols = []
+            for m in metas:
+                fn = os.path.join(out_dir, f'{m[0]}_seg.npy')
+                if not os.path.isfile(fn):
+                    raise ValueError(f'{fn}: no such label volume (phase predict writes it)')
+                try:
+                    v = np.load(fn, allow_pickle=False)
+                except Exception as e:
+                    raise ValueError(f'{fn}: not a readable .npy file ({e})') from e
+                if v.dtype != np.uint8 or tuple(v.shape) != shape:
+                    raise ValueError(f'{fn}: a uint8 {shape} label volume is wanted, got {v.dtype} {tuple(v.shape)}')
+                vols.append(torch.from_numpy(np.ascontiguousarray(v)))
+            labels = torch.stack(vols).to(self.device)
+            ptrs = torch.tensor([int(m[4]) for m in metas], dtype=torch.int64).to(self.device)
+            regions.append(region_scores(labels, ptrs))
+            subj += [m[0] for m in metas]
+        if not subj:
+            raise RuntimeError(f'score({set_!r}): the loader serves no subject')
+        stat = write_region_csv(os.path.join(out_dir, 'predict_regions.csv'), subj, {k: torch.cat([r[k] for r in regions]) for k in SCORE_KEYS})
+        stat['n'] = len(subj)
+        self.log(f'score {set_}: {len(subj)} volumes under {out_dir}, ' + ', '.join(f'{k} {v:.4f}' for k, v in stat.items() if k != 'n'))
         return stat
 
 
@@ -315,6 +389,8 @@ def main(argv=None):
         run.train()
     elif run.config['phase'] == 'predict':
         print(run.predict())
+    elif run.config['phase'] == 'score':
+        print(run.score())
     else:
         print(run.evaluate('test'))
     return run
