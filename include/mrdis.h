@@ -562,7 +562,8 @@ int mrdis_sumsq_finite(const float* g, long long n, float* out, void* workspace,
  * there, :273-278), with max_norm = 0 the pair only gates.
  * step_count / step_state: bias correction uses the 1-based host `step_count`, or -- when step_state (device float[2]) is
  * given -- a device-side counter: [0] = steps applied (incremented by this call unless it is skipped), [1] = steps skipped
- * as non-finite; a skipped step does not advance the bias correction.
+ * as non-finite; a skipped step does not advance the bias correction.  Either way 1 - beta^t is formed on the device: the
+ * same count from the host or from step_state gives the same bits.
  * gates (n_gates <= 32): HOST arrays gate_ranges[2k], [2k+1] = index range [lo, hi) of the arena, gate_flag_index[k] = entry
  * of the DEVICE array gate_flags that gates it: a range whose flag is 0 is left untouched (torch's Adam skips parameters
  * whose grad is None: a decoder whose modality is absent from the whole batch).

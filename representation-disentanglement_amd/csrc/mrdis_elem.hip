@@ -1835,7 +1835,7 @@ __global__ void adam_advance_kernel(float* __restrict__ step_state, const float*
     }
 }
 __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, float* __restrict__ vmax,
-                            long long n, float lr, float b1, float b2, float eps, float wd, float bc1, float sbc2,
+                            long long n, float lr, float b1, float b2, float eps, float wd, float host_step,
                             const float* __restrict__ norm_finite, float max_norm, float gscale,
                             const float* __restrict__ step_state, const float* __restrict__ gate_flags, AdamGates gates,
                             const float* __restrict__ gate_steps, int n_flags) {
@@ -1848,14 +1848,13 @@ __global__ void adam_kernel(float* __restrict__ p, const float* __restrict__ g, 
             coef = gscale * (cc < 1.f ? cc : 1.f);
         }
     }
-    if (step_state) {                                           // bias corrections from the device-side step counter
-        const float t = step_state[0];
-        bc1 = 1.f - powf(b1, t); sbc2 = sqrtf(1.f - powf(b2, t));
-    }
-    const float step0 = lr / bc1, sbc20 = sbc2;
+    // bias corrections from the device-side step counter or the caller's count: formed HERE either way, so that both give the same bits (the host's
+    // powf is not the device's: with the corrections formed on the host, p differed in its last bit in ~1 % of the elements)
+    const float t = step_state ? step_state[0] : host_step;
+    const float bc1 = 1.f - powf(b1, t), sbc20 = sqrtf(1.f - powf(b2, t));
+    const float step0 = lr / bc1;
     EW_LOOP(n) {
-        float step = step0;
-        sbc2 = sbc20;
+        float step = step0, sbc2 = sbc20;
         if (gate_flags) {
             bool off = false;
             int gk = -1;
@@ -1889,17 +1888,13 @@ extern "C" int mrdis_adam_amsgrad_step(float* p, const float* g, float* m, float
     AdamGates gates{};
     gates.n = n_gates;
     for (int k = 0; k < n_gates; ++k) { gates.lo[k] = gate_ranges[2 * k]; gates.hi[k] = gate_ranges[2 * k + 1]; gates.flag[k] = gate_flag_index[k]; }
-    float bc1 = 1.f, sbc2 = 1.f;
     if (step_state) {
         MRDIS_LAUNCH(adam_advance_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, step_state, norm_finite,
                            gate_steps, n_gates > 0 ? gate_flags : (const float*)nullptr, n_flags, beta1, beta2);
         MRDIS_CHECK_LAUNCH();
-    } else {
-        bc1 = 1.f - powf(beta1, (float)step_count);
-        sbc2 = sqrtf(1.f - powf(beta2, (float)step_count));
     }
     MRDIS_LAUNCH(adam_kernel, dim3(ew_blocks(n)), dim3(256), 0, (hipStream_t)stream, p, g, m, v, vmax, n, lr, beta1, beta2, eps,
-                       weight_decay, bc1, sbc2, norm_finite, max_norm, grad_scale, (const float*)step_state,
+                       weight_decay, (float)step_count, norm_finite, max_norm, grad_scale, (const float*)step_state,
                        n_gates > 0 ? gate_flags : (const float*)nullptr, gates, (const float*)gate_steps, n_flags);
     MRDIS_CHECK_LAUNCH();
     return MRDIS_OK;
