@@ -544,6 +544,32 @@ int mrdis_edt_sq(const unsigned char* src, const unsigned char* src_masks, int S
 int mrdis_surface_hist(const unsigned char* flags, int R, int* hist, long long bins, void* workspace, size_t workspace_bytes, int B, int H,
                        int W, int D, void* stream);
 
+/* ---- connected components of label volumes and the clean-up rules built on them (csrc/mrdis_cc.hip).  Integer arithmetic throughout: exact,
+ * and the same bits from run to run.  Volumes are (B, H, W, D) uint8, D contiguous, as mrdis_seg_label_volume writes them.  A voxel is
+ * FOREGROUND iff its label l is at most 7 and bit l of fg_mask is set (bit 0 must be clear, some bit of 1 .. 7 set, else MRDIS_EINVAL); every
+ * other voxel, values above 7 included, is background and is never joined to anything.  connectivity: 6 (faces), 18 (faces and edges) or 26
+ * (faces, edges and corners), else MRDIS_EINVAL.  Components never cross a sample and never wrap from the end of a D line, a W row or an H
+ * plane into the start of the next.  B in 1 .. 65535, each of H, W, D in 1 .. 1024, H W D < 2^31: anything else returns MRDIS_EUNSUPPORTED
+ * (checked before every other argument).
+ * mrdis_cc_label: comp, size (B, H, W, D) int32, 4-byte aligned, every element written.  comp = -1 on background, on foreground the SMALLEST
+ *   in-sample flat index (h W + w) D + d of the voxel's component: a canonical value, independent of scheduling.  size = the component's voxel
+ *   count at its root voxel (where comp equals the voxel's own index), 0 everywhere else.  Block-local union-find in LDS over tiles of
+ *   4 x 4 x 64 voxels, a lock-free merge of the tile faces (find both roots, atomicMin the larger root's parent; no workgroup waits for
+ *   another), a compress-and-count pass: THREE launches whatever B, shape and content, each counted as "cclabel"; no host sync.
+ * mrdis_cc_clean: the rules of postproc.clean_labels -- THIS PACKAGE'S CONVENTION -- on labels and the comp / size mrdis_cc_label made of them.
+ *   (1) a component is kept iff its size >= min_voxels; with keep_largest = 1 only the largest component of the sample is a candidate (a size
+ *   tie goes to the smaller root index) and it is kept iff its size >= min_voxels.  Voxels of components that are not kept become 0,
+ *   background voxels pass through unchanged.  (2) n = the voxels of the sample whose label then equals et_label: if et_min_voxels > 0 and
+ *   0 < n < et_min_voxels they become et_replace.  out (B, H, W, D) uint8 and stats (B, 6) int32 = { components found, components kept,
+ *   foreground voxels, voxels removed, n, replaced (0 | 1) } are written whole (the kernels clear stats).  et_label, et_replace in 0 .. 7,
+ *   thresholds >= 0, keep_largest 0 | 1, else MRDIS_EINVAL.  workspace: mrdis_cc_clean_workspace(B) bytes, 8-byte aligned.  Four launches
+ *   whatever the arguments; one count of "ccclean" per call.                                                                              */
+int mrdis_cc_label(const unsigned char* labels, int fg_mask, int connectivity, int* comp, int* size, int B, int H, int W, int D, void* stream);
+size_t mrdis_cc_clean_workspace(int B);
+int mrdis_cc_clean(const unsigned char* labels, const int* comp, const int* size, int min_voxels, int keep_largest, int et_label,
+                   int et_min_voxels, int et_replace, unsigned char* out, int* stats, void* workspace, size_t workspace_bytes, int B, int H,
+                   int W, int D, void* stream);
+
 /* ---- max_pool2d(kernel k x k, stride k): model.py:3448-3451 ---------------- */
 int mrdis_maxpool_fwd(const float* x, int ldx, float* y, int32_t* argmax, int N, int H, int W, int C,
                       int k, void* stream);

@@ -8,6 +8,9 @@ the command line, then key=value overrides), trains with a validation pass per e
     python main_3d.py cfg3d.yaml phase=predict   # <ckpt_path>/result_test/<subj_id>_seg.npy + predict.csv
     python main_3d.py cfg3d.yaml phase=predict predict_regions=true     # + predict_regions.csv: Dice, sensitivity, specificity, HD95 of WT / TC / ET
     python main_3d.py cfg3d.yaml phase=score     # the same csv for label volumes already under result_test/ (no model is built or loaded)
+    python main_3d.py cfg3d.yaml phase=predict predict_post=true post_min_voxels=50     # + post/<subj_id>_seg.npy cleaned by connected components, post/postprocess.csv
+    python main_3d.py cfg3d.yaml phase=postprocess post_keep=largest    # the same post/ files from label volumes already under result_test/ (no model)
+    python main_3d.py cfg3d.yaml phase=score score_subdir=post          # region scores of the cleaned volumes
 """
 import os
 import sys

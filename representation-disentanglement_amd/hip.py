@@ -104,6 +104,9 @@ _SIGS = {
     'mrdis_edt_workspace': (_Z, [_I, _I, _I, _I, _I]),
     'mrdis_edt_sq': (_I, [_P, _c.c_char_p, _I, _P, _P, _Z, _I, _I, _I, _I, _P]),
     'mrdis_surface_hist': (_I, [_P, _I, _P, _L, _P, _Z, _I, _I, _I, _I, _P]),
+    'mrdis_cc_label': (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
+    'mrdis_cc_clean_workspace': (_Z, [_I]),
+    'mrdis_cc_clean': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_bwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_sumsq_workspace': (_Z, []),
@@ -230,6 +233,9 @@ FUSE_FAMILIES = ('fuse',)
 # distance-transform pass (three per mrdis_edt_sq call, two per mrdis_surface_hist call), 'surfhist' one per mrdis_surface_hist call (its last
 # pass, which adds into the histogram instead of storing distances).  None depends on the batch size.
 SURFDIST_FAMILIES = ('regsurf', 'edt', 'surfhist')
+# connected components of label volumes and their clean-up (csrc/mrdis_cc.hip): 'cclabel' counts one per LAUNCH of a labelling pass (three per
+# mrdis_cc_label call, whatever B, shape and content), 'ccclean' one per mrdis_cc_clean call.
+CC_FAMILIES = ('cclabel', 'ccclean')
 # the dispatch choices of the statistics, norm and resize entry points (csrc/mrdis_elem.hip), host-side counts only: which partial-sum kernel a
 # statistics pass took ('stat_vec' | 'stat_scalar' | 'stat_interp': one per pass), the route of mrdis_instnorm_spade_bwd_up2 (one per call), the
 # kernel of mrdis_bilinear_fwd / _bwd (one per call), and 'elem_v1': an element-wise pass that took its one-channel-per-thread instantiation.
@@ -243,6 +249,9 @@ EDT_FAR = 1 << 30                 # include/mrdis.h MRDIS_EDT_FAR
 EDT_MAX_SRC = 8                   # include/mrdis.h MRDIS_EDT_MAX_SRC
 EDT_MAX_EXTENT = 1024             # each of H, W, D of a distance transform
 SURF_MAX_REGIONS = 4              # include/mrdis.h MRDIS_SURF_MAX_REGIONS
+CC_MAX_EXTENT = 1024              # each of H, W, D of a connected-component labelling
+CC_LABEL_LAUNCHES = 3             # kernel launches of one mrdis_cc_label call
+CC_CONNECTIVITIES = (6, 18, 26)
 
 
 def stream_fill(t, value=0.0):
@@ -272,7 +281,7 @@ def launch_counts(reset=False, elem=False):
     elem=True adds ELEM_FAMILIES: they count dispatch choices of passes that run beside almost every counted kernel (the statistics in front of a fused
     SPADE convolution, say), so callers that assert "this family and no other" over the whole dictionary only see them when they ask."""
     lib = load()
-    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES
+    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES
     out = {f: int(lib.mrdis_launch_count(f.encode())) for f in fams + (ELEM_FAMILIES if elem else ())}
     if reset:
         lib.mrdis_launch_count_reset()
@@ -1355,6 +1364,48 @@ def surface_hist(flags, R):
     ws = torch.empty(nws, dtype=torch.uint8, device=flags.device)    # (1.29 GB for four BraTS subjects: not kept in the binding's grow-only scratch)
     _chk(lib.mrdis_surface_hist(_ptr(flags), int(R), _ptr(hist), bins, _ptr(ws), nws, B, H, W, D, _stream()), 'surface_hist')
     return hist
+
+
+def _cc_geometry(B, H, W, D, what):
+    if not (1 <= B <= 65535 and all(1 <= n <= CC_MAX_EXTENT for n in (H, W, D)) and H * W * D < (1 << 31)):
+        raise MrdisError(f'{what}: unsupported geometry {(B, H, W, D)}: B in 1 .. 65535, each of H, W, D in 1 .. {CC_MAX_EXTENT}, H W D < 2^31')
+
+
+def cc_label(labels, fg_mask, connectivity=26):
+    """-> (comp, size), both (B, H, W, D) int32 on the device (include/mrdis.h mrdis_cc_label).  labels (B, H, W, D) uint8 contiguous; a voxel
+    is foreground iff its label l <= 7 and bit l of `fg_mask` (2 .. 254, bit 0 clear) is set.  comp: -1 on background, else the smallest
+    in-sample flat index of the voxel's component; size: the component's voxel count at its root voxel, 0 elsewhere.  Three launches."""
+    lib = load()
+    B, H, W, D = _volume_u8(labels, 'cc_label: labels')
+    _cc_geometry(B, H, W, D, 'cc_label')
+    fg_mask, connectivity = int(fg_mask), int(connectivity)
+    if not 2 <= fg_mask <= 255 or fg_mask & 1 or connectivity not in CC_CONNECTIVITIES:
+        raise MrdisError(f'cc_label: fg_mask in 2 .. 254 with bit 0 clear and connectivity in {CC_CONNECTIVITIES}, got {fg_mask} and {connectivity}')
+    comp = torch.empty((B, H, W, D), dtype=torch.int32, device=labels.device)
+    size = torch.empty((B, H, W, D), dtype=torch.int32, device=labels.device)
+    _chk(lib.mrdis_cc_label(_ptr(labels), fg_mask, connectivity, _ptr(comp), _ptr(size), B, H, W, D, _stream()), 'cc_label')
+    return comp, size
+
+
+def cc_clean(labels, comp, size, min_voxels=0, keep_largest=False, et_label=4, et_min_voxels=0, et_replace=1):
+    """-> (cleaned (B, H, W, D) uint8, stats (B, 6) int32), both on the device (include/mrdis.h mrdis_cc_clean): the keep rule and the ET rule
+    of `postproc.clean_labels` on `labels` and the (comp, size) `cc_label` made of them.  Four launches."""
+    lib = load()
+    B, H, W, D = _volume_u8(labels, 'cc_clean: labels')
+    _cc_geometry(B, H, W, D, 'cc_clean')
+    for t, what in ((comp, 'comp'), (size, 'size')):
+        if t.dtype != torch.int32 or tuple(t.shape) != (B, H, W, D) or not t.is_contiguous() or t.device != labels.device:
+            raise MrdisError(f'cc_clean: {what} must be a contiguous int32 {(B, H, W, D)} tensor on {labels.device}, got {t.dtype} {tuple(t.shape)}')
+    args = [int(min_voxels), int(bool(keep_largest)), int(et_label), int(et_min_voxels), int(et_replace)]
+    if args[0] < 0 or args[3] < 0 or not 0 <= args[2] <= 7 or not 0 <= args[4] <= 7:
+        raise MrdisError(f'cc_clean: thresholds >= 0 and labels in 0 .. 7, got min_voxels={min_voxels} et_label={et_label} '
+                         f'et_min_voxels={et_min_voxels} et_replace={et_replace}')
+    out = torch.empty((B, H, W, D), dtype=torch.uint8, device=labels.device)
+    stats = torch.empty((B, 6), dtype=torch.int32, device=labels.device)
+    nws = _ws_bytes(lib.mrdis_cc_clean_workspace, B)
+    ws = _ws(nws, labels.device)
+    _chk(lib.mrdis_cc_clean(_ptr(labels), _ptr(comp), _ptr(size), *args, _ptr(out), _ptr(stats), _ptr(ws), nws, B, H, W, D, _stream()), 'cc_clean')
+    return out, stats
 
 
 def synth_accum(recons, centres, acc, cnt, c_lo, c_hi):

@@ -10,7 +10,10 @@ Dice / IoU (`compute_segmentation_metrics`, util.py:946-992) from the integer co
 highest validation Dice.  `phase: predict` loads it and writes one label volume per subject over the FULL depth (sliding window,
 model3d.predict_volumes) with its Dice / IoU; with `predict_regions: true` also the BraTS region scores (Dice, sensitivity, specificity, HD95
 of WT / TC / ET: surfdist.region_scores) in predict_regions.csv.  `phase: score` writes that file for label volumes that already lie under
-result_<predict_set>/ -- predicted earlier or post-processed elsewhere -- without building or loading a model.
+result_<predict_set>/ -- predicted earlier or post-processed elsewhere -- without building or loading a model.  `predict_post: true` also
+writes, during `phase: predict`, the label volumes cleaned by connected components (postproc.clean_labels: small or non-largest components
+removed, a tiny enhancing tumour relabelled) under result_<predict_set>/post/; `phase: postprocess` makes the same files from label volumes
+that are already written, again without a model, and `score_subdir: post` lets `phase: score` read and write there.
 
 A checkpoint also carries the host and device RNG states (np.random, torch default, the torch device generator, the loaders' own generator
 if any), written after the epoch's validation pass: `continue_train` then continues exactly where the run stopped -- the shuffles, augmentation
@@ -30,6 +33,7 @@ import yaml
 
 from . import hip
 from .data3d import VolumeData3D
+from .postproc import CONNECTIVITIES, KEEP_MODES, STATS_COLUMNS, clean_labels, write_stats_csv
 from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, predict_volumes, seg_metrics_from_counts
 from .surfdist import BRATS_REGIONS, SCORE_KEYS, region_scores
 from .train import parse_overrides, save_config_file, save_result_stat
@@ -38,6 +42,7 @@ from .trainer import ArenaAdam, load_checkpoint_model, save_checkpoint
 DEFAULT_CONFIG_3D = {
     'phase': 'train',                  # train | test (load model_best.pth.tar, print the test-set stat) | predict (load it, write whole-volume label maps)
                                        # | score (region scores of the label maps already under result_<predict_set>/: no model)
+                                       # | postprocess (clean the label maps already under result_<predict_set>/ into post/: no model)
     'dataset_name': 'BraTS', 'data_path': '../data/', 'norm_type': 'z-score', 'fold': 0,
     'contrast_list': ['T1', 'T1c', 'T2', 'T2_FLAIR'], 'batch_size': 4,
     'model_name': 'NVNet3D',           # NVNet3D | UNet3D (Dice-only objective)
@@ -54,8 +59,17 @@ DEFAULT_CONFIG_3D = {
     'predict_stride': None,            # depth stride of the sliding window; None: half the trained depth
     'predict_flip': False,             # also average the prediction of the H-flipped input
     'predict_regions': False,          # phase predict: also write predict_regions.csv (Dice, sensitivity, specificity, HD95 of WT / TC / ET; BraTS only)
+    'predict_post': False,             # phase predict: also write the cleaned label maps under result_<predict_set>/post/ (postproc.clean_labels)
+    'post_connectivity': 26,           # connectivity of the components: 6 | 18 | 26
+    'post_min_voxels': 0,              # components of fewer voxels are removed
+    'post_keep': 'all',                # all | largest (only the largest component of a subject is a candidate)
+    'post_et_min_voxels': 0,           # > 0: an enhancing tumour (label 4) of fewer voxels becomes necrotic core (label 1); BraTS only
+    'score_subdir': '',                # phase score: the sub-directory of result_<predict_set>/ it reads and writes ('post': the cleaned maps)
 }
-PHASES = ('train', 'test', 'predict', 'score')
+PHASES = ('train', 'test', 'predict', 'score', 'postprocess')
+NO_MODEL_PHASES = ('score', 'postprocess')
+POST_SUBDIR = 'post'
+POST_FG = (1, 2, 3, 4, 5, 6, 7)        # every non-zero label is foreground
 REGION_CSV_KEYS = (('dice', 'dice'), ('sens', 'sensitivity'), ('spec', 'specificity'), ('hd95', 'hd95'))      # csv column prefix, region_scores key
 MODEL_NAMES = ('NVNet3D', 'UNet3D')
 LR_SCHEDULES = ('none', 'poly')
@@ -91,6 +105,20 @@ def load_config3d(path=None, overrides=None):
         raise ValueError(f'predict_regions {cfg["predict_regions"]!r}: true or false')
     if (cfg['predict_regions'] or cfg['phase'] == 'score') and cfg['dataset_name'] != 'BraTS':
         raise ValueError(f'region scores (predict_regions, phase score) are defined for dataset_name BraTS only, not {cfg["dataset_name"]!r}')
+    if not isinstance(cfg['predict_post'], bool):
+        raise ValueError(f'predict_post {cfg["predict_post"]!r}: true or false')
+    if isinstance(cfg['post_connectivity'], bool) or cfg['post_connectivity'] not in CONNECTIVITIES:
+        raise ValueError(f'post_connectivity {cfg["post_connectivity"]!r}: one of {CONNECTIVITIES}')
+    if cfg['post_keep'] not in KEEP_MODES:
+        raise ValueError(f'post_keep {cfg["post_keep"]!r}: one of {KEEP_MODES}')
+    for k in ('post_min_voxels', 'post_et_min_voxels'):
+        if isinstance(cfg[k], bool) or not isinstance(cfg[k], int) or cfg[k] < 0:
+            raise ValueError(f'{k} {cfg[k]!r}: an integer >= 0')
+    if cfg['post_et_min_voxels'] > 0 and cfg['dataset_name'] != 'BraTS':
+        raise ValueError(f'post_et_min_voxels > 0 (the enhancing-tumour rule) is defined for dataset_name BraTS only, not {cfg["dataset_name"]!r}')
+    sub = cfg['score_subdir']
+    if not isinstance(sub, str) or os.path.isabs(sub) or any(p in ('.', '..') for p in sub.replace('\\', '/').split('/')):
+        raise ValueError(f'score_subdir {sub!r}: a relative sub-directory of result_<predict_set>/ (or the empty string)')
     return cfg
 
 
@@ -174,7 +202,7 @@ class Run3D:
         self.input_shape = (H, W, ds.crop()[1])
         self.start_epoch = -1
         self.best_dice = -1.0
-        if cfg['phase'] == 'score':            # scores label volumes that are already written: no model, no optimizer, no checkpoint
+        if cfg['phase'] in NO_MODEL_PHASES:    # works on label volumes that are already written: no model, no optimizer, no checkpoint
             self.model = self.optimizer = None
             return
         M = len(cfg['contrast_list'])
@@ -316,16 +344,23 @@ class Run3D:
         result_<set>/predict.csv with a header and one `subj_id,dice,iou` row per subject (the reference's Dice / IoU over the FULL depth);
         returns their means.  One D2H copy of the labels per batch, one of all counts at the end; no window syncs with the host.
         `predict_regions: true` also scores every batch by BraTS region on the labels it holds on the device (surfdist.region_scores; one more small
-        D2H copy per batch), writes result_<set>/predict_regions.csv (`write_region_csv`) and adds the per-region means to the returned stat."""
+        D2H copy per batch), writes result_<set>/predict_regions.csv (`write_region_csv`) and adds the per-region means to the returned stat.
+        `predict_post: true` also cleans the labels of every batch on the device (`clean`), writes them as result_<set>/post/<subj_id>_seg.npy
+        with post/postprocess.csv (and, with `predict_regions`, post/predict_regions.csv: the region scores of the cleaned labels), and adds
+        'post_<column>' means to the returned stat: one more D2H copy of the cleaned labels and one small copy of the stats per batch.  The raw
+        files are written exactly as without it."""
         cfg = self.config
         set_ = cfg['predict_set'] if set_ is None else set_
         out_dir = os.path.join(cfg['ckpt_path'], f'result_{set_}')
         os.makedirs(out_dir, exist_ok=True)
         subj, counts, regions = [], [], []
+        post = _PostWriter(out_dir, cfg['predict_regions']) if cfg['predict_post'] else None
         for res in predict_volumes(self.model, self.loaders[set_], stride=cfg['predict_stride'], flip=cfg['predict_flip'],
                                    limit=cfg['max_batches'] or None):
             if cfg['predict_regions']:
                 regions.append(region_scores(res['labels'], res['target_ptrs']))
+            if post is not None:
+                post.add(res['subj_id'], *self.clean(res['labels']), res['target_ptrs'])
             labels = res['labels'].cpu().numpy()
             for i, sid in enumerate(res['subj_id']):
                 np.save(os.path.join(out_dir, f'{sid}_seg.npy'), labels[i])
@@ -342,23 +377,29 @@ class Run3D:
         if cfg['predict_regions']:
             stat.update(write_region_csv(os.path.join(out_dir, 'predict_regions.csv'), subj,
                                          {k: torch.cat([r[k] for r in regions]) for k in SCORE_KEYS}))
+        if post is not None:
+            stat.update({f'post_{k}': v for k, v in post.finish().items()})
         self.log(f'predict {set_}: {len(subj)} volumes under {out_dir}, dice {stat["dice"]:.4f}, iou {stat["iou"]:.4f}')
         return stat
 
-    def score(self, set_=None):
-        """region scores of the label volumes ALREADY under <ckpt_path>/result_<set>/ (`<subj_id>_seg.npy`, uint8 (H, W, D) in the store's geometry,
-        as `predict` writes them) against the store's ground truth: writes result_<set>/predict_regions.csv and returns the per-region means.
-        Every subject the `set_` loader serves must have its file; a missing file, a wrong shape or a wrong dtype raises ValueError naming it."""
+    def clean(self, labels):
+        """(cleaned, stats) of a batch of label volumes on the device under the `post_*` keys (postproc.clean_labels; every non-zero label
+        is foreground, the ET rule relabels BraTS's 4 as 1)"""
         cfg = self.config
-        set_ = cfg['predict_set'] if set_ is None else set_
-        out_dir = os.path.join(cfg['ckpt_path'], f'result_{set_}')
+        return clean_labels(labels, fg=POST_FG, connectivity=cfg['post_connectivity'], min_voxels=cfg['post_min_voxels'], keep=cfg['post_keep'],
+                            et_label=4, et_min_voxels=cfg['post_et_min_voxels'], et_replace=1)
+
+    def _stored_labels(self, in_dir, set_):
+        """the label volumes ALREADY under `in_dir` (`<subj_id>_seg.npy`, uint8 (H, W, D) in the store's geometry), batch by batch in the
+        loader's plain order: yields (subject ids, labels (B, H, W, D) on the device, ground-truth pointer table).  A missing file, a wrong
+        shape or a wrong dtype raises ValueError naming it."""
+        cfg = self.config
         loader = self.loaders[set_]
         shape = tuple(loader.dataset.store.shape)
-        subj, regions = [], []
         for _, _, metas in loader.plain_plan(cfg['max_batches'] or None):
             vols = []
             for m in metas:
-                fn = os.path.join(out_dir, f'{m[0]}_seg.npy')
+                fn = os.path.join(in_dir, f'{m[0]}_seg.npy')
                 if not os.path.isfile(fn):
                     raise ValueError(f'{fn}: no such label volume (phase predict writes it)')
                 try:
@@ -370,13 +411,75 @@ class Run3D:
                 vols.append(torch.from_numpy(np.ascontiguousarray(v)))
             labels = torch.stack(vols).to(self.device)
             ptrs = torch.tensor([int(m[4]) for m in metas], dtype=torch.int64).to(self.device)
+            yield [m[0] for m in metas], labels, ptrs
+
+    def postprocess(self, set_=None):
+        """cleans the label volumes ALREADY under <ckpt_path>/result_<set>/ (as `predict` writes them; the checks of `score`) under the
+        `post_*` keys: writes result_<set>/post/<subj_id>_seg.npy and post/postprocess.csv, for BraTS also post/predict_regions.csv (the
+        region scores of the cleaned labels) -- the files `predict` writes with `predict_post: true`, byte for byte.  Returns the means of
+        the stats columns and, for BraTS, the per-region means."""
+        cfg = self.config
+        set_ = cfg['predict_set'] if set_ is None else set_
+        in_dir = os.path.join(cfg['ckpt_path'], f'result_{set_}')
+        post = None
+        for ids, labels, ptrs in self._stored_labels(in_dir, set_):
+            if post is None:
+                post = _PostWriter(in_dir, cfg['dataset_name'] == 'BraTS')
+            post.add(ids, *self.clean(labels), ptrs)
+        if post is None:
+            raise RuntimeError(f'postprocess({set_!r}): the loader serves no subject')
+        stat = post.finish()
+        stat['n'] = len(post.subj)
+        self.log(f'postprocess {set_}: {len(post.subj)} volumes under {post.out_dir}, ' + ', '.join(f'{k} {v:.4f}' for k, v in stat.items() if k != 'n'))
+        return stat
+
+    def score(self, set_=None):
+        """region scores of the label volumes ALREADY under <ckpt_path>/result_<set>/ (`<subj_id>_seg.npy`, uint8 (H, W, D) in the store's geometry,
+        as `predict` writes them) against the store's ground truth: writes result_<set>/predict_regions.csv and returns the per-region means.
+        Every subject the `set_` loader serves must have its file; a missing file, a wrong shape or a wrong dtype raises ValueError naming it.
+        With `score_subdir` the files are read and written under result_<set>/<score_subdir>/ instead ('post': the cleaned volumes)."""
+        cfg = self.config
+        set_ = cfg['predict_set'] if set_ is None else set_
+        out_dir = os.path.join(cfg['ckpt_path'], f'result_{set_}')
+        if cfg['score_subdir']:
+            out_dir = os.path.join(out_dir, cfg['score_subdir'])
+        subj, regions = [], []
+        for ids, labels, ptrs in self._stored_labels(out_dir, set_):
             regions.append(region_scores(labels, ptrs))
-            subj += [m[0] for m in metas]
+            subj += ids
         if not subj:
             raise RuntimeError(f'score({set_!r}): the loader serves no subject')
         stat = write_region_csv(os.path.join(out_dir, 'predict_regions.csv'), subj, {k: torch.cat([r[k] for r in regions]) for k in SCORE_KEYS})
         stat['n'] = len(subj)
         self.log(f'score {set_}: {len(subj)} volumes under {out_dir}, ' + ', '.join(f'{k} {v:.4f}' for k, v in stat.items() if k != 'n'))
+        return stat
+
+
+class _PostWriter:
+    """the files under result_<set>/post/: `add` takes a batch of cleaned labels and stats on the device (one D2H copy each, and with
+    `regions` their region scores), `finish` writes postprocess.csv (and predict_regions.csv) and returns the column (and region) means"""
+
+    def __init__(self, result_dir, regions):
+        self.out_dir = os.path.join(result_dir, POST_SUBDIR)
+        os.makedirs(self.out_dir, exist_ok=True)
+        self.subj, self.stats, self.regions = [], [], ([] if regions else None)
+
+    def add(self, ids, cleaned, stats, target_ptrs):
+        if self.regions is not None:
+            self.regions.append(region_scores(cleaned, target_ptrs))
+        vols = cleaned.cpu().numpy()
+        for i, sid in enumerate(ids):
+            np.save(os.path.join(self.out_dir, f'{sid}_seg.npy'), vols[i])
+        self.subj += list(ids)
+        self.stats.append(stats.cpu().numpy())
+
+    def finish(self):
+        rows = np.concatenate(self.stats)
+        write_stats_csv(os.path.join(self.out_dir, 'postprocess.csv'), self.subj, rows)
+        stat = {k: float(rows[:, i].mean()) for i, k in enumerate(STATS_COLUMNS)}
+        if self.regions is not None:
+            stat.update(write_region_csv(os.path.join(self.out_dir, 'predict_regions.csv'), self.subj,
+                                         {k: torch.cat([r[k] for r in self.regions]) for k in SCORE_KEYS}))
         return stat
 
 
@@ -391,6 +494,8 @@ def main(argv=None):
         print(run.predict())
     elif run.config['phase'] == 'score':
         print(run.score())
+    elif run.config['phase'] == 'postprocess':
+        print(run.postprocess())
     else:
         print(run.evaluate('test'))
     return run
