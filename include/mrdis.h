@@ -84,7 +84,7 @@ long long mrdis_get_option(const char* name);
  * "split6_c4" | "split6_c16" | "split6_wgrad16" | "split6_co4" | "split6_c3d" | "split6_w3d" | "split6_tap" (option split6: the 4 -> C kernel, the 32 -> 16 forward, its weight gradient, the
  * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "zsearch" (mrdis_cosine_top1); "conv2src" | "ana_act" (the others variants); "kl" | "avgpool" (the latent-code options); "chatt" | "symdiff" | "rgate" (the attention output decoders);
  * "direct3d" | "c3d16" | "wgrad3d" | "wgrad3d16" | "wino_wgrad3d" (the 3-D tap-table, 16-cout, generic and narrow weight-gradient kernels and the hybrid
- * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "volgather"; "loss3d" | "segcounts" (the fused 3-D objective, one count per forward and per backward call, and the segmentation counts); "segaccum" | "seglabels" (whole-volume prediction of the 3-D nets); "synthaccum" | "synthfinish" (whole-subject synthesis of the 2-D model, one count per call); "fuse" (mrdis_fuse_present_fwd / _bwd, one count per call);
+ * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "volgather"; "loss3d" | "segcounts" (the fused 3-D objective, one count per forward and per backward call, and the segmentation counts); "segaccum" | "seglabels" (whole-volume prediction of the 3-D nets); "synthaccum" | "synthfinish" (whole-subject synthesis of the 2-D model, one count per call); "seg2dlabels" | "seg2dfinish" (whole-subject segmentation by the 2-D model, one count per call); "fuse" (mrdis_fuse_present_fwd / _bwd, one count per call);
  * "stat_vec" | "stat_scalar" | "stat_interp" (the partial-sum kernel of a statistics pass), "spade_up2_onepass" | "spade_up2_twopass" (the route of
  * mrdis_instnorm_spade_bwd_up2, one per call), "bil_fwd_x2" | "bil_fwd_general", "bil_bwd_x2" | "bil_bwd_tight3" | "bil_bwd_tight5" | "bil_bwd_general"
  * (mrdis_bilinear_fwd / _bwd, one per call), "elem_v1" (an element-wise pass in its one-channel-per-thread form): dispatch choices, not launches;
@@ -480,6 +480,30 @@ int mrdis_seg_label_volume(const float* acc, const int* cover, const void* targe
 int mrdis_synth_accum(const float* const* srcs, int n_src, float* acc, int* cnt, int B, int C, int H, int W, int D, int s0, int c_lo, int c_hi,
                       void* stream);
 int mrdis_synth_finish(float* acc, const int* cnt, float* out, int D, int H, int W, float fill, void* stream);
+
+/* ---- whole-subject tumour segmentation by the 2-D model (csrc/mrdis_seg2d.hip; segment.segment_volumes): logits of a batch of consecutive
+ * centre slices -> label planes of one volume per missing-contrast pattern ("set") -> the store's (H, W, D) volumes.  The label rule is this
+ * package's own convention: the reference assembles no volume and never fuses for M > 1.
+ * mrdis_seg2d_label_planes: views: HOST array of n_sets * n_views device pointers, set-major, handed to the kernel by value; each a dense
+ *   channels-last (B, C, H, W) fp32 logit tensor (memory [B][H][W][C]) of B samples with CONSECUTIVE centres s0, s0 + 1, ...  flips: HOST array
+ *   of n_views codes, 0 none | 1 H | 2 W: view v is the prediction of an input flipped along that axis and is read at the mirrored pixel.
+ *   planes (n_sets, D, H, W) uint8: planes[s][s0 + r][h][w] = the label of pixel (h, w) of sample r of set s; exactly the bytes of planes
+ *   s0 .. s0 + B - 1 of every set are written, nothing else.
+ *     one view:  argmax_c y_c over the logits themselves (no exp), the lowest c on a tie;
+ *     two views: p_c = 0.5 (softmax(y^0)_c + softmax(y^1)_c), each softmax exp(y_c - max) / sum in fp32 (accurate expf, IEEE division, the sum
+ *                in increasing c); argmax_c p_c, the lowest c on a tie.
+ *   Class c is written as label c, a 3 as 4 if `relabel` (BraTS labels 0 / 1 / 2 / 4).  No atomics, one owner per byte: the same bits from run
+ *   to run.  2 <= C <= 4, 1 <= n_sets <= MRDIS_SEG2D_MAX_SETS, 1 <= n_views <= MRDIS_SEG2D_MAX_VIEWS, 0 <= s0, s0 + B <= D, H W < 2^31, flip
+ *   codes in 0 .. 2: anything else returns MRDIS_EINVAL before any launch.  The logits are read 16 bytes per lane when C == 4 and every view is
+ *   16-byte aligned, else 4 (a view that is not 4-byte aligned: MRDIS_EALIGN); the stores are coalesced along w.  ONE launch whatever n_sets,
+ *   counted as "seg2dlabels".
+ * mrdis_seg2d_finish: out[s][h][w][d] = planes[s][d][h][w], (n_sets, D, H, W) uint8 -> (n_sets, H, W, D) uint8, through LDS (both sides
+ *   coalesced for any D).  n_sets >= 1.  One launch whatever n_sets, counted as "seg2dfinish".                                          */
+#define MRDIS_SEG2D_MAX_SETS 16
+#define MRDIS_SEG2D_MAX_VIEWS 2
+int mrdis_seg2d_label_planes(const float* const* views, int n_sets, int n_views, const int* flips, unsigned char* planes, int B, int C, int H,
+                             int W, int D, int s0, int relabel, void* stream);
+int mrdis_seg2d_finish(const unsigned char* planes, unsigned char* out, int n_sets, int D, int H, int W, void* stream);
 
 /* ---- fusion of the anatomy maps over the contrasts a sample has (csrc/mrdis_fuse.hip; lambda_recon_y_fused).  The rule is this package's own
  * convention: the reference's `si_cat[mask == 1]` (model.py:3239-3258) never fuses and fails for M > 1.

@@ -11,7 +11,7 @@ import it through the `mrdis` alias at the repository root:
 Layout: csrc/ (hand-written HIP kernels + C ABI, include/mrdis.h), hip.py (ctypes
 binding), ops.py (autograd pairing + torch.ops.mrdis.*), model.py (mirror of the
 reference's module interface), trainer.py (train step, flat-arena Adam, gradient
-all-reduce), data.py / data3d.py (HBM-resident slice and volume loaders), train.py (the runnable main_missing.py-equivalent: epoch loop, scheduler, stat.csv, checkpoints), synth.py (whole-subject synthesis of missing contrasts: phase synthesize), surfdist.py (region scoring of label volumes: Dice, sensitivity, specificity, HD95), postproc.py (clean-up of label volumes by 3-D connected components), train3d.py (the same for the 3-D nets: main_3d.py).  No CPU fallback exists for the hot path.
+all-reduce), data.py / data3d.py (HBM-resident slice and volume loaders), train.py (the runnable main_missing.py-equivalent: epoch loop, scheduler, stat.csv, checkpoints), synth.py (whole-subject synthesis of missing contrasts: phase synthesize), segment.py (whole-subject tumour segmentation per missing-contrast pattern: phase segment), surfdist.py (region scoring of label volumes: Dice, sensitivity, specificity, HD95), postproc.py (clean-up of label volumes by 3-D connected components), train3d.py (the same for the 3-D nets: main_3d.py).  No CPU fallback exists for the hot path.
 """
 from . import hip, ops, model, model3d, trainer               # noqa: F401
 from .hip import MrdisError, MrdisLibraryError, LIB_PATH      # noqa: F401
@@ -28,6 +28,8 @@ from .data import VolumeStore, SliceDataset, BatchLoader, load_idx_list   # noqa
 from .data3d import VolumeStore3D, VolumeDataset3D, VolumeLoader3D, VolumeData3D, load_subj_list   # noqa: F401
 from .synth import synthesize_volumes, synth_plan, synth_source, synth_targets, SYNTH_BLOCKS   # noqa: F401,E402
 from . import synth   # noqa: F401,E402
+from . import segment   # noqa: F401,E402
+from .segment import segment_volumes, seg_patterns   # noqa: F401,E402
 from . import surfdist   # noqa: F401,E402
 from .surfdist import EDT_FAR, BRATS_REGIONS, edt3d_sq, region_scores, scores_from_counts, percentile_ranks, region_masks   # noqa: F401,E402
 from . import postproc   # noqa: F401,E402

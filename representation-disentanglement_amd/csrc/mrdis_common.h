@@ -63,6 +63,7 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
     X(LOSS3D, "loss3d") X(SEGCOUNTS, "segcounts") /* mrdis_loss3d.hip: one count per mrdis_nvnet_loss_fwd / _bwd call; one per mrdis_seg_counts call */ \
     X(SEGACCUM, "segaccum") X(SEGLABELS, "seglabels") /* mrdis_segvol.hip: one count per mrdis_seg_accum / mrdis_seg_label_volume call */ \
     X(SYNTHACCUM, "synthaccum") X(SYNTHFINISH, "synthfinish") /* mrdis_synth.hip: one count per mrdis_synth_accum / mrdis_synth_finish call */ \
+    X(SEG2DLABELS, "seg2dlabels") X(SEG2DFINISH, "seg2dfinish") /* mrdis_seg2d.hip: one count per mrdis_seg2d_label_planes / mrdis_seg2d_finish call */ \
     X(FUSE, "fuse") /* mrdis_fuse.hip: one count per mrdis_fuse_present_fwd / _bwd call */ \
     X(REGSURF, "regsurf") X(EDT, "edt") X(SURFHIST, "surfhist") /* mrdis_surfdist.hip: one count per mrdis_region_surfaces call; one per launch of a distance-transform pass; one per histogram pass (one per mrdis_surface_hist call) */ \
     X(CCLABEL, "cclabel") X(CCCLEAN, "ccclean") /* mrdis_cc.hip: one count per launch of a labelling pass (three per mrdis_cc_label call); one per mrdis_cc_clean call */ \

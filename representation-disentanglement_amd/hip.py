@@ -98,6 +98,8 @@ _SIGS = {
     'mrdis_seg_label_volume': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_synth_accum': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_synth_finish': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
+    'mrdis_seg2d_label_planes': (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'mrdis_seg2d_finish': (_I, [_P, _P, _I, _I, _I, _I, _P]),
     'mrdis_fuse_present_fwd': (_I, [_P, _P, _I, _P, _I, _P, _I, _I, _L, _I, _P]),
     'mrdis_fuse_present_bwd': (_I, [_P, _I, _P, _P, _I, _P, _I, _P, _P, _I, _L, _I, _P]),
     'mrdis_region_surfaces': (_I, [_P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _P]),
@@ -226,6 +228,9 @@ SEGVOL_FAMILIES = ('segaccum', 'seglabels')
 # whole-subject synthesis of missing contrasts by the 2-D model (csrc/mrdis_synth.hip): 'synthaccum' counts one per mrdis_synth_accum call (one per
 # batch and target), 'synthfinish' one per mrdis_synth_finish call (one per target).
 SYNTH_FAMILIES = ('synthaccum', 'synthfinish')
+# whole-subject segmentation by the 2-D model per missing-contrast pattern (csrc/mrdis_seg2d.hip): 'seg2dlabels' counts one per
+# mrdis_seg2d_label_planes call (one per batch, whatever the number of patterns), 'seg2dfinish' one per mrdis_seg2d_finish call (one per subject).
+SEG2D_FAMILIES = ('seg2dlabels', 'seg2dfinish')
 # the fusion of the anatomy maps over the contrasts a sample has (csrc/mrdis_fuse.hip; lambda_recon_y_fused): 'fuse' counts one per
 # mrdis_fuse_present_fwd and one per mrdis_fuse_present_bwd call.  Outside KERNEL_FAMILIES for the same reason as the tables above.
 FUSE_FAMILIES = ('fuse',)
@@ -243,6 +248,9 @@ CC_FAMILIES = ('cclabel', 'ccclean')
 ELEM_FAMILIES = ('stat_vec', 'stat_scalar', 'stat_interp', 'spade_up2_onepass', 'spade_up2_twopass', 'bil_fwd_x2', 'bil_fwd_general',
                  'bil_bwd_x2', 'bil_bwd_tight3', 'bil_bwd_tight5', 'bil_bwd_general', 'elem_v1')
 SYNTH_MAX_SRC = 8                 # include/mrdis.h MRDIS_SYNTH_MAX_SRC
+SEG2D_MAX_SETS = 16               # include/mrdis.h MRDIS_SEG2D_MAX_SETS
+SEG2D_MAX_VIEWS = 2               # include/mrdis.h MRDIS_SEG2D_MAX_VIEWS
+SEG2D_FLIPS = {'': 0, 'h': 1, 'w': 2}      # the flip codes of mrdis_seg2d_label_planes
 FUSE_MAX_SRC = 8                  # include/mrdis.h MRDIS_FUSE_MAX_SRC
 FUSE_METHODS = ('mean', 'max', 'mean-max-min')      # MRDIS_FUSE_MEAN | _MAX | _MEAN_MAX_MIN, in this order
 EDT_FAR = 1 << 30                 # include/mrdis.h MRDIS_EDT_FAR
@@ -281,8 +289,8 @@ def launch_counts(reset=False, elem=False):
     elem=True adds ELEM_FAMILIES: they count dispatch choices of passes that run beside almost every counted kernel (the statistics in front of a fused
     SPADE convolution, say), so callers that assert "this family and no other" over the whole dictionary only see them when they ask."""
     lib = load()
-    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES
-    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in fams + (ELEM_FAMILIES if elem else ())}
+    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES
+    out ={f: int(lib.mrdis_launch_count(f.encode())) for f in fams + (ELEM_FAMILIES if elem else ())}
     if reset:
         lib.mrdis_launch_count_reset()
     return out
@@ -1450,6 +1458,59 @@ def synth_finish(acc, cnt, fill=0.0):
     out = torch.empty((H, W, D), dtype=torch.float32, device=acc.device)
     _chk(lib.mrdis_synth_finish(_ptr(acc), _ptr(cnt), _ptr(out), D, H, W, float(fill), _stream()), 'synth_finish')
     return acc, out
+
+
+def seg2d_label_planes(views, flips, planes, s0, relabel=False):
+    """planes[s][s0 + r] = the label plane of sample r of set s (include/mrdis.h mrdis_seg2d_label_planes), in place; returns planes.  views: 1 .. 16
+    sets (one per missing-contrast pattern), each a list of 1 .. 2 view tensors: fp32 (B, C, H, W) dense channels-last logits, 2 <= C <= 4, of B
+    samples with consecutive centres s0, s0 + 1, ...; flips: one code per view, 0 | 1 (H) | 2 (W): the view is the prediction of an input flipped
+    along that axis.  One view: argmax of the logits; two: argmax of the mean of the two softmaxes; the lowest class on a tie; relabel: 3 -> 4.
+    planes (n_sets, D, H, W) uint8 contiguous on the same device: only planes s0 .. s0 + B - 1 are written.  This package's own convention (the
+    reference assembles no volume).  Any other layout raises MrdisError: nothing is copied."""
+    lib = load()
+    views = [list(v) for v in views]
+    flips = [int(f) for f in flips]
+    if not 1 <= len(views) <= SEG2D_MAX_SETS:
+        raise MrdisError(f'seg2d_label_planes: 1 to {SEG2D_MAX_SETS} sets, got {len(views)}')
+    n_views = len(views[0])
+    if not 1 <= n_views <= SEG2D_MAX_VIEWS or any(len(v) != n_views for v in views) or len(flips) != n_views:
+        raise MrdisError(f'seg2d_label_planes: 1 to {SEG2D_MAX_VIEWS} views per set and one flip code per view, got {[len(v) for v in views]} views, '
+                         f'{len(flips)} codes')
+    if any(f not in (0, 1, 2) for f in flips):
+        raise MrdisError(f'seg2d_label_planes: flip codes 0 (none), 1 (H) or 2 (W), got {flips}')
+    x0 = views[0][0]
+    if x0.dim() != 4 or not 2 <= x0.shape[1] <= 4:
+        raise MrdisError(f'seg2d_label_planes: (B, C, H, W) logits with 2 <= C <= 4 wanted, got {tuple(x0.shape)}')
+    B, C, H, W = x0.shape
+    for x in (x for v in views for x in v):
+        if x.dtype != torch.float32 or tuple(x.shape) != (B, C, H, W) or x.device != planes.device or not x.permute(0, 2, 3, 1).is_contiguous():
+            raise MrdisError(f'seg2d_label_planes: every view must be a dense channels-last fp32 {(B, C, H, W)} tensor on {planes.device}, got '
+                             f'{x.dtype} {tuple(x.shape)} strides {x.stride()} on {x.device}')
+    if planes.dtype != torch.uint8 or planes.dim() != 4 or planes.shape[0] != len(views) or tuple(planes.shape[2:]) != (H, W) or not planes.is_contiguous():
+        raise MrdisError(f'seg2d_label_planes: planes must be a contiguous uint8 ({len(views)}, D, {H}, {W}) tensor, got {planes.dtype} '
+                         f'{tuple(planes.shape)} strides {planes.stride()}')
+    D, s0 = planes.shape[1], int(s0)
+    if s0 < 0 or s0 + B > D:
+        raise MrdisError(f'seg2d_label_planes: planes {s0} .. {s0 + B - 1} are outside a volume of {D}')
+    ptrs = (_c.c_void_p * (len(views) * n_views))(*[x.data_ptr() for v in views for x in v])
+    codes = (_c.c_int * n_views)(*flips)
+    _chk(lib.mrdis_seg2d_label_planes(ptrs, len(views), n_views, codes, _ptr(planes), B, C, H, W, D, s0, int(bool(relabel)), _stream()),
+         'seg2d_label_planes')
+    return planes
+
+
+def seg2d_finish(planes):
+    """(n_sets, D, H, W) uint8 label planes -> the same volumes as a new contiguous (n_sets, H, W, D) tensor, the volume store's layout
+    (include/mrdis.h mrdis_seg2d_finish).  planes contiguous uint8, else MrdisError.  This package's own convention, like the label planes: the
+    reference assembles no volume."""
+    lib = load()
+    if planes.dtype != torch.uint8 or planes.dim() != 4 or not planes.is_contiguous() or planes.numel() == 0:
+        raise MrdisError(f'seg2d_finish: planes must be a contiguous uint8 (n_sets, D, H, W) tensor, got {planes.dtype} {tuple(planes.shape)} '
+                         f'strides {planes.stride()}')
+    S, D, H, W = planes.shape
+    out = torch.empty((S, H, W, D), dtype=torch.uint8, device=planes.device)
+    _chk(lib.mrdis_seg2d_finish(_ptr(planes), _ptr(out), S, D, H, W, _stream()), 'seg2d_finish')
+    return out
 
 
 def _fuse_args(what, srcs, mask, method):

@@ -15,7 +15,8 @@ What is kept from the reference, statement by statement:
     `model_best.pth.tar` when the monitor improves (util.py:148-153, 854-866)
   * evaluate() (:337-609): eval-mode pass over a loader, loss means + mean MSE / PSNR / SSIM of the mix
     reconstructions, capped at 502 batches (:562-563).  Result dumping to h5 (:565-606) is out of scope (SURVEY 8);
-    `phase: synthesize` (Run.synthesize, synth.py) writes whole-subject volumes instead, by this package's own rules.
+    `phase: synthesize` (Run.synthesize, synth.py) writes whole-subject volumes instead, by this package's own rules, and
+    `phase: segment` (Run.segment, segment.py) whole-subject label volumes per missing-contrast pattern with their region scores.
 Data parallel (north_star; BASELINE configs[2] / [3]: the entry point as the 8-GPU job).  Launched as
 `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 main_missing.py ...` (or with the
 reserved config key `ddp: true` under such a launcher) every rank runs this file on `cuda:LOCAL_RANK`: one RCCL process group
@@ -43,9 +44,12 @@ from .trainer import (DEFAULT_CONFIG, LOSS_KEYS, EVAL_INFOS, EvalStep, eval_metr
                       load_config_yaml, save_checkpoint)
 
 from .synth import check_synth_options, synthesize_volumes
+from .postproc import STATS_COLUMNS
+from .segment import REGION_COLUMNS, check_seg_options, score_rows, segment_volumes
 
 SEED = 10                                                                   # main_missing.py:18
 SYNTH_KEYS = ('synth_info', 'synth_drop', 'synth_block', 'synth_set')
+SEG_KEYS = ('seg_patterns', 'seg_flip', 'seg_set', 'seg_post', 'seg_post_min_voxels', 'seg_post_keep', 'seg_post_et_min_voxels')
 
 
 # --------------------------------------------------------------------------- data-parallel launch (replaces main_missing.py:28)
@@ -142,7 +146,7 @@ def setup_config(config_path='config.yaml', overrides=None, ckpt_root='../ckpt/'
         device = torch.device('cuda:' + str(config['gpu']))
     config = derive_config(config, device)
     rank, world = dist_info()
-    if config['ckpt_timelabel'] and (config['phase'] in ('test', 'synthesize') or config['continue_train'] is True):
+    if config['ckpt_timelabel'] and (config['phase'] in ('test', 'synthesize', 'segment') or config['continue_train'] is True):
         label = config['ckpt_timelabel']
     else:
         label = _bcast_object(time_label_now())                             # one directory per job: rank 0's clock names it
@@ -167,7 +171,7 @@ def setup_config(config_path='config.yaml', overrides=None, ckpt_root='../ckpt/'
         flag, saved = load_config_yaml(os.path.join(config['ckpt_path'], 'config.yaml'))
         if flag:
             for k, v in saved.items():                                      # :45-51
-                if k in ('phase', 'continue_train', 'eval_info', 'eval_drop') + SYNTH_KEYS or k not in config:    # eval_info, eval_drop, synth_*: per invocation, like phase
+                if k in ('phase', 'continue_train', 'eval_info', 'eval_drop') + SYNTH_KEYS + SEG_KEYS or k not in config:    # eval_info, eval_drop, synth_*, seg_*: per invocation, like phase
                     continue
                 config[k] = v
             config = derive_config(config, device)
@@ -289,7 +293,7 @@ class Run:
         self.optimizer, self.optimizer_d_s = self.step.optimizer, self.step.optimizer_d_s
         self.scheduler = torch.optim.lr_scheduler.ReduceLROnPlateau(self.optimizer, mode='min', factor=0.1, patience=5, min_lr=1e-5)   # :119
         self.start_epoch = -1
-        if config['continue_train'] or config['phase'] in ('test', 'synthesize'):    # :125-135
+        if config['continue_train'] or config['phase'] in ('test', 'synthesize', 'segment'):    # :125-135
             _, self.start_epoch, loaded = load_checkpoint_by_key([self.optimizer, self.scheduler, self.model], config['ckpt_path'],
                                                                  ['optimizer', 'scheduler', 'model'], config['device'], config['ckpt_name'])
             log(f'loaded {loaded} from {config["ckpt_name"]} (epoch {self.start_epoch})')
@@ -472,6 +476,83 @@ class Run:
                  f'mse {stat["rmse"]:.5f}, psnr {stat["psnr"]:.3f}, ssim {stat["ssim"]:.4f}')
         return stat
 
+    def segment(self, set_=None, patterns=None, flip=None, batch_size=None):
+        """whole-subject tumour segmentation per missing-contrast pattern (segment.segment_volumes) of the distinct subjects of `set_`'s slice list,
+        in order of first appearance (None: the config's seg_set / seg_patterns / seg_flip; cleaning by the config's seg_post* keys).  Writes
+          <ckpt_path>/result_<set>/seg/<pattern>/<subj_id>_seg.npy -- uint8 (H, W, D), the store's own geometry, BraTS labels 0 / 1 / 2 / 4;
+          result_<set>/seg_regions.csv -- `subj_id,pattern,n_present,dice_wt,...,hd95_et`, one row per subject and pattern (n_present 0: the pattern
+          leaves the subject nothing, no volume; NaN: nothing to score against), floats written with repr;
+          result_<set>/seg_patterns.csv -- `pattern,subjects,dice_wt,...,hd95_et`: per pattern the number of scored subjects and the mean of
+          each score over them;
+        with seg_post the same three under result_<set>/seg/post/ for the cleaned volumes, plus seg/post/postprocess.csv
+        (`subj_id,pattern,components,...`).  Returns {'subjects', 'patterns', 'scored', '<pattern>/<column>': mean}.  The rules are this package's own
+        convention: the reference assembles no volume and never fuses for M > 1.  World size 1 only."""
+        cfg = self.config
+        if getattr(self, 'world', 1) > 1 or (dist.is_available() and dist.is_initialized()):
+            raise NotImplementedError('segment under a process group: the subjects are not sharded; segment on one process')
+        set_ = cfg.get('seg_set', 'test') if set_ is None else set_
+        patterns = cfg.get('seg_patterns', 'full') if patterns is None else patterns
+        flip = (cfg.get('seg_flip') or '') if flip is None else flip
+        if not isinstance(cfg.get('seg_post', False), bool):
+            raise ValueError(f'seg_post {cfg["seg_post"]!r}: true or false')
+        post = None
+        if cfg.get('seg_post', False):
+            post = {'min_voxels': cfg.get('seg_post_min_voxels', 0), 'keep': cfg.get('seg_post_keep', 'all'),
+                    'et_min_voxels': cfg.get('seg_post_et_min_voxels', 0)}
+        names = [str(c) for c in cfg['contrast_list']]
+        pats, post = check_seg_options(names, patterns, flip, post)
+        if set_ not in ('train', 'val', 'test'):
+            raise ValueError(f'seg_set {set_!r}: train, val or test')
+        ds = self.loaders[set_].dataset
+        subjects = list(dict.fromkeys(str(x) for x in ds.subj_list))
+        out_dir = os.path.join(cfg['ckpt_path'], 'result_' + set_)
+        kinds = [('scores', 'labels', out_dir, 'seg')] + ([('post_scores', 'post', os.path.join(out_dir, 'seg', 'post'), '')] if post else [])
+        for _, _, base, sub in kinds:
+            for name, _ in pats:
+                os.makedirs(os.path.join(base, sub, name), exist_ok=True)
+        rows = {k: [] for k, _, _, _ in kinds}
+        stats_rows = []
+        for res in segment_volumes(self.model, cfg, ds.store, subjects, pats, flip=flip, batch_size=batch_size, post=post):
+            sid = res['subj_id']
+            live = [k for k, pr in enumerate(res['present']) if any(pr)]
+            for skey, vkey, base, sub in kinds:
+                vols = res[vkey].cpu().numpy() if res[vkey] is not None else None
+                for j, k in enumerate(live):
+                    np.save(os.path.join(base, sub, res['patterns'][k], f'{sid}_seg.npy'), vols[j])
+                rows[skey] += [(sid,) + r for r in score_rows(res, skey)]
+            if post and res['post_stats'] is not None:
+                st = res['post_stats'].cpu().tolist()
+                stats_rows += [(sid, res['patterns'][k], st[j]) for j, k in enumerate(live)]
+        stat = {'subjects': len(subjects), 'patterns': len(pats)}
+        for skey, _, base, _ in kinds:
+            means = self._write_seg_csvs(base, [n for n, _ in pats], rows[skey])
+            if skey == 'scores':
+                stat.update(means)
+        if post:
+            with open(os.path.join(out_dir, 'seg', 'post', 'postprocess.csv'), 'w') as f:
+                f.write('subj_id,pattern,' + ','.join(STATS_COLUMNS) + '\n')
+                f.write(''.join(f'{sid},{name},' + ','.join(str(int(v)) for v in st) + '\n' for sid, name, st in stats_rows))
+        self.log(f'segment {set_}: {len(subjects)} subjects x {len(pats)} patterns under {out_dir}/seg, {stat["scored"]} volumes scored')
+        return stat
+
+    @staticmethod
+    def _write_seg_csvs(base, pattern_names, rows):
+        """seg_regions.csv and seg_patterns.csv under `base` from (subj_id, pattern, n_present, values) rows -> {'scored', '<pattern>/<column>': mean}"""
+        with open(os.path.join(base, 'seg_regions.csv'), 'w') as f:
+            f.write('subj_id,pattern,n_present,' + ','.join(REGION_COLUMNS) + '\n')
+            f.write(''.join(f'{sid},{name},{n},' + ','.join(repr(v) for v in vals) + '\n' for sid, name, n, vals in rows))
+        means, scored = {}, 0
+        with open(os.path.join(base, 'seg_patterns.csv'), 'w') as f:
+            f.write('pattern,subjects,' + ','.join(REGION_COLUMNS) + '\n')
+            for name in pattern_names:
+                have = np.array([vals for _, p, _, vals in rows if p == name and not np.isnan(vals[0])], dtype=np.float64).reshape(-1, len(REGION_COLUMNS))
+                mean = have.mean(0) if len(have) else np.full(len(REGION_COLUMNS), np.nan)
+                scored += len(have)
+                f.write(f'{name},{len(have)},' + ','.join(repr(float(v)) for v in mean) + '\n')
+                means.update({f'{name}/{c}': float(v) for c, v in zip(REGION_COLUMNS, mean)})
+        means['scored'] = scored
+        return means
+
 
 def parse_overrides(args):
     out = {}
@@ -496,6 +577,10 @@ def main(argv=None):
             run.train()
         elif config['phase'] == 'synthesize':
             stat = run.synthesize()
+            if run.rank == 0:
+                print(stat)
+        elif config['phase'] == 'segment':
+            stat = run.segment()
             if run.rank == 0:
                 print(stat)
         else:

@@ -44,6 +44,14 @@ DEFAULT_CONFIG = {
     'synth_block': 'centre',           # 'centre': a plane is the centre slice of its own sample | 'mean': the mean of every prediction of it
     'synth_set': 'test',               # train | val | test: the slice list whose distinct subjects are synthesised
     'eval_drop': [],                   # contrast names hidden during evaluation (EvalStep): their input channels become the store's absent value (0), their mask column 0
+    # phase: segment -- whole-subject label volumes per missing-contrast pattern, scored by region (segment.segment_volumes, Run.segment)
+    'seg_patterns': 'full',            # 'full' | 'leave_one_out' | 'all' | a list of lists of contrast names hidden together (segment.seg_patterns)
+    'seg_flip': '',                    # '' | 'h' | 'w': a second view of the flipped slices, averaged in probability
+    'seg_set': 'test',                 # train | val | test: the slice list whose distinct subjects are segmented
+    'seg_post': False,                 # true: the volumes are also cleaned by connected components (postproc.clean_labels, connectivity 26)
+    'seg_post_min_voxels': 0,          # components smaller than this are removed
+    'seg_post_keep': 'all',            # 'all' | 'largest'
+    'seg_post_et_min_voxels': 0,       # fewer enhancing-tumour voxels than this (and more than 0) become label 1
 }
 
 
