@@ -294,9 +294,6 @@ static int launch_bconv(const TapConvParams& p, const BConvGeom& g, int grid, si
                                     : launch_bconv_t<KC, WAVES_C, WP, WC, float>(p, g, grid, lds, s);
 }
 
-int mrdis_run_bconv3(const TapConvParams& t, hipStream_t s);      // mrdis_bf16p.hip
-int mrdis_run_bconv4(const TapConvParams& t, hipStream_t s);      // mrdis_bf16q.hip
-
 // Eligibility: reduction axis a multiple of 16, 16-byte aligned views, cout a multiple of 4 (16-byte stores).
 int mrdis_run_bconv(TapConvParams p, int dh_max, int dw_max, hipStream_t s, BConvLaunch* defer) {
     if (defer) defer->set = false;

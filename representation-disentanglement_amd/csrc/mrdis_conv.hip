@@ -28,6 +28,7 @@
 #include "mrdis_common.h"
 #include "mrdis_tapconv.h"
 #include "mrdis_s6conv.h"
+#include "mrdis_wino4.h"
 #include <stdlib.h>
 #include <type_traits>
 
@@ -1330,26 +1331,10 @@ static int run_c4conv(const float* x, int ldx, const float* w, const float* bias
     return MRDIS_OK;
 }
 
-// fused Winograd F(2x2, 3x3) kernel (mrdis_wino.hip)
-int mrdis_run_wino(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy,
-                   int N, int H, int W, int Ci, int Co, int flip, int lrelu, hipStream_t s);
 // MRDIS_WINO: 0 never | 1 (default) measured policy | 2 wherever the kernel applies.  Policy (tools/layer_bench.py, B = 32
 // layer zoo): Winograd wins for Cout >= 32 and Cin >= 16 once the grid fills the chip (>= 256 workgroups): 1.13x on
 // 32 -> 32, 1.3-1.5x on the 64..512-channel layers; a 16-cout layer wastes half of its 32-wide cout tile (slower).
 // software-pipelined variant for Cout > 32 (mrdis_wino2.hip); option wino_pipe = 0 keeps the phase-by-phase kernel everywhere
-int mrdis_run_wino2(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy,
-                    int N, int H, int W, int Ci, int Co, int flip, int lrelu, hipStream_t s, const float* u_img);
-// F(4x4, 3x3) (mrdis_wino4.hip): takes the layers whose filter image is of format 4 (mrdis_wino_u_format; the image carries the flip, so
-// forward and data gradient are the same call); MRDIS_EUNSUPPORTED where its shape limits / grid test decline
-int mrdis_run_wino4(const float* x, int ldx, const float* bias, float* y, int ldy, int N, int H, int W, int Ci, int Co, int lrelu,
-                    hipStream_t s, const float* u_img);
-#include "mrdis_wino4.h"
-int mrdis_run_wino4n(const float* x, int ldx, const float* bias, float* y, int ldy, int N, int H, int W, int Ci, int Co, int lrelu,
-                     hipStream_t s, const float* u_img);
-int mrdis_run_wino4r(const float* x, int ldx, const float* bias, float* y, int ldy, int N, int H, int W, int Ci, int Co, int lrelu,
-                     hipStream_t s, const float* u_img);     // the register-fed form of the same layers (mrdis_wino4r.hip)
-int mrdis_run_wino4_spade(const float* x, int ldx, const float* bias, const float* z, int ldz, const float* mean, const float* rstd,
-                          float* mix, int ldmix, float* gamma, int ldg, int N, int H, int W, int Ci, int C, hipStream_t s, const float* u_img);
 // u_fmt: the format the image u_img was BUILT in (2 | 4 | 5: mrdis_wino_u_format at build time; it travels with the pointer, the option
 // 'wino4' may have changed since).  The option decides only whether the F(4x4) kernels run; the layout read is always the image's own.
 static int run_wino(const float* x, int ldx, const float* w, const float* bias, float* y, int ldy,
@@ -1398,12 +1383,6 @@ static bool bf16m_wanted(int dtype, const void* w_bf16, int Cred, int Cout) {
 // pipelined Winograd kernel (mrdis_wino2.hip), only where that kernel is the kernel of choice for the 2C-cout layer; bf16 activations
 // (MRDIS_DT_BF16): the SPADE epilogue of the pipelined bf16 kernel (mrdis_bf16p.hip).  MRDIS_EUNSUPPORTED otherwise (the caller then runs
 // mrdis_conv2d_fwd + mrdis_instnorm_spade_fwd).
-int mrdis_run_wino2_spade(const float* x, int ldx, const float* w, const float* bias, const float* z, int ldz, const float* mean, const float* rstd,
-                          float* mix, int ldmix, float* gamma, int ldg, int N, int H, int W, int Ci, int C, hipStream_t s, const float* u_img);
-int mrdis_run_bconv3_spade(const void* x, int ldx, const void* w_bf16, const float* bias, const void* z, int ldz, const float* mean, const float* rstd,
-                           void* mix, int ldmix, void* gamma, int ldg, int N, int H, int W, int Ci, int C, hipStream_t s);
-int mrdis_run_bconv4_spade(const void* x, int ldx, const void* w_bf16, const float* bias, const void* z, int ldz, const float* mean, const float* rstd,
-                           void* mix, int ldmix, void* gamma, int ldg, int N, int H, int W, int Ci, int C, hipStream_t s);
 extern "C" int mrdis_conv2d_fwd_spade(const void* x, int ldx, const float* w_tck, const void* w_bf16_tkc, const float* bias, const void* z, int ldz,
                                       const float* mean, const float* rstd, void* mix, int ldmix, void* gamma, int ldg,
                                       int N, int H, int W, int Ci, int C, int dtype, const float* w_wino, int w_wino_fmt, void* stream) {
@@ -1429,21 +1408,6 @@ extern "C" int mrdis_conv2d_fwd_spade(const void* x, int ldx, const float* w_tck
     return mrdis_run_wino2_spade((const float*)x, ldx, w_tck, bias, (const float*)z, ldz, mean, rstd, (float*)mix, ldmix, (float*)gamma, ldg, N, H, W, Ci, C,
                                  (hipStream_t)stream, w_wino);
 }
-
-// mrdis_pointwise.hip: the 1x1 decoder head (16 -> <= 8 channels) as streaming kernels
-int mrdis_run_pw_fwd(const void* x, int ldx, const float* w_tck, const float* bias, float* y, int ldy, long long npix, int Ci, int Co, int lrelu, int x16_bf16, hipStream_t s);
-// mrdis_wgrad_s2.hip: forward of the stride-2 first layers (Cin <= 7)
-int mrdis_run_conv_s2_fwd(const float* x, int ldx, const float* w_tck, const float* bias, float* y, int ldy, int N, int H, int W, int Ci, int Co,
-                          int kh, int kw, int stride, int pad, int lrelu, hipStream_t s);
-int mrdis_run_dgrad_s2(const float* dy, int lddy, const float* w_tkc, float* dx, int lddx, int N, int H, int W, int Ci, int Co,
-                       int kh, int kw, int stride, int pad, hipStream_t s);
-// mrdis_co4.hip: 3x3 s1 p1 with 4 output channels: window-free GEMM + tap gather
-int mrdis_run_co4(const void* x, int ldx, const float* w, const float* bias, float* y, int ldy, int N, int H, int W, int Ci, int Co, int flip, int lrelu, hipStream_t s,
-                  int x_bf16 = 0, int wld = 4);
-// mrdis_c16.hip: 3x3 s1 p1 with 16 output channels, filter in registers
-int mrdis_run_c16(const float* x, int ldx, const float* w_tck, const float* bias, float* y, int ldy, int N, int H, int W, int Ci, int Co, int lrelu, hipStream_t s);
-int mrdis_run_c16t_split6(const float* x, int ldx, const float* w_t_ci_co, float* y, int ldy, int N, int H, int W, int flip, hipStream_t s);      // mrdis_c16.hip: 16 -> 32, six bf16 products
-int mrdis_run_pw_dgrad(const float* dy, int lddy, const float* w_tkc, void* dx, int lddx, long long npix, int Ci, int Co, int x16_bf16, hipStream_t s);
 
 extern "C" int mrdis_conv2d_fwd(const void* x_, int ldx, const float* w_tck, const void* w_bf16_tkc, const float* bias,
                                 void* y_, int ldy, int N, int H, int W, int Ci, int Co,
@@ -2591,26 +2555,6 @@ static size_t wgrad_need(const WgradPlan& pl) {
     return sizeof(float) * (size_t)(pl.slab_floats + pl.part_floats + pl.bias_floats) + 256;
 }
 
-size_t mrdis_wgrad16_workspace(int N, int H, int W, int Ci, int Co);            // mrdis_wgrad16.hip: Cout <= 16, 3x3 s1 p1
-size_t mrdis_wgrad_s2_workspace(int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad);     // mrdis_wgrad_s2.hip: Cin <= 7 stride-2 first layers
-size_t mrdis_wgrad_c4_workspace(int N, int H, int W, int Ci, int Co);              // mrdis_wgrad_s2.hip: the 4 -> C si_layers
-size_t mrdis_wgrad_co4b_workspace(int N, int H, int W, int Ci, int Co);
-int mrdis_run_wgrad_co4b(const void* x_bf16, int ldx, const float* dy, int lddy, float* dw_tck, float* dbias, void* workspace, size_t workspace_bytes,
-                         int N, int H, int W, int Ci, int Co, int accumulate_bias, hipStream_t s, int pad16);
-int mrdis_run_wgrad_c4(const float* x, int ldx, const void* dy, int lddy, float* dw_tck, float* dbias, void* workspace, size_t workspace_bytes,
-                       int N, int H, int W, int Ci, int Co, int accumulate_bias, int dy_bf16, hipStream_t s, int pad16 = 0);
-size_t mrdis_pw_wgrad_workspace(long long npix, int Ci, int Co, int x16_bf16);      // mrdis_pointwise.hip: the 1x1 16 -> <= 8 head
-int mrdis_run_pw_wgrad(const void* x, int ldx, const float* dy, int lddy, float* dw_tck, float* dbias, void* workspace, size_t workspace_bytes,
-                       long long npix, int Ci, int Co, int accumulate_bias, int x16_bf16, hipStream_t s);
-int mrdis_run_wgrad_s2(const float* x, int ldx, const float* dy, int lddy, float* dw_tck, float* dbias, void* workspace, size_t workspace_bytes,
-                       int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int accumulate_bias, hipStream_t s);
-int mrdis_run_wgrad16_bf16(const void* x, int ldx, const void* dy, int lddy, float* dw_tck, float* dbias, void* workspace, size_t workspace_bytes,
-                           int N, int H, int W, int Ci, int Co, int accumulate_bias, hipStream_t s);      // mrdis_wgrad16.hip: bf16 views, 32 -> 16
-int mrdis_run_wgrad16(const float* x, int ldx, const float* dy, int lddy, float* dw_tck, float* dbias, void* workspace,
-                      size_t workspace_bytes, int N, int H, int W, int Ci, int Co, int accumulate_bias, hipStream_t s);
-size_t mrdis_wino_wgrad_workspace(int N, int H, int W, int Ci, int Co);
-int mrdis_run_wino_wgrad(const float* x, int ldx, const float* dy, int lddy, float* dw_tck, float* dbias, void* workspace,
-                         size_t workspace_bytes, int N, int H, int W, int Ci, int Co, int accumulate_bias, hipStream_t s);
 // Winograd weight gradient (mrdis_wino.hip): 3x3 s1 p1 layers with Ci, Co multiples of 32 / 64 and enough tiles per split
 static bool wino_wgrad_wanted(int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad) {
     const int mode = (int)mrdis_opt(MRDIS_OPT_WINO);          // MRDIS_WINO at load; mrdis_set_option("wino", v) afterwards
@@ -2622,11 +2566,6 @@ static bool wino_wgrad_wanted(int N, int H, int W, int Ci, int Co, int kh, int k
     if (Co % 64 != 0 && Ci < 64) return false;
     return (long long)N * ((H + 3) / 4) * ((W + 7) / 8) >= 256;
 }
-
-// mrdis_bf16.hip: weight gradient on bf16 MFMA operands (stride-1 "same" convolutions, Ci % 32 == 0)
-size_t mrdis_bwgrad_workspace(int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad);
-int mrdis_run_bwgrad(const void* x, int ldx, const void* dy, int lddy, float* dw_tck, float* dbias, void* workspace, size_t workspace_bytes,
-                     int N, int H, int W, int Ci, int Co, int kh, int kw, int stride, int pad, int accumulate_bias, int dtype, hipStream_t s);
 
 extern "C" size_t mrdis_conv2d_bwd_weight_workspace(int N, int H, int W, int Ci, int Co,
                                                     int kh, int kw, int stride, int pad) {

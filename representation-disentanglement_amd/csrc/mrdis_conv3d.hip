@@ -534,11 +534,6 @@ static int check_conv3d_geom(int N, int D, int H, int W, int Ci, int Co, int k, 
 }
 
 // hybrid Winograd path (mrdis_wino.hip): F(2x2,3x3) in (h, w), direct in depth
-int mrdis_run_wino3d(const float* x, int ldx, const float* w, const float* bias, const float* res, int ldres, float* y, int ldy,
-                     int N, int D, int H, int W, int Ci, int Co, int flip, hipStream_t s);
-size_t mrdis_wino_wgrad3d_workspace(int N, int D, int H, int W, int Ci, int Co);
-int mrdis_run_wino_wgrad3d(const float* x, int ldx, const float* dy, int lddy, float* dw_tck, float* dbias, void* workspace,
-                           size_t workspace_bytes, int N, int D, int H, int W, int Ci, int Co, hipStream_t s);
 static bool wino3d_wgrad_wanted(int N, int D, int H, int W, int Ci, int Co, int stride) {
     const int mode = (int)mrdis_opt(MRDIS_OPT_WINO);          // MRDIS_WINO at load; mrdis_set_option("wino", v) afterwards
     if (mode == 0 || stride != 1 || mrdis_wino_wgrad3d_workspace(N, D, H, W, Ci, Co) == 0) return false;

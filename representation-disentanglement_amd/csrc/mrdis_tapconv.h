@@ -51,3 +51,7 @@ static inline TileChoice choose_tile(int N, int A, int B, int BMv = TC_BM) {
 // mrdis_bf16.hip: the same tap-table launch on v_mfma_f32_32x32x16_bf16; MRDIS_EUNSUPPORTED = not eligible (caller falls back)
 int mrdis_run_bconv(TapConvParams p, int dh_max, int dw_max, hipStream_t s, BConvLaunch* defer = nullptr);
 int mrdis_launch_bconv_planned(const BConvLaunch (&L)[4], hipStream_t s);
+// the 3x3 stride-1 bf16-activation layers: pipelined kernel (mrdis_bf16p.hip) and its LDS-DMA form for launches that fill the chip
+// (mrdis_bf16q.hip); MRDIS_EUNSUPPORTED: the caller (mrdis_run_bconv) takes the next form down, bconv_kernel last
+int mrdis_run_bconv3(const TapConvParams& t, hipStream_t s);
+int mrdis_run_bconv4(const TapConvParams& t, hipStream_t s);

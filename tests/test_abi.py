@@ -161,3 +161,72 @@ def test_launch_setup_lives_in_one_place():
             if setup_call.search(code) or local_static.search(code):
                 bad.append(f'{os.path.basename(f)}:{n}')
     assert not bad, bad
+
+
+def _file_scope_statements(text):
+    """(head, end, scopes) of every file-scope statement of a C++ source, comments / literals / preprocessor lines stripped: head is the text up to its
+    ';' (end == ';': a declaration) or up to the '{' of its body (end == '{': a definition, whose body is skipped); scopes names the `extern "C" { }` ('C')
+    and namespace ('anon' / 'named') blocks around it, which do not end file scope"""
+    import re
+    text = re.sub(r'//[^\n]*|/\*.*?\*/|"(?:\\.|[^"\\\n])*"|\'(?:\\.|[^\'\\\n])*\'',
+                  lambda m: '"C"' if m.group(0) == '"C"' else ('""' if m.group(0)[0] == '"' else ' '), text, flags=re.S)
+    text = re.sub(r'^[ \t]*#(?:[^\n]*\\\n)*[^\n]*', '', text, flags=re.M)
+    out, stack, start = [], [], 0              # stack: one entry per open '{': 'body' or a transparent scope
+    for i, c in enumerate(text):
+        inside = 'body' in stack
+        if c == '{':
+            head = text[start:i]
+            if not inside and re.search(r'\bextern\s+"C"\s*$', head):
+                stack.append('C'); start = i + 1
+            elif not inside and re.search(r'\bnamespace(\s+\w+)?\s*$', head):
+                stack.append('named' if re.search(r'\bnamespace\s+\w+\s*$', head) else 'anon'); start = i + 1
+            else:
+                if not inside:
+                    out.append((head, '{', tuple(stack)))
+                stack.append('body')
+        elif c == '}':
+            if stack:
+                stack.pop()
+            if 'body' not in stack:
+                start = i + 1
+        elif c == ';' and not inside:
+            out.append((text[start:i], ';', tuple(stack)))
+            start = i + 1
+    return out
+
+
+def test_internal_launchers_are_declared_once_in_a_header():
+    """a function that crosses a file boundary is declared in ONE header that both its defining file and its callers include (mrdis_launchers.h for the kernel
+    launchers; mrdis_common.h includes it), so a parameter list that drifts is a compile or link error (the Makefile links with --no-undefined) and not an
+    undefined symbol at dlopen.  No .hip file types a prototype of its own, and every mrdis_* function that a .hip file defines with external linkage (not
+    static, not in an anonymous namespace, not extern "C") has exactly one declaration among csrc/*.h and include/mrdis.h"""
+    import glob
+    import re
+    repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    root = os.path.join(repo, 'representation-disentanglement_amd', 'csrc')
+    named = re.compile(r'\s*([^()=]*?)\b(mrdis_\w+)\s*\(')        # `type mrdis_name(`: the name comes before the first parenthesis, a type before the name
+
+    def functions(path):
+        for head, end, scopes in _file_scope_statements(open(path).read()):
+            m = named.match(head)
+            if m and m.group(1).strip():
+                yield m.group(2), m.group(1), end, scopes
+
+    prototypes, defined = [], {}
+    sources = sorted(glob.glob(os.path.join(root, '*.hip')))
+    assert len(sources) >= 32
+    for f in sources:
+        for name, pre, end, scopes in functions(f):
+            if end == ';':
+                prototypes.append(f'{os.path.basename(f)}: {name}')
+            elif not (re.search(r'\b(static|__device__|__global__)\b|extern\s+"C"', pre) or 'C' in scopes or 'anon' in scopes):
+                defined.setdefault(name, os.path.basename(f))
+    declared = {}
+    for h in sorted(glob.glob(os.path.join(root, '*.h'))) + [os.path.join(repo, 'include', 'mrdis.h')]:
+        for name, pre, end, scopes in functions(h):
+            if end == ';':
+                declared.setdefault(name, []).append(os.path.basename(h))
+    assert not prototypes, (len(prototypes), prototypes)
+    assert len(defined) >= 50 and 'mrdis_run_wino4' in defined and 'mrdis_opt' in defined, sorted(defined)       # the scan sees the launchers at all
+    wrong = {n: (f, declared.get(n, [])) for n, f in defined.items() if len(declared.get(n, [])) != 1}
+    assert not wrong, wrong
