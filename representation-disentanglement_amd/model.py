@@ -22,6 +22,11 @@ def _pair(v):
     return (v, v) if isinstance(v, int) else tuple(v)
 
 
+def _groups(inputs_type):
+    """G when `inputs_type` is a list / tuple of G label tensors (a grouped call, see CondConv2d), 0 for one label tensor or None."""
+    return len(inputs_type) if isinstance(inputs_type, (list, tuple)) else 0
+
+
 # =============================================================================
 # operator seam: model.py:2065-2120
 # =============================================================================
@@ -47,6 +52,13 @@ class CondConv2d(nn.Module):
     3169, 3190, 3211) the experts are mixed ONCE and one batched conv runs;
     otherwise the per-sample path of the reference is taken (one mix + one
     batch-1 conv per sample).  Both are the same arithmetic.
+
+    The `inputs_type` convention of this class and of every block built on it:
+    a tensor (B, embeddings) is one label, the reference's signature; a list or
+    tuple of G batch-constant label tensors is a grouped call -- the input holds
+    G sample blocks, block g belongs to inputs_type[g], and the result is the G
+    outputs of the reference's per-modality loop, batch-concatenated (one op per
+    convolution layer, ops.conv2d_grouped; BatchNorm statistics per block).
     """
 
     def __init__(self, in_channels, out_channels, kernel_size, stride=1, padding=0, dilation=1, groups=1,
@@ -93,49 +105,43 @@ class CondConv2d(nn.Module):
         key = (id(self), inputs_type.data_ptr(), inputs_type._version)
         return ops.cached_mix(key, lambda: self._mixed(inputs_type[:1]))
 
-    def forward(self, inputs, inputs_type, lrelu=False):
+    def _conv(self, op, srcs, inputs_type, lrelu, **uniform_kw):
+        """op (ops.conv2d | ops.conv2d_2src) over the sources with this layer's mixed filter: mixed once for a batch-constant label,
+        else the per-sample path of the reference (model.py:2114-2117)"""
         kh, kw = self.kernel_size
-        B = inputs.shape[0]
+        tail = (self.bias, kh, kw, self.stride[0], self.padding[0], lrelu)
+        B = srcs[0].shape[0]
         if B == 1 or inputs_type.stride(0) == 0:
-            if not ops.mix_cache_active() and not ops.storage_bf16():
-                # the seam as ONE dispatcher-visible op (mix + conv, torch.ops.mrdis.cond_conv2d): plain module use
-                return torch.ops.mrdis.cond_conv2d(inputs, inputs_type[:1], self.weight, self._routing_fn.fc.weight,
-                                                   self._routing_fn.fc.bias, self.bias, self.stride[0], self.padding[0], lrelu,
-                                                   ops.compute_dtype())        # 0 exact fp32 | 1 bf16 MFMA operands
             # inside a training step the mixed kernels of all modality labels are cached and shared by every call
-            w_tck, w_tkc = self.mixed_uniform(inputs_type)
-            return ops.conv2d(inputs, w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu, co=self.out_channels)
-        outs = []                                    # per-sample path, model.py:2114-2117
-        for i in range(B):
-            w_tck, w_tkc = self._mixed(inputs_type[i:i + 1])
-            outs.append(ops.conv2d(inputs[i:i + 1], w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu))
-        return torch.cat(outs, 0)
-
-    def forward_2src(self, x, s, inputs_type, lrelu=False):
-        """forward(cat([x, s], 1), inputs_type) with the concatenation never written (ops.conv2d_2src): the modality encoder's first
-        layer under others.mod_enc_s (model.py:2374).  Same expert mixing as forward(); per-sample types take the per-sample path."""
-        kh, kw = self.kernel_size
-        B = x.shape[0]
-        if B == 1 or inputs_type.stride(0) == 0:
-            w_tck, w_tkc = self.mixed_uniform(inputs_type)
-            return ops.conv2d_2src(x, s, w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu)
+            return op(*srcs, *self.mixed_uniform(inputs_type), *tail, **uniform_kw)
         outs = []
         for i in range(B):
             w_tck, w_tkc = self._mixed(inputs_type[i:i + 1])
-            outs.append(ops.conv2d_2src(x[i:i + 1], s[i:i + 1], w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu))
+            outs.append(op(*[a[i:i + 1] for a in srcs], w_tck, w_tkc, *tail))
         return torch.cat(outs, 0)
 
-    def forward_grouped(self, x, types, lrelu=False):
-        """x: G sample blocks (block g belongs to the batch-constant type tensor types[g]) -> the G outputs, batch-concatenated:
-        ONE op for the G calls of the reference's per-modality loop (ops.conv2d_grouped)."""
-        kh, kw = self.kernel_size
-        G = len(types)
-        if ops.storage_bf16() and self.stride[0] != 1 and min(self.in_channels, self.out_channels) < 16:
-            # the stride-2 first layers under bf16 storage keep ops.conv2d's policy (fp32 kernels between view casts), block by block
-            B = x.shape[0] // G
-            return torch.cat([self.forward(x[g * B:(g + 1) * B], types[g], lrelu) for g in range(G)], 0)
-        return ops.conv2d_grouped(x, [self.mixed_uniform(t) for t in types], self.bias, kh, kw, self.padding[0], lrelu=lrelu,
-                                  co=self.out_channels, stride=self.stride[0])
+    def forward(self, inputs, inputs_type, lrelu=False):
+        G = _groups(inputs_type)
+        if G:
+            if ops.storage_bf16() and self.stride[0] != 1 and min(self.in_channels, self.out_channels) < 16:
+                # the stride-2 first layers under bf16 storage keep ops.conv2d's policy (fp32 kernels between view casts), block by block
+                B = inputs.shape[0] // G
+                return torch.cat([self.forward(inputs[g * B:(g + 1) * B], inputs_type[g], lrelu) for g in range(G)], 0)
+            kh, kw = self.kernel_size
+            return ops.conv2d_grouped(inputs, [self.mixed_uniform(t) for t in inputs_type], self.bias, kh, kw, self.padding[0], lrelu=lrelu,
+                                      co=self.out_channels, stride=self.stride[0])
+        if (inputs.shape[0] == 1 or inputs_type.stride(0) == 0) and not ops.mix_cache_active() and not ops.storage_bf16():
+            # the seam as ONE dispatcher-visible op (mix + conv, torch.ops.mrdis.cond_conv2d): plain module use
+            return torch.ops.mrdis.cond_conv2d(inputs, inputs_type[:1], self.weight, self._routing_fn.fc.weight,
+                                               self._routing_fn.fc.bias, self.bias, self.stride[0], self.padding[0], lrelu,
+                                               ops.compute_dtype())        # 0 exact fp32 | 1 bf16 MFMA operands
+        return self._conv(ops.conv2d, (inputs,), inputs_type, lrelu, co=self.out_channels)
+
+    def forward_2src(self, x, s, inputs_type, lrelu=False):
+        """forward(cat([x, s], 1), inputs_type) with the concatenation never written (ops.conv2d_2src): the modality encoder's first
+        layer under others.mod_enc_s (model.py:2374).  Same expert mixing as forward(); per-sample types take the per-sample path.
+        One label only: the two-source convolution takes one filter per call."""
+        return self._conv(ops.conv2d_2src, (x, s), inputs_type, lrelu)
 
 
 class HipConv2d(nn.Conv2d):
@@ -147,19 +153,22 @@ class HipConv2d(nn.Conv2d):
         if self.bias is not None:
             self.bias._mrdis_sink = True           # gradient accumulated in-kernel (ops._grad_sink)
 
+    def _filters(self, device):
+        """(w_tck, w_tkc): the weight in the kernels' two layouts (a one-expert mix), memoised for the step"""
+        one = torch.ones(1, dtype=torch.float32, device=device)
+        return ops.cached_mix((id(self), 0, 0), lambda: ops.mix_experts(self.weight.unsqueeze(0), one))
+
     def forward(self, x, lrelu=False):
         if self.dilation != (1, 1) or self.groups != 1 or self.padding_mode != 'zeros':
             raise NotImplementedError
         kh, kw = self.kernel_size
-        one = torch.ones(1, dtype=torch.float32, device=x.device)
-        w_tck, w_tkc = ops.cached_mix((id(self), 0, 0), lambda: ops.mix_experts(self.weight.unsqueeze(0), one))
+        w_tck, w_tkc = self._filters(x.device)
         return ops.conv2d(x, w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu)
 
     def forward_2src(self, x, s, lrelu=False):
         """forward(cat([x, s], 1)) from the two sources (ops.conv2d_2src)"""
         kh, kw = self.kernel_size
-        one = torch.ones(1, dtype=torch.float32, device=x.device)
-        w_tck, w_tkc = ops.cached_mix((id(self), 0, 0), lambda: ops.mix_experts(self.weight.unsqueeze(0), one))
+        w_tck, w_tkc = self._filters(x.device)
         return ops.conv2d_2src(x, s, w_tck, w_tkc, self.bias, kh, kw, self.stride[0], self.padding[0], lrelu)
 
 
@@ -272,21 +281,7 @@ class Conv_BN_Act_New(nn.Module):
         the first C channels of a 2C-channel buffer that the decoder level completes (ops.cat_join): no concatenation copy"""
         x = self.conv(x, inputs_type) if self.is_cond else self.conv(x)
         if self.is_bn:
-            if (skip and self.training and x.is_cuda and ops.cat_elision() and isinstance(self.act, nn.Sequential) and len(self.act) == 0):
-                N, C, H, W = x.shape
-                buf = ops.hip.empty_nhwc(N, 2 * C, H, W, x.device, x.dtype)
-                x = self.bn(x, into=(buf, 0))
-                x._mrdis_catbuf = buf
-                return x
-            x = self.bn(x)
-        return self.act(x)
-
-
-    def forward_grouped(self, x, types, skip=False):
-        """forward for G modality labels on the batch-concatenated input (block g: types[g]); BatchNorm statistics per block"""
-        G = len(types)
-        x = self.conv.forward_grouped(x, types)
-        if self.is_bn:
+            G = max(_groups(inputs_type), 1)                  # a grouped call: BatchNorm statistics per sample block
             if (skip and self.training and x.is_cuda and ops.cat_elision() and isinstance(self.act, nn.Sequential) and len(self.act) == 0):
                 N, C, H, W = x.shape
                 buf = ops.hip.empty_nhwc(N, 2 * C, H, W, x.device, x.dtype)
@@ -317,32 +312,13 @@ class Act_Deconv_BN_Concat_New(nn.Module):
         x_up = self.conv(x_up, inputs_type) if self.is_cond else self.conv(x_up)
         if self.is_last:
             return x_up
+        G = max(_groups(inputs_type), 1)                      # a grouped call: BatchNorm statistics per sample block
         if self.is_bn and self.training and x_up.is_cuda and ops.cat_elision() and x_down.dtype == x_up.dtype and isinstance(self.act, nn.Sequential) \
                 and x_down.shape[0] == x_up.shape[0] and x_down.shape[2:] == x_up.shape[2:]:
             Cd, Cu = x_down.shape[1], x_up.shape[1]
             buf = getattr(x_down, '_mrdis_catbuf', None)
             if buf is not None and buf.shape[1] == Cd + Cu and buf.dtype == x_up.dtype:
                 x_down._mrdis_catbuf = None                   # one consumer only: a second decoder reading this skip tensor must not rewrite the upper half
-                x_up = self.bn(x_up, into=(buf, Cd))
-                return ops.cat_join(x_down, x_up, buf)
-        if self.is_bn:
-            x_up = self.bn(x_up)
-        return torch.cat([x_down, x_up], 1)
-
-
-    def forward_grouped(self, x_down, x_up, types):
-        G = len(types)
-        x_up = self.act(x_up)
-        x_up = ops.bilinear(x_up, (2 * x_up.shape[2], 2 * x_up.shape[3]), True)
-        x_up = self.conv.forward_grouped(x_up, types)
-        if self.is_last:
-            return x_up
-        if self.is_bn and self.training and x_up.is_cuda and ops.cat_elision() and x_down.dtype == x_up.dtype and isinstance(self.act, nn.Sequential) \
-                and x_down.shape[0] == x_up.shape[0] and x_down.shape[2:] == x_up.shape[2:]:
-            Cd, Cu = x_down.shape[1], x_up.shape[1]
-            buf = getattr(x_down, '_mrdis_catbuf', None)
-            if buf is not None and buf.shape[1] == Cd + Cu and buf.dtype == x_up.dtype:
-                x_down._mrdis_catbuf = None
                 x_up = self.bn(x_up, into=(buf, Cd), groups=G)
                 return ops.cat_join(x_down, x_up, buf)
         if self.is_bn:
@@ -372,14 +348,6 @@ class AnatomyEncoderEncNew(nn.Module):
         d5 = self.down_5(d4, inputs_type)
         return [d1, d2, d3, d4, d5]
 
-    def forward_grouped(self, x, types):
-        d1 = self.down_1.forward_grouped(x, types, lrelu=True)
-        d2 = self.down_2.forward_grouped(d1, types, skip=True)
-        d3 = self.down_3.forward_grouped(d2, types, skip=True)
-        d4 = self.down_4.forward_grouped(d3, types, skip=True)
-        d5 = self.down_5.forward_grouped(d4, types)
-        return [d1, d2, d3, d4, d5]
-
 
 class AnatomyEncoderDecNew(nn.Module):
     """model.py:2271-2296."""
@@ -405,16 +373,6 @@ class AnatomyEncoderDecNew(nn.Module):
         if not need_out:
             return None, None
         out = self.output(None, u1, inputs_type)
-        return out, out
-
-    def forward_grouped(self, down_list, types, need_out=True):
-        u4 = self.up_4.forward_grouped(down_list[3], down_list[4], types)
-        u3 = self.up_3.forward_grouped(down_list[2], u4, types)
-        u2 = self.up_2.forward_grouped(down_list[1], u3, types)
-        u1 = self.up_1.forward_grouped(down_list[0], u2, types)
-        if not need_out:
-            return None, None
-        out = self.output.forward_grouped(None, u1, types)
         return out, out
 
 
@@ -443,6 +401,10 @@ class ModalityEncoderNew(nn.Module):
         self.log_var = nn.Linear(2 * c, z_size)
 
     def forward(self, xi, si, inputs_type=None):
+        if _groups(inputs_type) and not (self.s_num_ch == 0 and self.is_cond):
+            # encoders that read the anatomy maps (others.mod_enc_s) are not grouped: their first layer is the two-source convolution, which
+            # takes one filter per call (MultimodalModel.compute_modality_encoding runs them per modality)
+            raise ValueError('a grouped call takes a conditional modality encoder that does not read the anatomy maps (s_num_ch == 0)')
         t = (inputs_type,) if self.is_cond else ()
         if self.s_num_ch == 0:
             x = self.conv1(xi, *t, lrelu=True)
@@ -456,18 +418,6 @@ class ModalityEncoderNew(nn.Module):
             x = getattr(self, f'conv{i + 1}')(x, *t, lrelu=True)                              # :2374-2383
         # `view(-1, 5*6*128)` flattens NCHW order (:2396): make that order physical (tiny tensor)
         x = x.contiguous(memory_format=torch.contiguous_format).reshape(x.shape[0], -1).float()     # bf16 storage: the Linears stay fp32
-        x = self.fcs(x)
-        return self.mean(x), self.log_var(x)
-
-    def forward_grouped(self, xi, types):
-        """the G per-modality calls on the batch-concatenated input (the Linear layers are type-independent).  Encoders that read the
-        anatomy maps (others.mod_enc_s) are not grouped: their first layer is the two-source convolution, which takes one filter per call
-        (MultimodalModel.compute_modality_encoding runs them per modality)."""
-        assert self.s_num_ch == 0 and self.is_cond
-        x = xi
-        for i in range(5):
-            x = getattr(self, f'conv{i + 1}').forward_grouped(x, types, lrelu=True)
-        x = x.contiguous(memory_format=torch.contiguous_format).reshape(x.shape[0], -1).float()
         x = self.fcs(x)
         return self.mean(x), self.log_var(x)
 
@@ -488,35 +438,46 @@ class SPADEBlockNew(nn.Module):
         self.beta = conv2d(in_num_ch, in_num_ch, 3, 1, padding=1)
         self.out = conv2d(in_num_ch, out_num_ch, 3, 1, padding=1)
 
+    def _fused_gb(self, inputs_type):
+        """((w_tck, w_tkc), bias) of gamma and beta as ONE convolution with concatenated (mixed) filters, for one batch-constant label:
+        they read the same input with the same geometry -- one pass over si_out forward, one K-doubled pass backward."""
+        hit = ops.lookup_type_row(inputs_type) if ops.mix_cache_active() else None
+        if hit is not None and self.gamma.weight.shape == self.beta.weight.shape:
+            # one of the model's modality labels: gamma and beta are mixed for ALL labels straight into the fused filters
+            table, row = hit
+            allw = ops.cached_mix((id(self), 'gb_all', table.data_ptr(), table._version),
+                                  lambda: ops.mix_pair_fused_all(self.gamma, self.beta, table))
+            bias = ops.cached_mix((id(self), 'gb_bias'), lambda: torch.cat([self.gamma.bias, self.beta.bias]))
+            return (allw[2 * row], allw[2 * row + 1]), bias
+
+        def fused():
+            g_tck, g_tkc = self.gamma.mixed_uniform(inputs_type)
+            b_tck, b_tkc = self.beta.mixed_uniform(inputs_type)
+            return ((torch.cat([g_tck, b_tck], 2), torch.cat([g_tkc, b_tkc], 1)),
+                    torch.cat([self.gamma.bias, self.beta.bias]))
+        return ops.step_cache((id(self), 'gb', inputs_type.data_ptr(), inputs_type._version), fused)
+
     def forward(self, si, zi, inputs_type=None):
+        """A grouped call (inputs_type a list of G labels, see CondConv2d): zi holds G sample blocks of B, block g for inputs_type[g];
+        `si` is the B anatomy maps that EVERY block reads, not G * B rows.  One launch per normalisation kernel, one op per convolution
+        layer (ops.conv2d_grouped).  A single label never goes through the grouped ops: they pick their kernels differently."""
         # the resize depends on (s_i, scale) only, not on the modality type: one resize per step serves
         # every decoder call that uses this s_i (autograd sums the gradients of all uses)
         size = self.input_size
         src = si                                   # the cache entry keeps `src` alive, so id(src) cannot be recycled
         si = ops.step_cache(('bil', id(src), size), lambda: (src, ops.bilinear(src, size, False)))[1]     # :2432/:2441
+        kh, kw = self.gamma.kernel_size
+        if _groups(inputs_type):
+            pad = self.gamma.padding[0]
+            si_out = ops.conv2d_grouped(si, [self.si_layers.mixed_uniform(t) for t in inputs_type], self.si_layers.bias, kh, kw, pad, share_x=True,
+                                        co=self.si_layers.out_channels)
+            fused = [self._fused_gb(t) for t in inputs_type]
+            mix = ops.gb_spade(si_out, zi, [f[0] for f in fused], fused[0][1], self.zi_layers.eps)        # :2440-2446, one node
+            return self.out(mix, inputs_type)
         t = (inputs_type,) if self.is_cond else ()
         si_out = self.si_layers(si, *t)
         if self.is_cond and (si_out.shape[0] == 1 or inputs_type.stride(0) == 0):
-            # gamma and beta read the same input with the same geometry: run them as ONE convolution with
-            # concatenated (mixed) filters -- one pass over si_out forward, one K-doubled pass backward
-            kh, kw = self.gamma.kernel_size
-            key = (id(self), 'gb', inputs_type.data_ptr(), inputs_type._version)
-
-            def fused():
-                g_tck, g_tkc = self.gamma.mixed_uniform(inputs_type)
-                b_tck, b_tkc = self.beta.mixed_uniform(inputs_type)
-                return (torch.cat([g_tck, b_tck], 2), torch.cat([g_tkc, b_tkc], 1),
-                        torch.cat([self.gamma.bias, self.beta.bias]))
-            hit = ops.lookup_type_row(inputs_type) if ops.mix_cache_active() else None
-            if hit is not None and self.gamma.weight.shape == self.beta.weight.shape:
-                # one of the model's modality labels: gamma and beta are mixed for ALL labels straight into the fused filters
-                table, row = hit
-                allw = ops.cached_mix((id(self), 'gb_all', table.data_ptr(), table._version),
-                                      lambda: ops.mix_pair_fused_all(self.gamma, self.beta, table))
-                bias = ops.cached_mix((id(self), 'gb_bias'), lambda: torch.cat([self.gamma.bias, self.beta.bias]))
-                w_tck, w_tkc = allw[2 * row], allw[2 * row + 1]
-            else:
-                w_tck, w_tkc, bias = ops.step_cache(key, fused)
+            (w_tck, w_tkc), bias = self._fused_gb(inputs_type)
             if ((kh, kw) == (3, 3) and self.gamma.padding[0] == 1 and type(si_out) is torch.Tensor and si_out.is_cuda
                     and ops.mix_cache_active() and torch.is_grad_enabled()):
                 mix = ops.gb_spade(si_out, zi, [(w_tck, w_tkc)], bias, self.zi_layers.eps)            # :2440 + :2446, one node
@@ -528,33 +489,6 @@ class SPADEBlockNew(nn.Module):
             beta = self.beta(si_out, *t)
             mix = ops.instnorm_spade(zi, gamma, beta, self.zi_layers.eps)
         return self.out(mix, *t)
-
-    def _fused_gb(self, inputs_type):
-        """((w_tck, w_tkc), bias) of the fused gamma | beta convolution for one modality label (see forward)."""
-        hit = ops.lookup_type_row(inputs_type) if ops.mix_cache_active() else None
-        if hit is not None and self.gamma.weight.shape == self.beta.weight.shape:
-            table, row = hit
-            allw = ops.cached_mix((id(self), 'gb_all', table.data_ptr(), table._version),
-                                  lambda: ops.mix_pair_fused_all(self.gamma, self.beta, table))
-            bias = ops.cached_mix((id(self), 'gb_bias'), lambda: torch.cat([self.gamma.bias, self.beta.bias]))
-            return (allw[2 * row], allw[2 * row + 1]), bias
-        g_tck, g_tkc = self.gamma.mixed_uniform(inputs_type)
-        b_tck, b_tkc = self.beta.mixed_uniform(inputs_type)
-        return (torch.cat([g_tck, b_tck], 2), torch.cat([g_tkc, b_tkc], 1)), torch.cat([self.gamma.bias, self.beta.bias])
-
-    def forward_grouped(self, si, z_cat, types):
-        """The block for G modality labels at once: z_cat holds G sample blocks of B (block g belongs to types[g]), `si` the B anatomy
-        maps every block reads.  One launch per normalisation kernel, one op per convolution layer (ops.conv2d_grouped)."""
-        size = self.input_size
-        src = si
-        si = ops.step_cache(('bil', id(src), size), lambda: (src, ops.bilinear(src, size, False)))[1]
-        kh, kw = self.gamma.kernel_size
-        pad = self.gamma.padding[0]
-        si_out = ops.conv2d_grouped(si, [self.si_layers.mixed_uniform(t) for t in types], self.si_layers.bias, kh, kw, pad, share_x=True,
-                                    co=self.si_layers.out_channels)
-        fused = [self._fused_gb(t) for t in types]
-        mix = ops.gb_spade(si_out, z_cat, [f[0] for f in fused], fused[0][1], self.zi_layers.eps)     # :2440-2446, one node
-        return ops.conv2d_grouped(mix, [self.out.mixed_uniform(t) for t in types], self.out.bias, kh, kw, pad, co=self.out.out_channels)
 
 
 def _up2(x, norm=None):
@@ -613,16 +547,8 @@ class SPADENewNotShared(nn.Module):
         x = self.out(x, inputs_type) if self.is_cond else self.out(x)
         return self.out_act(x)
 
-    def forward_grouped(self, si, z_cat, types):
-        """forward for G modality labels on batch-concatenated inputs (see SPADEBlockNew.forward_grouped)."""
-        x = self.sp4.forward_grouped(si, z_cat, types)
-        x = self.sp5.forward_grouped(si, _up2(x, self.sp5.zi_layers), types)
-        x = self.sp6.forward_grouped(si, _up2(x, self.sp6.zi_layers), types)
-        kh, kw = self.out.kernel_size
-        x = ops.conv2d_grouped(x, [self.out.mixed_uniform(t) for t in types], self.out.bias, kh, kw, self.out.padding[0], co=self.out.out_channels)
-        return self.out_act(x)
-
     def grouped_ok(self):
+        """whether forward takes a grouped call (a list of labels, see SPADEBlockNew.forward)"""
         blocks = (self.sp4, self.sp5, self.sp6)
         return (self.is_cond and all(b.si_layers.stride == (1, 1) and b.gamma.kernel_size == b.out.kernel_size == b.si_layers.kernel_size
                                      and b.gamma.weight.shape == b.beta.weight.shape for b in blocks)
@@ -1172,8 +1098,8 @@ class MultimodalModel(nn.Module):
             M, B = self.modality_num, inputs_list[0].shape[0]
             types = [self._type(i, B) for i in range(M)]
             x = self._cat_inputs(inputs_list)
-            feats = self.anatomy_encoder_enc_list[0].forward_grouped(x, types)
-            si, _ = self.anatomy_encoder_dec.forward_grouped(feats, types, need_out=need_maps)
+            feats = self.anatomy_encoder_enc_list[0](x, types)
+            si, _ = self.anatomy_encoder_dec(feats, types, need_out=need_maps)
             if not need_maps:
                 return [None] * M
             m_all = mask_img.repeat(M, 1, 1) if (mask_img is not None and self.variant.endswith('softmax_remove_mask')) else mask_img
@@ -1200,7 +1126,7 @@ class MultimodalModel(nn.Module):
         B = inputs_list[0].shape[0]
         if self._encoders_grouped() and self.modality_encoder_list[0].s_num_ch == 0:
             M = self.modality_num
-            mu, lv = self.modality_encoder_list[0].forward_grouped(self._cat_inputs(inputs_list), [self._type(i, B) for i in range(M)])
+            mu, lv = self.modality_encoder_list[0](self._cat_inputs(inputs_list), None, [self._type(i, B) for i in range(M)])
             for i in range(M):
                 mu_i, lv_i = mu[i * B:(i + 1) * B], lv[i * B:(i + 1) * B]
                 zi_list.append(self.sample(mu_i, lv_i) if phase == 'train' else mu_i)       # eps drawn per modality, in order (:3159-3162)
@@ -1246,8 +1172,8 @@ class MultimodalModel(nn.Module):
     def _notshared_all(self, si_list, zi_list):
         """Every (decoder i, label j) reconstruction of the step, or None when the grouped path does not apply.  Decoder i serves
         (s_i, z_j) for all M labels j (model.py:3200-3203, 3219-3224): run as ONE batch-concatenated call per decoder, sample block j
-        with the kernels mixed for label j (SPADENewNotShared.forward_grouped) -- the normalisation / resize kernels and the Python
-        op dispatches of the four calls collapse into one."""
+        with the kernels mixed for label j (SPADENewNotShared.forward with the list of labels) -- the normalisation / resize kernels and
+        the Python op dispatches of the four calls collapse into one."""
         decs = [self.input_decoder_list[i] for i in range(self.modality_num)]
         if not (ops.grouped_applies() and all(hasattr(d, 'grouped_ok') and d.grouped_ok() for d in decs)):
             return None
@@ -1264,7 +1190,7 @@ class MultimodalModel(nn.Module):
                 sts = [getattr(mids[(i, j)], '_mrdis_in_stats', None) for j in range(M)]
                 if all(s_ is not None and s_[2] == sts[0][2] for s_ in sts):
                     z_cat._mrdis_in_stats = (torch.cat([s_[0] for s_ in sts]), torch.cat([s_[1] for s_ in sts]), sts[0][2])
-                y = self.input_decoder_list[i].forward_grouped(si_list[i], z_cat, types)
+                y = self.input_decoder_list[i](si_list[i], z_cat, types)
                 for j, part in enumerate(ops.split_batch(y, M)):
                     outs[(i, j)] = part
             return (list(si_list), list(zi_list), outs)
@@ -1292,47 +1218,31 @@ class MultimodalModel(nn.Module):
             return (list(si_list), list(zi_list), outs)
         return ops.step_cache(key, make)[2]
 
-    # ---- model.py:3187-3203
-    def reconstruct_input_si_zi(self, si_list, zi_list):
-        out = []
-        B = si_list[0].shape[0]
-        if self.shared_inp_dec:                                            # :3195
-            allo = self._shared_dec_all(si_list, zi_list)
-            if allo is not None:
-                return [allo[(i, i)] for i in range(self.modality_num)]
-            self.premix('dec')
-            return [self.input_decoder_list[0](si_list[i], zi_list[i], self._type(i, B)) for i in range(self.modality_num)]
-        allo = self._notshared_all(si_list, zi_list)
+    def _reconstruct(self, si_list, zi_list, pairs):
+        """decoder i on (s_i, z_j, label j) for the (i, j) of `pairs` (i-major): from the step's all-pairs pass where the grouped path
+        applies, else call by call"""
+        allo = self._shared_dec_all(si_list, zi_list) if self.shared_inp_dec else self._notshared_all(si_list, zi_list)
         if allo is not None:
-            return [allo[(i, i)] for i in range(self.modality_num)]
+            return [allo[p] for p in pairs]
+        B = si_list[0].shape[0]
+        if self.shared_inp_dec:                                            # :3195, :3216
+            self.premix('dec')
+            return [self.input_decoder_list[0](si_list[i], zi_list[j], self._type(j, B)) for i, j in pairs]
         mids = self._shared_mids(si_list, zi_list)
+        out = []
         for i in range(self.modality_num):
             self.premix(f'dec{i}')
-            out.append(self.input_decoder_list[i](si_list[i], mids[(i, i)], self._type(i, B)))
+            out += [self.input_decoder_list[i](si_list[i], mids[(i, j)], self._type(j, B)) for a, j in pairs if a == i]
         return out
+
+    # ---- model.py:3187-3203
+    def reconstruct_input_si_zi(self, si_list, zi_list):
+        return self._reconstruct(si_list, zi_list, [(i, i) for i in range(self.modality_num)])
 
     # ---- model.py:3205-3224: decoder index i, type j, z_j
     def reconstruct_input_si_zj(self, si_list, zi_list):
-        out = []
-        B = si_list[0].shape[0]
         M = self.modality_num
-        if self.shared_inp_dec:                                            # :3216
-            allo = self._shared_dec_all(si_list, zi_list)
-            if allo is not None:
-                return [allo[(i, j)] for i in range(M) for j in range(M) if i != j]
-            self.premix('dec')
-            return [self.input_decoder_list[0](si_list[i], zi_list[j], self._type(j, B)) for i in range(M) for j in range(M) if i != j]
-        allo = self._notshared_all(si_list, zi_list)
-        if allo is not None:
-            return [allo[(i, j)] for i in range(self.modality_num) for j in range(self.modality_num) if i != j]
-        mids = self._shared_mids(si_list, zi_list)
-        for i in range(self.modality_num):
-            self.premix(f'dec{i}')
-            for j in range(self.modality_num):
-                if i == j:
-                    continue
-                out.append(self.input_decoder_list[i](si_list[i], mids[(i, j)], self._type(j, B)))
-        return out
+        return self._reconstruct(si_list, zi_list, [(i, j) for i in range(M) for j in range(M) if i != j])
 
     # ---- model.py:3230-3258.  QUIRK: `si_cat[mask == 1]` flattens (batch, modality) into ONE axis, so "fusion" is a
     # mean (max, or mean / max / min concatenated) over a singleton axis: every present (b, m) anatomy map becomes its own sample and the output has sum(mask)

@@ -1,6 +1,7 @@
 """GPU parity of the module mirror + training step: (1) against the golden vectors that
 oracle/gen_golden.py captured from the real reference at 160x192, (2) against the CPU oracle on
 seeded inputs at sizes the reference itself cannot run (64x64, 96x128)."""
+import copy
 import json
 import os
 
@@ -407,8 +408,8 @@ def test_train_step_vs_oracle_other_sizes(mrdis, B, M, H, W, drop, adv):
 
 @pytest.mark.parametrize('mode', ['f32', 'bf16m', 'bf16'])
 def test_grouped_decoder_matches_per_type_calls(mrdis, mode):
-    """The not-shared decoders run batch-concatenated over the modality labels (SPADENewNotShared.forward_grouped, ops.conv2d_grouped)
-    launch the same kernels per sample block as the 16 per-type calls: loss, reconstructions and parameter gradients agree to rounding
+    """The not-shared decoders run batch-concatenated over the modality labels (SPADENewNotShared.forward with the list of labels,
+    ops.conv2d_grouped) launch the same kernels per sample block as the 16 per-type calls: loss, reconstructions and parameter gradients agree to rounding
     of the gradient sums (the order in which the four labels' contributions meet changes)."""
     B, M, H, W = 2, 4, 64, 96
     cfg = _cfg(mrdis, M, H, W, B, adv=True)
@@ -443,6 +444,70 @@ def test_grouped_decoder_matches_per_type_calls(mrdis, mode):
             # norm (biases in front of a BatchNorm have an analytically zero gradient: pure rounding noise, skipped).  The second term is
             # the noise floor of the handful of three-element routing weights deep in the encoders, in units of the whole gradient's norm.
             assert float((a - b).norm()) <= 3e-2 * float(b.norm()) + 2e-5 * tot, (n, float((a - b).norm()), float(b.norm()), tot)
+
+
+def test_grouped_call_matches_per_label_calls(mrdis):
+    """A block called ONCE with the list [t0, t1] on G = 2 batch-concatenated sample blocks (the `inputs_type` convention documented at
+    CondConv2d) against a deep copy called once per label on the two halves; for the SPADE block both read the same B anatomy maps.
+    Train mode, inside ops.mix_cache() with a registered two-row label table (the state of a training step), B = 2 per block, 64x64.
+    Compared: outputs, BatchNorm running statistics, num_batches_tracked after flush_batch_counters() (2 on both sides), and the
+    input / parameter gradients of a fixed random cotangent.  Every comparison is torch.equal: the grouped ops launch the same kernels
+    per sample block and the library's reductions have a fixed order (the separate grouped methods that the list form replaced met
+    every one of these bit for bit at these shapes, measured before they were merged).
+    A modality encoder that reads the anatomy maps (s_num_ch != 0) refuses a grouped call with ValueError."""
+    ops = mrdis.ops
+    B, G = 2, 2
+    # (name, constructor, shapes of the inputs that hold G sample blocks, shapes of the inputs every block reads, call)
+    cases = [('conv_bn_act', lambda: mrdis.Conv_BN_Act_New(8, 16, is_cond=True), [(G * B, 8, 64, 64)], [],
+              lambda m, blk, sh, t: m(blk[0], t, skip=True)),
+             ('deconv_bn_cat', lambda: mrdis.Act_Deconv_BN_Concat_New(16, 8, is_cond=True), [(G * B, 8, 64, 64), (G * B, 16, 32, 32)], [],
+              lambda m, blk, sh, t: m(blk[0], blk[1], t)),
+             ('spade', lambda: mrdis.SPADEBlockNew((16, 16), 32, 32, 4, is_cond=True), [(G * B, 32, 16, 16)], [(B, 4, 64, 64)],
+              lambda m, blk, sh, t: m(sh[0], blk[0], t))]
+    table = ops.register_type_table(torch.tensor([[1.], [2.]], device=DEV))
+    types = [table[g:g + 1].expand(B, 1) for g in range(G)]
+    bad = []
+
+    def check(case, what, got, ref):
+        same = torch.equal(got, ref)
+        print(f'{case} {what}: equal={same} err={float((got.double() - ref.double()).norm()):.3e} ||ref||={float(ref.double().norm()):.3e}')
+        if not same:
+            bad.append((case, what))
+
+    for ci, (case, make, blocked, shared, call) in enumerate(cases):
+        torch.manual_seed(200 + ci)
+        m = make().to(DEV).train()
+        ref = copy.deepcopy(m)
+        # two sets of leaves with the same values: [0] for the grouped call, [1] for the per-label calls
+        blk = [[cl(seeded(s, 20 + 10 * ci + k)).requires_grad_(True) for k, s in enumerate(blocked)] for _ in range(2)]
+        sh = [[cl(torch.softmax(seeded(s, 25 + 10 * ci + k), 1)).requires_grad_(True) for k, s in enumerate(shared)] for _ in range(2)]
+        with ops.mix_cache():
+            y = call(m, blk[0], sh[0], types)
+            cot = cl(seeded(tuple(y.shape), 29 + 10 * ci))
+            y.backward(cot)
+            ys = [call(ref, [x[g * B:(g + 1) * B] for x in blk[1]], sh[1], types[g]) for g in range(G)]
+            torch.autograd.backward(ys, [cot[g * B:(g + 1) * B] for g in range(G)])
+        mrdis.model.flush_batch_counters()
+        check(case, 'y', y.detach(), torch.cat([t.detach() for t in ys], 0))
+        ref_mods = dict(ref.named_modules())
+        bns = [(n, a, ref_mods[n]) for n, a in m.named_modules() if isinstance(a, mrdis.BatchNorm2d)]
+        assert len(bns) == (0 if case == 'spade' else 1)
+        for n, a, b in bns:
+            check(case, f'{n}.running_mean', a.running_mean, b.running_mean)
+            check(case, f'{n}.running_var', a.running_var, b.running_var)
+            assert int(a.num_batches_tracked) == int(b.num_batches_tracked) == G, (case, n)
+        grads = [(f'd_in{k}', a.grad, b.grad) for k, (a, b) in enumerate(zip(blk[0] + sh[0], blk[1] + sh[1]))]
+        pm = dict(m.named_parameters())
+        grads += [(n, pm[n].grad, p.grad) for n, p in ref.named_parameters()]
+        missing = [(case, n) for n, a, b in grads if a is None or b is None]
+        assert not missing, missing                      # every input and every parameter of these blocks gets a gradient
+        for n, a, b in grads:
+            check(case, n, a, b)
+    assert not bad, bad
+
+    enc = mrdis.ModalityEncoderNew(img_num_ch=7, s_num_ch=4, first_num_ch=16, z_size=16, is_cond=True, feat_hw=4).to(DEV)
+    with pytest.raises(ValueError, match='grouped'):
+        enc(cl(seeded((G * B, 7, 64, 64), 90)), cl(torch.softmax(seeded((G * B, 4, 64, 64), 91), 1)), types)
 
 
 @pytest.mark.parametrize('mode', ['f32', 'bf16'])

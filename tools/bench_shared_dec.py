@@ -2,7 +2,7 @@
 (B = 32, M = 4, 256x256, adversarial loss on), eager and graph-replayed, against the shipped config (split decoders) on the same box:
 the configurations are built once and timed in alternating rounds after their warm-up, so clock and thermal drift hit all of them alike.
 Also times the alternative decode that DESIGN.md 4.15 weighs: the second half (sp4 - sp6, out) as ONE grouped call per layer over the M
-labels on the batch-concatenated maps (SPADENewNotShared.forward_grouped with the anatomy maps shared), which needs the M label blocks
+labels on the batch-concatenated maps (SPADENewNotShared.forward with the list of labels, the anatomy maps shared), which needs the M label blocks
 of the sp4 input concatenated first.  Writes profiles/shared_dec_bench.txt.
 
     python tools/bench_shared_dec.py [--steps 10 --warmup 3 --rounds 3 --out profiles/shared_dec_bench.txt]
@@ -41,7 +41,7 @@ def grouped_tail_decode(model):
             s_cat = torch.cat(list(si_list), 0)
             types = [model._type(j, M * B) for j in range(M)]
             z_cat = torch.cat([dec.head(s_cat, zi_list[j].repeat(M, 1), types[j]) for j in range(M)], 0)
-            y = mrdis.SPADENewNotShared.forward_grouped(dec, s_cat, z_cat, types)
+            y = mrdis.SPADENewNotShared.forward(dec, s_cat, z_cat, types)
             outs = {}
             for j, blk in enumerate(ops.split_batch(y, M)):
                 for i, part in enumerate(ops.split_batch(blk, M)):
