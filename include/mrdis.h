@@ -757,6 +757,39 @@ int mrdis_rgate_fwd(const float* x, int ldx, const float* alpha, float* out, int
 int mrdis_rgate_bwd(const float* dy, int lddy, const float* x, int ldx, const float* alpha, float* dx, int lddx, float* rsum,
                     int B, int H, int W, int C, void* stream);
 
+/* ---- preprocessing of raw scans into store volumes (data_preprocessing_BraTS.py:79-96, commented out there; the same rule is live in
+ * data_preprocessing_ZeroDose.py:124-134), csrc/mrdis_prep.hip.  raw: the voxel array of a NIfTI-1 file in its own dtype (the NIfTI datatype
+ * codes below), voxel (h, w, d) at raw[h stride_h + w stride_w + d stride_d] (element strides >= 1; the file's own order is stride_h = 1,
+ * stride_w = H, stride_d = H W, and it is the fast path; any other triple is only correct).  v = (double)raw * slope + inter in float64, NaN -> 0.
+ * The crop removes h0 / h1 voxels at the low / high end of H and w0 / w1 of W; the depth is kept whole: H' = H - h0 - h1, W' = W - w0 - w1.
+ * Each of H, W, D in 1 .. 1024, H W D < 2^31, H' >= 1, W' >= 1; anything else: MRDIS_EUNSUPPORTED before any launch.
+ * mrdis_prep_stats: stats (5 float64, device) = { n = #(v > 0), sum = sum v, ssd = sum_{v > 0} (v - sum / (n + 1))^2 } over the cropped volume,
+ * { vmax = max v with NaN ignored, nan_inner = #NaN with d in [d_lo, D - d_hi) } over the uncropped one.  Four launches (partial sums and
+ * their fixed-order sum, twice: ssd needs n and sum), no atomics: two runs give the same bits.  workspace: >= mrdis_prep_workspace bytes
+ * (0 for an unsupported geometry), 8-byte aligned, used by this call only.
+ * mrdis_prep_write: reads stats from the device (no host synchronisation in between) and writes fp32, rounded once at the store, as
+ * (D, H', W') (MRDIS_PREP_DHW) or (H', W', D) (MRDIS_PREP_HWD), dense.  MRDIS_PREP_ZSCORE: (v - norm) / (std + 1e-8) with norm = sum / (n + 1),
+ * std = sqrt(ssd / (n + 1)), and -10 where v <= 0; MRDIS_PREP_MEAN: v / norm; MRDIS_PREP_LABEL: v (stats is not read).  One launch.
+ * Launch counter families "prepstats" / "prepwrite": one count per call.                                                                   */
+#define MRDIS_PREP_U8 2
+#define MRDIS_PREP_I16 4
+#define MRDIS_PREP_I32 8
+#define MRDIS_PREP_F32 16
+#define MRDIS_PREP_F64 64
+#define MRDIS_PREP_U16 512
+#define MRDIS_PREP_ZSCORE 0
+#define MRDIS_PREP_MEAN 1
+#define MRDIS_PREP_LABEL 2
+#define MRDIS_PREP_DHW 0
+#define MRDIS_PREP_HWD 1
+size_t mrdis_prep_workspace(int H, int W, int D);
+int mrdis_prep_stats(const void* raw, int dtype, long long stride_h, long long stride_w, long long stride_d, int H, int W, int D,
+                     int h0, int h1, int w0, int w1, int d_lo, int d_hi, double slope, double inter, double* stats,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int mrdis_prep_write(const void* raw, int dtype, long long stride_h, long long stride_w, long long stride_d, int H, int W, int D,
+                     int h0, int h1, int w0, int w1, double slope, double inter, const double* stats, int kind, int layout,
+                     float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -44,6 +44,23 @@ class VolumeStore:
             raise ValueError(f'{key}: shape {tuple(a.shape)} != {self.shape}')
         self.vols[key] = a.permute(2, 0, 1).contiguous().to(self.device)
 
+    def _check_device_volume(self, key, vol, shape_hwd):
+        """the shape check of `add` for a volume that is already on the device, in the store's own layout"""
+        same = isinstance(vol, torch.Tensor) and vol.device.type == self.device.type and (vol.device.index or 0) == (self.device.index or 0)
+        if not same or vol.dtype != torch.float32 or not vol.is_contiguous():
+            raise ValueError(f'{key}: a contiguous fp32 tensor on {self.device} wanted, got {getattr(vol, "dtype", type(vol))} on {getattr(vol, "device", "the host")}')
+        if vol.dim() != 3:
+            raise ValueError('volume must be (H, W, D)')
+        if self.shape is None:
+            self.shape = tuple(shape_hwd)
+        elif tuple(shape_hwd) != self.shape:
+            raise ValueError(f'{key}: shape {tuple(shape_hwd)} != {self.shape}')
+
+    def add_device(self, key, vol_dhw):
+        """key = 'subject/contrast'; an fp32 device tensor already laid out as the store keeps it, (D, H, W) (prep.prep_write layout 'dhw'): kept as it is."""
+        self._check_device_volume(key, vol_dhw, tuple(vol_dhw.shape[i] for i in (1, 2, 0)) if getattr(vol_dhw, 'ndim', 0) == 3 else ())
+        self.vols[key] = vol_dhw
+
     @classmethod
     def from_arrays(cls, arrays, device):
         st = cls(device)

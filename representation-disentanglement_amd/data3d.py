@@ -49,6 +49,12 @@ class VolumeStore3D(VolumeStore):
         self.vols[key] = a.to(self.device)
         self._mins.clear()
 
+    def add_device(self, key, vol_hwd):
+        """key = 'subject/contrast'; an fp32 device tensor already laid out as the store keeps it, (H, W, D) (prep.prep_write layout 'hwd'): kept as it is."""
+        self._check_device_volume(key, vol_hwd, tuple(vol_hwd.shape) if getattr(vol_hwd, 'ndim', 0) == 3 else ())
+        self.vols[key] = vol_hwd
+        self._mins.clear()
+
     def crop_min_ptr(self, key, z0, Dz):
         """device address of min(vol[:, :, z0:z0+Dz]) (fp32), 0 for a key the store does not hold.  No host read, no sync."""
         ent = self._mins.get((z0, Dz))

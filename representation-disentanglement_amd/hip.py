@@ -145,6 +145,9 @@ _SIGS = {
     'mrdis_symdiff_bwd': (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_rgate_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_rgate_bwd': (_I, [_P, _I, _P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'mrdis_prep_workspace': (_Z, [_I, _I, _I]),
+    'mrdis_prep_stats': (_I, [_P, _I, _L, _L, _L] + [_I] * 9 + [_c.c_double, _c.c_double, _P, _P, _Z, _P]),
+    'mrdis_prep_write': (_I, [_P, _I, _L, _L, _L] + [_I] * 7 + [_c.c_double, _c.c_double, _P, _I, _I, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -241,6 +244,9 @@ SURFDIST_FAMILIES = ('regsurf', 'edt', 'surfhist')
 # connected components of label volumes and their clean-up (csrc/mrdis_cc.hip): 'cclabel' counts one per LAUNCH of a labelling pass (three per
 # mrdis_cc_label call, whatever B, shape and content), 'ccclean' one per mrdis_cc_clean call.
 CC_FAMILIES = ('cclabel', 'ccclean')
+# preprocessing of raw scans into store volumes (csrc/mrdis_prep.hip): 'prepstats' counts one per mrdis_prep_stats call (four launches),
+# 'prepwrite' one per mrdis_prep_write call.
+PREP_FAMILIES = ('prepstats', 'prepwrite')
 # the dispatch choices of the statistics, norm and resize entry points (csrc/mrdis_elem.hip), host-side counts only: which partial-sum kernel a
 # statistics pass took ('stat_vec' | 'stat_scalar' | 'stat_interp': one per pass), the route of mrdis_instnorm_spade_bwd_up2 (one per call), the
 # kernel of mrdis_bilinear_fwd / _bwd (one per call), and 'elem_v1': an element-wise pass that took its one-channel-per-thread instantiation.
@@ -289,7 +295,7 @@ def launch_counts(reset=False, elem=False):
     elem=True adds ELEM_FAMILIES: they count dispatch choices of passes that run beside almost every counted kernel (the statistics in front of a fused
     SPADE convolution, say), so callers that assert "this family and no other" over the whole dictionary only see them when they ask."""
     lib = load()
-    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES
+    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES + PREP_FAMILIES
     out ={f: int(lib.mrdis_launch_count(f.encode())) for f in fams + (ELEM_FAMILIES if elem else ())}
     if reset:
         lib.mrdis_launch_count_reset()
@@ -1458,6 +1464,69 @@ def synth_finish(acc, cnt, fill=0.0):
     out = torch.empty((H, W, D), dtype=torch.float32, device=acc.device)
     _chk(lib.mrdis_synth_finish(_ptr(acc), _ptr(cnt), _ptr(out), D, H, W, float(fill), _stream()), 'synth_finish')
     return acc, out
+
+
+PREP_DTYPES = {torch.uint8: 2, torch.int16: 4, torch.int32: 8, torch.float32: 16, torch.float64: 64, torch.uint16: 512}     # include/mrdis.h MRDIS_PREP_U8 ...: the NIfTI-1 datatype codes
+PREP_KINDS = ('zscore', 'mean', 'label')          # MRDIS_PREP_ZSCORE | _MEAN | _LABEL, in this order
+PREP_LAYOUTS = ('dhw', 'hwd')                     # MRDIS_PREP_DHW | _HWD, in this order
+PREP_ORDERS = ('file', 'c')                       # raw is (D, W, H) as a NIfTI file holds it | (H, W, D)
+PREP_MAX_EXTENT = 1024                            # each of H, W, D
+
+
+def _prep_view(raw, crop, order, what):
+    """-> (dtype code, (stride_h, stride_w, stride_d), (H, W, D), (h0, h1, w0, w1)) of a raw device volume; MrdisError for anything the kernels do not
+    take, 'unsupported geometry' for extents and crops outside include/mrdis.h's limits."""
+    if not isinstance(raw, torch.Tensor) or raw.dim() != 3 or raw.dtype not in PREP_DTYPES or not raw.is_cuda:
+        raise MrdisError(f'{what}: raw must be a 3-D device tensor of dtype uint8, int16, uint16, int32, float32 or float64, got '
+                         f'{getattr(raw, "dtype", type(raw))} {tuple(getattr(raw, "shape", ()))} on {getattr(raw, "device", "the host")}')
+    if order not in PREP_ORDERS:
+        raise MrdisError(f'{what}: order {order!r}: one of {PREP_ORDERS}')
+    (H, W, D), (sh, sw, sd) = (raw.shape[::-1], raw.stride()[::-1]) if order == 'file' else (raw.shape, raw.stride())
+    try:
+        (h0, h1), (w0, w1) = [[int(v) for v in c] for c in crop]
+    except (TypeError, ValueError):
+        raise MrdisError(f'{what}: crop {crop!r}: ((h0, h1), (w0, w1))') from None
+    if min(sh, sw, sd) < 1:
+        raise MrdisError(f'{what}: raw needs positive strides, got {raw.stride()}')
+    if not (1 <= min(H, W, D) and max(H, W, D) <= PREP_MAX_EXTENT and H * W * D < 2 ** 31 and min(h0, h1, w0, w1) >= 0 and h0 + h1 < H and w0 + w1 < W):
+        raise MrdisError(f'{what}: unsupported geometry: (H, W, D) = {(H, W, D)} with crop {((h0, h1), (w0, w1))}; each extent in 1 .. {PREP_MAX_EXTENT}, '
+                         f'H W D < 2^31, and the crop must leave at least one voxel per axis')
+    return PREP_DTYPES[raw.dtype], (sh, sw, sd), (H, W, D), (h0, h1, w0, w1)
+
+
+def prep_stats(raw, crop, slope=1.0, inter=0.0, order='file', inner=(50, 50)):
+    """(5,) float64 device tensor (n, sum, ssd, vmax, nan_inner) of a raw volume (include/mrdis.h mrdis_prep_stats): n, sum and ssd over the volume
+    cropped by crop = ((h0, h1), (w0, w1)), vmax and the NaN count of the planes [inner[0], D - inner[1]) over the whole one.  raw: a device tensor in
+    the file's order (D, W, H) (order 'file') or (H, W, D) (order 'c'), any strides.  No host read."""
+    lib = load()
+    code, strides, (H, W, D), cr = _prep_view(raw, crop, order, 'prep_stats')
+    d_lo, d_hi = int(inner[0]), int(inner[1])
+    stats = torch.empty(5, dtype=torch.float64, device=raw.device)
+    nws = int(lib.mrdis_prep_workspace(H, W, D))
+    ws = _ws(nws, raw.device)
+    _chk(lib.mrdis_prep_stats(_ptr(raw), code, *strides, H, W, D, *cr, d_lo, d_hi, float(slope), float(inter), _ptr(stats), _ptr(ws), nws, _stream()), 'prep_stats')
+    return stats
+
+
+def prep_write(raw, stats, kind, crop, layout, slope=1.0, inter=0.0, order='file', out=None):
+    """the fp32 store volume of a raw one (include/mrdis.h mrdis_prep_write): kind 'zscore' | 'mean' | 'label', layout 'dhw' -> (D, H', W') (VolumeStore) |
+    'hwd' -> (H', W', D) (VolumeStore3D); stats: what prep_stats gave for the same raw, crop, slope and inter, read on the device.  `out`: a contiguous
+    fp32 tensor of that shape to write into.  No host read."""
+    lib = load()
+    code, strides, (H, W, D), cr = _prep_view(raw, crop, order, 'prep_write')
+    if kind not in PREP_KINDS or layout not in PREP_LAYOUTS:
+        raise MrdisError(f'prep_write: kind {kind!r} must be one of {PREP_KINDS} and layout {layout!r} one of {PREP_LAYOUTS}')
+    if not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or tuple(stats.shape) != (5,) or not stats.is_contiguous() or stats.device != raw.device:
+        raise MrdisError(f'prep_write: stats must be the contiguous (5,) float64 tensor of prep_stats on {raw.device}')
+    Hc, Wc = H - cr[0] - cr[1], W - cr[2] - cr[3]
+    shape = (D, Hc, Wc) if layout == 'dhw' else (Hc, Wc, D)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=raw.device)
+    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != raw.device:
+        raise MrdisError(f'prep_write: out must be a contiguous fp32 {shape} tensor on {raw.device}, got {out.dtype} {tuple(out.shape)} strides {out.stride()}')
+    _chk(lib.mrdis_prep_write(_ptr(raw), code, *strides, H, W, D, *cr, float(slope), float(inter), _ptr(stats), PREP_KINDS.index(kind),
+                              PREP_LAYOUTS.index(layout), _ptr(out), _stream()), 'prep_write')
+    return out
 
 
 def seg2d_label_planes(views, flips, planes, s0, relabel=False):

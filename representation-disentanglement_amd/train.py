@@ -26,7 +26,9 @@ the validation statistics summed over the ranks BEFORE `scheduler.step` (every r
 lr and the same `is_best`), and `config.*`, `stat.csv`, `epochNNN.pth.tar`, `model_best.pth.tar` written by rank 0 only, with a
 barrier behind the writes.  BatchNorm statistics stay per replica (the reference has no SyncBN); rank 0's are checkpointed.
 What differs, deliberately: no per-iteration `.item()` syncs (device accumulators, one D2H copy per epoch);
-`data_source: synthetic` (added key) builds BraTS-shaped volumes in HBM instead of opening the private h5 file;
+`data_source: synthetic` (added key) builds BraTS-shaped volumes in HBM instead of opening the private h5 file, and
+`data_source: raw` builds the store from the NIfTI files of a BraTS download under `raw_path` (prep.py; `raw_slices`, default
+[50, 105], and `raw_crop`, default [[40, 40], [24, 24]], are the slice range of the fold lists it writes and the crop);
 `16 // batch_size` is guarded for batch_size > 16 (:282 divides by zero there).
 """
 import copy
@@ -40,6 +42,7 @@ import torch.distributed as dist
 import yaml
 
 from .data import BatchLoader, SliceDataset, VolumeStore, load_idx_list
+from .prep import BRATS_CROP, build_store_from_raw, ensure_fold_lists
 from .trainer import (DEFAULT_CONFIG, LOSS_KEYS, EVAL_INFOS, EvalStep, eval_metric_keys, ZGallery, build_z_gallery, TrainStep, make_train_step, build_model, derive_config, load_checkpoint_model,
                       load_config_yaml, save_checkpoint)
 
@@ -253,6 +256,17 @@ def make_loaders(config):
         store, subj, idx = synthetic_store(config, dev)
         n = len(subj); a, b = int(0.6 * n), int(0.8 * n)
         split = {'train': (subj[:a], idx[:a]), 'val': (subj[a:b], idx[a:b]), 'test': (subj[b:], idx[b:])}
+    elif config.get('data_source', 'h5') == 'raw':
+        # the NIfTI files of a BraTS download under `raw_path`, preprocessed on the device (prep.py); fold lists that `data_path` lacks are written first
+        if name != 'BraTS':
+            raise NotImplementedError(f'data_source raw: only the BraTS directory naming is restated (prep.subject_files), not {name}')
+        if not config.get('raw_path'):
+            raise ValueError('data_source raw needs raw_path: the directory of the subjects')
+        store, kept = build_store_from_raw(config['raw_path'], dev, norm_type=config['norm_type'], crop=config.get('raw_crop', BRATS_CROP),
+                                           contrasts=config['contrast_list'])
+        lists = {s: FOLD_FILES[name][2].format(f=config['fold'], s=s) for s in ('train', 'val', 'test')}
+        ensure_fold_lists(kept, config['data_path'], lists.values(), dataset=name, slices=config.get('raw_slices', [50, 105]))
+        split = {s: load_idx_list(os.path.join(config['data_path'], lists[s])) for s in lists}
     else:
         if name not in FOLD_FILES:
             raise NotImplementedError(f'dataset {name}: only BraTS / NCANDA / Tau file naming is restated (util.py:643-694)')

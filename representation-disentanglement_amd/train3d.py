@@ -32,7 +32,8 @@ import torch.distributed as dist
 import yaml
 
 from . import hip
-from .data3d import VolumeData3D
+from .data3d import VolumeData3D, VolumeStore3D
+from .prep import build_store_from_raw, ensure_fold_lists
 from .postproc import CONNECTIVITIES, KEEP_MODES, STATS_COLUMNS, clean_labels, write_stats_csv
 from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, predict_volumes, seg_metrics_from_counts
 from .surfdist import BRATS_REGIONS, SCORE_KEYS, region_scores
@@ -44,6 +45,9 @@ DEFAULT_CONFIG_3D = {
                                        # | score (region scores of the label maps already under result_<predict_set>/: no model)
                                        # | postprocess (clean the label maps already under result_<predict_set>/ into post/: no model)
     'dataset_name': 'BraTS', 'data_path': '../data/', 'norm_type': 'z-score', 'fold': 0,
+    'data_source': 'h5',               # h5: the reference's file under data_path | raw: the NIfTI files of a BraTS download under raw_path (prep.py)
+    'raw_path': '',                    # data_source raw: the directory of the subjects; fold lists that data_path lacks are written first
+    'raw_crop': [[40, 40], [24, 24]],  # data_source raw: voxels removed at the low and high end of H and of W
     'contrast_list': ['T1', 'T1c', 'T2', 'T2_FLAIR'], 'batch_size': 4,
     'model_name': 'NVNet3D',           # NVNet3D | UNet3D (Dice-only objective)
     'init_channels': 16, 'p': 0.2,
@@ -73,6 +77,7 @@ POST_FG = (1, 2, 3, 4, 5, 6, 7)        # every non-zero label is foreground
 REGION_CSV_KEYS = (('dice', 'dice'), ('sens', 'sensitivity'), ('spec', 'specificity'), ('hd95', 'hd95'))      # csv column prefix, region_scores key
 MODEL_NAMES = ('NVNet3D', 'UNet3D')
 LR_SCHEDULES = ('none', 'poly')
+DATA_SOURCES = ('h5', 'raw')
 STAT_KEYS = ('loss', 'loss_dice', 'loss_l2', 'loss_kl')
 
 
@@ -93,6 +98,10 @@ def load_config3d(path=None, overrides=None):
         raise ValueError(f'model_name {cfg["model_name"]!r}: one of {MODEL_NAMES}')
     if cfg['lr_schedule'] not in LR_SCHEDULES:
         raise ValueError(f'lr_schedule {cfg["lr_schedule"]!r}: one of {LR_SCHEDULES}')
+    if cfg['data_source'] not in DATA_SOURCES:
+        raise ValueError(f'data_source {cfg["data_source"]!r}: one of {DATA_SOURCES}')
+    if cfg['data_source'] == 'raw' and not cfg['raw_path']:
+        raise ValueError('data_source raw needs raw_path: the directory of the subjects')
     if cfg['phase'] not in PHASES:
         raise ValueError(f'phase {cfg["phase"]!r}: one of {PHASES}')
     if cfg['predict_set'] not in ('train', 'val', 'test'):
@@ -191,6 +200,12 @@ class Run3D:
         torch.manual_seed(cfg['seed']); np.random.seed(cfg['seed'])
         if dev.type == 'cuda':
             torch.cuda.manual_seed(cfg['seed'])
+        if data is None and store is None and cfg['data_source'] == 'raw':
+            if cfg['dataset_name'] != 'BraTS':
+                raise NotImplementedError(f'data_source raw: only the BraTS directory naming is restated (prep.subject_files), not {cfg["dataset_name"]}')
+            store, kept = build_store_from_raw(cfg['raw_path'], dev, store_cls=VolumeStore3D, norm_type=cfg['norm_type'], crop=cfg['raw_crop'],
+                                               contrasts=cfg['contrast_list'], log=log)
+            ensure_fold_lists(kept, cfg['data_path'], VolumeData3D.file_names('BraTS', cfg['norm_type'], cfg['fold'])[1:])
         if data is None:
             data = VolumeData3D(cfg['dataset_name'], cfg['data_path'], norm_type=cfg['norm_type'], batch_size=cfg['batch_size'], fold=cfg['fold'],
                                 shuffle=True, contrast_list=cfg['contrast_list'], aug=cfg['aug'], dropoff=cfg['dropoff'], store=store,
