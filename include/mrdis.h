@@ -84,7 +84,7 @@ long long mrdis_get_option(const char* name);
  * "split6_c4" | "split6_c16" | "split6_wgrad16" | "split6_co4" | "split6_c3d" | "split6_w3d" | "split6_tap" (option split6: the 4 -> C kernel, the 32 -> 16 forward, its weight gradient, the
  * C -> 4 kernel, the 3-D 16 -> 16 forward / data-gradient and weight-gradient kernels, the tap-table kernel fed by mrdis_s6_filter_image, as six bf16 products per fp32 product); "zsearch" (mrdis_cosine_top1); "conv2src" | "ana_act" (the others variants); "kl" | "avgpool" (the latent-code options); "chatt" | "symdiff" | "rgate" (the attention output decoders);
  * "direct3d" | "c3d16" | "wgrad3d" | "wgrad3d16" | "wino_wgrad3d" (the 3-D tap-table, 16-cout, generic and narrow weight-gradient kernels and the hybrid
- * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "volgather"; "loss3d" | "segcounts" (the fused 3-D objective, one count per forward and per backward call, and the segmentation counts); "segaccum" | "seglabels" (whole-volume prediction of the 3-D nets); "synthaccum" | "synthfinish" (whole-subject synthesis of the 2-D model, one count per call); "seg2dlabels" | "seg2dfinish" (whole-subject segmentation by the 2-D model, one count per call); "fuse" (mrdis_fuse_present_fwd / _bwd, one count per call);
+ * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "volgather"; "loss3d" | "segcounts" (the fused 3-D objective, one count per forward and per backward call, and the segmentation counts); "segaccum" | "seglabels" (whole-volume prediction of the 3-D nets); "synthaccum" | "synthfinish" (whole-subject synthesis of the 2-D model, one count per call); "seg2dlabels" | "seg2dfinish" (whole-subject segmentation by the 2-D model, one count per call); "fuse" (mrdis_fuse_present_fwd / _bwd, one count per call); "export" (mrdis_export_volume, one count and one launch per call);
  * "stat_vec" | "stat_scalar" | "stat_interp" (the partial-sum kernel of a statistics pass), "spade_up2_onepass" | "spade_up2_twopass" (the route of
  * mrdis_instnorm_spade_bwd_up2, one per call), "bil_fwd_x2" | "bil_fwd_general", "bil_bwd_x2" | "bil_bwd_tight3" | "bil_bwd_tight5" | "bil_bwd_general"
  * (mrdis_bilinear_fwd / _bwd, one per call), "elem_v1" (an element-wise pass in its one-channel-per-thread form): dispatch choices, not launches;
@@ -789,6 +789,27 @@ int mrdis_prep_stats(const void* raw, int dtype, long long stride_h, long long s
 int mrdis_prep_write(const void* raw, int dtype, long long stride_h, long long stride_w, long long stride_d, int H, int W, int D,
                      int h0, int h1, int w0, int w1, double slope, double inter, const double* stats, int kind, int layout,
                      float* out, void* stream);
+
+/* ---- the inverse of mrdis_prep_write: store volumes back to the order and canvas of a NIfTI file, csrc/mrdis_export.hip.  src: B volumes of one
+ * geometry, dense and back to back, uint8 (MRDIS_PREP_U8) or fp32 (MRDIS_PREP_F32), each (H', W', D) (MRDIS_PREP_HWD: a VolumeStore3D, label and
+ * synthesized volumes) or (D, H', W') (MRDIS_PREP_DHW: a VolumeStore).  dst: (B, D, W, H) dense, h fastest -- the order of the file --, on the full
+ * canvas H = H' + h0 + h1, W = W' + w0 + w1; uint8, int16 (MRDIS_PREP_I16) or fp32, aligned to its element only (no 4-byte promise for the narrow types).
+ * Per output voxel (b, d, w, h): outside [h0, H - h1) x [w0, W - w1) y = fill; inside, with s = src[b](h - h0, w - w0, d),
+ *   MRDIS_EXPORT_COPY      y = s
+ *   MRDIS_EXPORT_UNZSCORE  y = 0 where s == -10.0f exactly, else (double)s * (std + 1e-8) + norm, multiply and add rounded separately in float64
+ *   MRDIS_EXPORT_UNMEAN    y = (double)s * norm
+ * with norm = sum / (n + 1), std = sqrt(ssd / (n + 1)) read on the device from stats + 5 b: B x 5 float64 in the layout mrdis_prep_stats writes (no
+ * host read).  Conversion: fp32 by one rounding of y; int16 / uint8 by NaN -> 0, round to nearest with ties to even, clamp to the type's range
+ * (+-inf saturate).  A uint8 source takes COPY only (uint8 -> uint8 is a byte copy).  stats may be NULL for COPY.
+ * One launch whatever B, on the caller's stream, no atomics: two runs give the same bits.  Launch counter family "export": one count per call.
+ * MRDIS_EUNSUPPORTED before any launch: H', W', D, H or W outside 1 .. 1024, H W D >= 2^31, B outside 1 .. 65535, a negative crop, an unknown dtype,
+ * layout or kind code, a uint8 source with another kind than COPY, stats NULL with a kind that reads it.  MRDIS_EINVAL: src or dst NULL.
+ * MRDIS_EALIGN: src / dst not aligned to their element, stats not to 8 bytes.                                                                    */
+#define MRDIS_EXPORT_COPY 0
+#define MRDIS_EXPORT_UNZSCORE 1
+#define MRDIS_EXPORT_UNMEAN 2
+int mrdis_export_volume(const void* src, int src_dtype, int layout, int Hc, int Wc, int D, int h0, int h1, int w0, int w1, int B,
+                        int kind, const double* stats, double fill, void* dst, int dst_dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -35,7 +35,7 @@ from .surfdist import EDT_FAR, BRATS_REGIONS, edt3d_sq, region_scores, scores_fr
 from . import postproc   # noqa: F401,E402
 from .postproc import components3d, clean_labels   # noqa: F401,E402
 from . import prep   # noqa: F401,E402
-from .prep import read_nifti, prep_stats, prep_write, prep_volume, build_store_from_raw, write_fold_lists   # noqa: F401,E402
+from .prep import read_nifti, prep_stats, prep_write, prep_volume, build_store_from_raw, write_fold_lists, write_nifti, save_nifti, export_store_volume   # noqa: F401,E402
 from . import train   # noqa: F401,E402
 from . import train3d   # noqa: F401,E402
 from .train3d import Run3D   # noqa: F401,E402

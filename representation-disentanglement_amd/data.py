@@ -32,6 +32,7 @@ class VolumeStore:
         self.device = torch.device(device)
         self.vols = {}
         self.shape = None           # (H, W, D) of every volume
+        self.raw_meta = None        # prep.build_store_from_raw: the crop, headers and statistics of the scans (what prep.save_nifti needs)
 
     def add(self, key, array_hwd):
         """key = 'subject/contrast' (h5 path); array in the reference layout (H, W, D)."""

@@ -148,6 +148,7 @@ _SIGS = {
     'mrdis_prep_workspace': (_Z, [_I, _I, _I]),
     'mrdis_prep_stats': (_I, [_P, _I, _L, _L, _L] + [_I] * 9 + [_c.c_double, _c.c_double, _P, _P, _Z, _P]),
     'mrdis_prep_write': (_I, [_P, _I, _L, _L, _L] + [_I] * 7 + [_c.c_double, _c.c_double, _P, _I, _I, _P, _P]),
+    'mrdis_export_volume': (_I, [_P] + [_I] * 11 + [_P, _c.c_double, _P, _I, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGS)
 
@@ -247,6 +248,8 @@ CC_FAMILIES = ('cclabel', 'ccclean')
 # preprocessing of raw scans into store volumes (csrc/mrdis_prep.hip): 'prepstats' counts one per mrdis_prep_stats call (four launches),
 # 'prepwrite' one per mrdis_prep_write call.
 PREP_FAMILIES = ('prepstats', 'prepwrite')
+# store volumes back to a NIfTI file's order and canvas (csrc/mrdis_export.hip): one count, and one launch, per mrdis_export_volume call.
+EXPORT_FAMILIES = ('export',)
 # the dispatch choices of the statistics, norm and resize entry points (csrc/mrdis_elem.hip), host-side counts only: which partial-sum kernel a
 # statistics pass took ('stat_vec' | 'stat_scalar' | 'stat_interp': one per pass), the route of mrdis_instnorm_spade_bwd_up2 (one per call), the
 # kernel of mrdis_bilinear_fwd / _bwd (one per call), and 'elem_v1': an element-wise pass that took its one-channel-per-thread instantiation.
@@ -295,7 +298,7 @@ def launch_counts(reset=False, elem=False):
     elem=True adds ELEM_FAMILIES: they count dispatch choices of passes that run beside almost every counted kernel (the statistics in front of a fused
     SPADE convolution, say), so callers that assert "this family and no other" over the whole dictionary only see them when they ask."""
     lib = load()
-    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES + PREP_FAMILIES
+    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES + PREP_FAMILIES + EXPORT_FAMILIES
     out ={f: int(lib.mrdis_launch_count(f.encode())) for f in fams + (ELEM_FAMILIES if elem else ())}
     if reset:
         lib.mrdis_launch_count_reset()
@@ -1526,6 +1529,66 @@ def prep_write(raw, stats, kind, crop, layout, slope=1.0, inter=0.0, order='file
         raise MrdisError(f'prep_write: out must be a contiguous fp32 {shape} tensor on {raw.device}, got {out.dtype} {tuple(out.shape)} strides {out.stride()}')
     _chk(lib.mrdis_prep_write(_ptr(raw), code, *strides, H, W, D, *cr, float(slope), float(inter), _ptr(stats), PREP_KINDS.index(kind),
                               PREP_LAYOUTS.index(layout), _ptr(out), _stream()), 'prep_write')
+    return out
+
+
+EXPORT_KINDS = ('copy', 'unzscore', 'unmean')     # MRDIS_EXPORT_COPY | _UNZSCORE | _UNMEAN, in this order
+EXPORT_SRC_DTYPES = (torch.uint8, torch.float32)
+EXPORT_DST_DTYPES = (torch.uint8, torch.int16, torch.float32)
+EXPORT_MAX_B = 65535
+
+
+def export_volume(src, crop, layout, kind='copy', stats=None, fill=0.0, dtype=torch.uint8, out=None):
+    """store volumes back in a NIfTI file's order, on the canvas the crop was cut from (include/mrdis.h mrdis_export_volume): the inverse of prep_write.
+    src: a device volume or a (B, ...) stack of them, uint8 or fp32, (H', W', D) each for layout 'hwd' or (D, H', W') for 'dhw'; a non-contiguous one is
+    copied.  -> (D, W, H) or (B, D, W, H) of `dtype` (uint8 | int16 | float32) with H = H' + h0 + h1, W = W' + w0 + w1 for crop = ((h0, h1), (w0, w1)):
+    `fill` outside the crop; inside the source voxel (kind 'copy'), s (std + 1e-8) + norm with -10 -> 0 ('unzscore') or s norm ('unmean') in float64,
+    converted once (integers: NaN -> 0, ties to even, clamped).  stats: what prep_stats gave, (5,) for every volume or (B, 5), read on the device.
+    `out`: a dense tensor of the result's shape and dtype to write into (it may start at any element of a larger buffer).  One launch whatever B, no
+    host read.  What the entry point refuses raises MrdisError('... unsupported geometry ...') before any launch."""
+    lib = load()
+    if not isinstance(src, torch.Tensor) or src.dim() not in (3, 4) or not src.is_cuda:
+        raise MrdisError(f'export_volume: src must be a 3-D device volume or a 4-D stack of them, got {getattr(src, "dtype", type(src))} '
+                         f'{tuple(getattr(src, "shape", ()))} on {getattr(src, "device", "the host")}')
+    try:
+        (h0, h1), (w0, w1) = [[int(v) for v in c] for c in crop]
+    except (TypeError, ValueError):
+        raise MrdisError(f'export_volume: crop {crop!r}: ((h0, h1), (w0, w1))') from None
+    stacked = src.dim() == 4
+    B = src.shape[0] if stacked else 1
+    vol = tuple(src.shape[1:]) if stacked else tuple(src.shape)
+    D, Hc, Wc = vol if layout == 'dhw' else (vol[2], vol[0], vol[1])
+    H, W = Hc + h0 + h1, Wc + w0 + w1
+    why = None
+    if layout not in PREP_LAYOUTS or kind not in EXPORT_KINDS or src.dtype not in EXPORT_SRC_DTYPES or dtype not in EXPORT_DST_DTYPES:
+        why = (f'layout {layout!r} must be one of {PREP_LAYOUTS}, kind {kind!r} one of {EXPORT_KINDS}, the source uint8 or float32 (got {src.dtype}) '
+               f'and the destination uint8, int16 or float32 (got {dtype})')
+    elif src.dtype == torch.uint8 and kind != 'copy':
+        why = f'a uint8 source takes kind copy only, got {kind!r}'
+    elif kind != 'copy' and stats is None:
+        why = f'kind {kind!r} reads stats, got None'
+    elif not (min(h0, h1, w0, w1) >= 0 and 1 <= min(Hc, Wc, D) and max(H, W, D) <= PREP_MAX_EXTENT and H * W * D < 2 ** 31 and 1 <= B <= EXPORT_MAX_B):
+        why = (f'each of H\', W\', D, H, W in 1 .. {PREP_MAX_EXTENT}, H W D < 2^31, B in 1 .. {EXPORT_MAX_B} and no negative crop')
+    if why:
+        raise MrdisError(f'export_volume: unsupported geometry: B = {B}, (H\', W\', D) = {(Hc, Wc, D)} with crop {((h0, h1), (w0, w1))}: {why}')
+    if stats is not None and kind != 'copy':
+        if not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or stats.device != src.device or tuple(stats.shape) not in ((5,), (1, 5), (B, 5)):
+            raise MrdisError(f'export_volume: stats must be a (5,) or ({B}, 5) float64 tensor of prep_stats on {src.device}')
+        stats = stats.reshape(-1, 5).expand(B, 5).contiguous()
+    else:
+        stats = None
+    shape = (B, D, W, H) if stacked else (D, W, H)
+    if out is None:
+        out = torch.empty(shape, dtype=dtype, device=src.device)
+    elif not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != src.device:
+        raise MrdisError(f'export_volume: out must be a dense {dtype} {shape} tensor on {src.device}, got {getattr(out, "dtype", type(out))} '
+                         f'{tuple(getattr(out, "shape", ()))}')
+    src = src.contiguous()
+    rc = lib.mrdis_export_volume(_ptr(src), PREP_DTYPES[src.dtype], PREP_LAYOUTS.index(layout), Hc, Wc, D, h0, h1, w0, w1, B, EXPORT_KINDS.index(kind),
+                                 _ptr(stats), float(fill), _ptr(out), PREP_DTYPES[dtype], _stream())
+    if rc == -2:        # MRDIS_EUNSUPPORTED: the entry point's list is the authority; the checks above only have to come before the allocation of `out`
+        raise MrdisError(f'export_volume: unsupported geometry: B = {B}, (H\', W\', D) = {(Hc, Wc, D)} with crop {((h0, h1), (w0, w1))}')
+    _chk(rc, 'export_volume')
     return out
 
 

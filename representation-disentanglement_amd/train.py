@@ -42,7 +42,7 @@ import torch.distributed as dist
 import yaml
 
 from .data import BatchLoader, SliceDataset, VolumeStore, load_idx_list
-from .prep import BRATS_CROP, build_store_from_raw, ensure_fold_lists
+from .prep import BRATS_CROP, build_store_from_raw, ensure_fold_lists, save_nifti
 from .trainer import (DEFAULT_CONFIG, LOSS_KEYS, EVAL_INFOS, EvalStep, eval_metric_keys, ZGallery, build_z_gallery, TrainStep, make_train_step, build_model, derive_config, load_checkpoint_model,
                       load_config_yaml, save_checkpoint)
 
@@ -53,6 +53,8 @@ from .segment import REGION_COLUMNS, check_seg_options, score_rows, segment_volu
 SEED = 10                                                                   # main_missing.py:18
 SYNTH_KEYS = ('synth_info', 'synth_drop', 'synth_block', 'synth_set')
 SEG_KEYS = ('seg_patterns', 'seg_flip', 'seg_set', 'seg_post', 'seg_post_min_voxels', 'seg_post_keep', 'seg_post_et_min_voxels')
+EXPORT_KEYS = ('write_nifti', 'synth_units')
+SYNTH_UNITS = ('store', 'scan')
 
 
 # --------------------------------------------------------------------------- data-parallel launch (replaces main_missing.py:28)
@@ -174,7 +176,7 @@ def setup_config(config_path='config.yaml', overrides=None, ckpt_root='../ckpt/'
         flag, saved = load_config_yaml(os.path.join(config['ckpt_path'], 'config.yaml'))
         if flag:
             for k, v in saved.items():                                      # :45-51
-                if k in ('phase', 'continue_train', 'eval_info', 'eval_drop') + SYNTH_KEYS + SEG_KEYS or k not in config:    # eval_info, eval_drop, synth_*, seg_*: per invocation, like phase
+                if k in ('phase', 'continue_train', 'eval_info', 'eval_drop') + SYNTH_KEYS + SEG_KEYS + EXPORT_KEYS or k not in config:    # eval_info, eval_drop, synth_*, seg_*, write_nifti: per invocation, like phase
                     continue
                 config[k] = v
             config = derive_config(config, device)
@@ -446,12 +448,23 @@ class Run:
             stat[k] = float(vec[nk + 1 + 2 * j] / vec[nk + 2 + 2 * j]) if vec[nk + 2 + 2 * j] > 0 else float('nan')
         return stat
 
+    def _nifti_options(self, store):
+        """the config's write_nifti, checked: true needs a store that kept the scans' crop and headers (data_source raw)"""
+        on = self.config.get('write_nifti', False)
+        if not isinstance(on, bool):
+            raise ValueError(f'write_nifti {on!r}: true or false')
+        if on and getattr(store, 'raw_meta', None) is None:
+            raise ValueError('write_nifti needs data_source raw: the store keeps no crop and no headers of the scans')
+        return on
+
     def synthesize(self, set_=None, info=None, drop=None, block=None, batch_size=None):
         """whole-subject synthesis (synth.synthesize_volumes) of the distinct subjects of `set_`'s slice list, in order of first appearance (None:
         the config's synth_set / synth_info / synth_drop / synth_block).  Writes <ckpt_path>/result_<set>/synth/<subj_id>_<contrast>.npy -- float32
         (H, W, D), the store's own geometry -- for every synthesised contrast and result_<set>/synth.csv with one
         `subj_id,contrast,present,dropped,n_sources,mse,psnr,ssim` row per subject and contrast (n_sources 0: not synthesised; NaN: nothing to score
         against); returns the mean metrics over the scored volumes.  With an `info` the z gallery of `set_` is loaded or built (Run.z_gallery).
+        `write_nifti: true` (data_source raw) also writes synth/<subj_id>_<contrast>.nii.gz on the scans' own canvas (prep.save_nifti), in the
+        store's units or, with `synth_units: scan`, in the scan's own units and datatype; the .npy and csv files do not change.
         World size 1 only."""
         cfg = self.config
         if getattr(self, 'world', 1) > 1 or (dist.is_available() and dist.is_initialized()):
@@ -466,6 +479,9 @@ class Run:
             raise ValueError(f'synth_set {set_!r}: train, val or test')
         ds = self.loaders[set_].dataset
         subjects = list(dict.fromkeys(str(x) for x in ds.subj_list))
+        nifti, units = self._nifti_options(ds.store), cfg.get('synth_units', 'store')
+        if units not in SYNTH_UNITS:
+            raise ValueError(f'synth_units {units!r}: one of {SYNTH_UNITS}')
         gallery = self.z_gallery(set_) if info else None
         out_dir = os.path.join(cfg['ckpt_path'], 'result_' + set_)
         os.makedirs(os.path.join(out_dir, 'synth'), exist_ok=True)
@@ -476,6 +492,8 @@ class Run:
                 done = i in res['targets']
                 if done:
                     np.save(os.path.join(out_dir, 'synth', f'{sid}_{c}.npy'), res['volumes'][c].cpu().numpy())
+                    if nifti:
+                        save_nifti(os.path.join(out_dir, 'synth', f'{sid}_{c}.nii.gz'), res['volumes'][c], ds.store, sid, c, units, log=self.log)
                 met = res['metrics'][c] if done else (float('nan'),) * 3
                 if done and not np.isnan(met[0]):
                     scored.append(met)
@@ -499,7 +517,8 @@ class Run:
           result_<set>/seg_patterns.csv -- `pattern,subjects,dice_wt,...,hd95_et`: per pattern the number of scored subjects and the mean of
           each score over them;
         with seg_post the same three under result_<set>/seg/post/ for the cleaned volumes, plus seg/post/postprocess.csv
-        (`subj_id,pattern,components,...`).  Returns {'subjects', 'patterns', 'scored', '<pattern>/<column>': mean}.  The rules are this package's own
+        (`subj_id,pattern,components,...`).  `write_nifti: true` (data_source raw) also writes <subj_id>_seg.nii.gz beside every <subj_id>_seg.npy, on
+        the scans' own canvas and in their geometry (prep.save_nifti): one export launch per subject for all its patterns.  Returns {'subjects', 'patterns', 'scored', '<pattern>/<column>': mean}.  The rules are this package's own
         convention: the reference assembles no volume and never fuses for M > 1.  World size 1 only."""
         cfg = self.config
         if getattr(self, 'world', 1) > 1 or (dist.is_available() and dist.is_initialized()):
@@ -519,6 +538,7 @@ class Run:
             raise ValueError(f'seg_set {set_!r}: train, val or test')
         ds = self.loaders[set_].dataset
         subjects = list(dict.fromkeys(str(x) for x in ds.subj_list))
+        nifti = self._nifti_options(ds.store)
         out_dir = os.path.join(cfg['ckpt_path'], 'result_' + set_)
         kinds = [('scores', 'labels', out_dir, 'seg')] + ([('post_scores', 'post', os.path.join(out_dir, 'seg', 'post'), '')] if post else [])
         for _, _, base, sub in kinds:
@@ -534,6 +554,10 @@ class Run:
                 for j, k in enumerate(live):
                     np.save(os.path.join(base, sub, res['patterns'][k], f'{sid}_seg.npy'), vols[j])
                 rows[skey] += [(sid,) + r for r in score_rows(res, skey)]
+            if nifti and live:                                               # every pattern's volume, raw and cleaned, in ONE export launch
+                have = [(vkey, base, sub) for _, vkey, base, sub in kinds if res[vkey] is not None]
+                save_nifti([os.path.join(base, sub, res['patterns'][k], f'{sid}_seg.nii.gz') for _, base, sub in have for k in live],
+                           torch.cat([res[vkey] for vkey, _, _ in have]), ds.store, sid, log=self.log)
             if post and res['post_stats'] is not None:
                 st = res['post_stats'].cpu().tolist()
                 stats_rows += [(sid, res['patterns'][k], st[j]) for j, k in enumerate(live)]

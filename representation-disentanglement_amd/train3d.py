@@ -33,7 +33,7 @@ import yaml
 
 from . import hip
 from .data3d import VolumeData3D, VolumeStore3D
-from .prep import build_store_from_raw, ensure_fold_lists
+from .prep import build_store_from_raw, ensure_fold_lists, save_nifti
 from .postproc import CONNECTIVITIES, KEEP_MODES, STATS_COLUMNS, clean_labels, write_stats_csv
 from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, predict_volumes, seg_metrics_from_counts
 from .surfdist import BRATS_REGIONS, SCORE_KEYS, region_scores
@@ -69,6 +69,8 @@ DEFAULT_CONFIG_3D = {
     'post_keep': 'all',                # all | largest (only the largest component of a subject is a candidate)
     'post_et_min_voxels': 0,           # > 0: an enhancing tumour (label 4) of fewer voxels becomes necrotic core (label 1); BraTS only
     'score_subdir': '',                # phase score: the sub-directory of result_<predict_set>/ it reads and writes ('post': the cleaned maps)
+    'write_nifti': False,              # phase predict / postprocess: also write <subj_id>_seg.nii.gz beside every <subj_id>_seg.npy, on the scans' own
+                                       # 240 x 240 x 155 canvas and in their geometry (prep.save_nifti); needs data_source raw
 }
 PHASES = ('train', 'test', 'predict', 'score', 'postprocess')
 NO_MODEL_PHASES = ('score', 'postprocess')
@@ -125,6 +127,10 @@ def load_config3d(path=None, overrides=None):
             raise ValueError(f'{k} {cfg[k]!r}: an integer >= 0')
     if cfg['post_et_min_voxels'] > 0 and cfg['dataset_name'] != 'BraTS':
         raise ValueError(f'post_et_min_voxels > 0 (the enhancing-tumour rule) is defined for dataset_name BraTS only, not {cfg["dataset_name"]!r}')
+    if not isinstance(cfg['write_nifti'], bool):
+        raise ValueError(f'write_nifti {cfg["write_nifti"]!r}: true or false')
+    if cfg['write_nifti'] and cfg['data_source'] != 'raw':
+        raise ValueError(f'write_nifti needs data_source raw (the crop and the headers of the scans), not {cfg["data_source"]!r}')
     sub = cfg['score_subdir']
     if not isinstance(sub, str) or os.path.isabs(sub) or any(p in ('.', '..') for p in sub.replace('\\', '/').split('/')):
         raise ValueError(f'score_subdir {sub!r}: a relative sub-directory of result_<predict_set>/ (or the empty string)')
@@ -363,13 +369,16 @@ class Run3D:
         `predict_post: true` also cleans the labels of every batch on the device (`clean`), writes them as result_<set>/post/<subj_id>_seg.npy
         with post/postprocess.csv (and, with `predict_regions`, post/predict_regions.csv: the region scores of the cleaned labels), and adds
         'post_<column>' means to the returned stat: one more D2H copy of the cleaned labels and one small copy of the stats per batch.  The raw
-        files are written exactly as without it."""
+        files are written exactly as without it.
+        `write_nifti: true` (data_source raw) also writes <subj_id>_seg.nii.gz beside every <subj_id>_seg.npy, under post/ too: uint8 on the scans'
+        own canvas, 0 outside the crop, in the geometry of the subject's seg file (prep.save_nifti); the .npy and csv files do not change."""
         cfg = self.config
         set_ = cfg['predict_set'] if set_ is None else set_
         out_dir = os.path.join(cfg['ckpt_path'], f'result_{set_}')
         os.makedirs(out_dir, exist_ok=True)
         subj, counts, regions = [], [], []
-        post = _PostWriter(out_dir, cfg['predict_regions']) if cfg['predict_post'] else None
+        nifti = self._nifti_writer(set_)
+        post = _PostWriter(out_dir, cfg['predict_regions'], nifti) if cfg['predict_post'] else None
         for res in predict_volumes(self.model, self.loaders[set_], stride=cfg['predict_stride'], flip=cfg['predict_flip'],
                                    limit=cfg['max_batches'] or None):
             if cfg['predict_regions']:
@@ -379,6 +388,8 @@ class Run3D:
             labels = res['labels'].cpu().numpy()
             for i, sid in enumerate(res['subj_id']):
                 np.save(os.path.join(out_dir, f'{sid}_seg.npy'), labels[i])
+            if nifti is not None:
+                nifti(out_dir, res['subj_id'], res['labels'])
             subj += res['subj_id']
             counts.append(res['counts'])
         if not subj:
@@ -396,6 +407,18 @@ class Run3D:
             stat.update({f'post_{k}': v for k, v in post.finish().items()})
         self.log(f'predict {set_}: {len(subj)} volumes under {out_dir}, dice {stat["dice"]:.4f}, iou {stat["iou"]:.4f}')
         return stat
+
+    def _nifti_writer(self, set_):
+        """`write_nifti: true`: f(directory, subject ids, (B, H, W, D) labels on the device) that writes <subj_id>_seg.nii.gz per subject (prep.save_nifti:
+        one launch, one D2H copy and one file each, in the subject's own geometry); else None, and no export kernel ever launches"""
+        if not self.config['write_nifti']:
+            return None
+        store = self.loaders[set_].dataset.store
+
+        def write(out_dir, ids, labels):
+            for i, sid in enumerate(ids):
+                save_nifti(os.path.join(out_dir, f'{sid}_seg.nii.gz'), labels[i], store, sid, log=self.log)
+        return write
 
     def clean(self, labels):
         """(cleaned, stats) of a batch of label volumes on the device under the `post_*` keys (postproc.clean_labels; every non-zero label
@@ -439,7 +462,7 @@ class Run3D:
         post = None
         for ids, labels, ptrs in self._stored_labels(in_dir, set_):
             if post is None:
-                post = _PostWriter(in_dir, cfg['dataset_name'] == 'BraTS')
+                post = _PostWriter(in_dir, cfg['dataset_name'] == 'BraTS', self._nifti_writer(set_))
             post.add(ids, *self.clean(labels), ptrs)
         if post is None:
             raise RuntimeError(f'postprocess({set_!r}): the loader serves no subject')
@@ -474,8 +497,9 @@ class _PostWriter:
     """the files under result_<set>/post/: `add` takes a batch of cleaned labels and stats on the device (one D2H copy each, and with
     `regions` their region scores), `finish` writes postprocess.csv (and predict_regions.csv) and returns the column (and region) means"""
 
-    def __init__(self, result_dir, regions):
+    def __init__(self, result_dir, regions, nifti=None):
         self.out_dir = os.path.join(result_dir, POST_SUBDIR)
+        self.nifti = nifti                 # Run3D._nifti_writer: also write the cleaned labels as NIfTI files
         os.makedirs(self.out_dir, exist_ok=True)
         self.subj, self.stats, self.regions = [], [], ([] if regions else None)
 
@@ -485,6 +509,8 @@ class _PostWriter:
         vols = cleaned.cpu().numpy()
         for i, sid in enumerate(ids):
             np.save(os.path.join(self.out_dir, f'{sid}_seg.npy'), vols[i])
+        if self.nifti is not None:
+            self.nifti(self.out_dir, ids, cleaned)
         self.subj += list(ids)
         self.stats.append(stats.cpu().numpy())
 

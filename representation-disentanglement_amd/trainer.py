@@ -52,6 +52,9 @@ DEFAULT_CONFIG = {
     'seg_post_min_voxels': 0,          # components smaller than this are removed
     'seg_post_keep': 'all',            # 'all' | 'largest'
     'seg_post_et_min_voxels': 0,       # fewer enhancing-tumour voxels than this (and more than 0) become label 1
+    # phase: segment / synthesize -- NIfTI files beside the .npy files, on the scans' own canvas and in their geometry (prep.save_nifti; data_source raw only)
+    'write_nifti': False,              # true: seg/<pattern>/<subj_id>_seg.nii.gz (and the seg/post/ ones) | synth/<subj_id>_<contrast>.nii.gz
+    'synth_units': 'store',            # 'store': float32 in the store's normalised units | 'scan': the scan's own units and datatype (the normalisation undone)
 }
 
 
