@@ -256,6 +256,10 @@ EXPORT_FAMILIES = ('export',)
 # Outside KERNEL_FAMILIES for the same reason as the tables above (tests/test_gpu_elem_paths.py covers them).
 ELEM_FAMILIES = ('stat_vec', 'stat_scalar', 'stat_interp', 'spade_up2_onepass', 'spade_up2_twopass', 'bil_fwd_x2', 'bil_fwd_general',
                  'bil_bwd_x2', 'bil_bwd_tight3', 'bil_bwd_tight5', 'bil_bwd_general', 'elem_v1')
+# every name of csrc/mrdis_common.h MRDIS_COUNTERS: what launch_counts() hands out, ELEM_FAMILIES on request (tests/test_abi.py pins the union)
+LAUNCH_COUNTERS = (WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES
+                    + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES + PREP_FAMILIES + EXPORT_FAMILIES)
+ALL_COUNTERS = LAUNCH_COUNTERS + ELEM_FAMILIES
 SYNTH_MAX_SRC = 8                 # include/mrdis.h MRDIS_SYNTH_MAX_SRC
 SEG2D_MAX_SETS = 16               # include/mrdis.h MRDIS_SEG2D_MAX_SETS
 SEG2D_MAX_VIEWS = 2               # include/mrdis.h MRDIS_SEG2D_MAX_VIEWS
@@ -273,7 +277,8 @@ CC_CONNECTIVITIES = (6, 18, 26)
 
 def stream_fill(t, value=0.0):
     """store-only probe over a dense fp32 tensor (include/mrdis.h mrdis_stream_fill)"""
-    assert t.dtype == torch.float32 and t.numel() % 4 == 0
+    if (t.dtype is not torch.float32 or t.numel() % 4 != 0
+            or not (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last))): _refuse('stream_fill', 'vec dtype dense', t)
     _chk(load().mrdis_stream_fill(t.data_ptr(), t.numel(), float(value), _stream()), 'stream_fill')
     return t
 
@@ -298,8 +303,7 @@ def launch_counts(reset=False, elem=False):
     elem=True adds ELEM_FAMILIES: they count dispatch choices of passes that run beside almost every counted kernel (the statistics in front of a fused
     SPADE convolution, say), so callers that assert "this family and no other" over the whole dictionary only see them when they ask."""
     lib = load()
-    fams = WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES + PREP_FAMILIES + EXPORT_FAMILIES
-    out ={f: int(lib.mrdis_launch_count(f.encode())) for f in fams + (ELEM_FAMILIES if elem else ())}
+    out = {f: int(lib.mrdis_launch_count(f.encode())) for f in (ALL_COUNTERS if elem else LAUNCH_COUNTERS)}
     if reset:
         lib.mrdis_launch_count_reset()
     return out
@@ -366,7 +370,7 @@ def _ws_bytes(fn, *args):
 def nhwc(t):
     """(tensor, ld) for a logical (N,C,H,W) fp32 or bf16 tensor whose memory is NHWC with pixel
     stride ld in elements (channels_last tensors and channel slices of them qualify as they are)."""
-    assert t.dim() == 4 and (t.dtype is torch.float32 or t.dtype is torch.bfloat16), (t.shape, t.dtype)
+    if t.dim() != 4 or not (t.dtype is torch.float32 or t.dtype is torch.bfloat16): _refuse('nhwc', 'dtype', t)
     if t.is_contiguous(memory_format=torch.channels_last) and t.shape[1] > 1 and t.shape[3] > 1:
         return t, t.shape[1]                         # the common case: a dense channels_last tensor
     N, C, H, W = t.shape
@@ -404,6 +408,44 @@ def _dt(*tensors):
     raise MrdisError(f'activation views must be fp32 or bf16, got {kind}')
 
 
+# ---------------------------------------------------------------- what a wrapper establishes before a library call
+# DESIGN.md "The binding's contract": hot wrappers (a training step's) check inline, without device compares; the cold ones through the helpers below.
+_CLAIMS = {'like': 'operands of one shape', 'layer': 'the shape the layer\'s kernel, stride and padding make of the input', 'filter': 'a (taps, reduce, out) filter for the layer',
+           'out': 'an output view of the result\'s shape, written in place', 'vec': 'vectors, tables and buffers of the element count the shapes and integers imply',
+           'dtype': 'the dtype the entry point reads', 'dense': 'dense memory (contiguous, NHWC or NDHWC as documented)', 'arg': 'arguments in their documented range'}
+
+
+def _refuse(what, claims, *ts):
+    """the failure path of every inline check: MrdisError naming the wrapper, the claims (keys of _CLAIMS) of which the call breaks one, and the operands"""
+    raise MrdisError(f'{what} wants ' + '; '.join(_CLAIMS[c] for c in claims.split()) + ', ' + _got(*ts))
+
+
+def _got(*ts):
+    """the operands of a refused call, for its message"""
+    return 'got ' + ', '.join(f'{t.dtype} {tuple(t.shape)} strides {t.stride()} on {t.device}' if isinstance(t, torch.Tensor) else repr(t) for t in ts)
+
+
+def _want(t, what, dtype, shape=None, device=None, cl=False, dense=True):
+    """tuple(t.shape) of a contiguous tensor of that dtype, and of that shape (a name stands for any extent) and device where given, else MrdisError.
+    cl: dense channels-last / channels-last-3d memory instead of contiguous; dense=False: any strides (the caller copies)."""
+    ok = isinstance(t, torch.Tensor) and t.dtype is dtype and (device is None or t.device == device)
+    if ok and shape is not None:
+        ok = t.dim() == len(shape) and all(isinstance(w, str) or w == n for w, n in zip(shape, t.shape))
+    if not (ok and (not dense or (t.movedim(1, -1) if cl else t).is_contiguous())):
+        claim = ' '.join(str(v) for v in (dtype, shape) if v is not None) + (' tensor' if device is None else f' tensor on {device}')
+        raise MrdisError(f'{what} must be a {"dense channels-last" if cl else "contiguous"} {claim}, {_got(t)}')
+    return tuple(t.shape)
+
+
+def _crop(crop, what):
+    """(h0, h1, w0, w1) of crop = ((h0, h1), (w0, w1))"""
+    try:
+        (h0, h1), (w0, w1) = [[int(v) for v in c] for c in crop]
+    except (TypeError, ValueError):
+        raise MrdisError(f'{what}: crop {crop!r}: ((h0, h1), (w0, w1))') from None
+    return h0, h1, w0, w1
+
+
 class _Mailbox:
     """Small host -> device transfers by a KERNEL that reads pinned host memory (mrdis_copy_bytes) instead of hipMemcpyAsync:
     a ring of pinned slots; a slot is rewritten only after the event recorded behind its last copy kernel has completed."""
@@ -437,7 +479,8 @@ _mailbox = None
 
 def copy_bytes(src, dst, nbytes):
     """word-wise copy by a kernel on the current stream (include/mrdis.h mrdis_copy_bytes); src may be a PINNED host tensor"""
-    assert nbytes % 4 == 0 and nbytes <= src.numel() * src.element_size() and nbytes <= dst.numel() * dst.element_size()
+    if (nbytes % 4 != 0 or not 0 <= nbytes <= min(src.numel() * src.element_size(), dst.numel() * dst.element_size())
+            or not (src.is_contiguous() and dst.is_contiguous())): _refuse('copy_bytes', 'vec dense', src, dst)
     _chk(load().mrdis_copy_bytes(src.data_ptr(), _ptr(dst), int(nbytes), _stream()), 'copy_bytes')
 
 
@@ -474,17 +517,20 @@ def wino_u_format(R, S, spadeC=0):
     return int(load().mrdis_wino_u_format(R, S, spadeC))
 
 
+def _struct_table(jobs, struct, lib_bytes, device):
+    """list of ctypes structs -> device tensor holding the table (checked against the library's struct size)"""
+    nb = _c.sizeof(struct)
+    if nb != lib_bytes:
+        raise MrdisError(f'{struct.__name__} layout mismatch: binding {nb} bytes, library {lib_bytes}')
+    arr = (struct * len(jobs))(*jobs)
+    return torch.frombuffer(bytearray(_c.string_at(_c.addressof(arr), nb * len(jobs))), dtype=torch.uint8).to(device)
+
+
 def wino_u_table(jobs, device):
-    lib = load()
-    nb = _c.sizeof(WinoUJob)
-    if nb != lib.mrdis_wino_u_job_bytes():
-        raise MrdisError(f'WinoUJob layout mismatch: binding {nb} bytes, library {lib.mrdis_wino_u_job_bytes()}')
     for j in jobs:
         if not j.fmt:                              # a caller may pin the format (MixPlan records the one it sized the image for)
             j.fmt = wino_u_format(j.R, j.S, j.spadeC)
-    arr = (WinoUJob * len(jobs))(*jobs)
-    host = torch.frombuffer(bytearray(_c.string_at(_c.addressof(arr), nb * len(jobs))), dtype=torch.uint8)
-    return host.to(device)
+    return _struct_table(jobs, WinoUJob, load().mrdis_wino_u_job_bytes(), device)
 
 
 def wino_u_image_floats(R, S, spadeC=0, fmt=None):
@@ -504,6 +550,7 @@ def s6_filter_image_bytes(taps, Cred, Cout):
 def s6_filter_image(w):
     """w [taps][Cred][Cout] fp32 (w_tck for the forward pass, w_tkc for the data gradient) -> its six-product image (mrdis_s6conv.hip), a float32-typed
     tensor that travels in the auxiliary-filter slot of conv2d_fwd / conv2d_bwd_data (attribute mrdis_fmt = 6); None where the layer has no such image."""
+    if w.dim() != 3: _refuse('s6_filter_image', 'filter', w)
     T, R, S = w.shape
     nb = s6_filter_image_bytes(T, R, S)
     if nb == 0 or nb >= 2 ** 31 or w.dtype is not torch.float32:
@@ -535,23 +582,34 @@ def wino_image_fmt(img, R, S, spadeC=0, taps=0):
     return fmt
 
 
+def _image_fmt(img, R, S, taps, kh, kw, what, spadeC=0):
+    """format code of the filter image in a convolution's auxiliary slot (0: none), which must be fp32, dense, and of the size its format has for the filter"""
+    if img is None:
+        return 0
+    if img.dtype is not torch.float32 or not img.is_contiguous(): _refuse(what, 'filter dtype dense', img)
+    fmt = wino_image_fmt(img, R, S, spadeC, taps)
+    if fmt != S6_IMAGE_FMT and (kh, kw) != (3, 3): _refuse(f'{what}: a Winograd image (format {fmt}) goes with a 3x3 filter, not {kh}x{kw}', 'arg', img)
+    return fmt
+
+
 def wino_u_job_blocks(R, S, spadeC=0):
     return int(load().mrdis_wino_u_job_blocks(R, S, spadeC))
 
 
+def _job_table(table, njobs, job, what, types=None):
+    """a device table of `njobs` structs as wino_u_table / mix_job_table built it and, for the mixing launches, their dense fp32 (M, emb) type rows"""
+    if table.dtype is not torch.uint8 or not table.is_contiguous() or not 1 <= njobs <= table.numel() // _c.sizeof(job): _refuse(what, 'vec dtype dense', table, njobs)
+    if types is not None and (types.dtype is not torch.float32 or types.dim() != 2 or not types.is_contiguous()): _refuse(what, 'dtype dense', types)
+
+
 def wino_u_jobs(table, njobs, total_blocks):
+    _job_table(table, njobs, WinoUJob, 'wino_u_jobs')
     _chk(load().mrdis_wino_u_jobs(_ptr(table), njobs, total_blocks, _stream()), 'wino_u_jobs')
 
 
 def mix_job_table(jobs, device):
     """list of MixJob -> device tensor holding the table (checked against the library's struct size)."""
-    lib = load()
-    nb = _c.sizeof(MixJob)
-    if nb != lib.mrdis_mix_job_bytes():
-        raise MrdisError(f'MixJob layout mismatch: binding {nb} bytes, library {lib.mrdis_mix_job_bytes()}')
-    arr = (MixJob * len(jobs))(*jobs)
-    host = torch.frombuffer(bytearray(_c.string_at(_c.addressof(arr), nb * len(jobs))), dtype=torch.uint8)
-    return host.to(device)
+    return _struct_table(jobs, MixJob, load().mrdis_mix_job_bytes(), device)
 
 
 def mix_job_blocks(Co, Ci, T):
@@ -559,12 +617,15 @@ def mix_job_blocks(Co, Ci, T):
 
 
 def mix_jobs_fwd(table, njobs, total_blocks, types):
+    _job_table(table, njobs, MixJob, 'mix_jobs_fwd', types)
     M, emb = types.shape
     _chk(load().mrdis_mix_jobs_fwd(_ptr(table), njobs, total_blocks, _ptr(types), emb, M, _stream()), 'mix_jobs_fwd')
 
 
 def mix_jobs_bwd(table, njobs, total_blocks, dw_table, types):
+    _job_table(table, njobs, MixJob, 'mix_jobs_bwd', types)
     M, emb = types.shape
+    if not dw_table.is_contiguous() or dw_table.numel() * dw_table.element_size() < njobs * 64: _refuse('mix_jobs_bwd', 'vec dense', dw_table)      # [njobs][8] addresses
     _chk(load().mrdis_mix_jobs_bwd(_ptr(table), njobs, total_blocks, _ptr(dw_table), _ptr(types), emb, M, _stream()), 'mix_jobs_bwd')
 
 
@@ -593,6 +654,7 @@ def mix_experts_fwd(W, r):
     lib = load()
     E, Co, Ci, kh, kw = W.shape
     T = kh * kw
+    if W.dtype is not torch.float32 or r.dtype is not torch.float32 or r.numel() != E: _refuse('mix_experts_fwd', 'vec dtype', W, r)
     W = W.contiguous(); r = r.contiguous()
     w_tck = torch.empty((T, Ci, Co), dtype=torch.float32, device=W.device)
     w_tkc = torch.empty((T, Co, Ci), dtype=torch.float32, device=W.device)
@@ -604,6 +666,8 @@ def mix_experts_bwd(dw_tck, W, r):
     lib = load()
     E, Co, Ci, kh, kw = W.shape
     T = kh * kw
+    if (not (W.dtype is r.dtype is dw_tck.dtype is torch.float32)
+            or r.numel() != E or dw_tck.numel() != T * Ci * Co): _refuse('mix_experts_bwd', 'vec dtype', dw_tck, W, r)
     W = W.contiguous(); r = r.contiguous(); dw_tck = dw_tck.contiguous()
     dW = torch.empty_like(W)
     dr = torch.zeros(E, dtype=torch.float32, device=W.device)
@@ -619,8 +683,10 @@ def mix_experts_routed_fwd(W, fcw, fcb, t_row):
     lib = load()
     E, Co, Ci, kh, kw = W.shape
     T = kh * kw
+    emb = fcw.shape[-1]
+    if (not (W.dtype is fcw.dtype is fcb.dtype is t_row.dtype is torch.float32)
+            or tuple(fcw.shape) != (E, emb) or fcb.numel() != E or t_row.numel() != emb): _refuse('mix_experts_routed_fwd', 'dtype', W, fcw, fcb, t_row)
     W = W.contiguous(); fcw = fcw.contiguous(); fcb = fcb.contiguous(); t_row = t_row.contiguous()
-    emb = fcw.shape[1]
     w_tck = torch.empty((T, Ci, Co), dtype=torch.float32, device=W.device)
     w_tkc = torch.empty((T, Co, Ci), dtype=torch.float32, device=W.device)
     r = torch.empty(E, dtype=torch.float32, device=W.device)
@@ -633,7 +699,9 @@ def mix_experts_routed_bwd(dw_tck, W, r, t_row, emb):
     lib = load()
     E, Co, Ci, kh, kw = W.shape
     T = kh * kw
-    W = W.contiguous(); dw_tck = dw_tck.contiguous(); t_row = t_row.contiguous()
+    if (not (W.dtype is r.dtype is dw_tck.dtype is t_row.dtype is torch.float32) or r.numel() != E
+            or dw_tck.numel() != T * Ci * Co or t_row.numel() != emb): _refuse('mix_experts_routed_bwd', 'vec dtype', dw_tck, W, r, t_row)
+    W = W.contiguous(); dw_tck = dw_tck.contiguous(); t_row = t_row.contiguous(); r = r.contiguous()
     dW = torch.empty_like(W)
     dfcw = torch.empty((E, emb), dtype=torch.float32, device=W.device)
     dfcb = torch.empty(E, dtype=torch.float32, device=W.device)
@@ -651,11 +719,18 @@ def mix_experts_routed_multi_fwd(W, fcw, fcb, types, want_bf16=False, into=None)
     lib = load()
     E, Co, Ci, kh, kw = W.shape
     T = kh * kw
+    if (not (W.dtype is fcw.dtype is fcb.dtype is types.dtype is torch.float32)
+            or types.dim() != 2 or tuple(fcw.shape) != (E, types.shape[1]) or fcb.numel() != E): _refuse('mix_experts_routed_multi_fwd', 'dtype', W, fcw, fcb, types)
     W = W.contiguous(); fcw = fcw.contiguous(); fcb = fcb.contiguous(); types = types.contiguous()
     M, emb = types.shape
     r = torch.empty((M, E), dtype=torch.float32, device=W.device)
     if into is not None:
         tck, tkc, btck, btkc, col0, cot = into
+        for ts, dtype, shape in ((tck, torch.float32, (T, Ci, cot)), (tkc, torch.float32, (T, cot, Ci)), (btck, torch.bfloat16, (T, Ci, cot)), (btkc, torch.bfloat16, (T, cot, Ci))):
+            if ts is None and dtype is torch.bfloat16 and btck is None:
+                continue
+            if (ts is None or not 0 <= col0 <= cot - Co or len(ts) != M
+                    or any(t.dtype is not dtype or tuple(t.shape) != shape or not t.is_contiguous() for t in ts)): _refuse('mix_experts_routed_multi_fwd', 'filter dtype dense arg', *(ts or ()))
         a = (_c.c_void_p * M)(*[t.data_ptr() + 4 * col0 for t in tck]); b = (_c.c_void_p * M)(*[t.data_ptr() + 4 * col0 * Ci for t in tkc])
         ba = bb = None
         if btck is not None:
@@ -685,12 +760,18 @@ def mix_experts_routed_multi_bwd(dw_list, W, r, types, sinks=None, col0=0, ld=0)
     lib = load()
     E, Co, Ci, kh, kw = W.shape
     T = kh * kw
-    W = W.contiguous(); types = types.contiguous()
+    if (not (W.dtype is r.dtype is types.dtype is torch.float32) or types.dim() != 2
+            or tuple(r.shape) != (types.shape[0], E) or len(dw_list) != types.shape[0]): _refuse('mix_experts_routed_multi_bwd', 'dtype', W, r, types)
+    W = W.contiguous(); types = types.contiguous(); r = r.contiguous()
     M, emb = types.shape
     dw_list = [None if g is None else g.contiguous() for g in dw_list]
+    if (not 0 <= col0 <= max(ld - Co, 0)
+            or any(g is not None and (g.dtype is not torch.float32 or g.numel() != T * Ci * (ld or Co)) for g in dw_list)): _refuse('mix_experts_routed_multi_bwd', 'vec dtype arg', *dw_list)
     a = (_c.c_void_p * M)(*[None if g is None else g.data_ptr() + 4 * col0 for g in dw_list])
     if sinks is not None:
         dW, dfcw, dfcb = sinks
+        if (any(s.dtype is not torch.float32 or not s.is_contiguous() for s in sinks)
+                or (dW.numel(), dfcw.numel(), dfcb.numel()) != (W.numel(), E * emb, E)): _refuse('mix_experts_routed_multi_bwd', 'vec dtype dense', *sinks)
     else:
         dW = torch.empty_like(W)
         dfcw = torch.empty((E, emb), dtype=torch.float32, device=W.device)
@@ -726,6 +807,7 @@ def _dt_xy(x, y):
 def cast_bf16(t):
     """fp32 tensor -> bf16 copy (round to nearest even) through the library's cast kernel."""
     lib = load()
+    if t.dtype is not torch.float32: _refuse('cast_bf16', 'dtype', t)
     t = t.contiguous()
     out = torch.empty(t.shape, dtype=torch.bfloat16, device=t.device)
     _chk(lib.mrdis_cast_bf16(_ptr(t), _ptr(out), t.numel(), _stream()), 'cast_bf16')
@@ -746,11 +828,11 @@ def conv2d_fwd(x, w_tck, bias, kh, kw, stride, pad, lrelu=False, out=None, w_bf1
     if out is None:
         out = empty_nhwc(N, Co, Ho, Wo, x.device, out_dtype or x.dtype)
     y, ldy = nhwc(out)
-    assert y.data_ptr() == out.data_ptr(), 'conv2d_fwd: `out` must already be an NHWC view'
     mixed = _dt_xy(x, y)
     if mixed == DT_XBF16_YF32 and kh == 3 and Co == 16 and out.shape[1] == 4:
         Co = 4                       # the C -> 4 layer with its filter in the column-padded [9][Ci][16] layout (ana_dec.output under bf16 storage)
-    assert T == kh * kw and (Ci2 == Ci or (mixed == DT_XF32_YBF16 and Ci2 == max(Ci, 16))), (w_tck.shape, x.shape, kh, kw)
+    if (y is not out or tuple(y.shape) != (N, Co, Ho, Wo) or T != kh * kw      # (bias: at least Co values; the column-padded C -> 4 layer comes with its 16)
+            or not (Ci2 == Ci or (mixed == DT_XF32_YBF16 and Ci2 == max(Ci, 16))) or (bias is not None and bias.numel() < Co)): _refuse('conv2d_fwd', 'filter out vec', out, w_tck, bias)
     if mixed in (DT_XBF16_YF32, DT_XF32_YBF16):
         rc = lib.mrdis_conv2d_fwd(_ptr(x), ldx, _ptr(w_tck), None, _ptr(bias), _ptr(y), ldy, N, H, W, Ci, Co, kh, kw, stride, pad,
                                   1 if lrelu else 0, mixed, None, 0, _stream())
@@ -760,13 +842,8 @@ def conv2d_fwd(x, w_tck, bias, kh, kw, stride, pad, lrelu=False, out=None, w_bf1
         return out
     if w_bf16 is not None and w_bf16.dtype is torch.float32:      # the auxiliary-filter slot carries the Winograd image on the fp32 path
         w_wino, w_bf16 = w_bf16, None
-    if w_bf16 is not None:
-        assert w_bf16.dtype == torch.bfloat16 and tuple(w_bf16.shape) == (T, Co, Ci) and w_bf16.is_contiguous()
-    wfmt = 0
-    if w_wino is not None:
-        assert w_wino.dtype == torch.float32
-        wfmt = wino_image_fmt(w_wino, Ci, Co, taps=T)
-        assert wfmt == S6_IMAGE_FMT or (kh == 3 and kw == 3)
+    if w_bf16 is not None and (w_bf16.dtype is not torch.bfloat16 or tuple(w_bf16.shape) != (T, Co, Ci) or not w_bf16.is_contiguous()): _refuse('conv2d_fwd', 'filter dtype dense', w_bf16)
+    wfmt = 0 if w_wino is None else _image_fmt(w_wino, Ci, Co, T, kh, kw, 'conv2d_fwd')
     dt = DT_BF16 if mixed == DT_BF16 else (DT_F32 if w_bf16 is None else DT_F32_BF16M)     # bf16 views: bf16 kernels only
     rc = lib.mrdis_conv2d_fwd(_ptr(x), ldx, _ptr(w_tck), _ptr(w_bf16), _ptr(bias), _ptr(y), ldy, N, H, W, Ci, Co, kh, kw, stride, pad,
                               1 if lrelu else 0, dt, _ptr(w_wino) if dt == DT_F32 else None, wfmt, _stream())
@@ -792,12 +869,13 @@ def conv2d_bwd_data(dy, w_tkc, in_hw, kh, kw, stride, pad, w_bf16=None, out=None
     mixed = out is not None and out.dtype != dy.dtype
     if mixed and kh == 3 and Ci == 16 and out.shape[1] == 4:
         Ci = 4                       # the si_layers' data gradient with the filter in the column-padded [9][Co][16] layout (bf16 dy -> fp32 dx: MRDIS_DT_XF32_YBF16)
-    assert (Co2 == Co or (mixed and Co2 == 16 and Co == 4 and kh == 3)) and conv_out_hw(H, W, kh, kw, stride, pad) == (Ho, Wo)
+    if (T != kh * kw or not (Co2 == Co or (mixed and Co2 == 16 and Co == 4 and kh == 3))
+            or conv_out_hw(H, W, kh, kw, stride, pad) != (Ho, Wo)): _refuse('conv2d_bwd_data', 'layer filter', w_tkc, dy)
     if out is None:
         dx = empty_nhwc(N, Ci, H, W, dy.device, dy.dtype); ldo = Ci
     else:
         dx, ldo = nhwc(out)          # a channel slice of a wider NHWC buffer is fine (ldo > Ci)
-        assert dx.data_ptr() == out.data_ptr() and ldo >= Ci and tuple(out.shape) == (N, Ci, H, W)
+        if dx is not out or ldo < Ci or tuple(out.shape) != (N, Ci, H, W): _refuse('conv2d_bwd_data', 'out', out)
         if mixed:                    # bf16 storage: dy fp32 -> dx bf16 (MRDIS_DT_XBF16_YF32), or dy bf16 -> dx fp32 (MRDIS_DT_XF32_YBF16)
             rc = lib.mrdis_conv2d_bwd_data(_ptr(dy), lddy, _ptr(w_tkc), None, _ptr(dx), ldo, N, H, W, Ci, Co, kh, kw, stride, pad, _dt_xy(dx, dy), None, 0, _stream())
             if rc == -2 and may_decline:
@@ -806,13 +884,8 @@ def conv2d_bwd_data(dy, w_tkc, in_hw, kh, kw, stride, pad, w_bf16=None, out=None
             return dx
     if w_bf16 is not None and w_bf16.dtype is torch.float32:
         w_wino, w_bf16 = w_bf16, None
-    if w_bf16 is not None:
-        assert w_bf16.dtype == torch.bfloat16 and tuple(w_bf16.shape) == (T, Ci, Co) and w_bf16.is_contiguous()
-    wfmt = 0
-    if w_wino is not None:
-        assert w_wino.dtype == torch.float32
-        wfmt = wino_image_fmt(w_wino, Co, Ci, taps=T)
-        assert wfmt == S6_IMAGE_FMT or (kh == 3 and kw == 3)
+    if w_bf16 is not None and (w_bf16.dtype is not torch.bfloat16 or tuple(w_bf16.shape) != (T, Ci, Co) or not w_bf16.is_contiguous()): _refuse('conv2d_bwd_data', 'filter dtype dense', w_bf16)
+    wfmt = 0 if w_wino is None else _image_fmt(w_wino, Co, Ci, T, kh, kw, 'conv2d_bwd_data')
     dt = DT_BF16 if _dt(dy) == DT_BF16 else (DT_F32 if w_bf16 is None else DT_F32_BF16M)
     rc = lib.mrdis_conv2d_bwd_data(_ptr(dy), lddy, _ptr(w_tkc), _ptr(w_bf16), _ptr(dx), ldo, N, H, W, Ci, Co, kh, kw, stride, pad, dt,
                                    _ptr(w_wino) if dt == DT_F32 else None, wfmt, _stream())
@@ -842,32 +915,25 @@ def conv2d_bwd_weight(x, dy, kh, kw, stride, pad, need_bias=True, bias_sink=None
     dy, lddy = nhwc(dy)
     N, Ci, H, W = x.shape
     Co = dy.shape[1]
-    if pad16:
-        assert x.dtype is not dy.dtype and 4 in (Ci, Co), 'pad16: the four-channel mixed-storage kernels only'
+    sink = bias_sink if (need_bias and bias_sink is not None) else None
+    mixed = x.dtype is not dy.dtype  # bf16 storage: the 1x1 head (x bf16, dy fp32: MRDIS_DT_XBF16_YF32), the si_layers (x fp32, dy bf16: MRDIS_DT_XF32_YBF16)
+    if (dy.shape[0] != N or conv_out_hw(H, W, kh, kw, stride, pad) != (dy.shape[2], dy.shape[3])
+            or (pad16 and not (mixed and 4 in (Ci, Co))) or (sink is not None and sink.numel() < Co)): _refuse('conv2d_bwd_weight', 'layer vec arg', x, dy, sink)
     dw = torch.empty((kh * kw, 16 if (pad16 and Ci == 4) else Ci, 16 if (pad16 and Co == 4 and Ci != 4) else Co), dtype=torch.float32, device=x.device)
     db = torch.empty(Co, dtype=torch.float32, device=x.device) if (need_bias and bias_sink is None) else None
     nb = _ws_bytes(lib.mrdis_conv2d_bwd_weight_workspace, N, H, W, Ci, Co, kh, kw, stride, pad)
     if nb == 0:
         raise MrdisError('conv2d_bwd_weight: unsupported geometry')
     ws = _ws(nb, x.device)
-    sink = bias_sink if (need_bias and bias_sink is not None) else None
-    if x.dtype is not dy.dtype:      # bf16 storage: the 1x1 head (x bf16, dy fp32: MRDIS_DT_XBF16_YF32), the si_layers (x fp32, dy bf16: MRDIS_DT_XF32_YBF16)
-        rc = lib.mrdis_conv2d_bwd_weight(_ptr(x), ldx, _ptr(dy), lddy, _ptr(dw), _ptr(sink if sink is not None else db), _ptr(ws), nb,
-                                         N, H, W, Ci, Co, kh, kw, stride, pad, 1 if sink is not None else 0, _dt_xy(x, dy) | (DT_DW_PAD16 if pad16 else 0), _stream())
-        if rc == -2 and may_decline:
-            return None
-        _chk(rc, 'conv2d_bwd_weight (mixed storage)')
-        return dw, db
-    if _dt(x, dy) == DT_BF16:
-        rc = lib.mrdis_conv2d_bwd_weight(_ptr(x), ldx, _ptr(dy), lddy, _ptr(dw), _ptr(sink if sink is not None else db), _ptr(ws), nb,
-                                         N, H, W, Ci, Co, kh, kw, stride, pad, 1 if sink is not None else 0, DT_BF16, _stream())
-        if rc == -2:      # tiny maps / shapes outside the bf16 kernels' domain: the fp32 weight-gradient kernels on fp32 copies of the two views
-            fallbacks['conv2d_bwd_weight_bf16'] += 1
-            return conv2d_bwd_weight(cast_view(x, torch.float32), cast_view(dy, torch.float32), kh, kw, stride, pad, need_bias, bias_sink, DT_F32)
-        _chk(rc, 'conv2d_bwd_weight')
-        return dw, db
-    _chk(lib.mrdis_conv2d_bwd_weight(_ptr(x), ldx, _ptr(dy), lddy, _ptr(dw), _ptr(sink if sink is not None else db), _ptr(ws), nb,
-                                     N, H, W, Ci, Co, kh, kw, stride, pad, 1 if sink is not None else 0, DT_BF16 if _dt(x, dy) == DT_BF16 else int(dtype), _stream()), 'conv2d_bwd_weight')
+    dt = (_dt_xy(x, dy) | (DT_DW_PAD16 if pad16 else 0)) if mixed else (DT_BF16 if _dt(x, dy) == DT_BF16 else int(dtype))
+    rc = lib.mrdis_conv2d_bwd_weight(_ptr(x), ldx, _ptr(dy), lddy, _ptr(dw), _ptr(sink if sink is not None else db), _ptr(ws), nb,
+                                     N, H, W, Ci, Co, kh, kw, stride, pad, 1 if sink is not None else 0, dt, _stream())
+    if rc == -2 and mixed and may_decline:      # mixed storage has only its dedicated kernels
+        return None
+    if rc == -2 and x.dtype is dy.dtype is torch.bfloat16:      # tiny maps / shapes outside the bf16 kernels' domain: the fp32 weight-gradient kernels on fp32 copies of the two views
+        fallbacks['conv2d_bwd_weight_bf16'] += 1
+        return conv2d_bwd_weight(cast_view(x, torch.float32), cast_view(dy, torch.float32), kh, kw, stride, pad, need_bias, bias_sink, DT_F32)
+    _chk(rc, 'conv2d_bwd_weight (mixed storage)' if mixed else 'conv2d_bwd_weight')
     return dw, db
 
 
@@ -875,6 +941,7 @@ def lrelu_bwd(dy, y, slope=0.2):
     lib = load()
     dy, lddy = nhwc(dy); y, ldy = nhwc(y)
     N, C, H, W = y.shape
+    if dy.shape != y.shape: _refuse('lrelu_bwd', 'like', dy, y)
     dx = empty_nhwc(N, C, H, W, y.device, y.dtype)
     _chk(lib.mrdis_lrelu_bwd(_ptr(dy), lddy, _ptr(y), ldy, _ptr(dx), C, N * H * W, C, slope, _dt(dy, y), _stream()), 'lrelu_bwd')
     return dx
@@ -887,12 +954,13 @@ def bn_train_fwd(x, gamma, beta, running_mean, running_var, eps, momentum, out=N
     lib = load()
     x, ldx = nhwc(x)
     N, C, H, W = x.shape
-    assert N % groups == 0
     P = (N // groups) * H * W
     if out is None:
         out = empty_nhwc(N, C, H, W, x.device, x.dtype)
     y, ldy = nhwc(out)
-    assert y.data_ptr() == out.data_ptr()
+    if (y is not out or out.shape != x.shape or N % groups != 0 or gamma.numel() != C or beta.numel() != C or running_mean.numel() != C
+            or running_var.numel() != C or not (gamma.dtype is beta.dtype is running_mean.dtype is running_var.dtype is torch.float32)):
+        _refuse('bn_train_fwd', 'like out vec dtype arg', out, gamma, beta, running_mean, running_var)
     mean = torch.empty(groups * C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(groups * C, dtype=torch.float32, device=x.device)
     nb = groups * _ws_bytes(lib.mrdis_norm_workspace, 1, P, C)
@@ -906,6 +974,8 @@ def bn_eval_fwd(x, gamma, beta, running_mean, running_var, eps):
     lib = load()
     x, ldx = nhwc(x)
     N, C, H, W = x.shape
+    if (gamma.numel() != C or beta.numel() != C or running_mean.numel() != C or running_var.numel() != C
+            or not (gamma.dtype is beta.dtype is running_mean.dtype is running_var.dtype is torch.float32)): _refuse('bn_eval_fwd', 'vec dtype', gamma, beta)
     y = empty_nhwc(N, C, H, W, x.device, x.dtype)
     _chk(lib.mrdis_bn_eval_fwd(_ptr(x), ldx, _ptr(y), C, _ptr(gamma), _ptr(beta), _ptr(running_mean), _ptr(running_var),
                                N * H * W, C, eps, _dt(x), _stream()), 'bn_eval_fwd')
@@ -918,13 +988,16 @@ def bn_train_bwd(dy, x, gamma, mean, rstd, sink=None, groups=1):
     lib = load()
     dy, lddy = nhwc(dy); x, ldx = nhwc(x)
     N, C, H, W = x.shape
+    ag, ab = sink if sink is not None else (None, None)
+    if (dy.shape != x.shape or N % groups != 0 or gamma.numel() != C or mean.numel() != groups * C or rstd.numel() != groups * C
+            or (ag is not None and (ag.numel() != C or ab.numel() != C)) or not (gamma.dtype is mean.dtype is rstd.dtype is torch.float32)):
+        _refuse('bn_train_bwd', 'like vec dtype arg', dy, x, gamma, mean, rstd, ag, ab)
     P = (N // groups) * H * W
     dx = empty_nhwc(N, C, H, W, x.device, x.dtype)
     dg = torch.empty(groups * C, dtype=torch.float32, device=x.device)
     db = torch.empty(groups * C, dtype=torch.float32, device=x.device)
     nb = groups * _ws_bytes(lib.mrdis_norm_workspace, 1, P, C)
     ws = _ws(nb, x.device)
-    ag, ab = sink if sink is not None else (None, None)
     _chk(lib.mrdis_bn_train_bwd(_ptr(dy), lddy, _ptr(x), ldx, _ptr(gamma), _ptr(mean), _ptr(rstd), _ptr(dx), C, _ptr(dg), _ptr(db),
                                 _ptr(ag), _ptr(ab), _ptr(ws), nb, P, C, groups, _dt(dy, x), _stream()), 'bn_train_bwd')
     if groups > 1 and sink is None:
@@ -937,10 +1010,12 @@ def instnorm_spade_fwd(z, gamma, beta, eps=1e-5, stats=None):
     lib = load()
     z, ldz = nhwc(z); gamma, ldg = nhwc(gamma); beta, ldb = nhwc(beta)
     N, C, H, W = z.shape
+    if (gamma.shape != z.shape or beta.shape != z.shape
+            or (stats is not None and not (stats[0].numel() == stats[1].numel() == N * C and stats[0].dtype is stats[1].dtype is torch.float32 and stats[0].is_contiguous() and stats[1].is_contiguous()))):
+        _refuse('instnorm_spade_fwd', 'like vec dense', z, gamma, beta, *(stats or ()))
     out = empty_nhwc(N, C, H, W, z.device, z.dtype)
     if stats is not None:
         mean, rstd = stats
-        assert mean.numel() == N * C and rstd.numel() == N * C and mean.is_contiguous() and rstd.is_contiguous()
         _chk(lib.mrdis_instnorm_spade_fwd(_ptr(z), ldz, _ptr(gamma), ldg, _ptr(beta), ldb, _ptr(out), C, _ptr(mean), _ptr(rstd),
                                           None, 0, N, H * W, C, eps, _dt(z, gamma, beta), _stream()), 'instnorm_spade_fwd')
         return out, mean, rstd
@@ -973,6 +1048,10 @@ def gb_spade_fwd(si_out, w_tck, bias, z, eps=1e-5, out=None, w_bf16=None, stats_
         gamma = empty_nhwc(N, C, H, W, z.device, z.dtype)
     else:
         mix, gamma, mean, rstd = out
+    if (mix.shape != z.shape or gamma.shape != z.shape or mean.numel() != N * C or rstd.numel() != N * C or not (mean.dtype is rstd.dtype is torch.float32)
+            or (bias is not None and (bias.numel() != 2 * C or bias.dtype is not torch.float32))
+            or (w_bf16 is not None and w_bf16.numel() != w_tck.numel())): _refuse('gb_spade_fwd', 'like out vec dtype', mix, gamma, mean, rstd, bias, w_bf16)
+    wfmt = 0 if w_wino is None else _image_fmt(w_wino, Ci, 2 * C, 0, 3, 3, 'gb_spade_fwd', spadeC=C)
     nb = _ws_bytes(lib.mrdis_norm_workspace, N, H * W, C)
     ws = _ws(nb, z.device)
     st = _stream()
@@ -980,10 +1059,6 @@ def gb_spade_fwd(si_out, w_tck, bias, z, eps=1e-5, out=None, w_bf16=None, stats_
     # (stats_ready: `out`'s mean / rstd already hold them -- the x2 resize that produced z took them on the way, bilinear_up2_stats)
     if not stats_ready:
         _chk(lib.mrdis_instnorm_stats(_ptr(z), ldz, _ptr(mean), _ptr(rstd), _ptr(ws), nb, N, H * W, C, eps, dt, st), 'instnorm_stats')
-    wfmt = 0
-    if w_wino is not None:
-        assert w_wino.dtype == torch.float32
-        wfmt = wino_image_fmt(w_wino, Ci, 2 * C, C)
     rc = lib.mrdis_conv2d_fwd_spade(_ptr(x), ldx, _ptr(w_tck), _ptr(w_bf16), _ptr(bias), _ptr(z), ldz, _ptr(mean), _ptr(rstd), _ptr(mix), C, _ptr(gamma), C,
                                     N, H, W, Ci, C, dt, _ptr(w_wino) if dt == DT_F32 else None, wfmt, st)
     if rc == -2:
@@ -1018,50 +1093,34 @@ def instnorm_spade_bwd(dout, z, gamma, mean, rstd, fused_gb=False, up2=False, xl
     if z is not None:
         z, ldz = nhwc(z)
     else:
-        assert up2 and xlo is not None
         ldz = 0
+    if (dout.shape != gamma.shape or mean.numel() != N * C or rstd.numel() != N * C or not (mean.dtype is rstd.dtype is torch.float32)
+            or (z.shape != gamma.shape if z is not None else not (up2 and xlo is not None))): _refuse('instnorm_spade_bwd', 'like vec dtype arg', dout, z, gamma, mean, rstd)
     dt = _dt(dout, gamma) if z is None else _dt(dout, z, gamma)
+    xl, ldxl = (None, 0) if xlo is None or not up2 else nhwc(xlo)
+    if up2 and (not fused_gb or H % 2 or W % 2
+                or (xl is not None and (tuple(xl.shape) != (N, C, H // 2, W // 2) or xl.dtype is not gamma.dtype))): _refuse('instnorm_spade_bwd', 'dtype arg', gamma, xlo)
     nb = _ws_bytes(lib.mrdis_instnorm_spade_bwd_up2_workspace, N, H // 2, W // 2, C, dt) if up2 else _ws_bytes(lib.mrdis_instnorm_spade_bwd_workspace, N, H * W, C)
     ws = _ws(nb, gamma.device)
+    dg, lddg, dbp, lddb = gb_slot(dout) if fused_gb else None, 2 * C, None, 0
+    if not fused_gb:
+        dg, lddg = empty_nhwc(N, C, H, W, gamma.device, gamma.dtype), C
+    elif dg is None:
+        dg = empty_nhwc(N, 2 * C, H, W, gamma.device, gamma.dtype)
+        dbp, lddb = dg.data_ptr() + dg.element_size() * C, 2 * C
+    # (else dout already IS channels [C, 2C) of a 2C-channel buffer -- its producer wrote it there, ops._GroupedConvFn: only dgamma is written, into
+    # the first half -- one pass over the tensor less)
     if up2:
-        assert fused_gb and H % 2 == 0 and W % 2 == 0
         dx = empty_nhwc(N, C, H // 2, W // 2, gamma.device, gamma.dtype)
-        xl, ldxl = (None, 0)
-        if xlo is not None:
-            xl, ldxl = nhwc(xlo)
-            assert tuple(xl.shape) == (N, C, H // 2, W // 2) and xl.dtype == gamma.dtype
-        zp = _ptr(z) if z is not None else None
-        xp = _ptr(xl) if xl is not None else None
-        base = gb_slot(dout)
-        if base is not None:
-            rc = lib.mrdis_instnorm_spade_bwd_up2(_ptr(dout), lddo, zp, ldz, _ptr(gamma), ldg, _ptr(mean), _ptr(rstd), _ptr(dx), C,
-                                                  base.data_ptr(), 2 * C, None, 0, _ptr(ws), nb, N, H // 2, W // 2, C, xp, ldxl, dt, _stream())
-            dgb = base
-        else:
-            dgb = empty_nhwc(N, 2 * C, H, W, gamma.device, gamma.dtype)
-            rc = lib.mrdis_instnorm_spade_bwd_up2(_ptr(dout), lddo, zp, ldz, _ptr(gamma), ldg, _ptr(mean), _ptr(rstd), _ptr(dx), C,
-                                                  dgb.data_ptr(), 2 * C, dgb.data_ptr() + dgb.element_size() * C, 2 * C, _ptr(ws), nb, N, H // 2, W // 2, C, xp, ldxl, dt, _stream())
+        rc = lib.mrdis_instnorm_spade_bwd_up2(_ptr(dout), lddo, _ptr(z), ldz, _ptr(gamma), ldg, _ptr(mean), _ptr(rstd), _ptr(dx), C, dg.data_ptr(), lddg, dbp, lddb,
+                                              _ptr(ws), nb, N, H // 2, W // 2, C, _ptr(xl), ldxl, dt, _stream())
         if rc == -2:
             return None
         _chk(rc, 'instnorm_spade_bwd_up2')
-        return dx, dgb
+        return dx, dg
     dz = empty_nhwc(N, C, H, W, z.device, z.dtype)
-    if fused_gb:
-        base = gb_slot(dout)
-        if base is not None:
-            # dout already IS channels [C, 2C) of a 2C-channel buffer (its producer wrote it there, ops._GroupedConvFn): only dgamma is
-            # written, into the first half -- one pass over the tensor less
-            _chk(lib.mrdis_instnorm_spade_bwd(_ptr(dout), lddo, _ptr(z), ldz, _ptr(gamma), ldg, _ptr(mean), _ptr(rstd), _ptr(dz), C,
-                                              base.data_ptr(), 2 * C, None, 0, _ptr(ws), nb, N, H * W, C, dt, _stream()), 'instnorm_spade_bwd')
-            return dz, base
-        dgb = empty_nhwc(N, 2 * C, H, W, z.device, z.dtype)
-        _chk(lib.mrdis_instnorm_spade_bwd(_ptr(dout), lddo, _ptr(z), ldz, _ptr(gamma), ldg, _ptr(mean), _ptr(rstd), _ptr(dz), C,
-                                          dgb.data_ptr(), 2 * C, dgb.data_ptr() + dgb.element_size() * C, 2 * C, _ptr(ws), nb, N, H * W, C, dt, _stream()),
-             'instnorm_spade_bwd')
-        return dz, dgb
-    dg = empty_nhwc(N, C, H, W, z.device, z.dtype)
-    _chk(lib.mrdis_instnorm_spade_bwd(_ptr(dout), lddo, _ptr(z), ldz, _ptr(gamma), ldg, _ptr(mean), _ptr(rstd), _ptr(dz), C,
-                                      _ptr(dg), C, None, 0, _ptr(ws), nb, N, H * W, C, dt, _stream()), 'instnorm_spade_bwd')
+    _chk(lib.mrdis_instnorm_spade_bwd(_ptr(dout), lddo, _ptr(z), ldz, _ptr(gamma), ldg, _ptr(mean), _ptr(rstd), _ptr(dz), C, dg.data_ptr(), lddg, dbp, lddb,
+                                      _ptr(ws), nb, N, H * W, C, dt, _stream()), 'instnorm_spade_bwd')
     return dz, dg
 
 
@@ -1094,10 +1153,12 @@ def bilinear_up2_stats(x, eps, out_blocks=None):
         y = empty_nhwc(N, C, 2 * Hi, 2 * Wi, x.device, x.dtype)
         yptr = _ptr(y)
     else:
+        if (out_blocks.dim() != 5 or out_blocks.shape[0] * out_blocks.shape[1] != N
+                or tuple(out_blocks.shape[2:]) != (C, 2 * Hi, 2 * Wi) or out_blocks.dtype is not x.dtype): _refuse('bilinear_up2_stats', 'out dtype', out_blocks)
         G, Bb = out_blocks.shape[0], out_blocks.shape[1]
         y0, ld0 = nhwc(out_blocks[0])
-        assert G * Bb == N and tuple(out_blocks.shape[2:]) == (C, 2 * Hi, 2 * Wi) and out_blocks.dtype == x.dtype and ld0 == C
-        assert y0.data_ptr() == out_blocks.data_ptr(), 'blocks must be dense NHWC'
+        if (ld0 != C or y0.data_ptr() != out_blocks.data_ptr()
+                or (G > 1 and out_blocks.stride(0) < Bb * 4 * Hi * Wi * C)): _refuse('bilinear_up2_stats', 'out dense', out_blocks)
         y, yptr, blk, bstride = out_blocks, _ptr(y0), Bb, out_blocks.stride(0)
     mean = torch.empty(N * C, dtype=torch.float32, device=x.device)
     rstd = torch.empty(N * C, dtype=torch.float32, device=x.device)
@@ -1119,7 +1180,7 @@ def bilinear_bwd(dy, in_hw, align_corners, out=None):
         dx = empty_nhwc(N, C, Hi, Wi, dy.device, dy.dtype)
     else:
         dx, ldo = nhwc(out)
-        assert dx.data_ptr() == out.data_ptr() and ldo == C and tuple(out.shape) == (N, C, Hi, Wi) and out.dtype == dy.dtype
+        if dx is not out or ldo != C or tuple(out.shape) != (N, C, Hi, Wi) or out.dtype is not dy.dtype: _refuse('bilinear_bwd', 'out dtype dense', out, dy)
     _chk(lib.mrdis_bilinear_bwd(_ptr(dy), lddy, _ptr(dx), C, N, Hi, Wi, Ho, Wo, C, 1 if align_corners else 0, _dt(dy), _stream()), 'bilinear_bwd')
     return dx
 
@@ -1128,6 +1189,8 @@ def softmax_mask_drop_fwd(s, mask_img, scale=100.0):
     lib = load()
     s, lds = nhwc(s)
     N, C, H, W = s.shape
+    if (s.dtype is not torch.float32
+            or (mask_img is not None and (mask_img.dtype is not torch.float32 or mask_img.numel() != N * H * W))): _refuse('softmax_mask_drop_fwd', 'vec dtype', s, mask_img)
     out = empty_nhwc(N, C, H, W, s.device)
     m = None if mask_img is None else mask_img.contiguous()
     _chk(lib.mrdis_softmax_mask_drop_fwd(_ptr(s), lds, _ptr(m), _ptr(out), C, N * H * W, C, scale, _stream()), 'softmax_mask_drop_fwd')
@@ -1138,6 +1201,7 @@ def softmax_mask_drop_bwd(dout, out):
     lib = load()
     dout, lddo = nhwc(dout); out, ldo = nhwc(out)
     N, C, H, W = out.shape
+    if dout.shape != out.shape or not (dout.dtype is out.dtype is torch.float32): _refuse('softmax_mask_drop_bwd', 'like out dtype', dout, out)
     ds = empty_nhwc(N, C, H, W, out.device)
     _chk(lib.mrdis_softmax_mask_drop_bwd(_ptr(dout), lddo, _ptr(out), ldo, _ptr(ds), C, N * H * W, C, _stream()), 'softmax_mask_drop_bwd')
     return ds
@@ -1147,6 +1211,7 @@ def recon_err_fwd(gt, x, p):
     lib = load()
     gt, ldgt = nhwc(gt); x, ldx = nhwc(x)
     N, C, H, W = x.shape
+    if gt.shape != x.shape or not (gt.dtype is x.dtype is torch.float32): _refuse('recon_err_fwd', 'like dtype', gt, x)
     out = torch.empty(N, dtype=torch.float32, device=x.device)
     nb = _ws_bytes(lib.mrdis_recon_err_workspace, N, H * W, C)
     ws = _ws(nb, x.device)
@@ -1159,6 +1224,8 @@ def recon_metrics(target, pred):
     lib = load()
     target, ldt = nhwc(target); pred, ldp = nhwc(pred)
     N, _, H, W = pred.shape
+    if ((target.shape[0], target.shape[2], target.shape[3]) != (N, H, W)
+            or not (target.dtype is pred.dtype is torch.float32)): _refuse('recon_metrics', 'dtype', target, pred)
     out = torch.empty(N, 3, dtype=torch.float32, device=pred.device)
     nb = _ws_bytes(lib.mrdis_recon_metrics_workspace, N, H)
     ws = _ws(nb, pred.device)
@@ -1170,7 +1237,9 @@ def slice_gather(vol_ptrs, slice_idx, drop, H, W, D, block):
     """vol_ptrs (B,M) int64, slice_idx (B) int32, drop (B) int32 on the device -> inputs (B,(2b+1)M,H,W) NHWC, mask (B,M),
     mask_img (B,H,W)."""
     lib = load()
-    B, M = vol_ptrs.shape
+    B, M = _want(vol_ptrs, 'slice_gather: vol_ptrs', torch.int64, ('B', 'M'))
+    _want(slice_idx, 'slice_gather: slice_idx', torch.int32, (B,), vol_ptrs.device)
+    _want(drop, 'slice_gather: drop', torch.int32, (B,), vol_ptrs.device)
     C = M * (2 * block + 1)
     inputs = empty_nhwc(B, C, H, W, vol_ptrs.device)
     mask = torch.empty((B, M), dtype=torch.float32, device=vol_ptrs.device)
@@ -1184,8 +1253,8 @@ def volume_gather(table, M, H, W, D, z0, Dz, targets=False, K=0, relabel=False):
     """table (B, >= 2M+3) int64 on the device (include/mrdis.h mrdis_volume_gather) -> inputs (B,M,H,W,Dz) channels-last-3d and mask (B,M), or
     with `targets` the label volume (B,H,W,Dz) / its K region channels (B,K,H,W,Dz) channels-last-3d.  One launch."""
     lib = load()
-    B, ld = table.shape
-    assert table.dtype == torch.int64 and table.is_contiguous()
+    B, ld = _want(table, 'volume_gather: table', torch.int64, ('B', 'ld'))
+    if ld < 2 * M + 3: _refuse(f'volume_gather: table rows of at least 2 M + 3 = {2 * M + 3} words', 'vec', table)
     dev = table.device
     if not targets:
         out = torch.empty((B, H, W, Dz, M), dtype=torch.float32, device=dev)
@@ -1199,26 +1268,25 @@ def volume_gather(table, M, H, W, D, z0, Dz, targets=False, K=0, relabel=False):
 
 def _layout_args(a, b, what):
     """(stride array of a, of b, shape array, ndim) for the entry points that take two tensors of one shape and check their layout themselves"""
-    if a.dtype != torch.float32 or b.dtype != torch.float32:
-        raise MrdisError(f'{what}: fp32 tensors only, got {a.dtype} and {b.dtype}')
-    if tuple(a.shape) != tuple(b.shape) or not 1 <= a.dim() <= 8:
-        raise MrdisError(f'{what}: shapes {tuple(a.shape)} and {tuple(b.shape)} must be equal (1 to 8 dimensions)')
+    if a.dtype != torch.float32 or b.dtype != torch.float32 or a.device != b.device: _refuse(what, 'dtype', a, b)
+    if tuple(a.shape) != tuple(b.shape) or not 1 <= a.dim() <= 8: _refuse(what + ' (1 to 8 dimensions)', 'like', a, b)
     nd = a.dim()
     arr = _c.c_longlong * nd
     return arr(*a.stride()), arr(*b.stride()), arr(*a.shape), nd
+
+
+def _nvnet_layouts(what, uout, target, vout, x):
+    """the layout arguments of the pairs (uout, target) and (vout, x) of the 3-D objective: the second pair comes whole or not at all"""
+    if (vout is None) != (x is None) or (vout is not None and vout.device != uout.device): _refuse(what + ': vout and x, together or not at all, on the device of uout', 'arg', vout, x)
+    second = (None, None, None, 0) if vout is None else _layout_args(vout, x, f'{what} (vout, x)')
+    return _layout_args(uout, target, f'{what} (uout, target)') + second
 
 
 def nvnet_loss_fwd(uout, target, vout=None, x=None, w_l2=0.1):
     """-> (sums (4,) float64 = [sum p t, sum p^2, sum t^2, sum (v - x)^2], terms (3,) float32 = [dice, l2, dice + w_l2 * l2]), both on the device
     (include/mrdis.h mrdis_nvnet_loss_fwd).  uout / target and vout / x: one shape and one dense layout per pair, else MrdisError; nothing is copied."""
     lib = load()
-    su, st, shu, ndu = _layout_args(uout, target, 'nvnet_loss_fwd (uout, target)')
-    if (vout is None) != (x is None):
-        raise MrdisError('nvnet_loss_fwd: vout and x come together or not at all')
-    sv = sx = shv = None
-    ndv = 0
-    if vout is not None:
-        sv, sx, shv, ndv = _layout_args(vout, x, 'nvnet_loss_fwd (vout, x)')
+    su, st, shu, ndu, sv, sx, shv, ndv = _nvnet_layouts('nvnet_loss_fwd', uout, target, vout, x)
     dev = uout.device
     sums = torch.empty(4, dtype=torch.float64, device=dev)
     terms = torch.empty(3, dtype=torch.float32, device=dev)
@@ -1232,11 +1300,8 @@ def nvnet_loss_fwd(uout, target, vout=None, x=None, w_l2=0.1):
 def nvnet_loss_bwd(g, sums, uout, target, vout=None, x=None, w_l2=0.1, need_du=True, need_dv=True):
     """-> (du, dv) in the layouts of uout / vout (None where not wanted); g: the gradient of terms[2], one fp32 value on the device."""
     lib = load()
-    su, st, shu, ndu = _layout_args(uout, target, 'nvnet_loss_bwd (uout, target)')
-    sv = sx = shv = None
-    ndv = 0
-    if vout is not None:
-        sv, sx, shv, ndv = _layout_args(vout, x, 'nvnet_loss_bwd (vout, x)')
+    su, st, shu, ndu, sv, sx, shv, ndv = _nvnet_layouts('nvnet_loss_bwd', uout, target, vout, x)
+    _want(sums, 'nvnet_loss_bwd: sums', torch.float64, (4,), uout.device)
     need_dv = need_dv and vout is not None
     if not (need_du or need_dv):
         return None, None
@@ -1257,8 +1322,7 @@ def seg_counts(pred, target, logits=False):
     (include/mrdis.h mrdis_seg_counts); `logits`: the kernel applies the sigmoid.  One launch on channels-last-3d inputs (what the nets and the
     loader write); an input in any other layout is first COPIED into that layout (`ndhwc`), unlike the objective's entry points, which refuse."""
     lib = load()
-    if tuple(pred.shape) != tuple(target.shape):
-        raise MrdisError(f'seg_counts: shapes {tuple(pred.shape)} and {tuple(target.shape)} differ')
+    if tuple(pred.shape) != tuple(target.shape) or pred.device != target.device: _refuse('seg_counts', 'like', pred, target)
     pred, _ = ndhwc(pred); target, _ = ndhwc(target)
     B, C = pred.shape[:2]
     P = pred[0, 0].numel()
@@ -1272,16 +1336,8 @@ def seg_accum(logits, acc, z0, flip_h=False):
     logits (B, C, H, W, Dz) fp32 dense channels-last-3d (the net's output), acc (B, H, W, D, C) fp32 contiguous.  Any other layout raises
     MrdisError: nothing is copied."""
     lib = load()
-    if logits.dtype != torch.float32 or acc.dtype != torch.float32 or logits.dim() != 5 or acc.dim() != 5:
-        raise MrdisError(f'seg_accum: fp32 5-d tensors only, got {logits.dtype} {tuple(logits.shape)} and {acc.dtype} {tuple(acc.shape)}')
-    B, C, H, W, Dz = logits.shape
-    D = acc.shape[3]
-    if tuple(acc.shape) != (B, H, W, D, C):
-        raise MrdisError(f'seg_accum: acc {tuple(acc.shape)} does not belong to logits {tuple(logits.shape)}: (B, H, W, D, C) wanted')
-    if not logits.permute(0, 2, 3, 4, 1).is_contiguous():
-        raise MrdisError(f'seg_accum: logits with strides {logits.stride()} are not dense channels-last-3d')
-    if not acc.is_contiguous():
-        raise MrdisError(f'seg_accum: acc with strides {acc.stride()} is not contiguous')
+    B, C, H, W, Dz = _want(logits, 'seg_accum: logits', torch.float32, ('B', 'C', 'H', 'W', 'Dz'), cl=True)
+    D = _want(acc, 'seg_accum: acc', torch.float32, (B, H, W, 'D', C), logits.device)[3]
     _chk(lib.mrdis_seg_accum(_ptr(logits), _ptr(acc), B, H, W, Dz, D, C, int(z0), int(bool(flip_h)), _stream()), 'seg_accum')
     return acc
 
@@ -1291,14 +1347,9 @@ def seg_label_volume(acc, cover, target_ptrs=None, relabel=False):
     fp32 contiguous as `seg_accum` leaves it, cover (D,) int32 on the device, target_ptrs (B,) int64 on the device: addresses of raw (H, W, D)
     fp32 label volumes, 0 = none (None: none for any sample).  A tensor that is not dense in that layout raises MrdisError; nothing is copied."""
     lib = load()
-    if acc.dtype != torch.float32 or acc.dim() != 5 or not acc.is_contiguous():
-        raise MrdisError(f'seg_label_volume: acc must be a contiguous fp32 (B, H, W, D, C) tensor, got {acc.dtype} {tuple(acc.shape)} strides {acc.stride()}')
-    B, H, W, D, C = acc.shape
-    if cover.dtype != torch.int32 or tuple(cover.shape) != (D,) or not cover.is_contiguous() or cover.device != acc.device:
-        raise MrdisError(f'seg_label_volume: cover must be a contiguous int32 ({D},) tensor on {acc.device}, got {cover.dtype} {tuple(cover.shape)}')
-    if target_ptrs is not None and (target_ptrs.dtype != torch.int64 or tuple(target_ptrs.shape) != (B,) or not target_ptrs.is_contiguous()
-                                    or target_ptrs.device != acc.device):
-        raise MrdisError(f'seg_label_volume: target_ptrs must be a contiguous int64 ({B},) tensor on {acc.device}')
+    B, H, W, D, C = _want(acc, 'seg_label_volume: acc', torch.float32, ('B', 'H', 'W', 'D', 'C'))
+    _want(cover, 'seg_label_volume: cover', torch.int32, (D,), acc.device)
+    target_ptrs is None or _want(target_ptrs, 'seg_label_volume: target_ptrs', torch.int64, (B,), acc.device)      # addresses of raw label volumes
     labels = torch.empty((B, H, W, D), dtype=torch.uint8, device=acc.device)
     counts = torch.zeros((B, C, 3), dtype=torch.int32, device=acc.device)
     _chk(lib.mrdis_seg_label_volume(_ptr(acc), _ptr(cover), _ptr(target_ptrs), _ptr(labels), _ptr(counts), B, H, W, D, C, int(bool(relabel)),
@@ -1308,9 +1359,7 @@ def seg_label_volume(acc, cover, target_ptrs=None, relabel=False):
 
 def _volume_u8(t, what):
     """(B, H, W, D) of a contiguous uint8 device volume, else MrdisError; nothing is copied"""
-    if t.dtype != torch.uint8 or t.dim() != 4 or not t.is_contiguous():
-        raise MrdisError(f'{what} must be a contiguous uint8 (B, H, W, D) tensor, got {t.dtype} {tuple(t.shape)} strides {t.stride()}')
-    return tuple(t.shape)
+    return _want(t, what, torch.uint8, ('B', 'H', 'W', 'D'))
 
 
 def edt_bins(H, W, D):
@@ -1334,11 +1383,8 @@ def region_surfaces(labels, target_ptrs, region_masks):
     R = len(masks)
     if not 1 <= R <= SURF_MAX_REGIONS or any(not 0 <= m <= 255 for m in masks):
         raise MrdisError(f'region_surfaces: 1 .. {SURF_MAX_REGIONS} region masks in 0 .. 255, got {masks}')
-    if B < 1 or H < 1 or W < 1 or D < 1:
-        raise MrdisError(f'region_surfaces: unsupported geometry {(B, H, W, D)}')
-    if target_ptrs is not None and (target_ptrs.dtype != torch.int64 or tuple(target_ptrs.shape) != (B,) or not target_ptrs.is_contiguous()
-                                    or target_ptrs.device != labels.device):
-        raise MrdisError(f'region_surfaces: target_ptrs must be a contiguous int64 ({B},) tensor on {labels.device}')
+    if B < 1 or H < 1 or W < 1 or D < 1: _refuse(f'region_surfaces: unsupported geometry {(B, H, W, D)}', 'arg', labels)
+    target_ptrs is None or _want(target_ptrs, 'region_surfaces: target_ptrs', torch.int64, (B,), labels.device)
     flags = torch.empty((B, H, W, D), dtype=torch.uint8, device=labels.device)
     counts = torch.zeros((B, R, 5), dtype=torch.int32, device=labels.device)
     _chk(lib.mrdis_region_surfaces(_ptr(labels), _ptr(target_ptrs), (_I * R)(*masks), R, _ptr(flags), _ptr(counts), B, H, W, D, _stream()),
@@ -1410,9 +1456,8 @@ def cc_clean(labels, comp, size, min_voxels=0, keep_largest=False, et_label=4, e
     lib = load()
     B, H, W, D = _volume_u8(labels, 'cc_clean: labels')
     _cc_geometry(B, H, W, D, 'cc_clean')
-    for t, what in ((comp, 'comp'), (size, 'size')):
-        if t.dtype != torch.int32 or tuple(t.shape) != (B, H, W, D) or not t.is_contiguous() or t.device != labels.device:
-            raise MrdisError(f'cc_clean: {what} must be a contiguous int32 {(B, H, W, D)} tensor on {labels.device}, got {t.dtype} {tuple(t.shape)}')
+    _want(comp, 'cc_clean: comp', torch.int32, (B, H, W, D), labels.device)
+    _want(size, 'cc_clean: size', torch.int32, (B, H, W, D), labels.device)
     args = [int(min_voxels), int(bool(keep_largest)), int(et_label), int(et_min_voxels), int(et_replace)]
     if args[0] < 0 or args[3] < 0 or not 0 <= args[2] <= 7 or not 0 <= args[4] <= 7:
         raise MrdisError(f'cc_clean: thresholds >= 0 and labels in 0 .. 7, got min_voxels={min_voxels} et_label={et_label} '
@@ -1434,22 +1479,14 @@ def synth_accum(recons, centres, acc, cnt, c_lo, c_hi):
     recons = list(recons)
     if not 1 <= len(recons) <= SYNTH_MAX_SRC:
         raise MrdisError(f'synth_accum: 1 to {SYNTH_MAX_SRC} sources, got {len(recons)}')
-    x0 = recons[0]
-    if x0.dim() != 4:
-        raise MrdisError(f'synth_accum: (B, C, H, W) reconstructions wanted, got {tuple(x0.shape)}')
-    B, C, H, W = x0.shape
-    for x in recons:
-        if x.dtype != torch.float32 or tuple(x.shape) != (B, C, H, W) or x.device != acc.device or not x.permute(0, 2, 3, 1).is_contiguous():
-            raise MrdisError(f'synth_accum: every source must be a dense channels-last fp32 {(B, C, H, W)} tensor on {acc.device}, got {x.dtype} '
-                             f'{tuple(x.shape)} strides {x.stride()} on {x.device}')
+    B, C, H, W = _want(recons[0], 'synth_accum: every source', torch.float32, ('B', 'C', 'H', 'W'), acc.device, cl=True)
+    for x in recons[1:]:
+        _want(x, 'synth_accum: every source', torch.float32, (B, C, H, W), acc.device, cl=True)
     centres = [int(c) for c in centres]
     if len(centres) != B or any(centres[r] != centres[0] + r for r in range(B)):
         raise MrdisError(f'synth_accum: the {B} samples need consecutive centre slices, got {centres}')
-    if acc.dtype != torch.float32 or acc.dim() != 3 or tuple(acc.shape[1:]) != (H, W) or not acc.is_contiguous():
-        raise MrdisError(f'synth_accum: acc must be a contiguous fp32 (D, {H}, {W}) tensor, got {acc.dtype} {tuple(acc.shape)} strides {acc.stride()}')
-    D = acc.shape[0]
-    if cnt.dtype != torch.int32 or tuple(cnt.shape) != (D,) or not cnt.is_contiguous() or cnt.device != acc.device:
-        raise MrdisError(f'synth_accum: cnt must be a contiguous int32 ({D},) tensor on {acc.device}, got {cnt.dtype} {tuple(cnt.shape)}')
+    D = _want(acc, 'synth_accum: acc', torch.float32, ('D', H, W))[0]
+    _want(cnt, 'synth_accum: cnt', torch.int32, (D,), acc.device)
     ptrs = (_c.c_void_p * len(recons))(*[x.data_ptr() for x in recons])
     _chk(lib.mrdis_synth_accum(ptrs, len(recons), _ptr(acc), _ptr(cnt), B, C, H, W, D, centres[0], int(c_lo), int(c_hi), _stream()), 'synth_accum')
     return acc
@@ -1459,11 +1496,8 @@ def synth_finish(acc, cnt, fill=0.0):
     """acc (D, H, W) becomes acc / cnt[d] in place (`fill` where cnt[d] == 0; include/mrdis.h mrdis_synth_finish) -> (acc, the same volume as a new
     contiguous (H, W, D) tensor, the volume store's layout).  acc fp32 and cnt (D,) int32 contiguous on one device, else MrdisError."""
     lib = load()
-    if acc.dtype != torch.float32 or acc.dim() != 3 or not acc.is_contiguous():
-        raise MrdisError(f'synth_finish: acc must be a contiguous fp32 (D, H, W) tensor, got {acc.dtype} {tuple(acc.shape)} strides {acc.stride()}')
-    D, H, W = acc.shape
-    if cnt.dtype != torch.int32 or tuple(cnt.shape) != (D,) or not cnt.is_contiguous() or cnt.device != acc.device:
-        raise MrdisError(f'synth_finish: cnt must be a contiguous int32 ({D},) tensor on {acc.device}, got {cnt.dtype} {tuple(cnt.shape)}')
+    D, H, W = _want(acc, 'synth_finish: acc', torch.float32, ('D', 'H', 'W'))
+    _want(cnt, 'synth_finish: cnt', torch.int32, (D,), acc.device)
     out = torch.empty((H, W, D), dtype=torch.float32, device=acc.device)
     _chk(lib.mrdis_synth_finish(_ptr(acc), _ptr(cnt), _ptr(out), D, H, W, float(fill), _stream()), 'synth_finish')
     return acc, out
@@ -1480,15 +1514,11 @@ def _prep_view(raw, crop, order, what):
     """-> (dtype code, (stride_h, stride_w, stride_d), (H, W, D), (h0, h1, w0, w1)) of a raw device volume; MrdisError for anything the kernels do not
     take, 'unsupported geometry' for extents and crops outside include/mrdis.h's limits."""
     if not isinstance(raw, torch.Tensor) or raw.dim() != 3 or raw.dtype not in PREP_DTYPES or not raw.is_cuda:
-        raise MrdisError(f'{what}: raw must be a 3-D device tensor of dtype uint8, int16, uint16, int32, float32 or float64, got '
-                         f'{getattr(raw, "dtype", type(raw))} {tuple(getattr(raw, "shape", ()))} on {getattr(raw, "device", "the host")}')
+        raise MrdisError(f'{what}: raw must be a 3-D device tensor of dtype uint8, int16, uint16, int32, float32 or float64, {_got(raw)}')
     if order not in PREP_ORDERS:
         raise MrdisError(f'{what}: order {order!r}: one of {PREP_ORDERS}')
     (H, W, D), (sh, sw, sd) = (raw.shape[::-1], raw.stride()[::-1]) if order == 'file' else (raw.shape, raw.stride())
-    try:
-        (h0, h1), (w0, w1) = [[int(v) for v in c] for c in crop]
-    except (TypeError, ValueError):
-        raise MrdisError(f'{what}: crop {crop!r}: ((h0, h1), (w0, w1))') from None
+    h0, h1, w0, w1 = _crop(crop, what)
     if min(sh, sw, sd) < 1:
         raise MrdisError(f'{what}: raw needs positive strides, got {raw.stride()}')
     if not (1 <= min(H, W, D) and max(H, W, D) <= PREP_MAX_EXTENT and H * W * D < 2 ** 31 and min(h0, h1, w0, w1) >= 0 and h0 + h1 < H and w0 + w1 < W):
@@ -1519,14 +1549,13 @@ def prep_write(raw, stats, kind, crop, layout, slope=1.0, inter=0.0, order='file
     code, strides, (H, W, D), cr = _prep_view(raw, crop, order, 'prep_write')
     if kind not in PREP_KINDS or layout not in PREP_LAYOUTS:
         raise MrdisError(f'prep_write: kind {kind!r} must be one of {PREP_KINDS} and layout {layout!r} one of {PREP_LAYOUTS}')
-    if not isinstance(stats, torch.Tensor) or stats.dtype != torch.float64 or tuple(stats.shape) != (5,) or not stats.is_contiguous() or stats.device != raw.device:
-        raise MrdisError(f'prep_write: stats must be the contiguous (5,) float64 tensor of prep_stats on {raw.device}')
+    _want(stats, 'prep_write: stats', torch.float64, (5,), raw.device)
     Hc, Wc = H - cr[0] - cr[1], W - cr[2] - cr[3]
     shape = (D, Hc, Wc) if layout == 'dhw' else (Hc, Wc, D)
     if out is None:
         out = torch.empty(shape, dtype=torch.float32, device=raw.device)
-    elif out.dtype != torch.float32 or tuple(out.shape) != shape or not out.is_contiguous() or out.device != raw.device:
-        raise MrdisError(f'prep_write: out must be a contiguous fp32 {shape} tensor on {raw.device}, got {out.dtype} {tuple(out.shape)} strides {out.stride()}')
+    else:
+        _want(out, 'prep_write: out', torch.float32, shape, raw.device)
     _chk(lib.mrdis_prep_write(_ptr(raw), code, *strides, H, W, D, *cr, float(slope), float(inter), _ptr(stats), PREP_KINDS.index(kind),
                               PREP_LAYOUTS.index(layout), _ptr(out), _stream()), 'prep_write')
     return out
@@ -1548,12 +1577,8 @@ def export_volume(src, crop, layout, kind='copy', stats=None, fill=0.0, dtype=to
     host read.  What the entry point refuses raises MrdisError('... unsupported geometry ...') before any launch."""
     lib = load()
     if not isinstance(src, torch.Tensor) or src.dim() not in (3, 4) or not src.is_cuda:
-        raise MrdisError(f'export_volume: src must be a 3-D device volume or a 4-D stack of them, got {getattr(src, "dtype", type(src))} '
-                         f'{tuple(getattr(src, "shape", ()))} on {getattr(src, "device", "the host")}')
-    try:
-        (h0, h1), (w0, w1) = [[int(v) for v in c] for c in crop]
-    except (TypeError, ValueError):
-        raise MrdisError(f'export_volume: crop {crop!r}: ((h0, h1), (w0, w1))') from None
+        raise MrdisError(f'export_volume: src must be a 3-D device volume or a 4-D stack of them, {_got(src)}')
+    h0, h1, w0, w1 = _crop(crop, 'export_volume')
     stacked = src.dim() == 4
     B = src.shape[0] if stacked else 1
     vol = tuple(src.shape[1:]) if stacked else tuple(src.shape)
@@ -1580,9 +1605,8 @@ def export_volume(src, crop, layout, kind='copy', stats=None, fill=0.0, dtype=to
     shape = (B, D, W, H) if stacked else (D, W, H)
     if out is None:
         out = torch.empty(shape, dtype=dtype, device=src.device)
-    elif not isinstance(out, torch.Tensor) or out.dtype != dtype or tuple(out.shape) != shape or not out.is_contiguous() or out.device != src.device:
-        raise MrdisError(f'export_volume: out must be a dense {dtype} {shape} tensor on {src.device}, got {getattr(out, "dtype", type(out))} '
-                         f'{tuple(getattr(out, "shape", ()))}')
+    else:
+        _want(out, 'export_volume: out', dtype, shape, src.device)
     src = src.contiguous()
     rc = lib.mrdis_export_volume(_ptr(src), PREP_DTYPES[src.dtype], PREP_LAYOUTS.index(layout), Hc, Wc, D, h0, h1, w0, w1, B, EXPORT_KINDS.index(kind),
                                  _ptr(stats), float(fill), _ptr(out), PREP_DTYPES[dtype], _stream())
@@ -1610,18 +1634,12 @@ def seg2d_label_planes(views, flips, planes, s0, relabel=False):
                          f'{len(flips)} codes')
     if any(f not in (0, 1, 2) for f in flips):
         raise MrdisError(f'seg2d_label_planes: flip codes 0 (none), 1 (H) or 2 (W), got {flips}')
-    x0 = views[0][0]
-    if x0.dim() != 4 or not 2 <= x0.shape[1] <= 4:
-        raise MrdisError(f'seg2d_label_planes: (B, C, H, W) logits with 2 <= C <= 4 wanted, got {tuple(x0.shape)}')
-    B, C, H, W = x0.shape
+    B, C, H, W = _want(views[0][0], 'seg2d_label_planes: every view', torch.float32, ('B', 'C', 'H', 'W'), planes.device, cl=True)
+    if not 2 <= C <= 4:
+        raise MrdisError(f'seg2d_label_planes: (B, C, H, W) logits with 2 <= C <= 4 wanted, got {(B, C, H, W)}')
     for x in (x for v in views for x in v):
-        if x.dtype != torch.float32 or tuple(x.shape) != (B, C, H, W) or x.device != planes.device or not x.permute(0, 2, 3, 1).is_contiguous():
-            raise MrdisError(f'seg2d_label_planes: every view must be a dense channels-last fp32 {(B, C, H, W)} tensor on {planes.device}, got '
-                             f'{x.dtype} {tuple(x.shape)} strides {x.stride()} on {x.device}')
-    if planes.dtype != torch.uint8 or planes.dim() != 4 or planes.shape[0] != len(views) or tuple(planes.shape[2:]) != (H, W) or not planes.is_contiguous():
-        raise MrdisError(f'seg2d_label_planes: planes must be a contiguous uint8 ({len(views)}, D, {H}, {W}) tensor, got {planes.dtype} '
-                         f'{tuple(planes.shape)} strides {planes.stride()}')
-    D, s0 = planes.shape[1], int(s0)
+        _want(x, 'seg2d_label_planes: every view', torch.float32, (B, C, H, W), planes.device, cl=True)
+    D, s0 = _want(planes, 'seg2d_label_planes: planes', torch.uint8, (len(views), 'D', H, W))[1], int(s0)
     if s0 < 0 or s0 + B > D:
         raise MrdisError(f'seg2d_label_planes: planes {s0} .. {s0 + B - 1} are outside a volume of {D}')
     ptrs = (_c.c_void_p * (len(views) * n_views))(*[x.data_ptr() for v in views for x in v])
@@ -1636,13 +1654,17 @@ def seg2d_finish(planes):
     (include/mrdis.h mrdis_seg2d_finish).  planes contiguous uint8, else MrdisError.  This package's own convention, like the label planes: the
     reference assembles no volume."""
     lib = load()
-    if planes.dtype != torch.uint8 or planes.dim() != 4 or not planes.is_contiguous() or planes.numel() == 0:
-        raise MrdisError(f'seg2d_finish: planes must be a contiguous uint8 (n_sets, D, H, W) tensor, got {planes.dtype} {tuple(planes.shape)} '
-                         f'strides {planes.stride()}')
-    S, D, H, W = planes.shape
+    S, D, H, W = _want(planes, 'seg2d_finish: planes', torch.uint8, ('n_sets', 'D', 'H', 'W'))
+    if planes.numel() == 0: _refuse('seg2d_finish', 'arg', planes)
     out = torch.empty((S, H, W, D), dtype=torch.uint8, device=planes.device)
     _chk(lib.mrdis_seg2d_finish(_ptr(planes), _ptr(out), S, D, H, W, _stream()), 'seg2d_finish')
     return out
+
+
+def _nhwc_on(t, device, shape, what, out=False):
+    """(view, ld) of an fp32 operand of a cold wrapper, of that (B, C, H, W) on that device: NHWC memory or a channel slice of it (else an input is copied, an output refused)"""
+    if not isinstance(t, torch.Tensor) or t.dtype is not torch.float32 or t.dim() != 4 or t.device != device or tuple(t.shape) != shape: _refuse(f'{what} on {device}', 'like dtype', t, shape)
+    return _out_view(t) if out else nhwc(t)
 
 
 def _fuse_args(what, srcs, mask, method):
@@ -1653,16 +1675,9 @@ def _fuse_args(what, srcs, mask, method):
     if not 1 <= len(srcs) <= FUSE_MAX_SRC:
         raise MrdisError(f'{what}: 1 to {FUSE_MAX_SRC} maps, got {len(srcs)}')
     x0 = srcs[0]
-    if x0.dim() != 4:
-        raise MrdisError(f'{what}: (B, C, H, W) maps wanted, got {tuple(x0.shape)}')
+    views = [_nhwc_on(x, x0.device, tuple(x0.shape), f'{what}: every map') for x in srcs]
     B, C, H, W = x0.shape
-    views = []
-    for x in srcs:
-        if x.dtype is not torch.float32 or tuple(x.shape) != (B, C, H, W) or x.device != x0.device:
-            raise MrdisError(f'{what}: every map must be an fp32 {(B, C, H, W)} tensor on {x0.device}, got {x.dtype} {tuple(x.shape)} on {x.device}')
-        views.append(nhwc(x))
-    if mask.dtype is not torch.float32 or tuple(mask.shape) != (B, len(srcs)) or not mask.is_contiguous() or mask.device != x0.device:
-        raise MrdisError(f'{what}: mask must be a contiguous fp32 ({B}, {len(srcs)}) tensor on {x0.device}, got {mask.dtype} {tuple(mask.shape)} on {mask.device}')
+    _want(mask, f'{what}: mask', torch.float32, (B, len(srcs)), x0.device)
     return [v for v, _ in views], [ld for _, ld in views], mask, FUSE_METHODS.index(method), B, C, H, W
 
 
@@ -1676,9 +1691,7 @@ def fuse_present_fwd(srcs, mask, method, out=None):
     there.  out: an NHWC view to write into (a channel slice of a wider buffer qualifies); default a new channels-last tensor.  One launch."""
     xs, lds, mask, code, B, C, H, W = _fuse_args('fuse_present_fwd', srcs, mask, method)
     F = 3 if code == 2 else 1
-    y, ldy = _out_view(empty_nhwc(B, F * C, H, W, xs[0].device) if out is None else out)
-    if y.dtype is not torch.float32 or tuple(y.shape) != (B, F * C, H, W):
-        raise MrdisError(f'fuse_present_fwd: out must be an fp32 {(B, F * C, H, W)} view, got {y.dtype} {tuple(y.shape)}')
+    y, ldy = _nhwc_on(empty_nhwc(B, F * C, H, W, xs[0].device) if out is None else out, xs[0].device, (B, F * C, H, W), 'fuse_present_fwd: out', out=True)
     ptrs, ldarr = _view_table(xs, lds)
     _chk(load().mrdis_fuse_present_fwd(ptrs, ldarr, len(xs), _ptr(mask), code, _ptr(y), ldy, B, H * W, C, _stream()), 'fuse_present_fwd')
     return y
@@ -1689,17 +1702,12 @@ def fuse_present_bwd(dout, srcs, mask, method, outs=None):
     g to the lowest present index that attains the max / the min (recomputed from the maps).  outs: K NHWC views to write into.  One launch."""
     xs, lds, mask, code, B, C, H, W = _fuse_args('fuse_present_bwd', srcs, mask, method)
     F = 3 if code == 2 else 1
-    if dout.dtype is not torch.float32 or tuple(dout.shape) != (B, F * C, H, W):
-        raise MrdisError(f'fuse_present_bwd: dout must be an fp32 {(B, F * C, H, W)} tensor, got {dout.dtype} {tuple(dout.shape)}')
-    dout, lddo = nhwc(dout)
+    dout, lddo = _nhwc_on(dout, xs[0].device, (B, F * C, H, W), 'fuse_present_bwd: dout')
     if outs is None:
         outs = [empty_nhwc(B, C, H, W, dout.device) for _ in xs]
     if len(outs) != len(xs):
         raise MrdisError(f'fuse_present_bwd: {len(xs)} maps, {len(outs)} gradient views')
-    dviews = [_out_view(t) for t in outs]
-    for d, _ in dviews:
-        if d.dtype is not torch.float32 or tuple(d.shape) != (B, C, H, W):
-            raise MrdisError(f'fuse_present_bwd: every gradient view must be fp32 {(B, C, H, W)}, got {d.dtype} {tuple(d.shape)}')
+    dviews = [_nhwc_on(t, dout.device, (B, C, H, W), 'fuse_present_bwd: every gradient view', out=True) for t in outs]
     ptrs, ldarr = _view_table(xs, lds)
     dptrs, dldarr = _view_table([d for d, _ in dviews], [ld for _, ld in dviews])
     _chk(load().mrdis_fuse_present_bwd(_ptr(dout), lddo, ptrs, ldarr, len(xs), _ptr(mask), code, dptrs, dldarr, B, H * W, C, _stream()),
@@ -1711,6 +1719,7 @@ def recon_err_bwd(gt, x, w, p):
     lib = load()
     gt, ldgt = nhwc(gt); x, ldx = nhwc(x)
     N, C, H, W = x.shape
+    if gt.shape != x.shape or not (gt.dtype is x.dtype is w.dtype is torch.float32) or w.numel() != N: _refuse('recon_err_bwd', 'like dtype', gt, x, w)
     dx = empty_nhwc(N, C, H, W, x.device)
     w = w.contiguous()
     _chk(lib.mrdis_recon_err_bwd(_ptr(gt), ldgt, _ptr(x), ldx, _ptr(w), _ptr(dx), C, N, H * W, C, p, _stream()), 'recon_err_bwd')
@@ -1721,6 +1730,7 @@ def maxpool_fwd(x, k):
     lib = load()
     x, ldx = nhwc(x)
     N, C, H, W = x.shape
+    if x.dtype is not torch.float32 or k < 1: _refuse('maxpool_fwd', 'dtype arg', x)
     y = empty_nhwc(N, C, H // k, W // k, x.device)
     arg = torch.empty((N, H // k, W // k, C), dtype=torch.int32, device=x.device)
     _chk(lib.mrdis_maxpool_fwd(_ptr(x), ldx, _ptr(y), _ptr(arg), N, H, W, C, k, _stream()), 'maxpool_fwd')
@@ -1731,6 +1741,8 @@ def maxpool_bwd(dy, arg, in_shape, k):
     lib = load()
     N, C, H, W = in_shape
     dy, lddy = nhwc(dy)
+    if (dy.dtype is not torch.float32 or k < 1 or tuple(dy.shape) != (N, C, H // k, W // k)
+            or arg.dtype is not torch.int32 or arg.numel() != dy.numel() or not arg.is_contiguous()): _refuse('maxpool_bwd', 'like dtype dense arg', dy, arg)
     if lddy != C:
         dy = dy.contiguous(memory_format=torch.channels_last)
     dx = empty_nhwc(N, C, H, W, dy.device)
@@ -1741,6 +1753,7 @@ def maxpool_bwd(dy, arg, in_shape, k):
 # ---------------------------------------------------------------- optimizer arena
 def sumsq_finite(g, out):
     lib = load()
+    if not (g.dtype is out.dtype is torch.float32) or out.numel() < 2 or not (g.is_contiguous() and out.is_contiguous()): _refuse('sumsq_finite', 'vec dtype dense', g, out)
     nb = _ws_bytes(lib.mrdis_sumsq_workspace)
     ws = _ws(nb, g.device)
     _chk(lib.mrdis_sumsq_finite(_ptr(g), g.numel(), _ptr(out), _ptr(ws), nb, _stream()), 'sumsq_finite')
@@ -1752,19 +1765,19 @@ def adam_amsgrad_step(p, g, m, v, vmax, lr, beta1, beta2, eps, weight_decay, ste
     gates: (ranges [(lo, hi), ...], flag_index [...], flags device tensor) or None.
     gate_steps: device float[3 * n_flags] per-flag step counters (+ scratch), see include/mrdis.h."""
     lib = load()
-    if gates is not None and len(gates[0]):
-        ranges, fidx, flags = gates
-        n_g = len(ranges)
-        ra = (_c.c_longlong * (2 * n_g))(*[int(x) for r in ranges for x in r])
-        fa = (_c.c_int * n_g)(*[int(i) for i in fidx])
-        fl = flags.data_ptr()
-    else:
-        n_g, ra, fa, fl = 0, None, None, None
-    n_flags = 0
-    if n_g and gate_steps is not None:
-        n_flags = gate_steps.numel() // 3
-    else:
+    n = p.numel()
+    ranges, fidx, flags = gates if gates is not None and len(gates[0]) else ((), (), None)
+    n_g = len(ranges)
+    if not (n_g and gate_steps is not None):
         gate_steps = None
+    n_flags = 0 if gate_steps is None else gate_steps.numel() // 3
+    for t, size in ((p, n), (g, n), (m, n), (v, n), (vmax, n), (step_state, 2), (norm_finite, 2), (flags, max(fidx, default=-1) + 1), (gate_steps, 3 * n_flags)):
+        if t is not None and (t.dtype is not torch.float32 or t.numel() < size or (size == n and t.numel() != n) or not t.is_contiguous()): _refuse('adam_amsgrad_step', 'vec dtype dense', t)
+    if (len(fidx) != n_g or any(not 0 <= int(lo) <= int(hi) <= n for lo, hi in ranges) or min(fidx, default=0) < 0
+            or (gate_steps is not None and (step_state is None or max(fidx) >= n_flags))): _refuse('adam_amsgrad_step', 'arg', list(ranges), list(fidx), step_state, gate_steps)
+    ra = (_c.c_longlong * (2 * n_g))(*[int(x) for r in ranges for x in r]) if n_g else None
+    fa = (_c.c_int * n_g)(*[int(i) for i in fidx]) if n_g else None
+    fl = flags.data_ptr() if n_g else None
     _chk(lib.mrdis_adam_amsgrad_step(_ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(vmax), p.numel(), lr, beta1, beta2, eps, weight_decay,
                                      int(step), _ptr(step_state), _ptr(norm_finite), max_norm, grad_scale, ra, fa, n_g, fl, _ptr(gate_steps), n_flags, _stream()),
          'adam_amsgrad_step')
@@ -1784,7 +1797,7 @@ def ndhwc_ld(t):
 def ndhwc(t, keep_slice=False):
     """(tensor, ld) of a logical (N,C,D,H,W) fp32 tensor stored NDHWC (channels_last_3d); copies if it is not.
     keep_slice: a channel slice of a wider NDHWC buffer goes through as it is, with its pixel stride as ld (no copy)."""
-    assert t.dim() == 5 and t.dtype == torch.float32, (t.shape, t.dtype)
+    if t.dim() != 5 or t.dtype is not torch.float32: _refuse('ndhwc', 'dtype', t)
     N, C, D, H, W = t.shape
     if keep_slice:
         ld = ndhwc_ld(t)
@@ -1806,9 +1819,8 @@ def _out3(D, H, W, k, stride, pad):
 
 def _out_view3(out, shape, what):
     """(out, ld) of a caller's output view: NDHWC, dense or a channel slice of a wider buffer (written in place, never copied)"""
-    assert out.dtype == torch.float32 and tuple(out.shape) == tuple(shape), (what, tuple(out.shape), tuple(shape))
-    ld = ndhwc_ld(out)
-    assert ld is not None, f'{what}: `out` must be an NDHWC view'
+    ld = ndhwc_ld(out) if out.dtype is torch.float32 and tuple(out.shape) == shape else None
+    if ld is None: _refuse(what, 'out dtype', out)
     return out, ld
 
 
@@ -1817,7 +1829,9 @@ def conv3d_fwd(x, w_tck, bias, k, stride, pad, residual=None, out=None, keep_sli
     in with their ld instead of as dense copies"""
     x, ldx = ndhwc(x, keep_slices)
     N, Ci, D, H, W = x.shape
-    Co = w_tck.shape[2]
+    Co = w_tck.shape[-1]
+    if (tuple(w_tck.shape) != (k * k * k, Ci, Co) or w_tck.dtype is not torch.float32
+            or not w_tck.is_contiguous() or (bias is not None and bias.numel() != Co)): _refuse('conv3d_fwd', 'filter vec dtype dense', w_tck, bias)
     Do, Ho, Wo = _out3(D, H, W, k, stride, pad)
     if out is None:
         y, ldy = empty_ndhwc(N, Co, Do, Ho, Wo, x.device), Co
@@ -1826,7 +1840,7 @@ def conv3d_fwd(x, w_tck, bias, k, stride, pad, residual=None, out=None, keep_sli
     ldr = 0
     if residual is not None:
         residual, ldr = ndhwc(residual, keep_slices)
-        assert tuple(residual.shape) == tuple(y.shape)
+        if residual.shape != y.shape: _refuse('conv3d_fwd', 'like', residual)
     _chk(load().mrdis_conv3d_fwd(x.data_ptr(), ldx, w_tck.data_ptr(), _ptr(bias), _ptr(residual), ldr, y.data_ptr(), ldy,
                                  N, D, H, W, Ci, Co, k, stride, pad, _stream()), 'conv3d_fwd')
     return y
@@ -1837,6 +1851,8 @@ def conv3d_bwd_data(dy, w_tkc, in_shape, k, stride, pad, out=None, keep_slices=F
     dy, lddy = ndhwc(dy, keep_slices)
     N, Ci, D, H, W = in_shape
     Co = dy.shape[1]
+    if (tuple(w_tkc.shape) != (k * k * k, Co, Ci) or w_tkc.dtype is not torch.float32 or not w_tkc.is_contiguous()
+            or (dy.shape[0],) + tuple(dy.shape[2:]) != (N,) + _out3(D, H, W, k, stride, pad)): _refuse('conv3d_bwd_data', 'layer filter dtype dense', w_tkc, dy)
     if out is None:
         dx, lddx = empty_ndhwc(N, Ci, D, H, W, dy.device), Ci
     else:
@@ -1852,6 +1868,7 @@ def conv3d_bwd_weight(x, dy, k, stride, pad, want_bias, out=None, keep_slices=Fa
     dy, lddy = ndhwc(dy, keep_slices)
     N, Ci, D, H, W = x.shape
     Co = dy.shape[1]
+    if (dy.shape[0],) + tuple(dy.shape[2:]) != (N,) + _out3(D, H, W, k, stride, pad): _refuse('conv3d_bwd_weight', 'layer', x, dy)
     lib = load()
     need = lib.mrdis_conv3d_bwd_weight_workspace(N, D, H, W, Ci, Co, k, stride, pad)
     if need == 0:
@@ -1862,8 +1879,8 @@ def conv3d_bwd_weight(x, dy, k, stride, pad, want_bias, out=None, keep_slices=Fa
         db = torch.empty((Co,), dtype=torch.float32, device=x.device) if want_bias else None
     else:
         dw, db = out
-        assert dw.dtype == torch.float32 and tuple(dw.shape) == (k * k * k, Ci, Co) and dw.is_contiguous(), (dw.shape, dw.dtype)
-        assert (db is not None) == bool(want_bias) and (db is None or (db.dtype == torch.float32 and tuple(db.shape) == (Co,) and db.is_contiguous()))
+        if (tuple(dw.shape) != (k * k * k, Ci, Co) or (db is not None) != bool(want_bias) or dw.dtype is not torch.float32 or not dw.is_contiguous()
+                or (db is not None and (db.dtype is not torch.float32 or db.numel() != Co or not db.is_contiguous()))): _refuse('conv3d_bwd_weight', 'out dtype dense', dw, db)
     _chk(lib.mrdis_conv3d_bwd_weight(x.data_ptr(), ldx, dy.data_ptr(), lddy, dw.data_ptr(), _ptr(db), ws.data_ptr(), ws.numel(),
                                      N, D, H, W, Ci, Co, k, stride, pad, _stream()), 'conv3d_bwd_weight')
     return dw, db
@@ -1872,6 +1889,7 @@ def conv3d_bwd_weight(x, dy, k, stride, pad, want_bias, out=None, keep_slices=Fa
 def groupnorm_relu_fwd(x, gamma, beta, G, eps, relu):
     x, ld = ndhwc(x)
     N, C, D, H, W = x.shape
+    if G < 1 or C % G != 0 or gamma.numel() != C or beta.numel() != C or not (gamma.dtype is beta.dtype is torch.float32): _refuse('groupnorm_relu_fwd', 'vec dtype arg', gamma, beta)
     P = D * H * W
     y = empty_ndhwc(N, C, D, H, W, x.device)
     mean = torch.empty((N, G), dtype=torch.float32, device=x.device)
@@ -1890,8 +1908,9 @@ def groupnorm_relu_bwd(dy, x, gamma, beta, mean, rstd, G, relu, add=None):
     ldadd = 0
     if add is not None:
         add, ldadd = ndhwc(add)
-        assert tuple(add.shape) == tuple(x.shape)
     N, C, D, H, W = x.shape
+    if (dy.shape != x.shape or (add is not None and add.shape != x.shape) or G < 1 or C % G != 0 or not (gamma.dtype is beta.dtype is mean.dtype is rstd.dtype is torch.float32)
+            or gamma.numel() != C or beta.numel() != C or mean.numel() != N * G or rstd.numel() != N * G): _refuse('groupnorm_relu_bwd', 'like vec dtype arg', dy, x, add, gamma, beta, mean, rstd)
     P = D * H * W
     dx = empty_ndhwc(N, C, D, H, W, x.device)
     dgamma = torch.empty((C,), dtype=torch.float32, device=x.device)
@@ -1909,7 +1928,7 @@ def upsample2x_add_fwd(x, skip):
     N, C, D, H, W = x.shape
     if skip is not None:
         skip, _ = ndhwc(skip)
-        assert tuple(skip.shape) == (N, C, 2 * D, 2 * H, 2 * W)
+        if tuple(skip.shape) != (N, C, 2 * D, 2 * H, 2 * W): _refuse('upsample2x_add_fwd', 'arg', skip)
     y = empty_ndhwc(N, C, 2 * D, 2 * H, 2 * W, x.device)
     _chk(load().mrdis_upsample2x_add_fwd(x.data_ptr(), _ptr(skip), y.data_ptr(), N, D, H, W, C, _stream()), 'upsample2x_add_fwd')
     return y
@@ -1918,6 +1937,7 @@ def upsample2x_add_fwd(x, skip):
 def upsample2x_bwd(dy):
     dy, _ = ndhwc(dy)
     N, C, D2, H2, W2 = dy.shape
+    if D2 % 2 or H2 % 2 or W2 % 2: _refuse('upsample2x_bwd', 'arg', dy)
     dx = empty_ndhwc(N, C, D2 // 2, H2 // 2, W2 // 2, dy.device)
     _chk(load().mrdis_upsample2x_bwd(dy.data_ptr(), dx.data_ptr(), N, D2 // 2, H2 // 2, W2 // 2, C, _stream()), 'upsample2x_bwd')
     return dx
@@ -1931,18 +1951,17 @@ def cosine_top1(gallery, gallery_label, query, query_label):
     """For each query row: the gallery row of highest cosine (reference compute_cosine, model.py:3407-3415) among the rows whose label differs
     from the query's; equal cosines -> the smaller index.  gallery (N, D) fp32 with unit column stride (row stride >= D), query (Q <= 64, D),
     labels int32 on the device.  Returns (idx (Q,) int32, cos (Q,) fp32); a query with every row excluded gets -1 / -inf (include/mrdis.h)."""
-    assert gallery.dtype == torch.float32 and query.dtype == torch.float32, (gallery.dtype, query.dtype)
-    assert gallery.dim() == 2 and query.dim() == 2 and gallery.shape[1] == query.shape[1], (gallery.shape, query.shape)
-    assert gallery_label.dtype == torch.int32 and query_label.dtype == torch.int32
+    if not isinstance(gallery, torch.Tensor) or gallery.dtype is not torch.float32 or gallery.dim() != 2: _refuse('cosine_top1', 'dtype', gallery)
     N, D = gallery.shape
-    Q = query.shape[0]
-    assert gallery_label.shape == (N,) and query_label.shape == (Q,) and 1 <= Q <= 64, (gallery_label.shape, query_label.shape)
     if gallery.stride(1) != 1 or gallery.stride(0) < D:
         gallery = gallery.contiguous()
-    query = query.contiguous()
-    gallery_label, query_label = gallery_label.contiguous(), query_label.contiguous()
-    lib = load()
     dev = gallery.device
+    Q = _want(query, 'cosine_top1: query', torch.float32, ('Q', D), dev, dense=False)[0]
+    _want(gallery_label, 'cosine_top1: gallery_label', torch.int32, (N,), dev, dense=False)
+    _want(query_label, 'cosine_top1: query_label', torch.int32, (Q,), dev, dense=False)
+    if not 1 <= Q <= 64: _refuse('cosine_top1: 1 .. 64 queries', 'arg', query)
+    query, query_label, gallery_label = query.contiguous(), query_label.contiguous(), gallery_label.contiguous()
+    lib = load()
     nb = _ws_bytes(lib.mrdis_cosine_top1_workspace, N, D, Q)
     if nb == 0:
         raise MrdisError(f'cosine_top1: unsupported geometry N={N} D={D} Q={Q}')
@@ -1959,8 +1978,7 @@ def cosine_top1(gallery, gallery_label, query, query_label):
 
 # ---------------------------------------------------------------- the `others` variants (csrc/mrdis_encs.hip)
 def _f32_nhwc(t, what):
-    if t.dtype is not torch.float32:
-        raise MrdisError(f'{what}: fp32 activations only (got {t.dtype})')
+    if t.dtype is not torch.float32: _refuse(what, 'dtype', t)
     return nhwc(t)
 
 
@@ -1970,11 +1988,11 @@ def conv2d_2src_fwd(x, s, w_tck, bias, kh, kw, stride, pad, lrelu=False, out=Non
     x, ldx = _f32_nhwc(x, 'conv2d_2src_fwd x'); s, lds = _f32_nhwc(s, 'conv2d_2src_fwd s')
     N, Cx, H, W = x.shape
     Cs = s.shape[1]
-    assert s.shape[0] == N and tuple(s.shape[2:]) == (H, W), (x.shape, s.shape)
-    Co = w_tck.shape[2]
-    assert w_tck.shape[:2] == (kh * kw, Cx + Cs) and w_tck.is_contiguous(), (w_tck.shape, Cx, Cs)
+    Co = w_tck.shape[-1]
+    if ((s.shape[0], s.shape[2], s.shape[3]) != (N, H, W) or tuple(w_tck.shape) != (kh * kw, Cx + Cs, Co) or w_tck.dtype is not torch.float32
+            or not w_tck.is_contiguous() or (bias is not None and bias.numel() != Co)): _refuse('conv2d_2src_fwd', 'filter vec dtype dense', x, s, w_tck, bias)
     Ho, Wo = conv_out_hw(H, W, kh, kw, stride, pad)
-    y, ldy = _out_view(empty_nhwc(N, Co, Ho, Wo, x.device) if out is None else out)
+    y, ldy = _out_view(empty_nhwc(N, Co, Ho, Wo, x.device) if out is None else out, (N, Co, Ho, Wo))
     _chk(load().mrdis_conv2d_2src_fwd(_ptr(x), ldx, Cx, _ptr(s), lds, Cs, _ptr(w_tck), _ptr(bias), _ptr(y), ldy, N, H, W, Co, kh, kw, stride, pad,
                                       1 if lrelu else 0, _stream()), 'conv2d_2src_fwd')
     return y
@@ -1985,11 +2003,12 @@ def conv2d_2src_bwd_data(dy, w_tkc, Cx, Cs, in_hw, kh, kw, stride, pad, need_dx=
     dy, lddy = _f32_nhwc(dy, 'conv2d_2src_bwd_data dy')
     N, Co = dy.shape[:2]
     H, W = in_hw
-    assert w_tkc.shape == (kh * kw, Co, Cx + Cs) and w_tkc.is_contiguous(), (w_tkc.shape, Co, Cx, Cs)
-    ds, ldds = _out_view(empty_nhwc(N, Cs, H, W, dy.device) if ds_out is None else ds_out)
+    if (tuple(w_tkc.shape) != (kh * kw, Co, Cx + Cs) or w_tkc.dtype is not torch.float32 or not w_tkc.is_contiguous()
+            or conv_out_hw(H, W, kh, kw, stride, pad) != (dy.shape[2], dy.shape[3])): _refuse('conv2d_2src_bwd_data', 'layer filter dtype dense', w_tkc, dy)
+    ds, ldds = _out_view(empty_nhwc(N, Cs, H, W, dy.device) if ds_out is None else ds_out, (N, Cs, H, W))
     dx, lddx = (None, Cx)
     if need_dx:
-        dx, lddx = _out_view(empty_nhwc(N, Cx, H, W, dy.device) if dx_out is None else dx_out)
+        dx, lddx = _out_view(empty_nhwc(N, Cx, H, W, dy.device) if dx_out is None else dx_out, (N, Cx, H, W))
     _chk(load().mrdis_conv2d_2src_bwd_data(_ptr(dy), lddy, _ptr(w_tkc), _ptr(dx), lddx, Cx, _ptr(ds), ldds, Cs, N, H, W, Co, kh, kw, stride, pad,
                                            _stream()), 'conv2d_2src_bwd_data')
     return dx, ds
@@ -2001,14 +2020,17 @@ def conv2d_2src_bwd_weight(x, s, dy, kh, kw, stride, pad, need_bias=True, bias_s
     dy, lddy = _f32_nhwc(dy, 'conv2d_2src_bwd_weight dy')
     N, Cx, H, W = x.shape
     Cs, Co = s.shape[1], dy.shape[1]
+    if ((s.shape[0], s.shape[2], s.shape[3]) != (N, H, W)
+            or (dy.shape[0], dy.shape[2], dy.shape[3]) != (N,) + conv_out_hw(H, W, kh, kw, stride, pad)): _refuse('conv2d_2src_bwd_weight', 'layer', x, s, dy)
     lib = load()
     nb = _ws_bytes(lib.mrdis_conv2d_2src_bwd_weight_workspace, N, H, W, Cx, Cs, Co, kh, kw, stride, pad)
     if nb == 0:
         raise MrdisError(f'conv2d_2src_bwd_weight: unsupported geometry Cx={Cx} Cs={Cs} Co={Co} k={kh}x{kw} stride={stride}')
     ws = _ws(nb, x.device)
     dw = torch.empty((kh * kw, Cx + Cs, Co), dtype=torch.float32, device=x.device) if dw_out is None else dw_out
-    assert dw.is_contiguous() and dw.numel() == kh * kw * (Cx + Cs) * Co
     sink = bias_sink if need_bias else None
+    if (dw.dtype is not torch.float32 or dw.numel() != kh * kw * (Cx + Cs) * Co or not dw.is_contiguous()
+            or (sink is not None and sink.numel() != Co)): _refuse('conv2d_2src_bwd_weight', 'vec dtype dense', dw, sink)
     db = torch.empty(Co, dtype=torch.float32, device=x.device) if (need_bias and sink is None) else None
     _chk(lib.mrdis_conv2d_2src_bwd_weight(_ptr(x), ldx, Cx, _ptr(s), lds, Cs, _ptr(dy), lddy, _ptr(dw), _ptr(sink if sink is not None else db),
                                           1 if sink is not None else 0, _ptr(ws), nb, N, H, W, Co, kh, kw, stride, pad, _stream()),
@@ -2016,50 +2038,44 @@ def conv2d_2src_bwd_weight(x, s, dy, kh, kw, stride, pad, need_bias=True, bias_s
     return dw, db
 
 
-def _out_view(t):
-    """(t, ld) for an output NHWC view that the kernel writes in place (never a silent copy)"""
+def _out_view(t, shape=None):
+    """(t, ld) for an fp32 output NHWC view (of that shape, where given) that the kernel writes in place (never a silent copy)"""
     v, ld = nhwc(t)
-    if v is not t:
-        raise MrdisError('output buffers must be NHWC views (channels_last, or a channel slice of one)')
+    if v is not t or (shape is not None and (tuple(t.shape) != shape or t.dtype is not torch.float32)): _refuse('output', 'out vec dtype', t)
     return v, ld
 
 
 def _act_views(what, *ts):
+    """[(view, ld)] of fp32 NHWC activations that share one shape"""
+    if any(t.shape != ts[0].shape for t in ts): _refuse(what, 'like', *ts)
     return [_f32_nhwc(t, what) for t in ts]
+
+
+def _elementwise(entry, what, ts, out, nhw=False):
+    """one element-wise pass over fp32 NHWC views of one shape -> the output view (out: an NHWC view to write into).  nhw: the entry point takes (B, H, W, C), not (pixels, C)"""
+    views = _act_views(what, *ts)
+    N, C, H, W = ts[0].shape
+    y, ldy = _out_view(empty_nhwc(N, C, H, W, ts[0].device) if out is None else out, (N, C, H, W))
+    _chk(entry(*[a for v, ld in views for a in (_ptr(v), ld)], _ptr(y), ldy, *((N, H, W, C) if nhw else (N * H * W, C)), _stream()), what)
+    return y
 
 
 def softplus_fwd(x, out=None):
     """F.softplus(x) (beta 1, threshold 20) over an NHWC view"""
-    (x, ldx), = _act_views('softplus_fwd', x)
-    N, C, H, W = x.shape
-    y, ldy = _out_view(empty_nhwc(N, C, H, W, x.device) if out is None else out)
-    _chk(load().mrdis_softplus_fwd(_ptr(x), ldx, _ptr(y), ldy, N * H * W, C, _stream()), 'softplus_fwd')
-    return y
+    return _elementwise(load().mrdis_softplus_fwd, 'softplus_fwd', (x,), out)
 
 
 def softplus_bwd(dy, x, out=None):
-    (dy, lddy), (x, ldx) = _act_views('softplus_bwd', dy, x)
-    N, C, H, W = x.shape
-    dx, lddx = _out_view(empty_nhwc(N, C, H, W, x.device) if out is None else out)
-    _chk(load().mrdis_softplus_bwd(_ptr(dy), lddy, _ptr(x), ldx, _ptr(dx), lddx, N * H * W, C, _stream()), 'softplus_bwd')
-    return dx
+    return _elementwise(load().mrdis_softplus_bwd, 'softplus_bwd', (dy, x), out)
 
 
 def softmax_fwd(s, out=None):
     """F.softmax(s, 1) over the channels of an NHWC view (C <= 8)"""
-    (s, lds), = _act_views('softmax_fwd', s)
-    N, C, H, W = s.shape
-    y, ldy = _out_view(empty_nhwc(N, C, H, W, s.device) if out is None else out)
-    _chk(load().mrdis_softmax_fwd(_ptr(s), lds, _ptr(y), ldy, N * H * W, C, _stream()), 'softmax_fwd')
-    return y
+    return _elementwise(load().mrdis_softmax_fwd, 'softmax_fwd', (s,), out)
 
 
 def softmax_bwd(dout, out_fwd, out=None):
-    (dout, lddo), (o, ldo) = _act_views('softmax_bwd', dout, out_fwd)
-    N, C, H, W = o.shape
-    ds, ldds = _out_view(empty_nhwc(N, C, H, W, o.device) if out is None else out)
-    _chk(load().mrdis_softmax_bwd(_ptr(dout), lddo, _ptr(o), ldo, _ptr(ds), ldds, N * H * W, C, _stream()), 'softmax_bwd')
-    return ds
+    return _elementwise(load().mrdis_softmax_bwd, 'softmax_bwd', (dout, out_fwd), out)
 
 
 # ---------------------------------------------------------------- the latent-code options (csrc/mrdis_latent.hip)
@@ -2068,8 +2084,7 @@ KL_MAXM = 8
 
 def _rows_view(t, what):
     """(t, row stride) of a (B, Z) fp32 device view whose rows are dense"""
-    if t.dtype is not torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1):
-        raise MrdisError(f'{what}: (B, Z) fp32 views with dense rows only (got {tuple(t.shape)} {t.dtype} strides {t.stride()})')
+    if t.dtype is not torch.float32 or t.dim() != 2 or (t.shape[1] > 1 and t.stride(1) != 1): _refuse(what + ' (B, Z) rows', 'dtype dense', t)
     return t, (t.stride(0) if t.shape[0] > 1 else t.shape[1])
 
 
@@ -2078,8 +2093,9 @@ def _ptr_array(ts):
 
 
 def _blocks(ts, what):
-    """M (B, Z) blocks sharing one row stride -> (host pointer array, ld)"""
+    """M (B, Z) blocks of one shape sharing one row stride -> (views, ld)"""
     views = [_rows_view(t, what) for t in ts]
+    if any(t.shape != ts[0].shape for t in ts): _refuse(what, 'like', *ts)
     lds = {ld for _, ld in views}
     if len(lds) != 1:
         ts = [t.contiguous() for t in ts]
@@ -2091,30 +2107,34 @@ def _prior_view(pmu, plv, M, B, Z):
     """the prior as (pmu, plv, ldp_m, ldp_b): (M, Z) tensors (one row per contrast, broadcast over the batch) or (M, B, Z) (one row per sample)"""
     if pmu is None:
         return None, None, 0, 0
-    assert pmu.shape == plv.shape and pmu.dtype == plv.dtype == torch.float32, (pmu.shape, plv.shape)
+    if (plv is None or pmu.shape != plv.shape or not (pmu.dtype is plv.dtype is torch.float32)
+            or tuple(pmu.shape) not in ((M, Z), (M, B, Z))): _refuse('kl', 'dtype', pmu, plv)
     if pmu.dim() == 2:
-        assert tuple(pmu.shape) == (M, Z), (pmu.shape, M, Z)
         if pmu.stride() != plv.stride() or pmu.stride(1) != 1:
             pmu, plv = pmu.contiguous(), plv.contiguous()
         return pmu, plv, pmu.stride(0), 0
-    assert tuple(pmu.shape) == (M, B, Z), (pmu.shape, M, B, Z)
     if pmu.stride() != plv.stride() or pmu.stride(2) != 1 or pmu.stride(0) == 0 or pmu.stride(1) == 0:
         pmu, plv = pmu.contiguous(), plv.contiguous()
     return pmu, plv, pmu.stride(0), pmu.stride(1)
+
+
+def _kl_views(what, mu_list, lv_list, weight):
+    """the operands kl_fwd / kl_bwd share: -> (mu views, ldmu, log-variance views, ldlv, the (M, B) weight table, B, Z)"""
+    M = len(mu_list)
+    if not 1 <= M <= KL_MAXM or len(lv_list) != M:
+        raise MrdisError(f'{what}: 1 .. {KL_MAXM} contrasts (got {M} mu, {len(lv_list)} log-variance blocks)')
+    mus, ldmu = _blocks(mu_list, f'{what} mu')
+    lvs, ldlv = _blocks(lv_list, f'{what} log-variance')
+    B, Z = mus[0].shape
+    if lvs[0].shape != mus[0].shape or weight.dtype is not torch.float32 or tuple(weight.shape) != (M, B): _refuse(what, 'like vec dtype', lvs[0], weight)
+    return mus, ldmu, lvs, ldlv, weight.contiguous(), B, Z
 
 
 def kl_fwd(mu_list, lv_list, weight, pmu=None, plv=None):
     """-> 0-dim loss: sum_{i,b} weight[i, b] sum_z kl(mu_list[i][b], lv_list[i][b] | prior) (include/mrdis.h mrdis_kl_fwd).
     mu_list / lv_list: M (B, Z) fp32 views; weight: (M, B); pmu / plv: None (standard), (M, Z) or (M, B, Z) (two-Gaussian)."""
     M = len(mu_list)
-    if not 1 <= M <= KL_MAXM or len(lv_list) != M:
-        raise MrdisError(f'kl_fwd: 1 .. {KL_MAXM} contrasts (got {M} mu, {len(lv_list)} log-variance blocks)')
-    B, Z = mu_list[0].shape
-    mus, ldmu = _blocks(mu_list, 'kl_fwd mu')
-    lvs, ldlv = _blocks(lv_list, 'kl_fwd log-variance')
-    assert all(tuple(t.shape) == (B, Z) for t in mus + lvs)
-    w = weight.contiguous()
-    assert tuple(w.shape) == (M, B) and w.dtype == torch.float32, (w.shape, w.dtype)
+    mus, ldmu, lvs, ldlv, w, B, Z = _kl_views('kl_fwd', mu_list, lv_list, weight)
     pmu, plv, ldp_m, ldp_b = _prior_view(pmu, plv, M, B, Z)
     loss = torch.empty((), dtype=torch.float32, device=mus[0].device)
     _chk(load().mrdis_kl_fwd(_ptr_array(mus), _ptr_array(lvs), ldmu, ldlv, _ptr(pmu), _ptr(plv), ldp_m, ldp_b, _ptr(w), _ptr(loss), M, B, Z,
@@ -2126,12 +2146,10 @@ def kl_bwd(dloss, mu_list, lv_list, weight, pmu=None, plv=None, need_prior=True)
     """-> (dmu (M, B, Z), dlv (M, B, Z), dpmu, dplv): the gradients of kl_fwd for the upstream gradient dloss (a 0-dim DEVICE tensor).
     dpmu / dplv have the prior's shape ((M, Z): summed over the batch), None without a prior or when need_prior is False."""
     M = len(mu_list)
-    B, Z = mu_list[0].shape
-    mus, ldmu = _blocks(mu_list, 'kl_bwd mu')
-    lvs, ldlv = _blocks(lv_list, 'kl_bwd log-variance')
-    w = weight.contiguous()
+    mus, ldmu, lvs, ldlv, w, B, Z = _kl_views('kl_bwd', mu_list, lv_list, weight)
     pmu, plv, ldp_m, ldp_b = _prior_view(pmu, plv, M, B, Z)
     dev = mus[0].device
+    if dloss.numel() != 1 or not dloss.is_floating_point(): _refuse('kl_bwd', 'arg', dloss)
     dmu = torch.empty((M, B, Z), dtype=torch.float32, device=dev)
     dlv = torch.empty((M, B, Z), dtype=torch.float32, device=dev)
     dpmu = dplv = None
@@ -2147,8 +2165,7 @@ def kl_bwd(dloss, mu_list, lv_list, weight, pmu=None, plv=None, need_prior=True)
 
 def avgpool_fwd(x, k):
     """F.avg_pool2d(x, k).view(N, -1) of an NHWC fp32 view: the dense (N, C * (H // k) * (W // k)) compact vector"""
-    if x.dtype is not torch.float32:
-        raise MrdisError(f'avgpool_fwd: fp32 maps only (got {x.dtype})')
+    if x.dtype is not torch.float32 or k < 1: _refuse('avgpool_fwd', 'dtype arg', x)
     x, ldx = nhwc(x)
     N, C, H, W = x.shape
     y = torch.empty((N, C * (H // k) * (W // k)), dtype=torch.float32, device=x.device)
@@ -2160,16 +2177,15 @@ def avgpool_bwd(dy, in_shape, k, out=None):
     """dx (N, C, H, W) NHWC of avgpool_fwd for dy (N, D); out: an NHWC view to write into"""
     N, C, H, W = in_shape
     dy = dy.contiguous()
-    assert tuple(dy.shape) == (N, C * (H // k) * (W // k)) and dy.dtype == torch.float32, (dy.shape, in_shape, k)
-    dx, lddx = _out_view(empty_nhwc(N, C, H, W, dy.device) if out is None else out)
+    if k < 1 or tuple(dy.shape) != (N, C * (H // k) * (W // k)) or dy.dtype is not torch.float32: _refuse('avgpool_bwd', 'dtype arg', dy)
+    dx, lddx = _out_view(empty_nhwc(N, C, H, W, dy.device) if out is None else out, (N, C, H, W))
     _chk(load().mrdis_avgpool_bwd(_ptr(dy), _ptr(dx), lddx, N, H, W, C, k, _stream()), 'avgpool_bwd')
     return dx
 
 
 # ---------------------------------------------------------------- the attention output decoders (csrc/mrdis_outdec.hip)
 def _dense_f32(t, shape, what):
-    if t.dtype is not torch.float32 or tuple(t.shape) != tuple(shape):
-        raise MrdisError(f'{what}: fp32 {tuple(shape)} expected (got {tuple(t.shape)} {t.dtype})')
+    if t.dtype is not torch.float32 or tuple(t.shape) != tuple(shape): _refuse(f'{what} {tuple(shape)}', 'vec dtype', t)
     return t.contiguous()
 
 
@@ -2179,13 +2195,10 @@ def chatt_fwd(x, s, wd, bd, wu, bu, out=None):
     -> (out, pool (B, C), hid (B, Hd), a (B, C)): the last three are what chatt_bwd reads."""
     (x, ldx), (s, lds) = _act_views('chatt_fwd', x, s)
     B, C, H, W = x.shape
-    if tuple(s.shape) != (B, C, H, W):
-        raise MrdisError(f'chatt_fwd: x {tuple(x.shape)} and s {tuple(s.shape)} differ')
     Hd = wd.shape[0]
     wd, bd = _dense_f32(wd, (Hd, C), 'chatt_fwd W_down'), _dense_f32(bd, (Hd,), 'chatt_fwd b_down')
     wu, bu = _dense_f32(wu, (C, Hd), 'chatt_fwd W_up'), _dense_f32(bu, (C,), 'chatt_fwd b_up')
-    o, ldo = _out_view(empty_nhwc(B, C, H, W, x.device) if out is None else out)
-    assert tuple(o.shape) == (B, C, H, W) and o.dtype == torch.float32, (o.shape, o.dtype)
+    o, ldo = _out_view(empty_nhwc(B, C, H, W, x.device) if out is None else out, (B, C, H, W))
     dev = x.device
     pool = torch.empty((B, C), dtype=torch.float32, device=dev)
     hid = torch.empty((B, Hd), dtype=torch.float32, device=dev)
@@ -2202,8 +2215,9 @@ def chatt_bwd(dy, x, a, hid, pool, wd, wu):
     """-> (dx, dwd, dbd, dwu, dbu) of chatt_fwd for the upstream gradient dy (an NHWC view); the gradient of s is dy itself"""
     (dy, lddy), (x, ldx) = _act_views('chatt_bwd', dy, x)
     B, C, H, W = x.shape
-    Hd = hid.shape[1]
+    Hd = hid.shape[-1]
     wd, wu = _dense_f32(wd, (Hd, C), 'chatt_bwd W_down'), _dense_f32(wu, (C, Hd), 'chatt_bwd W_up')
+    a, hid, pool = _dense_f32(a, (B, C), 'chatt_bwd a'), _dense_f32(hid, (B, Hd), 'chatt_bwd hid'), _dense_f32(pool, (B, C), 'chatt_bwd pool')
     dev = x.device
     dx = empty_nhwc(B, C, H, W, dev)
     dwd = torch.empty((Hd, C), dtype=torch.float32, device=dev)
@@ -2220,33 +2234,19 @@ def chatt_bwd(dy, x, a, hid, pool, wd, wu):
 
 def symdiff_fwd(g, out=None):
     """|g - g.flip(2)| of an NHWC view (include/mrdis.h mrdis_symdiff_fwd)"""
-    (g, ldg), = _act_views('symdiff_fwd', g)
-    B, C, H, W = g.shape
-    o, ldo = _out_view(empty_nhwc(B, C, H, W, g.device) if out is None else out)
-    _chk(load().mrdis_symdiff_fwd(_ptr(g), ldg, _ptr(o), ldo, B, H, W, C, _stream()), 'symdiff_fwd')
-    return o
+    return _elementwise(load().mrdis_symdiff_fwd, 'symdiff_fwd', (g,), out, nhw=True)
 
 
 def symdiff_bwd(dgd, g, out=None):
-    (dgd, lddgd), (g, ldg) = _act_views('symdiff_bwd', dgd, g)
-    B, C, H, W = g.shape
-    dg, lddg = _out_view(empty_nhwc(B, C, H, W, g.device) if out is None else out)
-    _chk(load().mrdis_symdiff_bwd(_ptr(dgd), lddgd, _ptr(g), ldg, _ptr(dg), lddg, B, H, W, C, _stream()), 'symdiff_bwd')
-    return dg
-
-
-def _alpha_map(alpha, B, H, W, what):
-    if alpha.dtype is not torch.float32 or tuple(alpha.shape) != (B, 1, H // 2, W // 2):
-        raise MrdisError(f'{what}: alpha must be fp32 (B, 1, H/2, W/2) = {(B, 1, H // 2, W // 2)} (got {tuple(alpha.shape)} {alpha.dtype})')
-    return alpha.contiguous()
+    return _elementwise(load().mrdis_symdiff_bwd, 'symdiff_bwd', (dgd, g), out, nhw=True)
 
 
 def rgate_fwd(x, alpha, out=None):
     """(1 + up2(alpha)) * x: x (B, C, H, W) NHWC view with even H, W; alpha (B, 1, H/2, W/2); up2 = bilinear x2, align_corners=False"""
     (x, ldx), = _act_views('rgate_fwd', x)
     B, C, H, W = x.shape
-    al = _alpha_map(alpha, B, H, W, 'rgate_fwd')
-    o, ldo = _out_view(empty_nhwc(B, C, H, W, x.device) if out is None else out)
+    al = _dense_f32(alpha, (B, 1, H // 2, W // 2), 'rgate_fwd alpha')
+    o, ldo = _out_view(empty_nhwc(B, C, H, W, x.device) if out is None else out, (B, C, H, W))
     _chk(load().mrdis_rgate_fwd(_ptr(x), ldx, _ptr(al), _ptr(o), ldo, B, H, W, C, _stream()), 'rgate_fwd')
     return o
 
@@ -2255,7 +2255,7 @@ def rgate_bwd(dy, x, alpha):
     """-> (dx, dalpha (B, 1, H/2, W/2)) of rgate_fwd: dx element-wise, dalpha = the bilinear backward of sum_c dy * x"""
     (dy, lddy), (x, ldx) = _act_views('rgate_bwd', dy, x)
     B, C, H, W = x.shape
-    al = _alpha_map(alpha, B, H, W, 'rgate_bwd')
+    al = _dense_f32(alpha, (B, 1, H // 2, W // 2), 'rgate_bwd alpha')
     dx = empty_nhwc(B, C, H, W, x.device)
     r = empty_nhwc(B, 1, H, W, x.device)
     _chk(load().mrdis_rgate_bwd(_ptr(dy), lddy, _ptr(x), ldx, _ptr(al), _ptr(dx), C, _ptr(r), B, H, W, C, _stream()), 'rgate_bwd')
