@@ -594,6 +594,47 @@ int mrdis_cc_clean(const unsigned char* labels, const int* comp, const int* size
                    int et_min_voxels, int et_replace, unsigned char* out, int* stats, void* workspace, size_t workspace_bytes, int B, int H,
                    int W, int D, void* stream);
 
+/* ---- lesion-wise scoring of label volumes (csrc/mrdis_lesion.hip): region membership planes, binary dilation, the matching of predicted
+ * components to dilated ground-truth lesions and the per-lesion masks that mrdis_region_surfaces / mrdis_surface_hist then score.  Integer
+ * arithmetic and integer atomics only: exact, and the same bits from run to run; no workgroup waits for another; the launches of a call do
+ * not depend on the volumes' content.  Volumes are (B, H, W, D), D contiguous.  Geometry as mrdis_cc_label (B in 1 .. 65535, each of H, W, D
+ * in 1 .. 1024, H W D < 2^31), anything else returns MRDIS_EUNSUPPORTED (checked before every other argument).
+ * mrdis_region_planes: labels, targets, region_masks, R exactly as mrdis_region_surfaces takes them.  planes (B, H, W, D) uint8, 4-byte
+ *   aligned, every byte written: bit r = the voxel lies in predicted region r, bit 4 + r = in ground-truth region r -- the membership
+ *   mrdis_region_surfaces counts as |P| and |T|, voxel for voxel.  One launch, counted as "dilate".
+ * mrdis_dilate: dst (B, H, W, D) uint8 = src dilated `iterations` (1 .. MRDIS_DILATE_MAX_ITERATIONS) times by the structuring element of
+ *   `connectivity`: 6 (a voxel and its face neighbours), 18 (faces and edges: scipy's generate_binary_structure(3, 2)) or 26 (the full
+ *   3 x 3 x 3 cube), else MRDIS_EINVAL.  Every bit of a byte dilates on its own: an output bit is the OR of that bit over the neighbourhood, so
+ *   the eight planes of mrdis_region_planes dilate in one pass (a 0 / 1 or 0 / 255 mask stays one).  Outside the volume is background; nothing
+ *   wraps around a border or crosses into another sample.  A workgroup stages a tile of 8 x 8 x 64 voxels and a halo of one voxel in LDS;
+ *   ONE LAUNCH PER ITERATION, each counted as "dilate": src -> dst for one iteration, ping-pong between dst and the workspace for more.  src
+ *   and dst must not alias.  workspace: mrdis_dilate_workspace bytes (B H W D for iterations >= 2, else 0; NULL allowed when 0).
+ * mrdis_lesion_match: items are (sample, region) pairs, item = b R + r, R in 1 .. MRDIS_SURF_MAX_REGIONS, B R <= 65535.  planes (B, H, W, D) as
+ *   mrdis_region_planes wrote them (undilated); comp_l, comp_p (B R, H, W, D) int32: what mrdis_cc_label made of the dilated ground-truth plane
+ *   and of the predicted plane of every item (-1 on background, else the component's root index); rank_l, rank_p (B R, H, W, D) int32: AT A ROOT
+ *   VOXEL the dense number of its component over the whole call, in (item, root index) order -- the caller's scan over size > 0; other voxels
+ *   are not read.  first_p (B R) int32: the dense number of the item's first predicted component.  Lesion j = a component of a dilated plane.
+ *   For every voxel inside lesion j: a predicted voxel of component k (k = its dense number - first_p[item], below 32 words) sets bit k % 32
+ *   of bits[j][k / 32] by atomicOr; a ground-truth voxel adds 1 to tcount[j]; the root voxel stores root[j] = its index and item[j].  bits
+ *   (n_lesions, words) and tcount (n_lesions) int32 are zeroed by the caller; root and item (n_lesions) are written whole when n_lesions is
+ *   the number of lesions.  A rank outside 0 .. n_lesions - 1, or a k outside the row, touches nothing.  One launch, counted as "lesmatch".
+ * mrdis_lesion_expand: the arrays of mrdis_lesion_match after it ran.  For lesions j0 .. j0 + n - 1 (n <= 65535, j0 + n <= n_lesions) writes
+ *   stack_t[i] (n, H, W, D) uint8 = 1 on a ground-truth voxel of the lesion's region whose dilated component is lesion j0 + i, stack_s[i] = 1
+ *   on a predicted voxel of that region whose component has its bit set in row j0 + i; 0 elsewhere.  Both 4-byte aligned, every byte
+ *   written.  One launch, counted as "lesexpand".                                                                                          */
+#define MRDIS_DILATE_MAX_ITERATIONS 8
+int mrdis_region_planes(const unsigned char* labels, const void* targets, const int* region_masks, int R, unsigned char* planes, int B, int H,
+                        int W, int D, void* stream);
+size_t mrdis_dilate_workspace(int iterations, int B, int H, int W, int D);
+int mrdis_dilate(const unsigned char* src, unsigned char* dst, int connectivity, int iterations, void* workspace, size_t workspace_bytes, int B,
+                 int H, int W, int D, void* stream);
+int mrdis_lesion_match(const unsigned char* planes, const int* comp_l, const int* rank_l, const int* comp_p, const int* rank_p,
+                       const int* first_p, int words, int n_lesions, int* bits, int* tcount, int* root, int* item, int B, int R, int H, int W,
+                       int D, void* stream);
+int mrdis_lesion_expand(const unsigned char* planes, const int* comp_l, const int* rank_l, const int* comp_p, const int* rank_p,
+                        const int* first_p, const int* bits, int words, const int* item, int n_lesions, int j0, int n, unsigned char* stack_s,
+                        unsigned char* stack_t, int B, int R, int H, int W, int D, void* stream);
+
 /* ---- max_pool2d(kernel k x k, stride k): model.py:3448-3451 ---------------- */
 int mrdis_maxpool_fwd(const float* x, int ldx, float* y, int32_t* argmax, int N, int H, int W, int C,
                       int k, void* stream);

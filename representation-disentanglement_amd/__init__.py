@@ -11,7 +11,7 @@ import it through the `mrdis` alias at the repository root:
 Layout: csrc/ (hand-written HIP kernels + C ABI, include/mrdis.h), hip.py (ctypes
 binding), ops.py (autograd pairing + torch.ops.mrdis.*), model.py (mirror of the
 reference's module interface), trainer.py (train step, flat-arena Adam, gradient
-all-reduce), data.py / data3d.py (HBM-resident slice and volume loaders), train.py (the runnable main_missing.py-equivalent: epoch loop, scheduler, stat.csv, checkpoints), synth.py (whole-subject synthesis of missing contrasts: phase synthesize), segment.py (whole-subject tumour segmentation per missing-contrast pattern: phase segment), surfdist.py (region scoring of label volumes: Dice, sensitivity, specificity, HD95), postproc.py (clean-up of label volumes by 3-D connected components), prep.py (raw NIfTI scans -> a filled volume store on the device, fold lists), train3d.py (the same for the 3-D nets: main_3d.py).  No CPU fallback exists for the hot path.
+all-reduce), data.py / data3d.py (HBM-resident slice and volume loaders), train.py (the runnable main_missing.py-equivalent: epoch loop, scheduler, stat.csv, checkpoints), synth.py (whole-subject synthesis of missing contrasts: phase synthesize), segment.py (whole-subject tumour segmentation per missing-contrast pattern: phase segment), surfdist.py (region scoring of label volumes: Dice, sensitivity, specificity, HD95), postproc.py (clean-up of label volumes by 3-D connected components), lesion.py (lesion-wise Dice and HD95 of label volumes, binary dilation), prep.py (raw NIfTI scans -> a filled volume store on the device, fold lists), train3d.py (the same for the 3-D nets: main_3d.py).  No CPU fallback exists for the hot path.
 """
 from . import hip, ops, model, model3d, trainer               # noqa: F401
 from .hip import MrdisError, MrdisLibraryError, LIB_PATH      # noqa: F401
@@ -34,6 +34,8 @@ from . import surfdist   # noqa: F401,E402
 from .surfdist import EDT_FAR, BRATS_REGIONS, edt3d_sq, region_scores, scores_from_counts, percentile_ranks, region_masks   # noqa: F401,E402
 from . import postproc   # noqa: F401,E402
 from .postproc import components3d, clean_labels   # noqa: F401,E402
+from . import lesion   # noqa: F401,E402
+from .lesion import dilate3d, lesion_scores, lesion_scores_from_rows   # noqa: F401,E402
 from . import prep   # noqa: F401,E402
 from .prep import read_nifti, prep_stats, prep_write, prep_volume, build_store_from_raw, write_fold_lists, write_nifti, save_nifti, export_store_volume   # noqa: F401,E402
 from . import train   # noqa: F401,E402

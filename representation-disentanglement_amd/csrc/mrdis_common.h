@@ -70,6 +70,7 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
     X(CCLABEL, "cclabel") X(CCCLEAN, "ccclean") /* mrdis_cc.hip: one count per launch of a labelling pass (three per mrdis_cc_label call); one per mrdis_cc_clean call */ \
     X(PREPSTATS, "prepstats") X(PREPWRITE, "prepwrite") /* mrdis_prep.hip: one count per mrdis_prep_stats / mrdis_prep_write call */ \
     X(EXPORT, "export") /* mrdis_export.hip: one count (and one launch) per mrdis_export_volume call */ \
+    X(DILATE, "dilate") X(LESMATCH, "lesmatch") X(LESEXPAND, "lesexpand") /* mrdis_lesion.hip: one count per launch of mrdis_region_planes / mrdis_dilate (one per iteration); one per mrdis_lesion_match call; one per mrdis_lesion_expand call */ \
     X(STAT_VEC, "stat_vec") X(STAT_SCALAR, "stat_scalar") X(STAT_INTERP, "stat_interp") /* mrdis_elem.hip launch_stats: which partial-sum kernel took the pass */ \
     X(SPADE_UP2_ONEPASS, "spade_up2_onepass") X(SPADE_UP2_TWOPASS, "spade_up2_twopass") /* mrdis_instnorm_spade_bwd_up2: one count per call, by route */ \
     X(BIL_FWD_X2, "bil_fwd_x2") X(BIL_FWD_GENERAL, "bil_fwd_general") /* mrdis_bilinear_fwd */ \

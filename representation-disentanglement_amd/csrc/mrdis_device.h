@@ -15,6 +15,9 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));      // a 16-byte access at 4-byte alignment
+typedef int i32x4u __attribute__((ext_vector_type(4), aligned(4)));
+typedef unsigned u32u1 __attribute__((aligned(1)));                        // a 4-byte access at any alignment (global memory: one dword instruction)
 
 // ------------------------------------------------------------------ buffer descriptors
 // Word 3 of a gfx950 raw buffer descriptor: DATA_FORMAT = 32 bit (bits 15..18 = 4), no stride, no swizzle; an access whose byte offset is not below
@@ -79,6 +82,16 @@ __device__ __forceinline__ float mrdis_ld1(const __bf16* p) { return (float)*p; 
 // the fp32 sigmoid torch computes: accurate expf and an IEEE division.  The objective, the segmentation counts and the sliding-window accumulation
 // (mrdis_loss3d.hip, mrdis_segvol.hip) must agree on which side of 0.5 a probability falls, so they share this one.
 __device__ __forceinline__ float mrdis_sigmoid(float u) { return 1.f / (1.f + expf(-u)); }
+
+// ------------------------------------------------------------------ region membership of a label value
+// lut: eight nibbles built on the host, bit r of nibble l = label l belongs to region r.  A predicted label above 7 and a ground-truth value that
+// is NaN, negative, above 7 or non-integral belong to no region.  mrdis_surfdist.hip (surfaces, counts) and mrdis_lesion.hip (planes) share it.
+__device__ __forceinline__ unsigned mrdis_region_nib(unsigned char l, unsigned lut) { return l <= 7 ? (lut >> (4 * l)) & 15u : 0u; }
+__device__ __forceinline__ unsigned mrdis_region_nib(float t, unsigned lut) {
+    if (!(t >= 0.f && t <= 7.f)) return 0u;                         // NaN, negative, above 7: no region
+    const int l = (int)t;
+    return t == (float)l ? (lut >> (4 * l)) & 15u : 0u;             // non-integral: no region
+}
 
 // ------------------------------------------------------------------ three-term bf16 split
 // v = h + m + l, each term the bf16 rounding (to nearest even) of what the terms before it left: 3 x 8 mantissa bits.  With both operands of a

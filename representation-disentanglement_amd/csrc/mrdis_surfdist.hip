@@ -43,27 +43,20 @@ constexpr int SD_LBINS = 256;                // squared distances below this go 
 constexpr int SD_IT = 4;                     // outputs per thread and pass over the line
 constexpr unsigned SD_FAR = (unsigned)MRDIS_EDT_FAR;
 
-typedef float f32x4u __attribute__((ext_vector_type(4), aligned(4)));      // a 16-byte access at 4-byte alignment
-
 // ---------------------------------------------------------------------------------------------- region surfaces
-__device__ __forceinline__ unsigned sd_nib(unsigned char l, unsigned lut) { return l <= 7 ? (lut >> (4 * l)) & 15u : 0u; }
-__device__ __forceinline__ unsigned sd_nib(float t, unsigned lut) {
-    if (!(t >= 0.f && t <= 7.f)) return 0u;                         // NaN, negative, above 7: no region
-    const int l = (int)t;
-    return t == (float)l ? (lut >> (4 * l)) & 15u : 0u;             // non-integral: no region
-}
+// (the nibble of a label: mrdis_region_nib, mrdis_device.h -- shared with mrdis_lesion.hip, whose planes must agree with these flags voxel for voxel)
 
 // the AND of the six neighbours' nibbles of voxel el = (h, w, d) of one sample; a neighbour beyond the border is outside every region
 template <typename T>
 __device__ __forceinline__ unsigned sd_neighbours(const T* __restrict__ v, long long el, int h, int w, int d, int H, int W, int D, unsigned lut) {
     const long long WD = (long long)W * D;
     unsigned all = 15u;
-    all &= d > 0 ? sd_nib(v[el - 1], lut) : 0u;
-    all &= d < D - 1 ? sd_nib(v[el + 1], lut) : 0u;
-    all &= w > 0 ? sd_nib(v[el - D], lut) : 0u;
-    all &= w < W - 1 ? sd_nib(v[el + D], lut) : 0u;
-    all &= h > 0 ? sd_nib(v[el - WD], lut) : 0u;
-    all &= h < H - 1 ? sd_nib(v[el + WD], lut) : 0u;
+    all &= d > 0 ? mrdis_region_nib(v[el - 1], lut) : 0u;
+    all &= d < D - 1 ? mrdis_region_nib(v[el + 1], lut) : 0u;
+    all &= w > 0 ? mrdis_region_nib(v[el - D], lut) : 0u;
+    all &= w < W - 1 ? mrdis_region_nib(v[el + D], lut) : 0u;
+    all &= h > 0 ? mrdis_region_nib(v[el - WD], lut) : 0u;
+    all &= h < H - 1 ? mrdis_region_nib(v[el + WD], lut) : 0u;
     return all;
 }
 
@@ -90,18 +83,18 @@ __global__ __launch_bounds__(SD_THREADS) void region_surfaces_kernel(const unsig
         if (whole) {
             const unsigned l4 = *reinterpret_cast<const unsigned*>(labels + e0);
 #pragma unroll
-            for (int k = 0; k < 4; ++k) lp[k] = sd_nib((unsigned char)((l4 >> (8 * k)) & 255u), lut);
+            for (int k = 0; k < 4; ++k) lp[k] = mrdis_region_nib((unsigned char)((l4 >> (8 * k)) & 255u), lut);
             if (tgt != nullptr) {
                 const f32x4u t4 = *reinterpret_cast<const f32x4u*>(tgt + (e0 - v0));
-                lt[0] = sd_nib(t4.x, lut); lt[1] = sd_nib(t4.y, lut); lt[2] = sd_nib(t4.z, lut); lt[3] = sd_nib(t4.w, lut);
+                lt[0] = mrdis_region_nib(t4.x, lut); lt[1] = mrdis_region_nib(t4.y, lut); lt[2] = mrdis_region_nib(t4.z, lut); lt[3] = mrdis_region_nib(t4.w, lut);
             }
         } else {
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 const long long e = e0 + k;
                 if (e >= v0 && e < v1) {
-                    lp[k] = sd_nib(labels[e], lut);
-                    if (tgt != nullptr) lt[k] = sd_nib(tgt[e - v0], lut);
+                    lp[k] = mrdis_region_nib(labels[e], lut);
+                    if (tgt != nullptr) lt[k] = mrdis_region_nib(tgt[e - v0], lut);
                 }
             }
         }

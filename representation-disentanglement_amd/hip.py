@@ -109,6 +109,11 @@ _SIGS = {
     'mrdis_cc_label': (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _P]),
     'mrdis_cc_clean_workspace': (_Z, [_I]),
     'mrdis_cc_clean': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _Z, _I, _I, _I, _I, _P]),
+    'mrdis_region_planes': (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
+    'mrdis_dilate_workspace': (_Z, [_I, _I, _I, _I, _I]),
+    'mrdis_dilate': (_I, [_P, _P, _I, _I, _P, _Z, _I, _I, _I, _I, _P]),
+    'mrdis_lesion_match': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    'mrdis_lesion_expand': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_fwd': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _P]),
     'mrdis_maxpool_bwd': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_sumsq_workspace': (_Z, []),
@@ -245,6 +250,9 @@ SURFDIST_FAMILIES = ('regsurf', 'edt', 'surfhist')
 # connected components of label volumes and their clean-up (csrc/mrdis_cc.hip): 'cclabel' counts one per LAUNCH of a labelling pass (three per
 # mrdis_cc_label call, whatever B, shape and content), 'ccclean' one per mrdis_cc_clean call.
 CC_FAMILIES = ('cclabel', 'ccclean')
+# lesion-wise scoring (csrc/mrdis_lesion.hip): 'dilate' counts one per LAUNCH of mrdis_region_planes (one) and mrdis_dilate (one per iteration),
+# 'lesmatch' one per mrdis_lesion_match call, 'lesexpand' one per mrdis_lesion_expand call.
+LESION_FAMILIES = ('dilate', 'lesmatch', 'lesexpand')
 # preprocessing of raw scans into store volumes (csrc/mrdis_prep.hip): 'prepstats' counts one per mrdis_prep_stats call (four launches),
 # 'prepwrite' one per mrdis_prep_write call.
 PREP_FAMILIES = ('prepstats', 'prepwrite')
@@ -258,7 +266,7 @@ ELEM_FAMILIES = ('stat_vec', 'stat_scalar', 'stat_interp', 'spade_up2_onepass', 
                  'bil_bwd_x2', 'bil_bwd_tight3', 'bil_bwd_tight5', 'bil_bwd_general', 'elem_v1')
 # every name of csrc/mrdis_common.h MRDIS_COUNTERS: what launch_counts() hands out, ELEM_FAMILIES on request (tests/test_abi.py pins the union)
 LAUNCH_COUNTERS = (WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES
-                    + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES + PREP_FAMILIES + EXPORT_FAMILIES)
+                    + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES + PREP_FAMILIES + EXPORT_FAMILIES + LESION_FAMILIES)
 ALL_COUNTERS = LAUNCH_COUNTERS + ELEM_FAMILIES
 SYNTH_MAX_SRC = 8                 # include/mrdis.h MRDIS_SYNTH_MAX_SRC
 SEG2D_MAX_SETS = 16               # include/mrdis.h MRDIS_SEG2D_MAX_SETS
@@ -273,6 +281,7 @@ SURF_MAX_REGIONS = 4              # include/mrdis.h MRDIS_SURF_MAX_REGIONS
 CC_MAX_EXTENT = 1024              # each of H, W, D of a connected-component labelling
 CC_LABEL_LAUNCHES = 3             # kernel launches of one mrdis_cc_label call
 CC_CONNECTIVITIES = (6, 18, 26)
+DILATE_MAX_ITERATIONS = 8         # include/mrdis.h MRDIS_DILATE_MAX_ITERATIONS
 
 
 def stream_fill(t, value=0.0):

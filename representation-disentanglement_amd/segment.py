@@ -38,6 +38,7 @@ from . import hip, ops
 from .model import flush_batch_counters
 from .postproc import KEEP_MODES, clean_labels
 from .surfdist import BRATS_REGIONS, region_scores
+from .lesion import MAX_DILATION, lesion_csv_header, lesion_csv_values, lesion_scores
 from .synth import synth_plan
 from .trainer import split_inputs
 
@@ -115,6 +116,21 @@ def check_seg_options(contrast_list, patterns='full', flip='', post=None):
     return pats, post
 
 
+LESION_COLUMNS = tuple(lesion_csv_header().split(','))        # the value columns of seg_lesions.csv and seg_lesion_patterns.csv
+
+
+def check_lesion_options(lesions):
+    """None, or {'dilation', 'min_voxels'} for `lesion_scores` (defaults 3 and 50); ValueError for a value it would refuse"""
+    if lesions is None:
+        return None
+    lesions = {'dilation': lesions.get('dilation', 3), 'min_voxels': lesions.get('min_voxels', 50)}
+    for k, hi in (('dilation', MAX_DILATION), ('min_voxels', None)):
+        v = lesions[k]
+        if isinstance(v, bool) or not isinstance(v, int) or v < 0 or (hi is not None and v > hi):
+            raise ValueError(f'seg_lesion_{k} {v!r}: an integer ' + (f'in 0 .. {hi}' if hi is not None else '>= 0'))
+    return lesions
+
+
 def _dense_nhwc(x):
     x = x.float()
     return x if x.permute(0, 2, 3, 1).is_contiguous() else x.permute(0, 2, 3, 1).contiguous().permute(0, 3, 1, 2)
@@ -168,15 +184,17 @@ def pattern_logits(model, config, shape, device, ptrs, presents, s0, B, flip='',
 
 
 @torch.no_grad()
-def segment_volumes(model, config, store, subjects, patterns='full', flip='', batch_size=None, post=None, share_encoder=True):
+def segment_volumes(model, config, store, subjects, patterns='full', flip='', batch_size=None, post=None, share_encoder=True, lesions=None):
     """generator over `subjects` (subj_id strings of `store`): one dict per subject with
       subj_id; patterns (the pattern names); present (per pattern, M bools: in the store and not hidden);
       labels ((P', H, W, D) uint8 device tensor over the patterns that leave a present contrast, in pattern order; None if there is none);
       scores (the `region_scores` dict of `labels` against the stored `/seg` volume, or None without one);
       post, post_scores, post_stats (the cleaned labels, their scores and the (P', 6) stats of `clean_labels`): only when cleaning is on;
+      lesions, post_lesions (the `lesion_scores` dicts of `labels` and of `post`, or None without ground truth): only with `lesions`;
       launches (the deltas of hip.SEG2D_FAMILIES over the subject).
     patterns: a spec of `seg_patterns` or its result; flip '' | 'h' | 'w': a second, flipped view averaged in probability; batch_size: centres
     per batch (None: config['batch_size']); post: None, or {'min_voxels', 'keep', 'et_min_voxels'} for `clean_labels` (connectivity 26).
+    lesions: None, or {'dilation', 'min_voxels'} for `lesion_scores` (no lesion kernel launches without it).
     share_encoder=False encodes per pattern instead of sharing the encoder passes (rule 3; the same bits, more work).
     More than hip.SEG2D_MAX_SETS patterns go through the label kernel in chunks of 16.  Needs a built output decoder and dataset_name 'BraTS'
     (ValueError naming lambda_recon_y_fused otherwise).  The rules are this package's own convention (module docstring): the reference
@@ -184,6 +202,7 @@ def segment_volumes(model, config, store, subjects, patterns='full', flip='', ba
     names = [str(c) for c in config['contrast_list']]
     b = int(config['block_size'])
     pats, post = check_seg_options(names, patterns, flip, post)
+    lesions = check_lesion_options(lesions)
     if getattr(model, 'output_decoder', None) is None or config.get('dataset_name') != 'BraTS':
         raise ValueError("segment_volumes needs the output decoder of a BraTS model: train with lambda_recon_y_fused > 0 (compute_dtype 'f32' or "
                          f"'bf16m') and dataset_name 'BraTS' (got dataset_name {config.get('dataset_name')!r}, output decoder "
@@ -202,6 +221,8 @@ def segment_volumes(model, config, store, subjects, patterns='full', flip='', ba
         res = {'subj_id': sid, 'patterns': [n for n, _ in pats], 'present': present, 'labels': None, 'scores': None}
         if post is not None:
             res.update(post=None, post_scores=None, post_stats=None)
+        if lesions is not None:
+            res.update(lesions=None, **({'post_lesions': None} if post is not None else {}))
         if live:
             planes = torch.zeros((len(live), D, H, W), dtype=torch.uint8, device=dev)          # planes nothing predicts stay 0
             for s0, B in plan:
@@ -216,11 +237,16 @@ def segment_volumes(model, config, store, subjects, patterns='full', flip='', ba
                 target = seg.permute(1, 2, 0).contiguous().float()           # the stored labels in (H, W, D), once per subject
                 table = torch.full((len(live),), target.data_ptr(), dtype=torch.int64).to(dev)
                 res['scores'] = region_scores(labels, table, BRATS_REGIONS)
+                if lesions is not None:
+                    res['lesions'] = lesion_scores(labels, table, BRATS_REGIONS, dilation=lesions['dilation'], min_voxels=lesions['min_voxels'])
             if post is not None:
                 res['post'], res['post_stats'] = clean_labels(labels, connectivity=26, min_voxels=post['min_voxels'], keep=post['keep'],
                                                               et_min_voxels=post['et_min_voxels'])
                 if table is not None:
                     res['post_scores'] = region_scores(res['post'], table, BRATS_REGIONS)
+                    if lesions is not None:
+                        res['post_lesions'] = lesion_scores(res['post'], table, BRATS_REGIONS, dilation=lesions['dilation'],
+                                                            min_voxels=lesions['min_voxels'])
         after = hip.launch_counts()
         res['launches'] = {f: after[f] - before[f] for f in hip.SEG2D_FAMILIES}
         return res
@@ -235,6 +261,20 @@ def segment_volumes(model, config, store, subjects, patterns='full', flip='', ba
         finally:
             model.train(was)
         yield res
+
+
+def lesion_rows(res, key='lesions'):
+    """[(pattern name, n_present, [the LESION_COLUMNS values as written: floats with repr, counts as integers, 'nan' where there is nothing to
+    score])] of one subject's result, one per pattern"""
+    live = [k for k, pr in enumerate(res['present']) if any(pr)]
+    sc = res.get(key)
+    rows = []
+    for k, name in enumerate(res['patterns']):
+        vals = ['nan'] * len(LESION_COLUMNS)
+        if sc is not None and k in live:
+            vals = lesion_csv_values(sc, live.index(k))
+        rows.append((name, sum(res['present'][k]), vals))
+    return rows
 
 
 def score_rows(res, key='scores'):

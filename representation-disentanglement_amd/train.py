@@ -48,11 +48,12 @@ from .trainer import (DEFAULT_CONFIG, LOSS_KEYS, EVAL_INFOS, EvalStep, eval_metr
 
 from .synth import check_synth_options, synthesize_volumes
 from .postproc import STATS_COLUMNS
-from .segment import REGION_COLUMNS, check_seg_options, score_rows, segment_volumes
+from .segment import LESION_COLUMNS, REGION_COLUMNS, check_lesion_options, check_seg_options, lesion_rows, score_rows, segment_volumes
 
 SEED = 10                                                                   # main_missing.py:18
 SYNTH_KEYS = ('synth_info', 'synth_drop', 'synth_block', 'synth_set')
 SEG_KEYS = ('seg_patterns', 'seg_flip', 'seg_set', 'seg_post', 'seg_post_min_voxels', 'seg_post_keep', 'seg_post_et_min_voxels')
+SEG_LESION_KEYS = ('seg_lesions', 'seg_lesion_dilation', 'seg_lesion_min_voxels')
 EXPORT_KEYS = ('write_nifti', 'synth_units')
 SYNTH_UNITS = ('store', 'scan')
 
@@ -176,7 +177,7 @@ def setup_config(config_path='config.yaml', overrides=None, ckpt_root='../ckpt/'
         flag, saved = load_config_yaml(os.path.join(config['ckpt_path'], 'config.yaml'))
         if flag:
             for k, v in saved.items():                                      # :45-51
-                if k in ('phase', 'continue_train', 'eval_info', 'eval_drop') + SYNTH_KEYS + SEG_KEYS + EXPORT_KEYS or k not in config:    # eval_info, eval_drop, synth_*, seg_*, write_nifti: per invocation, like phase
+                if k in ('phase', 'continue_train', 'eval_info', 'eval_drop') + SYNTH_KEYS + SEG_KEYS + SEG_LESION_KEYS + EXPORT_KEYS or k not in config:    # eval_info, eval_drop, synth_*, seg_*, write_nifti: per invocation, like phase
                     continue
                 config[k] = v
             config = derive_config(config, device)
@@ -517,7 +518,10 @@ class Run:
           result_<set>/seg_patterns.csv -- `pattern,subjects,dice_wt,...,hd95_et`: per pattern the number of scored subjects and the mean of
           each score over them;
         with seg_post the same three under result_<set>/seg/post/ for the cleaned volumes, plus seg/post/postprocess.csv
-        (`subj_id,pattern,components,...`).  `write_nifti: true` (data_source raw) also writes <subj_id>_seg.nii.gz beside every <subj_id>_seg.npy, on
+        (`subj_id,pattern,components,...`).  `seg_lesions: true` also writes, beside each seg_regions.csv, seg_lesions.csv --
+        `subj_id,pattern,n_present,ldice_wt,...,fp_et` (segment.LESION_COLUMNS: the lesion-wise scores of lesion.lesion_scores under
+        seg_lesion_dilation / seg_lesion_min_voxels), one row per subject and pattern -- and seg_lesion_patterns.csv -- `pattern,subjects,` and the
+        per-pattern means of those columns; the other csv files keep their columns.  `write_nifti: true` (data_source raw) also writes <subj_id>_seg.nii.gz beside every <subj_id>_seg.npy, on
         the scans' own canvas and in their geometry (prep.save_nifti): one export launch per subject for all its patterns.  Returns {'subjects', 'patterns', 'scored', '<pattern>/<column>': mean}.  The rules are this package's own
         convention: the reference assembles no volume and never fuses for M > 1.  World size 1 only."""
         cfg = self.config
@@ -532,6 +536,11 @@ class Run:
         if cfg.get('seg_post', False):
             post = {'min_voxels': cfg.get('seg_post_min_voxels', 0), 'keep': cfg.get('seg_post_keep', 'all'),
                     'et_min_voxels': cfg.get('seg_post_et_min_voxels', 0)}
+        if not isinstance(cfg.get('seg_lesions', False), bool):
+            raise ValueError(f'seg_lesions {cfg["seg_lesions"]!r}: true or false')
+        lesions = None
+        if cfg.get('seg_lesions', False):
+            lesions = check_lesion_options({'dilation': cfg.get('seg_lesion_dilation', 3), 'min_voxels': cfg.get('seg_lesion_min_voxels', 50)})
         names = [str(c) for c in cfg['contrast_list']]
         pats, post = check_seg_options(names, patterns, flip, post)
         if set_ not in ('train', 'val', 'test'):
@@ -545,8 +554,9 @@ class Run:
             for name, _ in pats:
                 os.makedirs(os.path.join(base, sub, name), exist_ok=True)
         rows = {k: [] for k, _, _, _ in kinds}
+        lrows = {k: [] for k, _, _, _ in kinds}
         stats_rows = []
-        for res in segment_volumes(self.model, cfg, ds.store, subjects, pats, flip=flip, batch_size=batch_size, post=post):
+        for res in segment_volumes(self.model, cfg, ds.store, subjects, pats, flip=flip, batch_size=batch_size, post=post, lesions=lesions):
             sid = res['subj_id']
             live = [k for k, pr in enumerate(res['present']) if any(pr)]
             for skey, vkey, base, sub in kinds:
@@ -554,6 +564,8 @@ class Run:
                 for j, k in enumerate(live):
                     np.save(os.path.join(base, sub, res['patterns'][k], f'{sid}_seg.npy'), vols[j])
                 rows[skey] += [(sid,) + r for r in score_rows(res, skey)]
+                if lesions is not None:
+                    lrows[skey] += [(sid,) + r for r in lesion_rows(res, 'lesions' if skey == 'scores' else 'post_lesions')]
             if nifti and live:                                               # every pattern's volume, raw and cleaned, in ONE export launch
                 have = [(vkey, base, sub) for _, vkey, base, sub in kinds if res[vkey] is not None]
                 save_nifti([os.path.join(base, sub, res['patterns'][k], f'{sid}_seg.nii.gz') for _, base, sub in have for k in live],
@@ -566,6 +578,10 @@ class Run:
             means = self._write_seg_csvs(base, [n for n, _ in pats], rows[skey])
             if skey == 'scores':
                 stat.update(means)
+            if lesions is not None:
+                means = self._write_seg_lesion_csvs(base, [n for n, _ in pats], lrows[skey])
+                if skey == 'scores':
+                    stat.update(means)
         if post:
             with open(os.path.join(out_dir, 'seg', 'post', 'postprocess.csv'), 'w') as f:
                 f.write('subj_id,pattern,' + ','.join(STATS_COLUMNS) + '\n')
@@ -589,6 +605,24 @@ class Run:
                 f.write(f'{name},{len(have)},' + ','.join(repr(float(v)) for v in mean) + '\n')
                 means.update({f'{name}/{c}': float(v) for c, v in zip(REGION_COLUMNS, mean)})
         means['scored'] = scored
+        return means
+
+
+    @staticmethod
+    def _write_seg_lesion_csvs(base, pattern_names, rows):
+        """seg_lesions.csv and seg_lesion_patterns.csv under `base` from (subj_id, pattern, n_present, written values) rows -> {'<pattern>/<column>': mean}"""
+        with open(os.path.join(base, 'seg_lesions.csv'), 'w') as f:
+            f.write('subj_id,pattern,n_present,' + ','.join(LESION_COLUMNS) + '\n')
+            f.write(''.join(f'{sid},{name},{n},' + ','.join(vals) + '\n' for sid, name, n, vals in rows))
+        means = {}
+        with open(os.path.join(base, 'seg_lesion_patterns.csv'), 'w') as f:
+            f.write('pattern,subjects,' + ','.join(LESION_COLUMNS) + '\n')
+            for name in pattern_names:
+                have = np.array([[float(v) for v in vals] for _, p, _, vals in rows if p == name and vals[0] != 'nan'],
+                                dtype=np.float64).reshape(-1, len(LESION_COLUMNS))
+                mean = have.mean(0) if len(have) else np.full(len(LESION_COLUMNS), np.nan)
+                f.write(f'{name},{len(have)},' + ','.join(repr(float(v)) for v in mean) + '\n')
+                means.update({f'{name}/{c}': float(v) for c, v in zip(LESION_COLUMNS, mean)})
         return means
 
 

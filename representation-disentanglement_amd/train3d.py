@@ -37,6 +37,7 @@ from .prep import build_store_from_raw, ensure_fold_lists, save_nifti
 from .postproc import CONNECTIVITIES, KEEP_MODES, STATS_COLUMNS, clean_labels, write_stats_csv
 from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, predict_volumes, seg_metrics_from_counts
 from .surfdist import BRATS_REGIONS, SCORE_KEYS, region_scores
+from .lesion import MAX_DILATION, lesion_csv_header, lesion_csv_values, lesion_scores
 from .train import parse_overrides, save_config_file, save_result_stat
 from .trainer import ArenaAdam, load_checkpoint_model, save_checkpoint
 
@@ -63,6 +64,9 @@ DEFAULT_CONFIG_3D = {
     'predict_stride': None,            # depth stride of the sliding window; None: half the trained depth
     'predict_flip': False,             # also average the prediction of the H-flipped input
     'predict_regions': False,          # phase predict: also write predict_regions.csv (Dice, sensitivity, specificity, HD95 of WT / TC / ET; BraTS only)
+    'predict_lesions': False,          # phase predict / score / postprocess: also write predict_lesions.csv (lesion-wise Dice and HD95 of WT / TC / ET; BraTS only)
+    'lesion_dilation': 3,              # lesion.lesion_scores: dilations of the ground truth by the 18-neighbourhood before it is split into lesions, 0 .. 8
+    'lesion_min_voxels': 50,           # lesion.lesion_scores: a ground-truth lesion of fewer voxels is not scored
     'predict_post': False,             # phase predict: also write the cleaned label maps under result_<predict_set>/post/ (postproc.clean_labels)
     'post_connectivity': 26,           # connectivity of the components: 6 | 18 | 26
     'post_min_voxels': 0,              # components of fewer voxels are removed
@@ -116,6 +120,14 @@ def load_config3d(path=None, overrides=None):
         raise ValueError(f'predict_regions {cfg["predict_regions"]!r}: true or false')
     if (cfg['predict_regions'] or cfg['phase'] == 'score') and cfg['dataset_name'] != 'BraTS':
         raise ValueError(f'region scores (predict_regions, phase score) are defined for dataset_name BraTS only, not {cfg["dataset_name"]!r}')
+    if not isinstance(cfg['predict_lesions'], bool):
+        raise ValueError(f'predict_lesions {cfg["predict_lesions"]!r}: true or false')
+    if cfg['predict_lesions'] and cfg['dataset_name'] != 'BraTS':
+        raise ValueError(f'region scores (predict_lesions) are defined for dataset_name BraTS only, not {cfg["dataset_name"]!r}')
+    if isinstance(cfg['lesion_dilation'], bool) or not isinstance(cfg['lesion_dilation'], int) or not 0 <= cfg['lesion_dilation'] <= MAX_DILATION:
+        raise ValueError(f'lesion_dilation {cfg["lesion_dilation"]!r}: an integer in 0 .. {MAX_DILATION}')
+    if isinstance(cfg['lesion_min_voxels'], bool) or not isinstance(cfg['lesion_min_voxels'], int) or cfg['lesion_min_voxels'] < 0:
+        raise ValueError(f'lesion_min_voxels {cfg["lesion_min_voxels"]!r}: an integer >= 0')
     if not isinstance(cfg['predict_post'], bool):
         raise ValueError(f'predict_post {cfg["predict_post"]!r}: true or false')
     if isinstance(cfg['post_connectivity'], bool) or cfg['post_connectivity'] not in CONNECTIVITIES:
@@ -153,6 +165,25 @@ def write_region_csv(path, subj, scores):
     means = {}
     for name, v in cols:
         have = [x for x in v if x == x]
+        means[name] = float(np.mean(have)) if have else float('nan')
+    return means
+
+
+def write_lesion_csv(path, subj, scores):
+    """predict_lesions.csv: `subj_id,ldice_wt,ldice_tc,ldice_et,lhd95_wt,...,lesions_wt,...,kept_*,missed_*,comps_*,fp_et`, one row per subject
+    (lesion.lesion_csv_header: floats written with repr, counts as integers); scores: the `lesion_scores` dicts of the batches, in the order of
+    `subj`.  -> the per-column means {'ldice_wt': ..., ...} over the subjects that have a value (NaN = no ground truth; NaN if none has one)."""
+    rows = [lesion_csv_values(sc, i) for sc in scores for i in range(sc['lesion_dice'].shape[0])]
+    if len(rows) != len(subj):
+        raise ValueError(f'write_lesion_csv: {len(subj)} subjects need {len(subj)} rows of scores, got {len(rows)}')
+    names = lesion_csv_header().split(',')
+    with open(path, 'w') as f:
+        f.write('subj_id,' + ','.join(names) + '\n')
+        for sid, row in zip(subj, rows):
+            f.write(sid + ',' + ','.join(row) + '\n')
+    means = {}
+    for c, name in enumerate(names):
+        have = [float(r[c]) for r in rows if float(r[c]) == float(r[c])]
         means[name] = float(np.mean(have)) if have else float('nan')
     return means
 
@@ -366,6 +397,9 @@ class Run3D:
         returns their means.  One D2H copy of the labels per batch, one of all counts at the end; no window syncs with the host.
         `predict_regions: true` also scores every batch by BraTS region on the labels it holds on the device (surfdist.region_scores; one more small
         D2H copy per batch), writes result_<set>/predict_regions.csv (`write_region_csv`) and adds the per-region means to the returned stat.
+        `predict_lesions: true` also scores every batch lesion by lesion (lesion.lesion_scores under `lesion_dilation` / `lesion_min_voxels`), writes
+        result_<set>/predict_lesions.csv (`write_lesion_csv`; with `predict_post` also post/predict_lesions.csv for the cleaned labels) and adds
+        the per-column means to the returned stat; false: no lesion kernel launches and every file is what it is without the key.
         `predict_post: true` also cleans the labels of every batch on the device (`clean`), writes them as result_<set>/post/<subj_id>_seg.npy
         with post/postprocess.csv (and, with `predict_regions`, post/predict_regions.csv: the region scores of the cleaned labels), and adds
         'post_<column>' means to the returned stat: one more D2H copy of the cleaned labels and one small copy of the stats per batch.  The raw
@@ -376,13 +410,15 @@ class Run3D:
         set_ = cfg['predict_set'] if set_ is None else set_
         out_dir = os.path.join(cfg['ckpt_path'], f'result_{set_}')
         os.makedirs(out_dir, exist_ok=True)
-        subj, counts, regions = [], [], []
+        subj, counts, regions, lesions = [], [], [], []
         nifti = self._nifti_writer(set_)
-        post = _PostWriter(out_dir, cfg['predict_regions'], nifti) if cfg['predict_post'] else None
+        post = _PostWriter(out_dir, cfg['predict_regions'], nifti, self.lesions if cfg['predict_lesions'] else None) if cfg['predict_post'] else None
         for res in predict_volumes(self.model, self.loaders[set_], stride=cfg['predict_stride'], flip=cfg['predict_flip'],
                                    limit=cfg['max_batches'] or None):
             if cfg['predict_regions']:
                 regions.append(region_scores(res['labels'], res['target_ptrs']))
+            if cfg['predict_lesions']:
+                lesions.append(self.lesions(res['labels'], res['target_ptrs']))
             if post is not None:
                 post.add(res['subj_id'], *self.clean(res['labels']), res['target_ptrs'])
             labels = res['labels'].cpu().numpy()
@@ -403,6 +439,8 @@ class Run3D:
         if cfg['predict_regions']:
             stat.update(write_region_csv(os.path.join(out_dir, 'predict_regions.csv'), subj,
                                          {k: torch.cat([r[k] for r in regions]) for k in SCORE_KEYS}))
+        if cfg['predict_lesions']:
+            stat.update(write_lesion_csv(os.path.join(out_dir, 'predict_lesions.csv'), subj, lesions))
         if post is not None:
             stat.update({f'post_{k}': v for k, v in post.finish().items()})
         self.log(f'predict {set_}: {len(subj)} volumes under {out_dir}, dice {stat["dice"]:.4f}, iou {stat["iou"]:.4f}')
@@ -419,6 +457,11 @@ class Run3D:
             for i, sid in enumerate(ids):
                 save_nifti(os.path.join(out_dir, f'{sid}_seg.nii.gz'), labels[i], store, sid, log=self.log)
         return write
+
+    def lesions(self, labels, target_ptrs):
+        """the lesion-wise scores of a batch of label volumes on the device under the `lesion_*` keys (lesion.lesion_scores, BraTS regions)"""
+        cfg = self.config
+        return lesion_scores(labels, target_ptrs, BRATS_REGIONS, dilation=cfg['lesion_dilation'], min_voxels=cfg['lesion_min_voxels'])
 
     def clean(self, labels):
         """(cleaned, stats) of a batch of label volumes on the device under the `post_*` keys (postproc.clean_labels; every non-zero label
@@ -454,7 +497,8 @@ class Run3D:
     def postprocess(self, set_=None):
         """cleans the label volumes ALREADY under <ckpt_path>/result_<set>/ (as `predict` writes them; the checks of `score`) under the
         `post_*` keys: writes result_<set>/post/<subj_id>_seg.npy and post/postprocess.csv, for BraTS also post/predict_regions.csv (the
-        region scores of the cleaned labels) -- the files `predict` writes with `predict_post: true`, byte for byte.  Returns the means of
+        region scores of the cleaned labels; with `predict_lesions` also post/predict_lesions.csv) -- the files `predict` writes with
+        `predict_post: true`, byte for byte.  Returns the means of
         the stats columns and, for BraTS, the per-region means."""
         cfg = self.config
         set_ = cfg['predict_set'] if set_ is None else set_
@@ -462,7 +506,7 @@ class Run3D:
         post = None
         for ids, labels, ptrs in self._stored_labels(in_dir, set_):
             if post is None:
-                post = _PostWriter(in_dir, cfg['dataset_name'] == 'BraTS', self._nifti_writer(set_))
+                post = _PostWriter(in_dir, cfg['dataset_name'] == 'BraTS', self._nifti_writer(set_), self.lesions if cfg['predict_lesions'] else None)
             post.add(ids, *self.clean(labels), ptrs)
         if post is None:
             raise RuntimeError(f'postprocess({set_!r}): the loader serves no subject')
@@ -475,19 +519,24 @@ class Run3D:
         """region scores of the label volumes ALREADY under <ckpt_path>/result_<set>/ (`<subj_id>_seg.npy`, uint8 (H, W, D) in the store's geometry,
         as `predict` writes them) against the store's ground truth: writes result_<set>/predict_regions.csv and returns the per-region means.
         Every subject the `set_` loader serves must have its file; a missing file, a wrong shape or a wrong dtype raises ValueError naming it.
-        With `score_subdir` the files are read and written under result_<set>/<score_subdir>/ instead ('post': the cleaned volumes)."""
+        With `score_subdir` the files are read and written under result_<set>/<score_subdir>/ instead ('post': the cleaned volumes).
+        `predict_lesions: true` also writes predict_lesions.csv there (the lesion-wise scores, as `predict` writes them)."""
         cfg = self.config
         set_ = cfg['predict_set'] if set_ is None else set_
         out_dir = os.path.join(cfg['ckpt_path'], f'result_{set_}')
         if cfg['score_subdir']:
             out_dir = os.path.join(out_dir, cfg['score_subdir'])
-        subj, regions = [], []
+        subj, regions, lesions = [], [], []
         for ids, labels, ptrs in self._stored_labels(out_dir, set_):
             regions.append(region_scores(labels, ptrs))
+            if cfg['predict_lesions']:
+                lesions.append(self.lesions(labels, ptrs))
             subj += ids
         if not subj:
             raise RuntimeError(f'score({set_!r}): the loader serves no subject')
         stat = write_region_csv(os.path.join(out_dir, 'predict_regions.csv'), subj, {k: torch.cat([r[k] for r in regions]) for k in SCORE_KEYS})
+        if cfg['predict_lesions']:
+            stat.update(write_lesion_csv(os.path.join(out_dir, 'predict_lesions.csv'), subj, lesions))
         stat['n'] = len(subj)
         self.log(f'score {set_}: {len(subj)} volumes under {out_dir}, ' + ', '.join(f'{k} {v:.4f}' for k, v in stat.items() if k != 'n'))
         return stat
@@ -497,15 +546,18 @@ class _PostWriter:
     """the files under result_<set>/post/: `add` takes a batch of cleaned labels and stats on the device (one D2H copy each, and with
     `regions` their region scores), `finish` writes postprocess.csv (and predict_regions.csv) and returns the column (and region) means"""
 
-    def __init__(self, result_dir, regions, nifti=None):
+    def __init__(self, result_dir, regions, nifti=None, lesions=None):
         self.out_dir = os.path.join(result_dir, POST_SUBDIR)
         self.nifti = nifti                 # Run3D._nifti_writer: also write the cleaned labels as NIfTI files
         os.makedirs(self.out_dir, exist_ok=True)
         self.subj, self.stats, self.regions = [], [], ([] if regions else None)
+        self.lesion_fn, self.lesions = lesions, []      # Run3D.lesions: also write predict_lesions.csv for the cleaned labels
 
     def add(self, ids, cleaned, stats, target_ptrs):
         if self.regions is not None:
             self.regions.append(region_scores(cleaned, target_ptrs))
+        if self.lesion_fn is not None:
+            self.lesions.append(self.lesion_fn(cleaned, target_ptrs))
         vols = cleaned.cpu().numpy()
         for i, sid in enumerate(ids):
             np.save(os.path.join(self.out_dir, f'{sid}_seg.npy'), vols[i])
@@ -521,6 +573,8 @@ class _PostWriter:
         if self.regions is not None:
             stat.update(write_region_csv(os.path.join(self.out_dir, 'predict_regions.csv'), self.subj,
                                          {k: torch.cat([r[k] for r in self.regions]) for k in SCORE_KEYS}))
+        if self.lesion_fn is not None:
+            stat.update(write_lesion_csv(os.path.join(self.out_dir, 'predict_lesions.csv'), self.subj, self.lesions))
         return stat
 
 

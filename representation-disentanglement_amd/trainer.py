@@ -52,6 +52,9 @@ DEFAULT_CONFIG = {
     'seg_post_min_voxels': 0,          # components smaller than this are removed
     'seg_post_keep': 'all',            # 'all' | 'largest'
     'seg_post_et_min_voxels': 0,       # fewer enhancing-tumour voxels than this (and more than 0) become label 1
+    'seg_lesions': False,              # true: also the lesion-wise Dice and HD95 (lesion.lesion_scores) into seg_lesions.csv and seg_lesion_patterns.csv
+    'seg_lesion_dilation': 3,          # dilations of the ground truth by the 18-neighbourhood before it is split into lesions, 0 .. 8
+    'seg_lesion_min_voxels': 50,       # a ground-truth lesion of fewer voxels is not scored
     # phase: segment / synthesize -- NIfTI files beside the .npy files, on the scans' own canvas and in their geometry (prep.save_nifti; data_source raw only)
     'write_nifti': False,              # true: seg/<pattern>/<subj_id>_seg.nii.gz (and the seg/post/ ones) | synth/<subj_id>_<contrast>.nii.gz
     'synth_units': 'store',            # 'store': float32 in the store's normalised units | 'scan': the scan's own units and datatype (the normalisation undone)
