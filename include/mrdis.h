@@ -416,6 +416,31 @@ int mrdis_slice_gather(const void* vol_ptrs, const int* slice_idx, const int* dr
 int mrdis_volume_gather(const void* table, int ld_table, float* out, float* mask, int B, int M, int H, int W, int D, int z0,
                         int Dz, int mode, int K, int relabel, void* stream);
 
+/* ---- patch training for the 3-D nets (csrc/mrdis_patch.hip): random (PH, PW, PD) sub-volumes of the whole stored (H, W, D) volume, a share
+ * of them centred on a voxel of a foreground class.  This package's conventions (the reference trains on one fixed depth crop).
+ * classes: K host integers in 1 .. 255, distinct (BraTS: 1, 2, 4); K <= MRDIS_PATCH_MAX_CLASSES.  nblk = ceil(H W D / 1024).
+ * mrdis_fg_block_counts: counts (nblk, K) int32, counts[j][c] = the voxels with seg == classes[c] among the flat indices
+ *   (h W + w) D + d in [1024 j, 1024 j + 1024).  K >= 1.  The caller makes the exclusive prefix (nblk + 1, K) of it, once per subject.
+ * table (B, ld_table) 64-bit words in device memory, ld_table >= 2 M + 7: the 2 M + 3 words of mrdis_volume_gather (the minima are those of
+ *   the WHOLE volumes), then [2M+3] pointer to the subject's int32 prefix table (0 = none), [2M+4] u_class | u_voxel << 32,
+ *   [2M+5] u_h | u_w << 32, [2M+6] u_d (uint32 draws); flag word [2M+1]: bit 0 flip H, bit 1 augment, bit 2 flip W, bit 3 flip D,
+ *   bit 4 foreground sample, bit 5 centre patch.
+ * mrdis_patch_origins: origins (B, 4) int32 = h0, w0, d0, index of the chosen class (-1 = none), with pick(u, n) = (u n) >> 32:
+ *   centre bit: h0 = (H - PH) / 2, likewise w0, d0.  Otherwise uniform: h0 = pick(u_h, H - PH + 1), likewise w0, d0; a foreground sample with a
+ *   label volume, a prefix table and a class of non-zero total instead takes class = present[pick(u_class, |present|)] (present classes in
+ *   list order), the r-th voxel (r = pick(u_voxel, n_class), 0-based, increasing flat index) of that class as centre (hc, wc, dc) and
+ *   h0 = clamp(hc - PH / 2, 0, H - PH), likewise w0, d0.  K = 0 (classes may be NULL): always uniform.  One workgroup per sample.
+ * mrdis_patch_gather: mode, K, relabel, out and mask as mrdis_volume_gather with (PH, PW, PD) for (H, W, Dz), read at the sample's origin
+ *   (clamped into the volume) and mirrored inside the patch on every axis whose flip bit is set.
+ * A patch larger than the volume on any axis: MRDIS_EINVAL (no padding).  One launch per call, counted as "fgcount" / "patchorigin" /
+ * "patchgather"; no host read, no atomics: the same bits on every run.                                                        */
+#define MRDIS_PATCH_MAX_CLASSES 8
+int mrdis_fg_block_counts(const float* seg, const int* classes, int K, int* counts, int H, int W, int D, void* stream);
+int mrdis_patch_origins(const void* table, int ld_table, int* origins, const int* classes, int K, int B, int M, int H, int W, int D, int PH,
+                        int PW, int PD, void* stream);
+int mrdis_patch_gather(const void* table, int ld_table, const int* origins, float* out, float* mask, int B, int M, int H, int W, int D,
+                       int PH, int PW, int PD, int mode, int K, int relabel, void* stream);
+
 /* ---- objective of the 3-D nets (model3d.nvnet_loss) fused: soft Dice of sigmoid(uout) against `target`, GLOBAL over the batch, plus
  * w_l2 times the mean squared error of vout against x (csrc/mrdis_loss3d.hip).  uout / target: fp32 of one shape (shape_ut, nd_ut <= 8
  * extents) and ONE dense memory layout, given by their element strides; vout / x likewise with shape_vx, or both NULL for the Dice-only

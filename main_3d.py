@@ -4,6 +4,7 @@ the command line, then key=value overrides), trains with a validation pass per e
 
     python main_3d.py                            # config3d.yaml in the working directory, else the built-in defaults
     python main_3d.py cfg3d.yaml epochs=2 batch_size=2 ckpt_path=/tmp/ckpt3d
+    python main_3d.py cfg3d.yaml patch_size=[128,128,128] patch_fg=0.33  # train on random 128^3 patches of the whole scan, a third of them on the tumour
     python main_3d.py cfg3d.yaml phase=test
     python main_3d.py cfg3d.yaml phase=predict   # <ckpt_path>/result_test/<subj_id>_seg.npy + predict.csv
     python main_3d.py cfg3d.yaml phase=predict predict_regions=true     # + predict_regions.csv: Dice, sensitivity, specificity, HD95 of WT / TC / ET

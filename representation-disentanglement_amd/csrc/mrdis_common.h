@@ -43,7 +43,7 @@
     X(C4_GRID, "c4_grid", "MRDIS_C4_GRID", 0, 0) /* persistent grid of the Cin = 4 kernels (run_c4conv): 0 = workgroups per CU from the occupancy query of the launched instantiation | k > 0: k workgroups per CU */ \
     X(C4_BLOCKS, "debug_c4_blocks", "MRDIS_DEBUG_C4_BLOCKS", 0, -1) /* read-only diagnostic: grid.x of the last run_c4conv launch */ \
     X(ZS_GRID, "zsearch_grid", "MRDIS_ZSEARCH_GRID", 0, 0) /* workgroups of mrdis_cosine_top1 (mrdis_zsearch.hip): 0 = min(tiles, 1024) | k > 0: min(k, tiles, 2048) */ \
-    X(VOLGEN, "debug_volgen", "MRDIS_DEBUG_VOLGEN", 1, 0) /* 1: mrdis_volume_gather always runs its element kernel (mrdis_volgather.hip), never the LDS-tile form */
+    X(VOLGEN, "debug_volgen", "MRDIS_DEBUG_VOLGEN", 1, 0) /* 1: mrdis_volume_gather and mrdis_patch_gather always run their element kernel (mrdis_volgather.hip, mrdis_patch.hip), never the LDS-tile form */
 #define MRDIS_X_OPT_ID(id, name, env, is_flag, dflt) MRDIS_OPT_##id,
 enum { MRDIS_OPTIONS(MRDIS_X_OPT_ID) MRDIS_OPT_COUNT };
 long long mrdis_opt(int id);      // mrdis_runtime.hip
@@ -61,6 +61,7 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
     X(CHATT, "chatt") X(SYMDIFF, "symdiff") X(RGATE, "rgate") /* mrdis_outdec.hip: the attention output decoders */ \
     X(DIRECT3D, "direct3d") X(C3D16, "c3d16") X(WGRAD3D, "wgrad3d") X(WGRAD3D16, "wgrad3d16") X(WINO_WGRAD3D, "wino_wgrad3d") /* mrdis_conv3d.hip / mrdis_wino.hip: the 3-D kernels */ \
     X(VOLGATHER, "volgather") /* mrdis_volgather.hip: the 3-D batch gather, one count per mrdis_volume_gather call */ \
+    X(FGCOUNT, "fgcount") X(PATCHORIGIN, "patchorigin") X(PATCHGATHER, "patchgather") /* mrdis_patch.hip: one count per mrdis_fg_block_counts / mrdis_patch_origins / mrdis_patch_gather call */ \
     X(LOSS3D, "loss3d") X(SEGCOUNTS, "segcounts") /* mrdis_loss3d.hip: one count per mrdis_nvnet_loss_fwd / _bwd call; one per mrdis_seg_counts call */ \
     X(SEGACCUM, "segaccum") X(SEGLABELS, "seglabels") /* mrdis_segvol.hip: one count per mrdis_seg_accum / mrdis_seg_label_volume call */ \
     X(SYNTHACCUM, "synthaccum") X(SYNTHFINISH, "synthfinish") /* mrdis_synth.hip: one count per mrdis_synth_accum / mrdis_synth_finish call */ \

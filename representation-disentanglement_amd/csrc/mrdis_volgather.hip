@@ -27,13 +27,9 @@
 // This is not the 2-D loader's first form (28-byte pieces at a 112-byte stride, 0.6 TB/s): no store here is narrower than a full line.
 // Any geometry the tile form does not take (C > 32, (H W Dz C) % 4 != 0, unaligned output) runs the element kernel below it: one thread per
 // output float, coalesced 4-byte stores, strided reads.
-#include "mrdis_common.h"
+#include "mrdis_volgather.h"                                    // the rules and the tile shared with mrdis_patch.hip
 
 namespace {
-constexpr int VG_TILE_FLOATS = 8192;        // 32 KB tile: P = 1024 positions at C <= 8, 512 at C <= 16, 256 at C <= 32
-constexpr int VG_MAXC_TILE = 32;
-constexpr int VG_LDS_FLOATS = VG_TILE_FLOATS + VG_MAXC_TILE * 4;
-
 struct VgGeom { int M, C, H, W, D, z0, Dz, N, relabel; };
 
 __device__ __forceinline__ long long vg_src(int p, const VgGeom& g, bool flip) {
@@ -42,28 +38,6 @@ __device__ __forceinline__ long long vg_src(int p, const VgGeom& g, bool flip) {
     const int hs = flip ? g.H - 1 - h : h;
     return ((long long)hs * g.W + w) * g.D + g.z0 + z;
 }
-// the item's raw minimum (see the header comment); every thread walks the M <= 64 uniform table words
-__device__ __forceinline__ float vg_item_min(const unsigned long long* row, int M) {
-    float m0 = __builtin_inff();
-    bool absent = false;
-    for (int m = 0; m < M; ++m) {
-        if (row[m] != 0ull) m0 = fminf(m0, *reinterpret_cast<const float*>(row[M + m]));
-        else absent = true;
-    }
-    return absent ? fminf(m0, 0.f) : m0;
-}
-__device__ __forceinline__ float vg_input(const float* vol, long long src, bool aug, float scale, float shift, float m0) {
-#pragma clang fp contract(off)              // two roundings, never one fused multiply-add (hipcc contracts by default, __fmul_rn / __fadd_rn included)
-    const float x = vol ? vol[src] : 0.f;
-    if (!aug) return x;
-    const float xs = x * scale;
-    return x == m0 ? -10.f : xs + shift;
-}
-__device__ __forceinline__ float vg_label(const float* seg, long long src, int relabel) {
-    const float t = seg ? seg[src] : 0.f;
-    return (relabel && t == 4.f) ? 3.f : t;              // util.py:785
-}
-__device__ __forceinline__ float vg_target(float t, int c, int K) { return K == 0 ? t : (t == (float)(c + 1) ? 1.f : 0.f); }
 
 // MODE 0: inputs (C = M), MODE 1: targets (C = max(K, 1)).  grid (tiles, B), 256 threads, P % 256 == 0, (N C) % 4 == 0, out 16-byte aligned.
 // CM = 4: M == 4 (the BraTS set) with the four loads of a position issued together; CM = 0: M at run time.
@@ -102,26 +76,7 @@ __global__ __launch_bounds__(256) void volgather_tile_kernel(const unsigned long
         }
     }
     __syncthreads();
-    const int C = g.C, nv = n * C / 4;
-    f32x4* dst = reinterpret_cast<f32x4*>(out + ((long long)b * g.N + p0) * C);
-    if ((C & 3) == 0) {
-        for (int f = tid; f < nv; f += 256) {
-            const int e = 4 * f, p = e / C, c = e - p * C;
-            const f32x4 v = {tile[c * S + p], tile[(c + 1) * S + p], tile[(c + 2) * S + p], tile[(c + 3) * S + p]};
-            dst[f] = v;
-        }
-    } else {
-        for (int f = tid; f < nv; f += 256) {
-            float v[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int e = 4 * f + k, p = e / C, c = e - p * C;
-                v[k] = tile[c * S + p];
-            }
-            const f32x4 v4 = {v[0], v[1], v[2], v[3]};
-            dst[f] = v4;
-        }
-    }
+    vg_store_tile(tile, out + ((long long)b * g.N + p0) * g.C, n, g.C, S, tid);
 }
 
 // every geometry: one thread per output float.  grid (x, B), grid-stride over the N C floats of a sample.
@@ -151,10 +106,8 @@ int launch_volgather(const unsigned long long* table, int ld, float* out, float*
     const bool tiled = !mrdis_opt(MRDIS_OPT_VOLGEN) && g.C <= VG_MAXC_TILE && (total & 3) == 0 && (((uintptr_t)out) & 15) == 0;
     mrdis_count(MRDIS_CNT_VOLGATHER);
     if (tiled) {
-        int P = VG_TILE_FLOATS / g.C / 256 * 256; if (P > 1024) P = 1024;
-        // row stride of the LDS tile: a lane's four reads of the store phase sit 4 S apart per neighbouring lane at C = 8 (S % 8 == 4 puts the two
-        // rows on opposite halves of the 32 banks) and at C = 16 (S % 8 == 2: four rows, 8 banks apart); C = 4 reads whole rows and needs none
-        const int S = P + ((g.C % 16) == 0 ? 2 : (g.C % 8) == 0 ? 4 : (g.C % 4) == 0 ? 0 : 1);
+        int P, S;
+        vg_tile_shape(g.C, &P, &S);
         if (MODE == 0 && g.M == 4)
             MRDIS_LAUNCH((volgather_tile_kernel<MODE, 4>), dim3(mrdis_cdiv(g.N, P), B), dim3(256), 0, s, table, ld, out, mask, g, K, P, S);
         else

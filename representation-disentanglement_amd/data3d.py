@@ -15,6 +15,18 @@ Host-side behaviour follows the reference statement by statement:
     then `inputs[inputs == inputs.min()] = -10` -- same global-RNG call order                                    util.py:798-805
   * slice_idx = 0                                                                                                util.py:807
   * batch order: `DataLoader(shuffle)`, reproduced draw for draw by BatchLoader._order.
+
+Patch training (`patch_size`; THIS PACKAGE'S CONVENTION, the reference has none; off by default, and then nothing below runs): a training item is
+a random (PH, PW, PD) sub-volume of the WHOLE stored scan instead of the depth crop, a share `patch_fg` of the items centred on a voxel of a
+tumour class the subject has (csrc/mrdis_patch.hip, patch3d.py).  Per item the host draws, from the stream `meta` uses anyway and in this order:
+  1. the reference's drop-off draws, unchanged
+  2. `fg = rand() < patch_fg`, only if patch_fg > 0
+  3. five uint32 `u_class, u_voxel, u_h, u_w, u_d` by one `randint(0, 2**32, size=5, dtype=np.uint32)`
+  4. with aug: one `rand() > 0.5` per axis named in `patch_flips`, in h, w, d order
+  5. with aug: scale and shift, as above
+and the device turns the draws into the patch origin (patch3d's docstring: pick, clamping instead of padding).  The `== min()` rule compares
+with the minimum of the whole stored volume.  The evaluation loaders serve the centre patch, without a draw; `crop()` is then the centre
+depth window of the trained depth PD, so the windowed reads slide PD over the full H x W.
 The commented-out mean-image imputation (`img_mean`, `BraTS_mean.npy`) and the `missing` argument the reference never reads are not built.
 """
 import os
@@ -22,7 +34,7 @@ import os
 import numpy as np
 import torch
 
-from . import hip
+from . import hip, patch3d
 from .data import VolumeStore, BatchLoader
 
 Z0 = 45                     # util.py:766-769
@@ -36,6 +48,7 @@ class VolumeStore3D(VolumeStore):
     def __init__(self, device):
         super().__init__(device)
         self._mins = {}             # (z0, Dz) -> (fp32 device tensor, {key: row})
+        self._prefix = {}           # (key, classes) -> int32 device tensor (nblk + 1, K): patch3d.fg_prefix of a label volume
 
     def add(self, key, array_hwd):
         """key = 'subject/contrast' (h5 path); array in the reference layout (H, W, D)."""
@@ -48,12 +61,14 @@ class VolumeStore3D(VolumeStore):
             raise ValueError(f'{key}: shape {tuple(a.shape)} != {self.shape}')
         self.vols[key] = a.to(self.device)
         self._mins.clear()
+        self._prefix.clear()
 
     def add_device(self, key, vol_hwd):
         """key = 'subject/contrast'; an fp32 device tensor already laid out as the store keeps it, (H, W, D) (prep.prep_write layout 'hwd'): kept as it is."""
         self._check_device_volume(key, vol_hwd, tuple(vol_hwd.shape) if getattr(vol_hwd, 'ndim', 0) == 3 else ())
         self.vols[key] = vol_hwd
         self._mins.clear()
+        self._prefix.clear()
 
     def crop_min_ptr(self, key, z0, Dz):
         """device address of min(vol[:, :, z0:z0+Dz]) (fp32), 0 for a key the store does not hold.  No host read, no sync."""
@@ -66,6 +81,17 @@ class VolumeStore3D(VolumeStore):
         i = rows.get(key)
         return 0 if i is None else mins.data_ptr() + 4 * i
 
+    def fg_prefix_ptr(self, key, classes):
+        """device address of the label volume's prefix table over `classes` (patch3d.fg_prefix: one kernel launch and a running sum, once per
+        volume, when a loader first asks), 0 for a key the store does not hold.  No host read, no sync."""
+        v = self.vols.get(key)
+        if v is None:
+            return 0
+        ent = self._prefix.get((key, classes))
+        if ent is None:
+            ent = self._prefix[(key, classes)] = patch3d.fg_prefix(v, classes)
+        return ent.data_ptr()
+
 
 def load_subj_list(path):
     """util.py:841-843: one subject id per line.  The reference reads the file with `pd.read_csv(path, sep=" ")` WITHOUT `header=None`, so pandas takes
@@ -75,21 +101,57 @@ def load_subj_list(path):
     return np.array(lines.iloc[:, 0])
 
 
+def patch_args(patch_size, patch_fg=0.0, patch_flips='h'):
+    """-> ((PH, PW, PD) or None, patch_fg, patch_flips) checked: three integers >= 1, a share in 0 .. 1, distinct axes of 'hwd'; else ValueError"""
+    if patch_size is not None:
+        try:
+            ok = len(patch_size) == 3 and all(not isinstance(v, bool) and int(v) == v and v >= 1 for v in patch_size)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError(f'patch_size {patch_size!r}: None or three integers >= 1 (PH, PW, PD)')
+        patch_size = tuple(int(v) for v in patch_size)
+    if isinstance(patch_fg, bool) or not isinstance(patch_fg, (int, float)) or not 0.0 <= patch_fg <= 1.0:
+        raise ValueError(f'patch_fg {patch_fg!r}: the share of foreground patches, 0 .. 1')
+    if not isinstance(patch_flips, str) or any(a not in 'hwd' for a in patch_flips) or len(set(patch_flips)) != len(patch_flips):
+        raise ValueError(f'patch_flips {patch_flips!r}: the axes that may flip, distinct letters of "hwd" (or the empty string)')
+    return patch_size, float(patch_fg), patch_flips
+
+
 class VolumeDataset3D:
-    """ZeroDoseDataset3D (util.py:723-810) over a VolumeStore3D: `meta(idx)` is the host part of `__getitem__`."""
+    """ZeroDoseDataset3D (util.py:723-810) over a VolumeStore3D: `meta(idx)` is the host part of `__getitem__`.  `patch_size` (PH, PW, PD):
+    patch training, see the module docstring; `patch_centre`: the deterministic centre patch instead of a random one (evaluation)."""
 
     TARGET_KEYS = {'ZeroDose': '/PET', 'BraTS': '/seg'}
+    FG_CLASSES = {'BraTS': (1, 2, 4)}      # the label values a foreground patch may be centred on
 
-    def __init__(self, dataset_name, store, subj_list, contrast_list=('T1',), aug=False, dropoff=False):
+    def __init__(self, dataset_name, store, subj_list, contrast_list=('T1',), aug=False, dropoff=False, patch_size=None, patch_fg=0.0,
+                 patch_flips='h', patch_centre=False):
         self.dataset_name, self.store = dataset_name, store
         self.subj_list, self.contrast_list = list(subj_list), list(contrast_list)
         self.aug, self.dropoff = aug, dropoff
+        self.set_patch(patch_size, patch_fg, patch_flips, patch_centre)
+
+    def set_patch(self, patch_size, patch_fg=0.0, patch_flips='h', patch_centre=False):
+        self.patch_size, self.patch_fg, self.patch_flips = patch_args(patch_size, patch_fg, patch_flips)
+        self.patch_centre = bool(patch_centre)
+        if self.patch_size is None:
+            return
+        if self.patch_fg > 0 and self.dataset_name not in self.FG_CLASSES:
+            raise ValueError(f'patch_fg > 0 needs a dataset with label targets ({sorted(self.FG_CLASSES)}), not {self.dataset_name!r}')
+        if self.store.shape is not None and any(p > n for p, n in zip(self.patch_size, self.store.shape)):
+            raise ValueError(f'patch_size {self.patch_size} does not fit the stored volumes {tuple(self.store.shape)}: no padding past the border')
 
     def __len__(self):
         return len(self.subj_list)
 
     def crop(self):
-        """(z0, Dz) of `[:, :, 45:-46]` (`45:-47` for 'ZeroDose')."""
+        """(z0, Dz) of `[:, :, 45:-46]` (`45:-47` for 'ZeroDose'); in patch mode the centre depth window of the trained depth, ((D - PD) // 2, PD)."""
+        if self.patch_size is not None:
+            D, PD = self.store.shape[2], self.patch_size[2]
+            if PD > D:
+                raise ValueError(f'patch depth {PD} beyond the stored depth {D}')
+            return (D - PD) // 2, PD
         Dz = self.store.shape[2] - Z0 - (47 if self.dataset_name == 'ZeroDose' else 46)
         if Dz < 1:
             raise ValueError(f'volumes of depth {self.store.shape[2]} leave nothing inside the crop')
@@ -98,7 +160,8 @@ class VolumeDataset3D:
     def meta(self, idx, rng=None, plain=False):
         """-> (subj_id, slice_idx = 0, volume pointers, dropped contrast or -1, target pointer, flip, scale, shift).  rng: None = the global np.random (the
         reference's own stream, draw for draw) or the loader's own np.random.RandomState (data-parallel runs, see BatchLoader).  `plain`: the item as
-        stored -- nothing dropped, not augmented -- and no draw from any stream (the windowed reads of VolumeLoader3D.batches(z0=...))."""
+        stored -- nothing dropped, not augmented -- and no draw from any stream (the windowed reads of VolumeLoader3D.batches(z0=...)).
+        In patch mode (and not `plain`) a ninth element follows: (fg, the five uint32 draws, (flip h, flip w, flip d), centre)."""
         rng = np.random if rng is None else rng
         subj_id = str(self.subj_list[idx])
         ptrs = [self.store.ptr(subj_id + '/' + c) for c in self.contrast_list]
@@ -111,12 +174,29 @@ class VolumeDataset3D:
         if self.dropoff and mask.sum() > 1:                           # :791-795, same RNG call order
             if rng.rand() > 0.8:
                 drop = int(rng.choice(np.where(mask == 1)[0], 1)[0])
+        if self.patch_size is not None:
+            return (subj_id, 0, ptrs, drop, tptr) + self._patch_draws(rng)
         flip, scale, shift = False, 1.0, 0.0
         if self.aug:                                                  # :798-804
             flip = bool(rng.rand() > 0.5)
             scale = 1 + 0.2 * (rng.rand() - 0.5)
             shift = 0.2 * (rng.rand() - 0.5)
         return subj_id, 0, ptrs, drop, tptr, flip, scale, shift
+
+    def _patch_draws(self, rng):
+        """the tail of a patch-mode meta, drawn in the order of the module docstring: (flip h, scale, shift, (fg, u[5], flips, centre))"""
+        if self.patch_centre:
+            return False, 1.0, 0.0, (False, np.zeros(5, dtype=np.uint32), (False, False, False), True)
+        fg = bool(rng.rand() < self.patch_fg) if self.patch_fg > 0 else False
+        u = rng.randint(0, 2 ** 32, size=5, dtype=np.uint32)
+        flips, scale, shift = [False, False, False], 1.0, 0.0
+        if self.aug:
+            for i, axis in enumerate('hwd'):
+                if axis in self.patch_flips:
+                    flips[i] = bool(rng.rand() > 0.5)
+            scale = 1 + 0.2 * (rng.rand() - 0.5)
+            shift = 0.2 * (rng.rand() - 0.5)
+        return flips[0], scale, shift, (fg, u, tuple(flips), False)
 
 
 class VolumeLoader3D(BatchLoader):
@@ -126,11 +206,18 @@ class VolumeLoader3D(BatchLoader):
     zeros, plus mask_host and batch_index as in the 2-D loader.  The partial last batch is served.
 
     Batch order, rank / world / equal_steps and the loader's own stream under world > 1 are BatchLoader's (see its docstring); here that
-    stream carries ALL per-item draws, drop-off and augmentation, for the same reason."""
+    stream carries ALL per-item draws, drop-off and augmentation, for the same reason.
 
-    def __init__(self, dataset, batch_size, shuffle=False, rank=0, world=1, equal_steps=False, generator=None, region_channels=0):
+    `patch_size` (with `patch_fg`, `patch_flips`, `patch_centre`): puts the dataset into patch mode (VolumeDataset3D.set_patch; None leaves it
+    as it was built).  A batch is then three launches -- origins, inputs, targets -- of (PH, PW, PD) patches, and carries 'origins' (B, 4) int32
+    on the device: h0, w0, d0 and the index of the class a foreground patch was centred on (-1: uniform or centre)."""
+
+    def __init__(self, dataset, batch_size, shuffle=False, rank=0, world=1, equal_steps=False, generator=None, region_channels=0,
+                 patch_size=None, patch_fg=0.0, patch_flips='h', patch_centre=False):
         super().__init__(dataset, batch_size, shuffle, rank, world, equal_steps, generator)
         self.region_channels = int(region_channels)
+        if patch_size is not None:
+            dataset.set_patch(patch_size, patch_fg, patch_flips, patch_centre)
 
     def table(self, metas, plain=False):
         """the per-batch table of mrdis_volume_gather (include/mrdis.h), on the host, and the host twin of `mask`.  `plain`: the augment bit stays
@@ -152,6 +239,37 @@ class VolumeLoader3D(BatchLoader):
             tab[r, 2 * M + 1] = (1 if flip else 0) | (2 if aug else 0)
             bits = np.array([scale, shift], dtype=np.float32).view(np.uint32).astype(np.uint64)
             tab[r, 2 * M + 2] = (bits[0] | (bits[1] << np.uint64(32))).view(np.int64)
+        return tab, mask_host
+
+    def patch_table(self, metas):
+        """the per-batch table of mrdis_patch_origins / mrdis_patch_gather (include/mrdis.h: the words of `table`, the minima those of the whole
+        volumes, then the prefix pointer, the flags and the packed draws), on the host, and the host twin of `mask`"""
+        ds, st = self.dataset, self.dataset.store
+        M = len(ds.contrast_list)
+        D = st.shape[2]
+        classes = ds.FG_CLASSES.get(ds.dataset_name, ())
+        B = len(metas)
+        tab = np.zeros((B, 2 * M + patch3d.TABLE_EXTRA), dtype=np.int64)
+        mask_host = np.zeros((B, M), dtype=np.float32)
+        for r, (subj_id, _, ptrs, drop, tptr, _, scale, shift, (fg, u, flips, centre)) in enumerate(metas):
+            for m, p in enumerate(ptrs):
+                if p and m != drop:
+                    tab[r, m] = p
+                    tab[r, M + m] = st.crop_min_ptr(subj_id + '/' + ds.contrast_list[m], 0, D)
+                    mask_host[r, m] = 1.0
+            tab[r, 2 * M] = tptr
+            flags = (patch3d.AUG if ds.aug else 0) | (patch3d.FG if fg else 0) | (patch3d.CENTRE if centre else 0)
+            for axis, on in zip('hwd', flips):
+                flags |= patch3d.FLIP_BITS[axis] if on else 0
+            tab[r, 2 * M + 1] = flags
+            bits = np.array([scale, shift], dtype=np.float32).view(np.uint32).astype(np.uint64)
+            tab[r, 2 * M + 2] = (bits[0] | (bits[1] << np.uint64(32))).view(np.int64)
+            if fg and tptr:
+                tab[r, 2 * M + 3] = st.fg_prefix_ptr(subj_id + ds.TARGET_KEYS[ds.dataset_name], classes)
+            w = np.asarray(u, dtype=np.uint32).astype(np.uint64)
+            tab[r, 2 * M + 4] = (w[0] | (w[1] << np.uint64(32))).view(np.int64)
+            tab[r, 2 * M + 5] = (w[2] | (w[3] << np.uint64(32))).view(np.int64)
+            tab[r, 2 * M + 6] = w[4].view(np.int64)
         return tab, mask_host
 
     def plain_plan(self, limit=None):
@@ -194,6 +312,23 @@ class VolumeLoader3D(BatchLoader):
             batch['table'] = d                                        # windowed reads only: `target_ptrs` reads the label-volume addresses from it
         return batch
 
+    def _gather_patch(self, k, metas):
+        ds, st = self.dataset, self.dataset.store
+        M = len(ds.contrast_list)
+        dev = st.device
+        tab, mask_host = self.patch_table(metas)
+        host = torch.from_numpy(tab)
+        if dev.type == 'cuda':
+            host = host.pin_memory()
+        d = host.to(dev, non_blocking=True)                           # one small H2D copy per batch
+        classes = ds.FG_CLASSES.get(ds.dataset_name, ()) if ds.patch_fg > 0 else ()
+        origins = patch3d.patch_origins(d, M, st.shape, ds.patch_size, classes)
+        inputs, mask = patch3d.patch_gather(d, origins, M, st.shape, ds.patch_size)
+        targets = patch3d.patch_gather(d, origins, M, st.shape, ds.patch_size, targets=True, K=self.region_channels, relabel=ds.dataset_name == 'BraTS')
+        return {'inputs': inputs, 'targets': targets, 'subj_id': [m[0] for m in metas],
+                'slice_idx': torch.zeros(len(metas), dtype=torch.int64, device=dev), 'mask': mask, 'mask_host': mask_host,
+                'batch_index': k, 'origins': origins}
+
     def window(self, k, metas, z0, flip=False):
         """one batch of `plain_plan` at depth offset z0 (same Dz as the crop), every item as stored, H-flipped by the gather itself if `flip`:
         the sample dict of `batches` plus 'table', the device gather table (`target_ptrs`)."""
@@ -206,12 +341,16 @@ class VolumeLoader3D(BatchLoader):
         return self._gather(k, metas, int(z0), plain=True)
 
     def batches(self, limit=None, z0=None, flip=False):
-        """`z0=None`: the reference's batches (crop [45:-46], drop-off, augmentation).  An integer serves the batches of `plain_plan` with that
+        """`z0=None`: the reference's batches (crop [45:-46], drop-off, augmentation) -- in patch mode the patch batches.  An integer serves the batches of `plain_plan` with that
         depth offset and the same Dz, every item as stored (no drop-off redraws, no augmentation, no shuffle): the windowed reads for
         whole-volume prediction (model3d.predict_volumes).  `flip` (with z0 only): every item H-flipped by the gather itself."""
         if z0 is None:
             if flip:
                 raise ValueError('flip belongs to the windowed reads: give z0')
+            if self.dataset.patch_size is not None:
+                for k, _, metas in self.batch_plan(limit):
+                    yield self._gather_patch(k, metas)
+                return
             crop_z0 = self.dataset.crop()[0]
             for k, _, metas in self.batch_plan(limit):
                 yield self._gather(k, metas, crop_z0, plain=False)
@@ -240,14 +379,17 @@ class VolumeData3D:
         raise ValueError(f'no 3-D dataset {dataset_name!r}: BraTS or ZeroDose')
 
     def __init__(self, dataset_name, data_path, norm_type='mean', batch_size=16, fold=0, shuffle=True, contrast_list=('T1',), aug=False,
-                 dropoff=False, store=None, device='cuda:0', rank=0, world=1, generator=None, region_channels=0):
+                 dropoff=False, store=None, device='cuda:0', rank=0, world=1, generator=None, region_channels=0, patch_size=None, patch_fg=0.0,
+                 patch_flips='h'):
         h5, *lists = self.file_names(dataset_name, norm_type, fold)
         if store is None:
             store = VolumeStore3D.from_h5(os.path.join(data_path, h5), device)
         self.store = store
         subj = [load_subj_list(os.path.join(data_path, f)) for f in lists]
-        mk = lambda s, a, d: VolumeDataset3D(dataset_name, store, s, contrast_list=contrast_list, aug=a, dropoff=d)
+        # patch mode: random patches for the train loader, the centre patch (no draw, no foreground share) for the evaluation loaders
+        mk = lambda s, a, d, centre: VolumeDataset3D(dataset_name, store, s, contrast_list=contrast_list, aug=a, dropoff=d, patch_size=patch_size,
+                                                     patch_fg=0.0 if centre else patch_fg, patch_flips=patch_flips, patch_centre=centre)
         kw = dict(rank=rank, world=world, generator=generator, region_channels=region_channels)
-        self.trainLoader = VolumeLoader3D(mk(subj[0], aug, dropoff), batch_size, shuffle=shuffle, equal_steps=True, **kw)
-        self.valLoader = VolumeLoader3D(mk(subj[1], False, dropoff), batch_size, shuffle=False, **kw)
-        self.testLoader = VolumeLoader3D(mk(subj[2], False, False), batch_size, shuffle=False, **kw)
+        self.trainLoader = VolumeLoader3D(mk(subj[0], aug, dropoff, False), batch_size, shuffle=shuffle, equal_steps=True, **kw)
+        self.valLoader = VolumeLoader3D(mk(subj[1], False, dropoff, True), batch_size, shuffle=False, **kw)
+        self.testLoader = VolumeLoader3D(mk(subj[2], False, False, True), batch_size, shuffle=False, **kw)

@@ -90,6 +90,9 @@ _SIGS = {
     'mrdis_recon_metrics': (_I, [_P, _I, _P, _I, _P, _P, _Z, _I, _I, _I, _P]),
     'mrdis_slice_gather': (_I, [_P, _P, _P, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_volume_gather': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
+    'mrdis_fg_block_counts': (_I, [_P, _P, _I, _P, _I, _I, _I, _P]),
+    'mrdis_patch_origins': (_I, [_P, _I, _P, _P, _I] + [_I] * 8 + [_P]),
+    'mrdis_patch_gather': (_I, [_P, _I, _P, _P, _P] + [_I] * 11 + [_P]),
     'mrdis_nvnet_loss_workspace': (_Z, [_L, _L]),
     'mrdis_nvnet_loss_fwd': (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_double, _P, _P, _P, _Z, _P]),
     'mrdis_nvnet_loss_bwd': (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_double, _P, _P, _P, _P, _P]),
@@ -228,6 +231,10 @@ OUTDEC_FAMILIES = ('chatt', 'symdiff', 'rgate')
 CONV3D_FAMILIES = ('direct3d', 'c3d16', 'wgrad3d', 'wgrad3d16', 'wino_wgrad3d')
 # the 3-D batch gather (csrc/mrdis_volgather.hip): one count per mrdis_volume_gather call, whichever of its two kernels ran.
 DATA_FAMILIES = ('volgather',)
+# patch training for the 3-D nets (csrc/mrdis_patch.hip; the wrappers live in patch3d.py): one count per mrdis_fg_block_counts call (once per
+# subject), per mrdis_patch_origins call (one per batch) and per mrdis_patch_gather call (two per batch: inputs and targets).
+PATCH_FAMILIES = ('fgcount', 'patchorigin', 'patchgather')
+PATCH_MAX_CLASSES = 8             # include/mrdis.h MRDIS_PATCH_MAX_CLASSES
 # the fused objective of the 3-D nets and the segmentation counts (csrc/mrdis_loss3d.hip): 'loss3d' counts one per mrdis_nvnet_loss_fwd and one per
 # mrdis_nvnet_loss_bwd call, 'segcounts' one per mrdis_seg_counts call.
 LOSS3D_FAMILIES = ('loss3d', 'segcounts')
@@ -265,7 +272,7 @@ EXPORT_FAMILIES = ('export',)
 ELEM_FAMILIES = ('stat_vec', 'stat_scalar', 'stat_interp', 'spade_up2_onepass', 'spade_up2_twopass', 'bil_fwd_x2', 'bil_fwd_general',
                  'bil_bwd_x2', 'bil_bwd_tight3', 'bil_bwd_tight5', 'bil_bwd_general', 'elem_v1')
 # every name of csrc/mrdis_common.h MRDIS_COUNTERS: what launch_counts() hands out, ELEM_FAMILIES on request (tests/test_abi.py pins the union)
-LAUNCH_COUNTERS = (WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES
+LAUNCH_COUNTERS = (WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + PATCH_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES
                     + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES + PREP_FAMILIES + EXPORT_FAMILIES + LESION_FAMILIES)
 ALL_COUNTERS = LAUNCH_COUNTERS + ELEM_FAMILIES
 SYNTH_MAX_SRC = 8                 # include/mrdis.h MRDIS_SYNTH_MAX_SRC

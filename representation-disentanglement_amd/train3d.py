@@ -32,7 +32,7 @@ import torch.distributed as dist
 import yaml
 
 from . import hip
-from .data3d import VolumeData3D, VolumeStore3D
+from .data3d import VolumeData3D, VolumeStore3D, patch_args
 from .prep import build_store_from_raw, ensure_fold_lists, save_nifti
 from .postproc import CONNECTIVITIES, KEEP_MODES, STATS_COLUMNS, clean_labels, write_stats_csv
 from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, predict_volumes, seg_metrics_from_counts
@@ -53,6 +53,9 @@ DEFAULT_CONFIG_3D = {
     'model_name': 'NVNet3D',           # NVNet3D | UNet3D (Dice-only objective)
     'init_channels': 16, 'p': 0.2,
     'aug': True, 'dropoff': True,
+    'patch_size': None,                # [PH, PW, PD]: train on random patches of the whole scan (data3d.py; each a multiple of 16 for NVNet3D); null: the reference's depth crop
+    'patch_fg': 0.33,                  # patch_size only: the share of training patches centred on a tumour voxel (needs label targets: BraTS)
+    'patch_flips': 'hwd',              # patch_size only, with aug: the axes a training patch may be mirrored on
     'epochs': 300, 'lr': 1e-4, 'weight_decay': 1e-5,
     'lr_schedule': 'poly',             # none | poly: lr * (1 - epoch / epochs) ** 0.9
     'fused_loss': True,                # false: the torch composition `nvnet_loss`
@@ -108,6 +111,13 @@ def load_config3d(path=None, overrides=None):
         raise ValueError(f'data_source {cfg["data_source"]!r}: one of {DATA_SOURCES}')
     if cfg['data_source'] == 'raw' and not cfg['raw_path']:
         raise ValueError('data_source raw needs raw_path: the directory of the subjects')
+    if cfg['patch_size'] is not None:          # (patch_fg and patch_flips are read only with it)
+        cfg['patch_size'], cfg['patch_fg'], cfg['patch_flips'] = patch_args(cfg['patch_size'], cfg['patch_fg'], cfg['patch_flips'])
+        cfg['patch_size'] = list(cfg['patch_size'])
+        if cfg['model_name'] == 'NVNet3D' and any(v % 16 for v in cfg['patch_size']):
+            raise ValueError(f'patch_size {cfg["patch_size"]}: every extent a multiple of 16 for NVNet3D (its VAE branch decodes from 1 / 16 of the input)')
+        if cfg['patch_fg'] > 0 and cfg['dataset_name'] != 'BraTS':
+            raise ValueError(f'patch_fg > 0 needs label targets (dataset_name BraTS), not {cfg["dataset_name"]!r}: set patch_fg=0')
     if cfg['phase'] not in PHASES:
         raise ValueError(f'phase {cfg["phase"]!r}: one of {PHASES}')
     if cfg['predict_set'] not in ('train', 'val', 'test'):
@@ -246,12 +256,13 @@ class Run3D:
         if data is None:
             data = VolumeData3D(cfg['dataset_name'], cfg['data_path'], norm_type=cfg['norm_type'], batch_size=cfg['batch_size'], fold=cfg['fold'],
                                 shuffle=True, contrast_list=cfg['contrast_list'], aug=cfg['aug'], dropoff=cfg['dropoff'], store=store,
-                                device=dev, region_channels=3)
+                                device=dev, region_channels=3, patch_size=cfg['patch_size'], patch_fg=cfg['patch_fg'], patch_flips=cfg['patch_flips'])
         self.data = data
         self.loaders = {'train': data.trainLoader, 'val': data.valLoader, 'test': data.testLoader}
         ds = data.trainLoader.dataset
         H, W, _ = ds.store.shape
-        self.input_shape = (H, W, ds.crop()[1])
+        patch = getattr(ds, 'patch_size', None)
+        self.input_shape = tuple(patch) if patch is not None else (H, W, ds.crop()[1])      # patch training: the net is built for the patch
         self.start_epoch = -1
         self.best_dice = -1.0
         if cfg['phase'] in NO_MODEL_PHASES:    # works on label volumes that are already written: no model, no optimizer, no checkpoint
