@@ -441,6 +441,25 @@ int mrdis_patch_origins(const void* table, int ld_table, int* origins, const int
 int mrdis_patch_gather(const void* table, int ld_table, const int* origins, float* out, float* mask, int B, int M, int H, int W, int D,
                        int PH, int PW, int PD, int mode, int K, int relabel, void* stream);
 
+/* ---- rotated and zoomed training patches (csrc/mrdis_warp.hip): mrdis_patch_gather with an affine resampling of the samples whose warp bit
+ * is set.  This package's conventions.  Parameters, out, mask, mode, K, relabel and the return codes are mrdis_patch_gather's, except
+ * ld_table >= 2 M + 12 (else MRDIS_EINVAL): the 2 M + 7 words above, flag word [2M+1] bit 6 = warp, and [2M+7 .. 2M+11] the nine entries
+ * a[r][c] of a 3 x 3 matrix in Q16 (int32, row-major, two per word, the low half first; the last high half is 0).
+ * Source coordinate of output voxel o (after the flip rule: o' = P - 1 - o on a flipped axis), integers in units of 2^-17 voxel, 64-bit:
+ *   s[r] = ((2 origin[r] + P[r] - 1) << 16) + sum_c a[r][c] (2 o'[c] - (P[c] - 1))
+ *   floor index i0 = s >> 17, fraction f = s & (2^17 - 1), nearest index = (s + 2^16) >> 17
+ * (a rotation about the centre of the unwarped patch).  Every corner index i0, i0 + 1 and the nearest index are clamped per axis into the
+ * volume (edge replication); the entries are clamped to +-2^18 first, so no table can send a read outside a volume.
+ * mode 1: the raw label at the nearest index, then relabel and the region channels as mrdis_patch_gather.
+ * mode 0, per contrast (absent: every voxel reads 0), m0 the item's whole-volume minimum: with the augment bit, -10 exactly where the voxel
+ *   at the nearest index equals m0; elsewhere every one of the eight corners that equals m0 takes the nearest voxel's value, the corners
+ *   are interpolated along d, then w, then h as a + (f / 2^17) (b - a) in fp32 (three roundings each, no fused multiply-add), and
+ *   x * scale + shift follows (two roundings).  Without the augment bit: the interpolated raw corners.
+ * A sample with the warp bit clear is mrdis_patch_gather's, bit for bit.  One launch per call, counted as "patchwarp"; no atomics.     */
+#define MRDIS_PATCH_WARP_FLAG 64
+int mrdis_patch_warp(const void* table, int ld_table, const int* origins, float* out, float* mask, int B, int M, int H, int W, int D,
+                     int PH, int PW, int PD, int mode, int K, int relabel, void* stream);
+
 /* ---- objective of the 3-D nets (model3d.nvnet_loss) fused: soft Dice of sigmoid(uout) against `target`, GLOBAL over the batch, plus
  * w_l2 times the mean squared error of vout against x (csrc/mrdis_loss3d.hip).  uout / target: fp32 of one shape (shape_ut, nd_ut <= 8
  * extents) and ONE dense memory layout, given by their element strides; vout / x likewise with shape_vx, or both NULL for the Dice-only

@@ -62,6 +62,7 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
     X(DIRECT3D, "direct3d") X(C3D16, "c3d16") X(WGRAD3D, "wgrad3d") X(WGRAD3D16, "wgrad3d16") X(WINO_WGRAD3D, "wino_wgrad3d") /* mrdis_conv3d.hip / mrdis_wino.hip: the 3-D kernels */ \
     X(VOLGATHER, "volgather") /* mrdis_volgather.hip: the 3-D batch gather, one count per mrdis_volume_gather call */ \
     X(FGCOUNT, "fgcount") X(PATCHORIGIN, "patchorigin") X(PATCHGATHER, "patchgather") /* mrdis_patch.hip: one count per mrdis_fg_block_counts / mrdis_patch_origins / mrdis_patch_gather call */ \
+    X(PATCHWARP, "patchwarp") /* mrdis_warp.hip: one count (and one launch) per mrdis_patch_warp call */ \
     X(LOSS3D, "loss3d") X(SEGCOUNTS, "segcounts") /* mrdis_loss3d.hip: one count per mrdis_nvnet_loss_fwd / _bwd call; one per mrdis_seg_counts call */ \
     X(SEGACCUM, "segaccum") X(SEGLABELS, "seglabels") /* mrdis_segvol.hip: one count per mrdis_seg_accum / mrdis_seg_label_volume call */ \
     X(SYNTHACCUM, "synthaccum") X(SYNTHFINISH, "synthfinish") /* mrdis_synth.hip: one count per mrdis_synth_accum / mrdis_synth_finish call */ \

@@ -24,6 +24,10 @@ tumour class the subject has (csrc/mrdis_patch.hip, patch3d.py).  Per item the h
   3. five uint32 `u_class, u_voxel, u_h, u_w, u_d` by one `randint(0, 2**32, size=5, dtype=np.uint32)`
   4. with aug: one `rand() > 0.5` per axis named in `patch_flips`, in h, w, d order
   5. with aug: scale and shift, as above
+With `patch_warp` > 0 (and aug) a step 4b follows the flips: one `r = rand(5)` per item, always drawn -- `warp = r[0] < patch_warp`,
+`angle_a = (2 r[1 + a] - 1) patch_rot[a]` degrees about the H, W, D axes, `zoom = lo + r[4] (hi - lo)` over `patch_zoom` -- and the batch is
+gathered by patch3d.patch_warp (csrc/mrdis_warp.hip: integer coordinates, exact labels) instead of patch_gather.  With `patch_warp` = 0
+no draw is added and every stream, batch and checkpoint is what it was.
 and the device turns the draws into the patch origin (patch3d's docstring: pick, clamping instead of padding).  The `== min()` rule compares
 with the minimum of the whole stored volume.  The evaluation loaders serve the centre patch, without a draw; `crop()` is then the centre
 depth window of the trained depth PD, so the windowed reads slide PD over the full H x W.
@@ -118,6 +122,27 @@ def patch_args(patch_size, patch_fg=0.0, patch_flips='h'):
     return patch_size, float(patch_fg), patch_flips
 
 
+def patch_warp_args(patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4)):
+    """-> (patch_warp, (rot h, rot w, rot d), (zoom lo, zoom hi)) checked: a share in 0 .. 1, three largest absolute angles in 0 .. 45 degrees,
+    lo <= hi both in 0.5 .. 2; else ValueError naming the key"""
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and np.isfinite(v)
+    if not num(patch_warp) or not 0.0 <= patch_warp <= 1.0:
+        raise ValueError(f'patch_warp {patch_warp!r}: the share of resampled training patches, 0 .. 1')
+    try:
+        ok = len(patch_rot) == 3 and all(num(v) and 0 <= v <= 45 for v in patch_rot)
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f'patch_rot {patch_rot!r}: the largest absolute rotation about the H, W and D axes, three numbers in 0 .. 45 degrees')
+    try:
+        ok = len(patch_zoom) == 2 and all(num(v) and 0.5 <= v <= 2 for v in patch_zoom) and patch_zoom[0] <= patch_zoom[1]
+    except TypeError:
+        ok = False
+    if not ok:
+        raise ValueError(f'patch_zoom {patch_zoom!r}: [lo, hi] with lo <= hi, both in 0.5 .. 2')
+    return float(patch_warp), tuple(float(v) for v in patch_rot), tuple(float(v) for v in patch_zoom)
+
+
 class VolumeDataset3D:
     """ZeroDoseDataset3D (util.py:723-810) over a VolumeStore3D: `meta(idx)` is the host part of `__getitem__`.  `patch_size` (PH, PW, PD):
     patch training, see the module docstring; `patch_centre`: the deterministic centre patch instead of a random one (evaluation)."""
@@ -126,15 +151,16 @@ class VolumeDataset3D:
     FG_CLASSES = {'BraTS': (1, 2, 4)}      # the label values a foreground patch may be centred on
 
     def __init__(self, dataset_name, store, subj_list, contrast_list=('T1',), aug=False, dropoff=False, patch_size=None, patch_fg=0.0,
-                 patch_flips='h', patch_centre=False):
+                 patch_flips='h', patch_centre=False, patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4)):
         self.dataset_name, self.store = dataset_name, store
         self.subj_list, self.contrast_list = list(subj_list), list(contrast_list)
         self.aug, self.dropoff = aug, dropoff
-        self.set_patch(patch_size, patch_fg, patch_flips, patch_centre)
+        self.set_patch(patch_size, patch_fg, patch_flips, patch_centre, patch_warp, patch_rot, patch_zoom)
 
-    def set_patch(self, patch_size, patch_fg=0.0, patch_flips='h', patch_centre=False):
+    def set_patch(self, patch_size, patch_fg=0.0, patch_flips='h', patch_centre=False, patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4)):
         self.patch_size, self.patch_fg, self.patch_flips = patch_args(patch_size, patch_fg, patch_flips)
         self.patch_centre = bool(patch_centre)
+        self.patch_warp, self.patch_rot, self.patch_zoom = patch_warp_args(patch_warp, patch_rot, patch_zoom)
         if self.patch_size is None:
             return
         if self.patch_fg > 0 and self.dataset_name not in self.FG_CLASSES:
@@ -161,7 +187,8 @@ class VolumeDataset3D:
         """-> (subj_id, slice_idx = 0, volume pointers, dropped contrast or -1, target pointer, flip, scale, shift).  rng: None = the global np.random (the
         reference's own stream, draw for draw) or the loader's own np.random.RandomState (data-parallel runs, see BatchLoader).  `plain`: the item as
         stored -- nothing dropped, not augmented -- and no draw from any stream (the windowed reads of VolumeLoader3D.batches(z0=...)).
-        In patch mode (and not `plain`) a ninth element follows: (fg, the five uint32 draws, (flip h, flip w, flip d), centre)."""
+        In patch mode (and not `plain`) a ninth element follows: (fg, the five uint32 draws, (flip h, flip w, flip d), centre), and with
+        `patch_warp` > 0 on an augmenting, non-centre dataset three more in it: (warp, (angle h, w, d) in degrees, zoom)."""
         rng = np.random if rng is None else rng
         subj_id = str(self.subj_list[idx])
         ptrs = [self.store.ptr(subj_id + '/' + c) for c in self.contrast_list]
@@ -184,19 +211,28 @@ class VolumeDataset3D:
         return subj_id, 0, ptrs, drop, tptr, flip, scale, shift
 
     def _patch_draws(self, rng):
-        """the tail of a patch-mode meta, drawn in the order of the module docstring: (flip h, scale, shift, (fg, u[5], flips, centre))"""
+        """the tail of a patch-mode meta, drawn in the order of the module docstring: (flip h, scale, shift, (fg, u[5], flips, centre)), the last
+        tuple followed by (warp, angles, zoom) where `warps()`"""
         if self.patch_centre:
             return False, 1.0, 0.0, (False, np.zeros(5, dtype=np.uint32), (False, False, False), True)
         fg = bool(rng.rand() < self.patch_fg) if self.patch_fg > 0 else False
         u = rng.randint(0, 2 ** 32, size=5, dtype=np.uint32)
-        flips, scale, shift = [False, False, False], 1.0, 0.0
+        flips, scale, shift, warp = [False, False, False], 1.0, 0.0, ()
         if self.aug:
             for i, axis in enumerate('hwd'):
                 if axis in self.patch_flips:
                     flips[i] = bool(rng.rand() > 0.5)
+            if self.patch_warp > 0:                                   # five doubles, always: the stream does not depend on the outcome
+                r = rng.rand(5)
+                lo, hi = self.patch_zoom
+                warp = (bool(r[0] < self.patch_warp), tuple(float((2 * r[1 + a] - 1) * self.patch_rot[a]) for a in range(3)), float(lo + r[4] * (hi - lo)))
             scale = 1 + 0.2 * (rng.rand() - 0.5)
             shift = 0.2 * (rng.rand() - 0.5)
-        return flips[0], scale, shift, (fg, u, tuple(flips), False)
+        return flips[0], scale, shift, (fg, u, tuple(flips), False) + warp
+
+    def warps(self):
+        """whether this dataset's batches go through patch3d.patch_warp: patch mode, augmenting, not the centre patch, patch_warp > 0"""
+        return self.patch_size is not None and bool(self.aug) and not self.patch_centre and self.patch_warp > 0
 
 
 class VolumeLoader3D(BatchLoader):
@@ -208,16 +244,16 @@ class VolumeLoader3D(BatchLoader):
     Batch order, rank / world / equal_steps and the loader's own stream under world > 1 are BatchLoader's (see its docstring); here that
     stream carries ALL per-item draws, drop-off and augmentation, for the same reason.
 
-    `patch_size` (with `patch_fg`, `patch_flips`, `patch_centre`): puts the dataset into patch mode (VolumeDataset3D.set_patch; None leaves it
-    as it was built).  A batch is then three launches -- origins, inputs, targets -- of (PH, PW, PD) patches, and carries 'origins' (B, 4) int32
+    `patch_size` (with `patch_fg`, `patch_flips`, `patch_centre`, `patch_warp`, `patch_rot`, `patch_zoom`): puts the dataset into patch mode
+    (VolumeDataset3D.set_patch; None leaves it as it was built).  A batch is then three launches -- origins, inputs, targets -- of (PH, PW, PD) patches, and carries 'origins' (B, 4) int32
     on the device: h0, w0, d0 and the index of the class a foreground patch was centred on (-1: uniform or centre)."""
 
     def __init__(self, dataset, batch_size, shuffle=False, rank=0, world=1, equal_steps=False, generator=None, region_channels=0,
-                 patch_size=None, patch_fg=0.0, patch_flips='h', patch_centre=False):
+                 patch_size=None, patch_fg=0.0, patch_flips='h', patch_centre=False, patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4)):
         super().__init__(dataset, batch_size, shuffle, rank, world, equal_steps, generator)
         self.region_channels = int(region_channels)
         if patch_size is not None:
-            dataset.set_patch(patch_size, patch_fg, patch_flips, patch_centre)
+            dataset.set_patch(patch_size, patch_fg, patch_flips, patch_centre, patch_warp, patch_rot, patch_zoom)
 
     def table(self, metas, plain=False):
         """the per-batch table of mrdis_volume_gather (include/mrdis.h), on the host, and the host twin of `mask`.  `plain`: the augment bit stays
@@ -243,15 +279,17 @@ class VolumeLoader3D(BatchLoader):
 
     def patch_table(self, metas):
         """the per-batch table of mrdis_patch_origins / mrdis_patch_gather (include/mrdis.h: the words of `table`, the minima those of the whole
-        volumes, then the prefix pointer, the flags and the packed draws), on the host, and the host twin of `mask`"""
+        volumes, then the prefix pointer, the flags and the packed draws), on the host, and the host twin of `mask`.  Where the dataset
+        `warps()` the rows are patch3d.WARP_EXTRA words longer (mrdis_patch_warp): the WARP flag and the packed Q16 matrix of the items that drew
+        a warp, zeros for the others."""
         ds, st = self.dataset, self.dataset.store
         M = len(ds.contrast_list)
         D = st.shape[2]
         classes = ds.FG_CLASSES.get(ds.dataset_name, ())
         B = len(metas)
-        tab = np.zeros((B, 2 * M + patch3d.TABLE_EXTRA), dtype=np.int64)
+        tab = np.zeros((B, 2 * M + patch3d.TABLE_EXTRA + (patch3d.WARP_EXTRA if ds.warps() else 0)), dtype=np.int64)
         mask_host = np.zeros((B, M), dtype=np.float32)
-        for r, (subj_id, _, ptrs, drop, tptr, _, scale, shift, (fg, u, flips, centre)) in enumerate(metas):
+        for r, (subj_id, _, ptrs, drop, tptr, _, scale, shift, (fg, u, flips, centre, *warp)) in enumerate(metas):
             for m, p in enumerate(ptrs):
                 if p and m != drop:
                     tab[r, m] = p
@@ -270,6 +308,9 @@ class VolumeLoader3D(BatchLoader):
             tab[r, 2 * M + 4] = (w[0] | (w[1] << np.uint64(32))).view(np.int64)
             tab[r, 2 * M + 5] = (w[2] | (w[3] << np.uint64(32))).view(np.int64)
             tab[r, 2 * M + 6] = w[4].view(np.int64)
+            if warp and warp[0]:
+                tab[r, 2 * M + 1] |= patch3d.WARP
+                tab[r, 2 * M + 7:2 * M + 12] = patch3d.pack_warp(patch3d.warp_matrix(warp[1], warp[2]))
         return tab, mask_host
 
     def plain_plan(self, limit=None):
@@ -323,8 +364,9 @@ class VolumeLoader3D(BatchLoader):
         d = host.to(dev, non_blocking=True)                           # one small H2D copy per batch
         classes = ds.FG_CLASSES.get(ds.dataset_name, ()) if ds.patch_fg > 0 else ()
         origins = patch3d.patch_origins(d, M, st.shape, ds.patch_size, classes)
-        inputs, mask = patch3d.patch_gather(d, origins, M, st.shape, ds.patch_size)
-        targets = patch3d.patch_gather(d, origins, M, st.shape, ds.patch_size, targets=True, K=self.region_channels, relabel=ds.dataset_name == 'BraTS')
+        gather = patch3d.patch_warp if ds.warps() else patch3d.patch_gather
+        inputs, mask = gather(d, origins, M, st.shape, ds.patch_size)
+        targets = gather(d, origins, M, st.shape, ds.patch_size, targets=True, K=self.region_channels, relabel=ds.dataset_name == 'BraTS')
         return {'inputs': inputs, 'targets': targets, 'subj_id': [m[0] for m in metas],
                 'slice_idx': torch.zeros(len(metas), dtype=torch.int64, device=dev), 'mask': mask, 'mask_host': mask_host,
                 'batch_index': k, 'origins': origins}
@@ -380,15 +422,16 @@ class VolumeData3D:
 
     def __init__(self, dataset_name, data_path, norm_type='mean', batch_size=16, fold=0, shuffle=True, contrast_list=('T1',), aug=False,
                  dropoff=False, store=None, device='cuda:0', rank=0, world=1, generator=None, region_channels=0, patch_size=None, patch_fg=0.0,
-                 patch_flips='h'):
+                 patch_flips='h', patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4)):
         h5, *lists = self.file_names(dataset_name, norm_type, fold)
         if store is None:
             store = VolumeStore3D.from_h5(os.path.join(data_path, h5), device)
         self.store = store
         subj = [load_subj_list(os.path.join(data_path, f)) for f in lists]
-        # patch mode: random patches for the train loader, the centre patch (no draw, no foreground share) for the evaluation loaders
+        # patch mode: random patches for the train loader, the centre patch (no draw, no foreground share, no warp) for the evaluation loaders
         mk = lambda s, a, d, centre: VolumeDataset3D(dataset_name, store, s, contrast_list=contrast_list, aug=a, dropoff=d, patch_size=patch_size,
-                                                     patch_fg=0.0 if centre else patch_fg, patch_flips=patch_flips, patch_centre=centre)
+                                                     patch_fg=0.0 if centre else patch_fg, patch_flips=patch_flips, patch_centre=centre,
+                                                     patch_warp=0.0 if centre else patch_warp, patch_rot=patch_rot, patch_zoom=patch_zoom)
         kw = dict(rank=rank, world=world, generator=generator, region_channels=region_channels)
         self.trainLoader = VolumeLoader3D(mk(subj[0], aug, dropoff, False), batch_size, shuffle=shuffle, equal_steps=True, **kw)
         self.valLoader = VolumeLoader3D(mk(subj[1], False, dropoff, True), batch_size, shuffle=False, **kw)

@@ -16,6 +16,9 @@ on a tumour voxel.  THIS PACKAGE'S CONVENTIONS -- the reference trains on one fi
 
 The table is data3d.VolumeLoader3D.patch_table's: one row of 2 M + TABLE_EXTRA 64-bit words per sample (include/mrdis.h).  Every draw comes
 from it, so the three launches of a batch replay from a captured graph with the next batch's table.
+
+Rotation and zoom of the patches (`patch_warp`, `warp_matrix`; rows WARP_EXTRA words longer, flag WARP): warp3d.py, whose docstring has the
+conventions.
 """
 import torch
 
@@ -24,8 +27,9 @@ from . import hip
 BLOCK = 1024                          # flat indices per counted block
 MAX_CLASSES = hip.PATCH_MAX_CLASSES
 TABLE_EXTRA = 7                       # words of a table row beyond the 2 M pointers
+WARP_EXTRA = 5                        # further words of a row that `patch_warp` reads: the nine Q16 matrix entries, two per word
 # the flag word [2M+1]
-FLIP_H, AUG, FLIP_W, FLIP_D, FG, CENTRE = 1, 2, 4, 8, 16, 32
+FLIP_H, AUG, FLIP_W, FLIP_D, FG, CENTRE, WARP = 1, 2, 4, 8, 16, 32, 64
 FLIP_BITS = {'h': FLIP_H, 'w': FLIP_W, 'd': FLIP_D}
 
 
@@ -116,3 +120,8 @@ def patch_gather(table, origins, M, shape, patch, targets=False, K=0, relabel=Fa
     hip._chk(lib.mrdis_patch_gather(hip._ptr(table), ld, hip._ptr(origins), hip._ptr(out), None, B, M, H, W, D, PH, PW, PD, 1, K, int(bool(relabel)), hip._stream()),
              'patch_gather')
     return out.permute(0, 4, 1, 2, 3) if K else out
+
+
+
+# rotated and zoomed patches (warp3d.py, csrc/mrdis_warp.hip), reached from here as patch3d.patch_warp / patch3d.warp_matrix
+from .warp3d import pack_warp, patch_warp, warp_matrix      # noqa: E402,F401

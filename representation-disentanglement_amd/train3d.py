@@ -32,7 +32,7 @@ import torch.distributed as dist
 import yaml
 
 from . import hip
-from .data3d import VolumeData3D, VolumeStore3D, patch_args
+from .data3d import VolumeData3D, VolumeStore3D, patch_args, patch_warp_args
 from .prep import build_store_from_raw, ensure_fold_lists, save_nifti
 from .postproc import CONNECTIVITIES, KEEP_MODES, STATS_COLUMNS, clean_labels, write_stats_csv
 from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, predict_volumes, seg_metrics_from_counts
@@ -56,6 +56,9 @@ DEFAULT_CONFIG_3D = {
     'patch_size': None,                # [PH, PW, PD]: train on random patches of the whole scan (data3d.py; each a multiple of 16 for NVNet3D); null: the reference's depth crop
     'patch_fg': 0.33,                  # patch_size only: the share of training patches centred on a tumour voxel (needs label targets: BraTS)
     'patch_flips': 'hwd',              # patch_size only, with aug: the axes a training patch may be mirrored on
+    'patch_warp': 0.0,                 # patch_size only, with aug: the share of training patches rotated and zoomed on the device (patch3d.patch_warp); 0: off
+    'patch_rot': [30, 30, 30],         # patch_warp only: the largest absolute rotation about the H, W and D axes in degrees, each in 0 .. 45
+    'patch_zoom': [0.7, 1.4],          # patch_warp only: [lo, hi] of the zoom, lo <= hi in 0.5 .. 2; above 1 magnifies
     'epochs': 300, 'lr': 1e-4, 'weight_decay': 1e-5,
     'lr_schedule': 'poly',             # none | poly: lr * (1 - epoch / epochs) ** 0.9
     'fused_loss': True,                # false: the torch composition `nvnet_loss`
@@ -111,9 +114,11 @@ def load_config3d(path=None, overrides=None):
         raise ValueError(f'data_source {cfg["data_source"]!r}: one of {DATA_SOURCES}')
     if cfg['data_source'] == 'raw' and not cfg['raw_path']:
         raise ValueError('data_source raw needs raw_path: the directory of the subjects')
-    if cfg['patch_size'] is not None:          # (patch_fg and patch_flips are read only with it)
+    if cfg['patch_size'] is not None:          # (patch_fg, patch_flips and the patch_warp keys are read only with it)
         cfg['patch_size'], cfg['patch_fg'], cfg['patch_flips'] = patch_args(cfg['patch_size'], cfg['patch_fg'], cfg['patch_flips'])
         cfg['patch_size'] = list(cfg['patch_size'])
+        cfg['patch_warp'], rot, zoom = patch_warp_args(cfg['patch_warp'], cfg['patch_rot'], cfg['patch_zoom'])
+        cfg['patch_rot'], cfg['patch_zoom'] = list(rot), list(zoom)
         if cfg['model_name'] == 'NVNet3D' and any(v % 16 for v in cfg['patch_size']):
             raise ValueError(f'patch_size {cfg["patch_size"]}: every extent a multiple of 16 for NVNet3D (its VAE branch decodes from 1 / 16 of the input)')
         if cfg['patch_fg'] > 0 and cfg['dataset_name'] != 'BraTS':
@@ -256,7 +261,8 @@ class Run3D:
         if data is None:
             data = VolumeData3D(cfg['dataset_name'], cfg['data_path'], norm_type=cfg['norm_type'], batch_size=cfg['batch_size'], fold=cfg['fold'],
                                 shuffle=True, contrast_list=cfg['contrast_list'], aug=cfg['aug'], dropoff=cfg['dropoff'], store=store,
-                                device=dev, region_channels=3, patch_size=cfg['patch_size'], patch_fg=cfg['patch_fg'], patch_flips=cfg['patch_flips'])
+                                device=dev, region_channels=3, patch_size=cfg['patch_size'], patch_fg=cfg['patch_fg'], patch_flips=cfg['patch_flips'],
+                                patch_warp=cfg['patch_warp'], patch_rot=cfg['patch_rot'], patch_zoom=cfg['patch_zoom'])
         self.data = data
         self.loaders = {'train': data.trainLoader, 'val': data.valLoader, 'test': data.testLoader}
         ds = data.trainLoader.dataset
