@@ -87,7 +87,8 @@ long long mrdis_get_option(const char* name);
  * Winograd weight gradient, one count per depth-tap launch; the hybrid 3-D forward / data gradient counts as "wino_spade"); "volgather"; "loss3d" | "segcounts" (the fused 3-D objective, one count per forward and per backward call, and the segmentation counts); "segaccum" | "seglabels" (whole-volume prediction of the 3-D nets); "synthaccum" | "synthfinish" (whole-subject synthesis of the 2-D model, one count per call); "seg2dlabels" | "seg2dfinish" (whole-subject segmentation by the 2-D model, one count per call); "fuse" (mrdis_fuse_present_fwd / _bwd, one count per call); "export" (mrdis_export_volume, one count and one launch per call);
  * "stat_vec" | "stat_scalar" | "stat_interp" (the partial-sum kernel of a statistics pass), "spade_up2_onepass" | "spade_up2_twopass" (the route of
  * mrdis_instnorm_spade_bwd_up2, one per call), "bil_fwd_x2" | "bil_fwd_general", "bil_bwd_x2" | "bil_bwd_tight3" | "bil_bwd_tight5" | "bil_bwd_general"
- * (mrdis_bilinear_fwd / _bwd, one per call), "elem_v1" (an element-wise pass in its one-channel-per-thread form): dispatch choices, not launches;
+ * (mrdis_bilinear_fwd / _bwd, one per call), "elem_v1" (an element-wise pass in its one-channel-per-thread form; also, once per call, mrdis_chatt_* / mrdis_symdiff_* /
+ * mrdis_rgate_* in their scalar forms: C % 4 != 0, a view not 16-byte aligned or a pixel stride % 4 != 0): dispatch choices, not launches;
  * "all" (every kernel launch of the library).  MRDIS_EINVAL for an unknown name.  Diagnostics: the parity tests
  * use it to prove that the form under test is the one that ran. */
 long long mrdis_launch_count(const char* family);

@@ -77,7 +77,7 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
     X(SPADE_UP2_ONEPASS, "spade_up2_onepass") X(SPADE_UP2_TWOPASS, "spade_up2_twopass") /* mrdis_instnorm_spade_bwd_up2: one count per call, by route */ \
     X(BIL_FWD_X2, "bil_fwd_x2") X(BIL_FWD_GENERAL, "bil_fwd_general") /* mrdis_bilinear_fwd */ \
     X(BIL_BWD_X2, "bil_bwd_x2") X(BIL_BWD_TIGHT3, "bil_bwd_tight3") X(BIL_BWD_TIGHT5, "bil_bwd_tight5") X(BIL_BWD_GENERAL, "bil_bwd_general") /* mrdis_bilinear_bwd */ \
-    X(ELEM_V1, "elem_v1") /* mrdis_elem.hip: an element-wise pass took its one-channel-per-thread (V = 1) instantiation (views not 16-byte aligned or C % 4 != 0) */ \
+    X(ELEM_V1, "elem_v1") /* mrdis_elem.hip: an element-wise pass took its one-channel-per-thread (V = 1) instantiation (views not 16-byte aligned or C % 4 != 0); also, once per call, the chatt / symdiff / rgate entry points of mrdis_outdec.hip when chatt_vec chose their scalar forms (a stride % 4 != 0 counts too) */ \
     X(ALL, "all") /* every launch of the library */
 #define MRDIS_X_CNT_ID(id, name) MRDIS_CNT_##id,
 enum { MRDIS_COUNTERS(MRDIS_X_CNT_ID) MRDIS_CNT_COUNT };

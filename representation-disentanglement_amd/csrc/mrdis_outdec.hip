@@ -353,6 +353,7 @@ extern "C" int mrdis_chatt_fwd(const float* x, int ldx, const float* s, int lds,
     if (ws_bytes < mrdis_chatt_workspace(B, HW, C, Hd)) return MRDIS_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int V = chatt_vec(C, {x, s, out}, {ldx, lds, ldo});
+    if (V == 1) mrdis_count(MRDIS_CNT_ELEM_V1);
     const ChattGeom g = chatt_geom(B, HW, C, V);
     float* part = (float*)ws;
     mrdis_count(MRDIS_CNT_CHATT);
@@ -379,6 +380,7 @@ extern "C" int mrdis_chatt_bwd(const float* dy, int lddy, const float* x, int ld
     if (ws_bytes < mrdis_chatt_workspace(B, HW, C, Hd)) return MRDIS_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
     const int V = chatt_vec(C, {dy, x, dx}, {lddy, ldx, lddx});
+    if (V == 1) mrdis_count(MRDIS_CNT_ELEM_V1);
     const ChattGeom g = chatt_geom(B, HW, C, V);
     float* part = (float*)ws;
     float* dzu = part + (long long)B * g.P * C;
@@ -401,6 +403,7 @@ extern "C" int mrdis_chatt_bwd(const float* dy, int lddy, const float* x, int ld
 extern "C" int mrdis_symdiff_fwd(const float* g, int ldg, float* gd, int ldo, int B, int H, int W, int C, void* stream) {
     if (!g || !gd || B < 1 || H < 1 || W < 1 || C < 1 || ldg < C || ldo < C) return MRDIS_EINVAL;
     const int V = chatt_vec(C, {g, gd}, {ldg, ldo});
+    if (V == 1) mrdis_count(MRDIS_CNT_ELEM_V1);
     const long long n = (long long)B * H * W * (C / V);
     mrdis_count(MRDIS_CNT_SYMDIFF);
     if (V == 4) MRDIS_LAUNCH((symdiff_fwd_kernel<4>), dim3(od_grid(n, OD_THREADS)), dim3(OD_THREADS), 0, (hipStream_t)stream, g, ldg, gd, ldo, B, H, W, C);
@@ -412,6 +415,7 @@ extern "C" int mrdis_symdiff_fwd(const float* g, int ldg, float* gd, int ldo, in
 extern "C" int mrdis_symdiff_bwd(const float* dgd, int lddgd, const float* g, int ldg, float* dg, int lddg, int B, int H, int W, int C, void* stream) {
     if (!dgd || !g || !dg || B < 1 || H < 1 || W < 1 || C < 1 || lddgd < C || ldg < C || lddg < C) return MRDIS_EINVAL;
     const int V = chatt_vec(C, {dgd, g, dg}, {lddgd, ldg, lddg});
+    if (V == 1) mrdis_count(MRDIS_CNT_ELEM_V1);
     const long long n = (long long)B * H * W * (C / V);
     mrdis_count(MRDIS_CNT_SYMDIFF);
     if (V == 4) MRDIS_LAUNCH((symdiff_bwd_kernel<4>), dim3(od_grid(n, OD_THREADS)), dim3(OD_THREADS), 0, (hipStream_t)stream, dgd, lddgd, g, ldg, dg, lddg, B, H, W, C);
@@ -423,6 +427,7 @@ extern "C" int mrdis_symdiff_bwd(const float* dgd, int lddgd, const float* g, in
 extern "C" int mrdis_rgate_fwd(const float* x, int ldx, const float* alpha, float* out, int ldo, int B, int H, int W, int C, void* stream) {
     if (!x || !alpha || !out || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 1 || ldx < C || ldo < C) return MRDIS_EINVAL;
     const int V = chatt_vec(C, {x, out}, {ldx, ldo});
+    if (V == 1) mrdis_count(MRDIS_CNT_ELEM_V1);
     const long long n = (long long)B * H * W * (C / V);
     mrdis_count(MRDIS_CNT_RGATE);
     if (V == 4) MRDIS_LAUNCH((rgate_fwd_kernel<4>), dim3(od_grid(n, OD_THREADS)), dim3(OD_THREADS), 0, (hipStream_t)stream, x, ldx, alpha, out, ldo, B, H, W, C);
@@ -436,6 +441,7 @@ extern "C" int mrdis_rgate_bwd(const float* dy, int lddy, const float* x, int ld
     if (!dy || !x || !alpha || !dx || !rsum || B < 1 || H < 2 || W < 2 || (H & 1) || (W & 1) || C < 1 || lddy < C || ldx < C || lddx < C)
         return MRDIS_EINVAL;
     const int V = chatt_vec(C, {dy, x, dx}, {lddy, ldx, lddx});
+    if (V == 1) mrdis_count(MRDIS_CNT_ELEM_V1);
     const long long npix = (long long)B * H * W;
     const int grid = od_grid(npix, OD_THREADS / RG_LANES);
     mrdis_count(MRDIS_CNT_RGATE);

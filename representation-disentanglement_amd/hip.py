@@ -271,7 +271,8 @@ PREP_FAMILIES = ('prepstats', 'prepwrite')
 EXPORT_FAMILIES = ('export',)
 # the dispatch choices of the statistics, norm and resize entry points (csrc/mrdis_elem.hip), host-side counts only: which partial-sum kernel a
 # statistics pass took ('stat_vec' | 'stat_scalar' | 'stat_interp': one per pass), the route of mrdis_instnorm_spade_bwd_up2 (one per call), the
-# kernel of mrdis_bilinear_fwd / _bwd (one per call), and 'elem_v1': an element-wise pass that took its one-channel-per-thread instantiation.
+# kernel of mrdis_bilinear_fwd / _bwd (one per call), and 'elem_v1': an element-wise pass that took its one-channel-per-thread instantiation (also, once per call, the chatt / symdiff / rgate
+# entry points of csrc/mrdis_outdec.hip in their scalar forms; tests/test_gpu_attn_paths.py).
 # Outside KERNEL_FAMILIES for the same reason as the tables above (tests/test_gpu_elem_paths.py covers them).
 ELEM_FAMILIES = ('stat_vec', 'stat_scalar', 'stat_interp', 'spade_up2_onepass', 'spade_up2_twopass', 'bil_fwd_x2', 'bil_fwd_general',
                  'bil_bwd_x2', 'bil_bwd_tight3', 'bil_bwd_tight5', 'bil_bwd_general', 'elem_v1')
