@@ -26,7 +26,9 @@ from .trainer import (TrainStep, GraphedTrainStep, make_train_step, regular_mask
 from .model3d import BasicBlock, VAEBranch, UNet3D, NVNet3D, HipConv3d, nvnet_loss, nvnet_loss_hip, seg_metrics, seg_metrics_from_counts, window_offsets, predict_volumes   # noqa: F401
 from .data import VolumeStore, SliceDataset, BatchLoader, load_idx_list   # noqa: F401
 from .data3d import VolumeStore3D, VolumeDataset3D, VolumeLoader3D, VolumeData3D, load_subj_list   # noqa: F401
-from . import patch3d   # noqa: F401,E402
+from . import patch3d, warp3d   # noqa: F401,E402
+# warp3d imports patch3d, never the reverse; its three functions are reached through patch3d as well, bound here once both are loaded
+patch3d.patch_warp, patch3d.warp_matrix, patch3d.pack_warp = warp3d.patch_warp, warp3d.warp_matrix, warp3d.pack_warp
 from .patch3d import fg_block_counts, fg_prefix, patch_origins, patch_gather, patch_warp, warp_matrix   # noqa: F401,E402
 from .synth import synthesize_volumes, synth_plan, synth_source, synth_targets, SYNTH_BLOCKS   # noqa: F401,E402
 from . import synth   # noqa: F401,E402

@@ -35,37 +35,16 @@ namespace {
 constexpr int WP_FLAG = MRDIS_PATCH_WARP_FLAG;
 constexpr int WP_AMAX = 1 << 18;            // |a[r][c]| on the device: 4.0 in Q16 (the host makes at most 2.0: zoom >= 0.5)
 
-struct WpGeom { int M, C, H, W, D, PH, PW, PD, N, relabel; };
-struct WpBrick { int lbh, lbw, lbd, nbw, nbd; };          // log2 of the brick extents; bricks along w and d
+struct WpBrick { int lbh, lbw, lbd, nbw, nbd, S; };       // log2 of the brick extents; bricks along w and d; the tile's row stride
 
-struct WpItem { int o[3]; bool fh, fw, fd, aug, warp; int a[9]; };
+// a patch (VgItem: the clamped origin and the flips), whether it is resampled, and its matrix
+struct WpItem : VgItem { bool warp; int a[9]; };
 // the eight corner offsets (bit 2: h + 1, bit 1: w + 1, bit 0: d + 1), the nearest voxel's offset and the three weights
 struct WpSrc { long long c[8]; long long n; float th, tw, td; };
 
-__device__ __forceinline__ int wp_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 __device__ __forceinline__ int wp_clamp64(long long v, int hi) { return v < 0 ? 0 : (v > hi ? hi : (int)v); }
 
-__device__ __forceinline__ WpItem wp_item(const unsigned long long* row, const int* __restrict__ origins, int b, const WpGeom& g) {
-    const unsigned flags = (unsigned)row[2 * g.M + 1];
-    WpItem it;
-    it.o[0] = wp_clamp(origins[4 * b], g.H - g.PH); it.o[1] = wp_clamp(origins[4 * b + 1], g.W - g.PW); it.o[2] = wp_clamp(origins[4 * b + 2], g.D - g.PD);
-    it.fh = flags & 1u; it.aug = flags & 2u; it.fw = flags & 4u; it.fd = flags & 8u; it.warp = flags & (unsigned)WP_FLAG;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) {
-        const unsigned long long w = row[2 * g.M + 7 + (e >> 1)];
-        const int v = (int)(unsigned)((e & 1) ? (w >> 32) : (w & 0xffffffffull));
-        it.a[e] = v < -WP_AMAX ? -WP_AMAX : (v > WP_AMAX ? WP_AMAX : v);
-    }
-    return it;
-}
-
-// the source of output voxel (i, j, k) of a sample without the warp bit: pt_src of mrdis_patch.hip
-__device__ __forceinline__ long long wp_copy_src(int i, int j, int k, const WpGeom& g, const WpItem& it) {
-    const int hs = it.o[0] + (it.fh ? g.PH - 1 - i : i), ws = it.o[1] + (it.fw ? g.PW - 1 - j : j), ds = it.o[2] + (it.fd ? g.PD - 1 - k : k);
-    return ((long long)hs * g.W + ws) * g.D + ds;
-}
-
-__device__ __forceinline__ WpSrc wp_src(int i, int j, int k, const WpGeom& g, const WpItem& it) {
+__device__ __forceinline__ WpSrc wp_src(int i, int j, int k, const VgGeom& g, const WpItem& it) {
     const int P[3] = {g.PH, g.PW, g.PD}, dim[3] = {g.H, g.W, g.D};
     const int op[3] = {it.fh ? g.PH - 1 - i : i, it.fw ? g.PW - 1 - j : j, it.fd ? g.PD - 1 - k : k};
     long long t[3];
@@ -119,61 +98,66 @@ __device__ __forceinline__ float wp_input(WpVals v, const WpSrc& src, bool aug, 
     const float xs = x * scale;
     return xs + shift;
 }
+__device__ __forceinline__ float wp_row_input(const VgRow& r, int m, const WpSrc& src) {
+    return wp_input(wp_fetch(reinterpret_cast<const float*>(r.w[m]), src), src, r.aug, r.scale, r.shift, r.m0);
+}
+
+// The position-to-source policy of this entry point (mrdis_volgather.h): VgPatch's box, a row with the warp bit resampled.  The matrix
+// entries are clamped as the origins are.
+struct WpWarp : VgPatch {
+    typedef WpItem Item;
+    __device__ __forceinline__ Item item(const VgRow& r, int b, const VgGeom& g) const {
+        Item it;
+        static_cast<VgItem&>(it) = VgPatch::item(r, b, g);
+        it.warp = r.flags & (unsigned)WP_FLAG;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) {
+            const unsigned long long w = r.w[2 * g.M + 7 + (e >> 1)];
+            const int v = (int)(unsigned)((e & 1) ? (w >> 32) : (w & 0xffffffffull));
+            it.a[e] = v < -WP_AMAX ? -WP_AMAX : (v > WP_AMAX ? WP_AMAX : v);
+        }
+        return it;
+    }
+    template <int MODE>
+    static __device__ __forceinline__ float value(const VgRow& r, const Item& it, int i, int j, int k, int c, const VgGeom& g, int K) {
+        if (!it.warp) return VgCopy::value<MODE>(r, it, i, j, k, c, g, K);
+        const WpSrc src = wp_src(i, j, k, g, it);
+        if (MODE == 0) return wp_row_input(r, c, src);
+        return vg_target(vg_label(r.seg, src.n, g.relabel), c, K);
+    }
+};
 
 // MODE 0: inputs (C = M), MODE 1: targets (C = max(K, 1)).  grid (bricks, B), 256 threads; (PD C) % 4 == 0, out 16-byte aligned.
 // CM = 4: M == 4 (the BraTS set) with the 36 loads of a position issued together; CM = 0: M at run time.
 template <int MODE, int CM>
-__global__ __launch_bounds__(256) void patchwarp_tile_kernel(const unsigned long long* __restrict__ table, int ld, const int* __restrict__ origins,
-                                                             float* __restrict__ out, float* __restrict__ mask, WpGeom g, int K, WpBrick br, int S) {
+__global__ __launch_bounds__(256) void patchwarp_tile_kernel(const unsigned long long* __restrict__ table, int ld, WpWarp pol, float* __restrict__ out,
+                                                             float* __restrict__ mask, VgGeom g, int K, WpBrick br) {
     __shared__ float tile[VG_LDS_FLOATS];
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int BD = 1 << br.lbd, BW = 1 << br.lbw, P = 1 << (br.lbh + br.lbw + br.lbd);
+    const int BD = 1 << br.lbd, BW = 1 << br.lbw, P = 1 << (br.lbh + br.lbw + br.lbd), S = br.S;
     // the brick of this workgroup: d fastest
     const int xd = blockIdx.x % br.nbd, xq = blockIdx.x / br.nbd;
     const int i0 = (xq / br.nbw) << br.lbh, j0 = (xq % br.nbw) << br.lbw, k0 = xd << br.lbd;
-    const unsigned long long* row = table + (long long)b * ld;
-    const WpItem it = wp_item(row, origins, b, g);
-    if (MODE == 0) {
-        const float scale = __uint_as_float((unsigned)(row[2 * g.M + 2] & 0xffffffffull)), shift = __uint_as_float((unsigned)(row[2 * g.M + 2] >> 32));
-        const float m0 = it.aug ? vg_item_min(row, g.M) : 0.f;
-        if (mask != nullptr && blockIdx.x == 0 && tid < g.M) mask[b * g.M + tid] = row[tid] != 0ull ? 1.f : 0.f;
-        for (int q = tid; q < P; q += 256) {
-            const int i = i0 + (q >> (br.lbd + br.lbw)), j = j0 + ((q >> br.lbd) & (BW - 1)), k = k0 + (q & (BD - 1));
-            if (i >= g.PH || j >= g.PW || k >= g.PD) continue;
-            if (it.warp) {
-                const WpSrc src = wp_src(i, j, k, g, it);
-                if (CM > 0) {
-                    WpVals v[CM > 0 ? CM : 1];
+    WpItem it;
+    const VgRow r = vg_row<MODE>(table, ld, b, g, mask, pol, &it);
+    for (int q = tid; q < P; q += 256) {
+        const int i = i0 + (q >> (br.lbd + br.lbw)), j = j0 + ((q >> br.lbd) & (BW - 1)), k = k0 + (q & (BD - 1));
+        if (i >= g.PH || j >= g.PW || k >= g.PD) continue;
+        if (MODE == 1) {
+            vg_fill_targets(tile + q, S, r, it.warp ? wp_src(i, j, k, g, it).n : vg_copy_src(i, j, k, g, it), g, K);
+        } else if (!it.warp) {
+            vg_fill_inputs<CM>(tile + q, S, r, vg_copy_src(i, j, k, g, it), g.M);
+        } else {
+            const WpSrc src = wp_src(i, j, k, g, it);
+            if (CM > 0) {
+                WpVals v[CM > 0 ? CM : 1];
 #pragma unroll
-                    for (int m = 0; m < CM; ++m) v[m] = wp_fetch(reinterpret_cast<const float*>(row[m]), src);
+                for (int m = 0; m < CM; ++m) v[m] = wp_fetch(reinterpret_cast<const float*>(r.w[m]), src);
 #pragma unroll
-                    for (int m = 0; m < CM; ++m) tile[m * S + q] = wp_input(v[m], src, it.aug, scale, shift, m0);
-                } else {
-                    for (int m = 0; m < g.M; ++m)
-                        tile[m * S + q] = wp_input(wp_fetch(reinterpret_cast<const float*>(row[m]), src), src, it.aug, scale, shift, m0);
-                }
+                for (int m = 0; m < CM; ++m) tile[m * S + q] = wp_input(v[m], src, r.aug, r.scale, r.shift, r.m0);
             } else {
-                const long long src = wp_copy_src(i, j, k, g, it);
-                if (CM > 0) {
-                    float v[CM > 0 ? CM : 1];
-#pragma unroll
-                    for (int m = 0; m < CM; ++m) v[m] = vg_input(reinterpret_cast<const float*>(row[m]), src, it.aug, scale, shift, m0);
-#pragma unroll
-                    for (int m = 0; m < CM; ++m) tile[m * S + q] = v[m];
-                } else {
-                    for (int m = 0; m < g.M; ++m)
-                        tile[m * S + q] = vg_input(reinterpret_cast<const float*>(row[m]), src, it.aug, scale, shift, m0);
-                }
+                for (int m = 0; m < g.M; ++m) tile[m * S + q] = wp_row_input(r, m, src);
             }
-        }
-    } else {
-        const float* seg = reinterpret_cast<const float*>(row[2 * g.M]);
-        for (int q = tid; q < P; q += 256) {
-            const int i = i0 + (q >> (br.lbd + br.lbw)), j = j0 + ((q >> br.lbd) & (BW - 1)), k = k0 + (q & (BD - 1));
-            if (i >= g.PH || j >= g.PW || k >= g.PD) continue;
-            const long long src = it.warp ? wp_src(i, j, k, g, it).n : wp_copy_src(i, j, k, g, it);
-            const float t = vg_label(seg, src, g.relabel);
-            for (int c = 0; c < g.C; ++c) tile[c * S + q] = vg_target(t, c, K);
         }
     }
     __syncthreads();
@@ -183,38 +167,10 @@ __global__ __launch_bounds__(256) void patchwarp_tile_kernel(const unsigned long
     const int kn = g.PD - k0 < BD ? g.PD - k0 : BD;
     const int rsub = tid / tpr, lane = tid - rsub * tpr;
     if (rsub < rpp) {
-        for (int r = rsub; r < rows; r += rpp) {
-            const int i = i0 + (r >> br.lbw), j = j0 + (r & (BW - 1));
+        for (int rw = rsub; rw < rows; rw += rpp) {
+            const int i = i0 + (rw >> br.lbw), j = j0 + (rw & (BW - 1));
             if (i < g.PH && j < g.PW)
-                vg_store_tile(tile + (r << br.lbd), out + ((long long)b * g.N + ((long long)i * g.PW + j) * g.PD + k0) * g.C, kn, g.C, S, lane);
-        }
-    }
-}
-
-// every geometry: one thread per output float.  grid (x, B), grid-stride over the N C floats of a sample.
-template <int MODE>
-__global__ __launch_bounds__(256) void patchwarp_elem_kernel(const unsigned long long* __restrict__ table, int ld, const int* __restrict__ origins,
-                                                             float* __restrict__ out, float* __restrict__ mask, WpGeom g, int K) {
-    const int b = blockIdx.y;
-    const unsigned long long* row = table + (long long)b * ld;
-    const WpItem it = wp_item(row, origins, b, g);
-    const float scale = __uint_as_float((unsigned)(row[2 * g.M + 2] & 0xffffffffull)), shift = __uint_as_float((unsigned)(row[2 * g.M + 2] >> 32));
-    const float m0 = (MODE == 0 && it.aug) ? vg_item_min(row, g.M) : 0.f;
-    if (MODE == 0 && mask != nullptr && blockIdx.x == 0 && (int)threadIdx.x < g.M) mask[b * g.M + threadIdx.x] = row[threadIdx.x] != 0ull ? 1.f : 0.f;
-    const long long total = (long long)g.N * g.C;
-    float* dst = out + (long long)b * total;
-    for (long long e = blockIdx.x * 256LL + threadIdx.x; e < total; e += gridDim.x * 256LL) {
-        const int p = (int)(e / g.C), c = (int)(e - (long long)p * g.C);
-        const int q = p / g.PD, k = p - q * g.PD;
-        const int i = q / g.PW, j = q - i * g.PW;
-        if (it.warp) {
-            const WpSrc src = wp_src(i, j, k, g, it);
-            if (MODE == 0) dst[e] = wp_input(wp_fetch(reinterpret_cast<const float*>(row[c]), src), src, it.aug, scale, shift, m0);
-            else dst[e] = vg_target(vg_label(reinterpret_cast<const float*>(row[2 * g.M]), src.n, g.relabel), c, K);
-        } else {
-            const long long src = wp_copy_src(i, j, k, g, it);
-            if (MODE == 0) dst[e] = vg_input(reinterpret_cast<const float*>(row[c]), src, it.aug, scale, shift, m0);
-            else dst[e] = vg_target(vg_label(reinterpret_cast<const float*>(row[2 * g.M]), src, g.relabel), c, K);
+                vg_store_tile(tile + (rw << br.lbd), out + ((long long)b * g.N + ((long long)i * g.PW + j) * g.PD + k0) * g.C, kn, g.C, S, lane);
         }
     }
 }
@@ -224,52 +180,34 @@ int wp_log2(int v) { int l = 0; while ((2 << l) <= v) ++l; return l; }
 // the brick and the tile stride for C channels: P = 1024 positions at C <= 8, 512 at C <= 16, 256 at C <= 32 (powers of two within
 // vg_tile_shape's P, with its padding); rows of 16 positions along d, longer ones under four channels while the patch is that deep, so that a
 // row of the output stays 256 bytes or more; the (h, w) extents as square as powers of two get
-void wp_brick(const WpGeom& g, WpBrick* br, int* S) {
-    int P, S0;
-    vg_tile_shape(g.C, &P, &S0);
-    const int pad = S0 - P;
-    P = 1 << wp_log2(P);
+WpBrick wp_brick(const VgGeom& g) {
+    const VgFlat flat = vg_tile_shape(g.C);
+    const int P = 1 << wp_log2(flat.P);
     int lbd = 4;
     if (g.C < 4) while (lbd < 6 && (1 << lbd) < g.PD) ++lbd;
     const int lrows = wp_log2(P) - lbd;
-    br->lbd = lbd; br->lbh = lrows / 2; br->lbw = lrows - lrows / 2;
-    br->nbw = mrdis_cdiv(g.PW, 1 << br->lbw); br->nbd = mrdis_cdiv(g.PD, 1 << lbd);
-    *S = P + pad;
-}
-
-template <int MODE>
-int launch_patchwarp(const unsigned long long* table, int ld, const int* origins, float* out, float* mask, const WpGeom& g, int K, int B, hipStream_t s) {
-    const long long total = (long long)g.N * g.C;
-    // a brick row is (PD - k0) C floats with k0 % 16 == 0: whole 16-byte stores need (PD C) % 4 == 0 (which implies (N C) % 4 == 0)
-    const bool tiled = !mrdis_opt(MRDIS_OPT_VOLGEN) && g.C <= VG_MAXC_TILE && (((long long)g.PD * g.C) & 3) == 0 && (((uintptr_t)out) & 15) == 0;
-    mrdis_count(MRDIS_CNT_PATCHWARP);
-    if (tiled) {
-        WpBrick br;
-        int S;
-        wp_brick(g, &br, &S);
-        const long long bricks = (long long)mrdis_cdiv(g.PH, 1 << br.lbh) * br.nbw * br.nbd;
-        if (MODE == 0 && g.M == 4)
-            MRDIS_LAUNCH((patchwarp_tile_kernel<MODE, 4>), dim3((unsigned)bricks, B), dim3(256), 0, s, table, ld, origins, out, mask, g, K, br, S);
-        else
-            MRDIS_LAUNCH((patchwarp_tile_kernel<MODE, 0>), dim3((unsigned)bricks, B), dim3(256), 0, s, table, ld, origins, out, mask, g, K, br, S);
-    } else {
-        long long gx = (total + 255) / 256; if (gx > 4096) gx = 4096;
-        MRDIS_LAUNCH((patchwarp_elem_kernel<MODE>), dim3((unsigned)gx, B), dim3(256), 0, s, table, ld, origins, out, mask, g, K);
-    }
-    MRDIS_CHECK_LAUNCH();
-    return MRDIS_OK;
+    WpBrick br;
+    br.lbd = lbd; br.lbh = lrows / 2; br.lbw = lrows - lrows / 2;
+    br.nbw = mrdis_cdiv(g.PW, 1 << br.lbw); br.nbd = mrdis_cdiv(g.PD, 1 << lbd);
+    br.S = P + (flat.S - flat.P);
+    return br;
 }
 }  // namespace
 
 extern "C" int mrdis_patch_warp(const void* table, int ld_table, const int* origins, float* out, float* mask, int B, int M, int H, int W, int D,
                                 int PH, int PW, int PD, int mode, int K, int relabel, void* stream) {
-    const bool geometry = H >= 1 && W >= 1 && D >= 1 && PH >= 1 && PW >= 1 && PD >= 1 && PH <= H && PW <= W && PD <= D;
-    if (!table || !origins || !out || B < 1 || M < 1 || M > 64 || !geometry || ld_table < 2 * M + 12 || (mode != 0 && mode != 1) || K < 0 || K > 64 ||
-        (mode == 0 && K != 0)) return MRDIS_EINVAL;
-    if (B > 65535 || (long long)H * W * D >= (1LL << 31)) return MRDIS_EUNSUPPORTED;
-    WpGeom g;
-    g.M = M; g.C = mode == 0 ? M : (K > 0 ? K : 1); g.H = H; g.W = W; g.D = D; g.PH = PH; g.PW = PW; g.PD = PD; g.N = PH * PW * PD; g.relabel = relabel;
+    VgGeom g;
+    const int rc = vg_check(origins != nullptr, table, out, ld_table, 12, B, M, H, W, D, PH, PW, PD, mode, K, relabel, &g);
+    if (rc != MRDIS_OK) return rc;
+    WpWarp pol;
+    pol.origins = origins;
     const unsigned long long* t = reinterpret_cast<const unsigned long long*>(table);
-    return mode == 0 ? launch_patchwarp<0>(t, ld_table, origins, out, mask, g, 0, B, (hipStream_t)stream)
-                     : launch_patchwarp<1>(t, ld_table, origins, out, nullptr, g, K, B, (hipStream_t)stream);
+    const WpBrick br = wp_brick(g);
+    const unsigned bricks = (unsigned)((long long)mrdis_cdiv(g.PH, 1 << br.lbh) * br.nbw * br.nbd);
+    // a brick row is (PD - k0) C floats with k0 % 16 == 0: whole 16-byte stores need (PD C) % 4 == 0 (which implies (N C) % 4 == 0)
+    const bool whole = (((long long)g.PD * g.C) & 3) == 0;
+    return mode == 0 ? vg_launch<0>(MRDIS_CNT_PATCHWARP, whole, bricks, patchwarp_tile_kernel<0, 4>, patchwarp_tile_kernel<0, 0>, br, t, ld_table, pol, out, mask, g, 0, B,
+                                    (hipStream_t)stream)
+                     : vg_launch<1>(MRDIS_CNT_PATCHWARP, whole, bricks, patchwarp_tile_kernel<1, 0>, patchwarp_tile_kernel<1, 0>, br, t, ld_table, pol, out, nullptr, g, K, B,
+                                    (hipStream_t)stream);
 }

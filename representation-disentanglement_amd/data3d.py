@@ -255,27 +255,31 @@ class VolumeLoader3D(BatchLoader):
         if patch_size is not None:
             dataset.set_patch(patch_size, patch_fg, patch_flips, patch_centre, patch_warp, patch_rot, patch_zoom)
 
-    def table(self, metas, plain=False):
-        """the per-batch table of mrdis_volume_gather (include/mrdis.h), on the host, and the host twin of `mask`.  `plain`: the augment bit stays
-        clear whatever the dataset says, and no crop minima are looked up (only the augmentation reads them; they belong to the crop's own z0)."""
+    def _table_head(self, metas, width, crop, aug):
+        """(B, width) int64 with the 2 M + 3 words every gather reads (include/mrdis.h mrdis_volume_gather) filled in and zeros beyond, and the
+        host twin of `mask`.  `crop`: the (z0, Dz) whose minima the rows point to, None: no minima; the flag word gets the H flip and `aug`."""
         ds, st = self.dataset, self.dataset.store
         M = len(ds.contrast_list)
-        z0, Dz = ds.crop()
-        aug = ds.aug and not plain
-        B = len(metas)
-        tab = np.zeros((B, 2 * M + 3), dtype=np.int64)
-        mask_host = np.zeros((B, M), dtype=np.float32)                 # host twin of `mask`: a loss may branch on it without a sync
-        for r, (subj_id, _, ptrs, drop, tptr, flip, scale, shift) in enumerate(metas):
+        tab = np.zeros((len(metas), width), dtype=np.int64)
+        mask_host = np.zeros((len(metas), M), dtype=np.float32)        # host twin of `mask`: a loss may branch on it without a sync
+        for r, (subj_id, _, ptrs, drop, tptr, flip, scale, shift, *_) in enumerate(metas):
             for m, p in enumerate(ptrs):
                 if p and m != drop:
                     tab[r, m] = p
-                    tab[r, M + m] = st.crop_min_ptr(subj_id + '/' + ds.contrast_list[m], z0, Dz) if not plain else 0
+                    tab[r, M + m] = st.crop_min_ptr(subj_id + '/' + ds.contrast_list[m], *crop) if crop is not None else 0
                     mask_host[r, m] = 1.0
             tab[r, 2 * M] = tptr
-            tab[r, 2 * M + 1] = (1 if flip else 0) | (2 if aug else 0)
+            tab[r, 2 * M + 1] = (patch3d.FLIP_H if flip else 0) | (patch3d.AUG if aug else 0)
             bits = np.array([scale, shift], dtype=np.float32).view(np.uint32).astype(np.uint64)
             tab[r, 2 * M + 2] = (bits[0] | (bits[1] << np.uint64(32))).view(np.int64)
         return tab, mask_host
+
+    def table(self, metas, plain=False):
+        """the per-batch table of mrdis_volume_gather (include/mrdis.h), on the host, and the host twin of `mask`.  `plain`: the augment bit stays
+        clear whatever the dataset says, and no crop minima are looked up (only the augmentation reads them; they belong to the crop's own z0)."""
+        ds = self.dataset
+        crop = ds.crop()
+        return self._table_head(metas, 2 * len(ds.contrast_list) + 3, None if plain else crop, ds.aug and not plain)
 
     def patch_table(self, metas):
         """the per-batch table of mrdis_patch_origins / mrdis_patch_gather (include/mrdis.h: the words of `table`, the minima those of the whole
@@ -284,24 +288,13 @@ class VolumeLoader3D(BatchLoader):
         a warp, zeros for the others."""
         ds, st = self.dataset, self.dataset.store
         M = len(ds.contrast_list)
-        D = st.shape[2]
         classes = ds.FG_CLASSES.get(ds.dataset_name, ())
-        B = len(metas)
-        tab = np.zeros((B, 2 * M + patch3d.TABLE_EXTRA + (patch3d.WARP_EXTRA if ds.warps() else 0)), dtype=np.int64)
-        mask_host = np.zeros((B, M), dtype=np.float32)
-        for r, (subj_id, _, ptrs, drop, tptr, _, scale, shift, (fg, u, flips, centre, *warp)) in enumerate(metas):
-            for m, p in enumerate(ptrs):
-                if p and m != drop:
-                    tab[r, m] = p
-                    tab[r, M + m] = st.crop_min_ptr(subj_id + '/' + ds.contrast_list[m], 0, D)
-                    mask_host[r, m] = 1.0
-            tab[r, 2 * M] = tptr
+        tab, mask_host = self._table_head(metas, 2 * M + patch3d.TABLE_EXTRA + (patch3d.WARP_EXTRA if ds.warps() else 0), (0, st.shape[2]), ds.aug)
+        for r, (subj_id, _, _, _, tptr, _, _, _, (fg, u, flips, centre, *warp)) in enumerate(metas):
             flags = (patch3d.AUG if ds.aug else 0) | (patch3d.FG if fg else 0) | (patch3d.CENTRE if centre else 0)
             for axis, on in zip('hwd', flips):
                 flags |= patch3d.FLIP_BITS[axis] if on else 0
             tab[r, 2 * M + 1] = flags
-            bits = np.array([scale, shift], dtype=np.float32).view(np.uint32).astype(np.uint64)
-            tab[r, 2 * M + 2] = (bits[0] | (bits[1] << np.uint64(32))).view(np.int64)
             if fg and tptr:
                 tab[r, 2 * M + 3] = st.fg_prefix_ptr(subj_id + ds.TARGET_KEYS[ds.dataset_name], classes)
             w = np.asarray(u, dtype=np.uint32).astype(np.uint64)
@@ -333,22 +326,29 @@ class VolumeLoader3D(BatchLoader):
         table = batch['table']
         return table[:, (table.shape[1] - 3)].contiguous()
 
+    def _upload(self, tab):
+        dev = self.dataset.store.device
+        host = torch.from_numpy(tab)
+        if dev.type == 'cuda':
+            host = host.pin_memory()
+        return host.to(dev, non_blocking=True)                        # one small H2D copy per batch
+
+    def _sample(self, k, metas, mask_host, gather):
+        """the sample dict of a batch: `gather()` -> inputs and mask, `gather(targets=True, K=, relabel=)` -> targets; one launch each"""
+        inputs, mask = gather()
+        targets = gather(targets=True, K=self.region_channels, relabel=self.dataset.dataset_name == 'BraTS')
+        return {'inputs': inputs, 'targets': targets, 'subj_id': [m[0] for m in metas],
+                'slice_idx': torch.zeros(len(metas), dtype=torch.int64, device=self.dataset.store.device), 'mask': mask, 'mask_host': mask_host,
+                'batch_index': k}
+
     def _gather(self, k, metas, z0, plain):
         ds, st = self.dataset, self.dataset.store
         H, W, D = st.shape
         M = len(ds.contrast_list)
         Dz = ds.crop()[1]
-        dev = st.device
         tab, mask_host = self.table(metas, plain=plain)
-        host = torch.from_numpy(tab)
-        if dev.type == 'cuda':
-            host = host.pin_memory()
-        d = host.to(dev, non_blocking=True)                           # one small H2D copy per batch
-        inputs, mask = hip.volume_gather(d, M, H, W, D, z0, Dz)
-        targets = hip.volume_gather(d, M, H, W, D, z0, Dz, targets=True, K=self.region_channels, relabel=ds.dataset_name == 'BraTS')
-        batch = {'inputs': inputs, 'targets': targets, 'subj_id': [m[0] for m in metas],
-                 'slice_idx': torch.zeros(len(metas), dtype=torch.int64, device=dev), 'mask': mask, 'mask_host': mask_host,
-                 'batch_index': k}
+        d = self._upload(tab)
+        batch = self._sample(k, metas, mask_host, lambda **kw: hip.volume_gather(d, M, H, W, D, z0, Dz, **kw))
         if plain:
             batch['table'] = d                                        # windowed reads only: `target_ptrs` reads the label-volume addresses from it
         return batch
@@ -356,20 +356,14 @@ class VolumeLoader3D(BatchLoader):
     def _gather_patch(self, k, metas):
         ds, st = self.dataset, self.dataset.store
         M = len(ds.contrast_list)
-        dev = st.device
         tab, mask_host = self.patch_table(metas)
-        host = torch.from_numpy(tab)
-        if dev.type == 'cuda':
-            host = host.pin_memory()
-        d = host.to(dev, non_blocking=True)                           # one small H2D copy per batch
+        d = self._upload(tab)
         classes = ds.FG_CLASSES.get(ds.dataset_name, ()) if ds.patch_fg > 0 else ()
         origins = patch3d.patch_origins(d, M, st.shape, ds.patch_size, classes)
         gather = patch3d.patch_warp if ds.warps() else patch3d.patch_gather
-        inputs, mask = gather(d, origins, M, st.shape, ds.patch_size)
-        targets = gather(d, origins, M, st.shape, ds.patch_size, targets=True, K=self.region_channels, relabel=ds.dataset_name == 'BraTS')
-        return {'inputs': inputs, 'targets': targets, 'subj_id': [m[0] for m in metas],
-                'slice_idx': torch.zeros(len(metas), dtype=torch.int64, device=dev), 'mask': mask, 'mask_host': mask_host,
-                'batch_index': k, 'origins': origins}
+        batch = self._sample(k, metas, mask_host, lambda **kw: gather(d, origins, M, st.shape, ds.patch_size, **kw))
+        batch['origins'] = origins
+        return batch
 
     def window(self, k, metas, z0, flip=False):
         """one batch of `plain_plan` at depth offset z0 (same Dz as the crop), every item as stored, H-flipped by the gather itself if `flip`:

@@ -236,7 +236,7 @@ DATA_FAMILIES = ('volgather',)
 # subject), per mrdis_patch_origins call (one per batch) and per mrdis_patch_gather call (two per batch: inputs and targets).
 PATCH_FAMILIES = ('fgcount', 'patchorigin', 'patchgather')
 PATCH_MAX_CLASSES = 8             # include/mrdis.h MRDIS_PATCH_MAX_CLASSES
-# rotated and zoomed training patches (csrc/mrdis_warp.hip; the wrapper lives in patch3d.py): one count, and one launch, per mrdis_patch_warp call
+# rotated and zoomed training patches (csrc/mrdis_warp.hip; the wrapper lives in warp3d.py): one count, and one launch, per mrdis_patch_warp call
 # (two per batch of a loader with patch_warp > 0, in place of the two 'patchgather').
 WARP_FAMILIES = ('patchwarp',)
 # the fused objective of the 3-D nets and the segmentation counts (csrc/mrdis_loss3d.hip): 'loss3d' counts one per mrdis_nvnet_loss_fwd and one per
@@ -1276,14 +1276,24 @@ def volume_gather(table, M, H, W, D, z0, Dz, targets=False, K=0, relabel=False):
     lib = load()
     B, ld = _want(table, 'volume_gather: table', torch.int64, ('B', 'ld'))
     if ld < 2 * M + 3: _refuse(f'volume_gather: table rows of at least 2 M + 3 = {2 * M + 3} words', 'vec', table)
+    return _gather3d(lib.mrdis_volume_gather, 'volume_gather', table, None, M, (H, W, D), (H, W, Dz), (z0, Dz), targets, K, relabel)
+
+
+def _gather3d(entry, what, table, origins, M, vol, box, box_args, targets, K, relabel):
+    """the call of the three gathers of the 3-D store -- volume_gather, patch3d.patch_gather, warp3d.patch_warp -- whose caller has checked
+    every argument: `entry` on table (B, ld) (and origins, where the entry point takes them), the stored volumes `vol` = (H, W, D), the
+    output `box` of a sample, `box_args` the integers the entry point takes for it -> inputs (B, M, *box) channels-last-3d and mask (B, M),
+    or with `targets` the labels (B, *box) / their K region channels (B, K, *box) channels-last-3d.  One launch."""
+    B, ld = table.shape
     dev = table.device
+    head = (_ptr(table), ld) + (() if origins is None else (_ptr(origins),))
     if not targets:
-        out = torch.empty((B, H, W, Dz, M), dtype=torch.float32, device=dev)
+        out = torch.empty((B, *box, M), dtype=torch.float32, device=dev)
         mask = torch.empty((B, M), dtype=torch.float32, device=dev)
-        _chk(lib.mrdis_volume_gather(_ptr(table), ld, _ptr(out), _ptr(mask), B, M, H, W, D, z0, Dz, 0, 0, 0, _stream()), 'volume_gather')
+        _chk(entry(*head, _ptr(out), _ptr(mask), B, M, *vol, *box_args, 0, 0, 0, _stream()), what)
         return out.permute(0, 4, 1, 2, 3), mask
-    out = torch.empty((B, H, W, Dz, K) if K else (B, H, W, Dz), dtype=torch.float32, device=dev)
-    _chk(lib.mrdis_volume_gather(_ptr(table), ld, _ptr(out), None, B, M, H, W, D, z0, Dz, 1, K, int(bool(relabel)), _stream()), 'volume_gather')
+    out = torch.empty((B, *box, K) if K else (B, *box), dtype=torch.float32, device=dev)
+    _chk(entry(*head, _ptr(out), None, B, M, *vol, *box_args, 1, K, int(bool(relabel)), _stream()), what)
     return out.permute(0, 4, 1, 2, 3) if K else out
 
 

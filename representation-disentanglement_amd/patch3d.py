@@ -17,8 +17,8 @@ on a tumour voxel.  THIS PACKAGE'S CONVENTIONS -- the reference trains on one fi
 The table is data3d.VolumeLoader3D.patch_table's: one row of 2 M + TABLE_EXTRA 64-bit words per sample (include/mrdis.h).  Every draw comes
 from it, so the three launches of a batch replay from a captured graph with the next batch's table.
 
-Rotation and zoom of the patches (`patch_warp`, `warp_matrix`; rows WARP_EXTRA words longer, flag WARP): warp3d.py, whose docstring has the
-conventions.
+Rotation and zoom of the patches (`patch_warp`, `warp_matrix`, `pack_warp`; rows WARP_EXTRA words longer, flag WARP): warp3d.py, whose
+docstring has the conventions.  warp3d imports this module for its checks; the package binds its three functions here under their names.
 """
 import torch
 
@@ -59,11 +59,22 @@ def _geometry(what, M, shape, patch):
     return M, H, W, D, PH, PW, PD
 
 
-def _table(table, what, M):
+def _table(table, what, M, extra=TABLE_EXTRA):
     B, ld = hip._want(table, f'{what}: table', torch.int64, ('B', 'ld'))
-    if ld < 2 * M + TABLE_EXTRA: hip._refuse(f'{what}: table rows of at least 2 M + {TABLE_EXTRA} = {2 * M + TABLE_EXTRA} words', 'vec', table)
+    if ld < 2 * M + extra: hip._refuse(f'{what}: table rows of at least 2 M + {extra} = {2 * M + extra} words', 'vec', table)
     if not 1 <= B <= 65535: hip._refuse(f'{what}: 1 .. 65535 samples', 'arg', table)
     return B, ld
+
+
+def _gather(entry, what, extra, table, origins, M, shape, patch, targets, K, relabel):
+    """`patch_gather` and warp3d.patch_warp: every check of a gather over rows of 2 M + `extra` words, then the call (hip._gather3d)"""
+    M, H, W, D, PH, PW, PD = _geometry(what, M, shape, patch)
+    B, ld = _table(table, what, M, extra)
+    hip._want(origins, f'{what}: origins', torch.int32, (B, 4), table.device)
+    if not targets:
+        if K: hip._refuse(f'{what}: K = 0 for the inputs', 'arg', K)
+    elif isinstance(K, bool) or not isinstance(K, int) or not 0 <= K <= 64: hip._refuse(f'{what}: K region channels in 0 .. 64', 'arg', K)
+    return hip._gather3d(entry, what, table, origins, M, (H, W, D), (PH, PW, PD), (PH, PW, PD), targets, K, relabel)
 
 
 def fg_block_counts(seg, classes):
@@ -104,24 +115,4 @@ def patch_origins(table, M, shape, patch, classes=()):
 def patch_gather(table, origins, M, shape, patch, targets=False, K=0, relabel=False):
     """table and origins of `patch_origins` -> inputs (B, M, PH, PW, PD) channels-last-3d and mask (B, M), or with `targets` the label patch
     (B, PH, PW, PD) / its K region channels (B, K, PH, PW, PD) channels-last-3d (include/mrdis.h mrdis_patch_gather).  One launch."""
-    lib = hip.load()
-    M, H, W, D, PH, PW, PD = _geometry('patch_gather', M, shape, patch)
-    B, ld = _table(table, 'patch_gather', M)
-    hip._want(origins, 'patch_gather: origins', torch.int32, (B, 4), table.device)
-    dev = table.device
-    if not targets:
-        if K: hip._refuse('patch_gather: K = 0 for the inputs', 'arg', K)
-        out = torch.empty((B, PH, PW, PD, M), dtype=torch.float32, device=dev)
-        mask = torch.empty((B, M), dtype=torch.float32, device=dev)
-        hip._chk(lib.mrdis_patch_gather(hip._ptr(table), ld, hip._ptr(origins), hip._ptr(out), hip._ptr(mask), B, M, H, W, D, PH, PW, PD, 0, 0, 0, hip._stream()), 'patch_gather')
-        return out.permute(0, 4, 1, 2, 3), mask
-    if isinstance(K, bool) or not isinstance(K, int) or not 0 <= K <= 64: hip._refuse('patch_gather: K region channels in 0 .. 64', 'arg', K)
-    out = torch.empty((B, PH, PW, PD, K) if K else (B, PH, PW, PD), dtype=torch.float32, device=dev)
-    hip._chk(lib.mrdis_patch_gather(hip._ptr(table), ld, hip._ptr(origins), hip._ptr(out), None, B, M, H, W, D, PH, PW, PD, 1, K, int(bool(relabel)), hip._stream()),
-             'patch_gather')
-    return out.permute(0, 4, 1, 2, 3) if K else out
-
-
-
-# rotated and zoomed patches (warp3d.py, csrc/mrdis_warp.hip), reached from here as patch3d.patch_warp / patch3d.warp_matrix
-from .warp3d import pack_warp, patch_warp, warp_matrix      # noqa: E402,F401
+    return _gather(hip.load().mrdis_patch_gather, 'patch_gather', TABLE_EXTRA, table, origins, M, shape, patch, targets, K, relabel)

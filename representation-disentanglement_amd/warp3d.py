@@ -22,9 +22,8 @@ patch3d.warp_matrix.  THIS PACKAGE'S CONVENTIONS -- the reference has no spatial
     targets = patch_warp(table, origins, M, (H, W, D), (PH, PW, PD), targets=True, K=3, relabel=True)
 """
 import numpy as np
-import torch
 
-from . import hip
+from . import hip, patch3d
 
 
 def warp_matrix(angles_deg, zoom):
@@ -67,22 +66,4 @@ def patch_warp(table, origins, M, shape, patch, targets=False, K=0, relabel=Fals
     (B, >= 2 M + TABLE_EXTRA + WARP_EXTRA) int64 on the device: the rows of `patch_gather` followed by `pack_warp(warp_matrix(...))`.  Results
     and layouts are patch_gather's: inputs (B, M, PH, PW, PD) channels-last-3d and mask (B, M), or with `targets` the label patch
     (B, PH, PW, PD) / its K region channels (B, K, PH, PW, PD).  Every tensor is checked first: MrdisError before any launch.  One launch."""
-    from . import patch3d as p
-    lib = hip.load()
-    M, H, W, D, PH, PW, PD = p._geometry('patch_warp', M, shape, patch)
-    B, ld = p._table(table, 'patch_warp', M)
-    need = 2 * M + p.TABLE_EXTRA + p.WARP_EXTRA
-    if ld < need: hip._refuse(f'patch_warp: table rows of at least 2 M + {p.TABLE_EXTRA + p.WARP_EXTRA} = {need} words', 'vec', table)
-    hip._want(origins, 'patch_warp: origins', torch.int32, (B, 4), table.device)
-    dev = table.device
-    if not targets:
-        if K: hip._refuse('patch_warp: K = 0 for the inputs', 'arg', K)
-        out = torch.empty((B, PH, PW, PD, M), dtype=torch.float32, device=dev)
-        mask = torch.empty((B, M), dtype=torch.float32, device=dev)
-        hip._chk(lib.mrdis_patch_warp(hip._ptr(table), ld, hip._ptr(origins), hip._ptr(out), hip._ptr(mask), B, M, H, W, D, PH, PW, PD, 0, 0, 0, hip._stream()), 'patch_warp')
-        return out.permute(0, 4, 1, 2, 3), mask
-    if isinstance(K, bool) or not isinstance(K, int) or not 0 <= K <= 64: hip._refuse('patch_warp: K region channels in 0 .. 64', 'arg', K)
-    out = torch.empty((B, PH, PW, PD, K) if K else (B, PH, PW, PD), dtype=torch.float32, device=dev)
-    hip._chk(lib.mrdis_patch_warp(hip._ptr(table), ld, hip._ptr(origins), hip._ptr(out), None, B, M, H, W, D, PH, PW, PD, 1, K, int(bool(relabel)), hip._stream()),
-             'patch_warp')
-    return out.permute(0, 4, 1, 2, 3) if K else out
+    return patch3d._gather(hip.load().mrdis_patch_warp, 'patch_warp', patch3d.TABLE_EXTRA + patch3d.WARP_EXTRA, table, origins, M, shape, patch, targets, K, relabel)

@@ -286,6 +286,49 @@ def test_whole_volume_patch_equals_volume_gather(mrdis):
     assert torch.equal(mrdis.patch3d.patch_gather(tab, far, 4, shape, shape)[0], wx)
 
 
+def test_three_entry_points_agree_bit_for_bit(mrdis):
+    """volume_gather (z0 = 0, Dz = D), patch_gather of the whole volume at origin 0 and patch_warp with the WARP flag clear (its rows carry a
+    matrix all the same) are one gather: the same bits for the inputs, the mask, the label targets and K = 3 region channels, as dispatched
+    and under debug_volgen, one launch of the entry point's own family per call.  (9, 10, 13): 1170 positions, two flat tiles with the second
+    partial at M = 4 (the CM = 4 tile); M = 3 (M at run time) and every target leave no multiple of four floats: the element kernel by itself.
+    Rows: plain, H flip, augmented, both with the second contrast absent."""
+    hip, p = mrdis.hip, mrdis.patch3d
+    shape = H, W, D = (9, 10, 13)
+    vols, seg = _volumes(4, shape, 12)
+    matrix = torch.from_numpy(p.pack_warp(p.warp_matrix((10.0, -20.0, 30.0), 1.2))).to(DEV)
+    origins = torch.zeros((4, 4), dtype=torch.int32, device=DEV)
+    before = hip.get_option('debug_volgen')
+    try:
+        for M in (4, 3):
+            rows = Rows(mrdis, M)
+            for i, (flip, aug) in enumerate(((False, False), (True, False), (False, True), (True, True))):
+                rows.add([v if (i, m) != (3, 1) else None for m, v in enumerate(vols[:M])], seg, flips=(flip, False, False), aug=aug, scale=1.06, shift=-0.03)
+            tab = rows.table()
+            warp_tab = torch.cat([tab, matrix.expand(4, -1)], dim=1).contiguous()
+            assert warp_tab.shape[1] == 2 * M + p.TABLE_EXTRA + p.WARP_EXTRA and not (tab[:, 2 * M + 1] & p.WARP).any()
+            for gen in (0, 1):
+                hip.set_option('debug_volgen', gen)
+                for kw in ({}, dict(targets=True, K=0, relabel=True), dict(targets=True, K=3, relabel=True)):
+                    got = []
+                    for family, call in (('volgather', lambda: hip.volume_gather(tab, M, H, W, D, 0, D, **kw)),
+                                         ('patchgather', lambda: p.patch_gather(tab, origins, M, shape, shape, **kw)),
+                                         ('patchwarp', lambda: p.patch_warp(warp_tab, origins, M, shape, shape, **kw))):
+                        hip.launch_counts(reset=True)
+                        out = call()
+                        c = hip.launch_counts()
+                        assert c[family] == 1 and c['all'] == 1, (family, M, gen, kw, c)
+                        got.append(out if isinstance(out, tuple) else (out,))
+                    for family, other in zip(('patchgather', 'patchwarp'), got[1:]):
+                        assert len(other) == len(got[0]), (family, M, gen, kw)
+                        for a, b in zip(got[0], other):
+                            assert a.shape == b.shape and a.stride() == b.stride() and torch.equal(a.view(torch.int32), b.view(torch.int32)), (family, M, gen, kw)
+                    if not kw:                                         # the rows are what they claim to be: a flip, a marker, an absent contrast
+                        x, mask = got[0]
+                        assert torch.equal(x[1], x[0].flip(1)) and int((x[2] == -10).sum()) > 0 and mask.tolist() == [[1.0] * M] * 3 + [[1.0, 0.0] + [1.0] * (M - 2)]
+    finally:
+        hip.set_option('debug_volgen', before)
+
+
 # ---------------------------------------------------------------- the loader
 CONTRASTS = ['T1', 'T1c', 'T2', 'T2_FLAIR']
 
