@@ -507,6 +507,31 @@ int mrdis_seg_accum(const float* logits, float* acc, int B, int H, int W, int Dz
 int mrdis_seg_label_volume(const float* acc, const int* cover, const void* targets, unsigned char* labels, int* counts, int B, int H,
                            int W, int D, int C, int relabel, void* stream);
 
+/* ---- tile-wise prediction of the 3-D nets (csrc/mrdis_segvol.hip; model3d.predict_tiles).  The rule is this package's own convention: the
+ * reference ships no 3-D inference.  Volume (H, W, D), tile (TH, TW, TD) <= the volume, nothing is padded.  Per axis the tile origins are
+ * 0, S, 2 S, ... below n - T, then n - T; the tiles are the Cartesian product, visited with h0 outermost and d0 innermost.  The views of a
+ * tile are the subsets of the mirrored axes, flag bits 1 (h) | 4 (w) | 8 (d) as in the gather table, in increasing binary count with the first
+ * named axis (in h, w, d order) as the lowest bit; view 0 is the identity.  Weights are separable, one fp32 vector per axis (uniform: ones;
+ * gaussian: exp(-0.5 ((x - (T - 1) / 2) / (sigma T))^2) evaluated in double, rounded once, clamped from below to 2^-20); the weight of tile
+ * position (i, j, k) is (wh[i] * ww[j]) * wd[k] in fp32: two roundings, in that order.
+ * mrdis_tile_accum: logits (B, TH, TW, TD, C) fp32 (channels-last-3d view of the net's output for one tile and view), acc (B, H, W, D, C) fp32,
+ *   16-byte aligned, wh (TH) / ww (TW) / wd (TD) fp32 on the device:
+ *     acc[b][h0 + i][w0 + j][d0 + k][c] = fmaf((wh[i] * ww[j]) * wd[k], sigmoid(logits[b][i'][j'][k'][c]), acc[b][h0 + i][w0 + j][d0 + k][c])
+ *   with i' = TH - 1 - i if flips & 1, else i; j' by flips & 4 and k' by flips & 8 likewise: the prediction of a mirrored input, put back.  The
+ *   weight is indexed by the position in the volume (i, j, k), not by the position in the net's output.  The sigmoid is mrdis_seg_accum's.
+ *   One thread owns an acc element within a launch and there are no atomics: calls add in launch order, bit-identical from run to run.
+ *   MRDIS_EINVAL: C outside 1 .. 4, a tile larger than the volume, an origin outside [0, n - T], flip bits other than 1 | 4 | 8, a null
+ *   pointer; MRDIS_EALIGN: acc not 16-byte aligned; MRDIS_EUNSUPPORTED: B TH TW (TD C + 6) / 4 >= 2^31.  One launch, counted as "tileaccum".
+ * mrdis_tile_label_volume: mrdis_seg_label_volume with the denominator den = (nh[h] * nw[w]) * nd[d] in fp32 in place of (float)cover[d] and
+ *   pbar_c = den > 0 ? acc_c / den : 0.  nh (H) / nw (W) / nd (D) fp32 on the device: the tiles are a Cartesian product, so the summed weight of
+ *   a voxel factorises; n_axis[x] = the sum over the axis' origins o of w_axis[x - o], summed in double from the fp32 weights and rounded once,
+ *   the number of views multiplied into nd before that rounding.  With nh = nw = 1 and nd = cover it gives mrdis_seg_label_volume's bits.
+ *   Labels, counts, targets, limits and alignment as there.  One launch, counted as "tilelabels".                                      */
+int mrdis_tile_accum(const float* logits, float* acc, const float* wh, const float* ww, const float* wd, int B, int H, int W, int D, int TH,
+                     int TW, int TD, int C, int h0, int w0, int d0, int flips, void* stream);
+int mrdis_tile_label_volume(const float* acc, const float* nh, const float* nw, const float* nd, const void* targets, unsigned char* labels,
+                            int* counts, int B, int H, int W, int D, int C, int relabel, void* stream);
+
 /* ---- whole-subject synthesis of missing contrasts by the 2-D model (csrc/mrdis_synth.hip): slice blocks -> volume.  The block rule is this
  * package's own convention: the reference ships no such path.
  * mrdis_synth_accum: srcs: HOST array of n_src (1 .. MRDIS_SYNTH_MAX_SRC) device pointers, handed to the kernel by value; each a dense

@@ -65,6 +65,7 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
     X(PATCHWARP, "patchwarp") /* mrdis_warp.hip: one count (and one launch) per mrdis_patch_warp call */ \
     X(LOSS3D, "loss3d") X(SEGCOUNTS, "segcounts") /* mrdis_loss3d.hip: one count per mrdis_nvnet_loss_fwd / _bwd call; one per mrdis_seg_counts call */ \
     X(SEGACCUM, "segaccum") X(SEGLABELS, "seglabels") /* mrdis_segvol.hip: one count per mrdis_seg_accum / mrdis_seg_label_volume call */ \
+    X(TILEACCUM, "tileaccum") X(TILELABELS, "tilelabels") /* mrdis_segvol.hip, tile-wise prediction: one count per mrdis_tile_accum / mrdis_tile_label_volume call */ \
     X(SYNTHACCUM, "synthaccum") X(SYNTHFINISH, "synthfinish") /* mrdis_synth.hip: one count per mrdis_synth_accum / mrdis_synth_finish call */ \
     X(SEG2DLABELS, "seg2dlabels") X(SEG2DFINISH, "seg2dfinish") /* mrdis_seg2d.hip: one count per mrdis_seg2d_label_planes / mrdis_seg2d_finish call */ \
     X(FUSE, "fuse") /* mrdis_fuse.hip: one count per mrdis_fuse_present_fwd / _bwd call */ \

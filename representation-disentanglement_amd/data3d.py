@@ -376,6 +376,35 @@ class VolumeLoader3D(BatchLoader):
             metas = [m[:5] + (True,) + m[6:] for m in metas]
         return self._gather(k, metas, int(z0), plain=True)
 
+    def tile(self, k, metas, origin, flips=0, tile=None):
+        """one batch of `plain_plan` at tile origin (h0, w0, d0), every item as stored, mirrored by the gather itself along the axes of `flips`
+        (patch3d.FLIP_H | FLIP_W | FLIP_D): the inputs and mask of `batches` (no targets: a prediction scores against the whole label volumes)
+        plus 'table' (`target_ptrs`) and 'origins'.  `tile`: (TH, TW, TD), None: the dataset's patch_size.  The existing mrdis_patch_gather
+        serves it: the augment bit is clear, the flip bits sit in the flag word, and the (B, 4) origins are written here, by the host
+        (model3d.predict_tiles)."""
+        ds, st = self.dataset, self.dataset.store
+        M = len(ds.contrast_list)
+        tile = ds.patch_size if tile is None else tile
+        try:
+            ok = len(tile) == 3 and len(origin) == 3 and all(int(v) == v for v in tuple(tile) + tuple(origin))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise ValueError(f'tile {tile!r} at origin {origin!r}: two triples of integers (a loader without patch_size needs `tile`)')
+        tile, origin = tuple(int(v) for v in tile), tuple(int(v) for v in origin)
+        if any(not (1 <= t <= n and 0 <= o <= n - t) for t, o, n in zip(tile, origin, st.shape)):
+            raise ValueError(f'tile {tile} at origin {origin} does not lie inside the stored volumes {tuple(st.shape)}')
+        if isinstance(flips, bool) or not isinstance(flips, int) or flips & ~(patch3d.FLIP_H | patch3d.FLIP_W | patch3d.FLIP_D):
+            raise ValueError(f'flips {flips!r}: bits of FLIP_H | FLIP_W | FLIP_D = {patch3d.FLIP_H | patch3d.FLIP_W | patch3d.FLIP_D}')
+        tab, mask_host = self._table_head(metas, 2 * M + patch3d.TABLE_EXTRA, None, False)
+        tab[:, 2 * M + 1] = flips
+        d = self._upload(tab)
+        origins = self._upload(np.array([origin + (-1,)] * len(metas), dtype=np.int32))
+        inputs, mask = patch3d.patch_gather(d, origins, M, st.shape, tile)
+        return {'inputs': inputs, 'subj_id': [m[0] for m in metas], 'slice_idx': torch.zeros(len(metas), dtype=torch.int64, device=st.device),
+                'mask': mask, 'mask_host': mask_host, 'batch_index': k, 'origins': origins,
+                'table': d[:, :2 * M + 3]}                            # the words every gather table starts with: `target_ptrs` reads [2M]
+
     def batches(self, limit=None, z0=None, flip=False):
         """`z0=None`: the reference's batches (crop [45:-46], drop-off, augmentation) -- in patch mode the patch batches.  An integer serves the batches of `plain_plan` with that
         depth offset and the same Dz, every item as stored (no drop-off redraws, no augmentation, no shuffle): the windowed reads for

@@ -100,6 +100,8 @@ _SIGS = {
     'mrdis_seg_counts': (_I, [_P, _P, _P, _I, _L, _I, _I, _P]),
     'mrdis_seg_accum': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_seg_label_volume': (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    'mrdis_tile_accum': (_I, [_P, _P, _P, _P, _P] + [_I] * 12 + [_P]),
+    'mrdis_tile_label_volume': (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_synth_accum': (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     'mrdis_synth_finish': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
     'mrdis_seg2d_label_planes': (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
@@ -245,6 +247,10 @@ LOSS3D_FAMILIES = ('loss3d', 'segcounts')
 # whole-volume sliding-window prediction (csrc/mrdis_segvol.hip): 'segaccum' counts one per mrdis_seg_accum call (one per window and flip),
 # 'seglabels' one per mrdis_seg_label_volume call (one per batch).
 SEGVOL_FAMILIES = ('segaccum', 'seglabels')
+# tile-wise prediction (csrc/mrdis_segvol.hip; model3d.predict_tiles): 'tileaccum' counts one per mrdis_tile_accum call (one per tile and view),
+# 'tilelabels' one per mrdis_tile_label_volume call (one per batch).
+TILEPRED_FAMILIES = ('tileaccum', 'tilelabels')
+TILE_FLIPS = 1 | 4 | 8            # the flip bits mrdis_tile_accum takes: h | w | d, the gather table's (patch3d.FLIP_H | FLIP_W | FLIP_D)
 # whole-subject synthesis of missing contrasts by the 2-D model (csrc/mrdis_synth.hip): 'synthaccum' counts one per mrdis_synth_accum call (one per
 # batch and target), 'synthfinish' one per mrdis_synth_finish call (one per target).
 SYNTH_FAMILIES = ('synthaccum', 'synthfinish')
@@ -277,7 +283,7 @@ EXPORT_FAMILIES = ('export',)
 ELEM_FAMILIES = ('stat_vec', 'stat_scalar', 'stat_interp', 'spade_up2_onepass', 'spade_up2_twopass', 'bil_fwd_x2', 'bil_fwd_general',
                  'bil_bwd_x2', 'bil_bwd_tight3', 'bil_bwd_tight5', 'bil_bwd_general', 'elem_v1')
 # every name of csrc/mrdis_common.h MRDIS_COUNTERS: what launch_counts() hands out, ELEM_FAMILIES on request (tests/test_abi.py pins the union)
-LAUNCH_COUNTERS = (WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + PATCH_FAMILIES + WARP_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES
+LAUNCH_COUNTERS = (WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + PATCH_FAMILIES + WARP_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + TILEPRED_FAMILIES
                     + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES + PREP_FAMILIES + EXPORT_FAMILIES + LESION_FAMILIES)
 ALL_COUNTERS = LAUNCH_COUNTERS + ELEM_FAMILIES
 SYNTH_MAX_SRC = 8                 # include/mrdis.h MRDIS_SYNTH_MAX_SRC

@@ -13,7 +13,7 @@ import torch.nn as nn
 import torch.nn.functional as F
 from torch.autograd import Function
 
-from . import hip, ops
+from . import hip, ops, patch3d, tilepred
 
 _GN_TAP = __import__('os').environ.get('MRDIS_GN_TAP', '1') != '0'      # BasicBlock: residual gradient summed inside the GroupNorm backward (0: autograd's add)
 
@@ -409,5 +409,122 @@ def predict_volumes(model, loader, stride=None, flip=False, limit=None):
                         del batch
                 labels, counts = hip.seg_label_volume(acc, cover, ptrs, relabel=relabel)
                 yield {'subj_id': subj_id, 'labels': labels, 'counts': counts, 'acc': acc, 'target_ptrs': ptrs}
+    finally:
+        net.train(was_training)
+
+
+# --------------------------------------------------------------------------- tile-wise prediction (csrc/mrdis_segvol.hip: mrdis_tile_accum, mrdis_tile_label_volume)
+TILE_WEIGHTS = ('gaussian', 'uniform')
+TILE_WEIGHT_FLOOR = 2.0 ** -20          # every weight entry is at least this: no product of three underflows
+TILE_SIGMA = (0.05, 1.0)
+
+
+def _triple(v, what, lo=1):
+    """three integers >= lo as a tuple, else ValueError naming `what`"""
+    try:
+        ok = len(v) == 3 and all(not isinstance(x, bool) and int(x) == x and x >= lo for x in v)
+    except (TypeError, ValueError):
+        ok = False
+    if not ok:
+        raise ValueError(f'{what} {v!r}: three integers >= {lo}')
+    return tuple(int(x) for x in v)
+
+
+def tile_weights(T, kind='gaussian', sigma=0.125):
+    """(T,) float32: the weight of one tile axis.  'uniform': ones.  'gaussian': exp(-0.5 ((x - (T - 1) / 2) / (sigma T))^2) evaluated in float64
+    and rounded once to fp32, every entry at least 2^-20; sigma in 0.05 .. 1.  Symmetric: w[x] == w[T - 1 - x] to the bit."""
+    T = int(T)
+    if T < 1:
+        raise ValueError(f'tile extent {T}: at least 1')
+    if kind not in TILE_WEIGHTS:
+        raise ValueError(f'weight {kind!r}: one of {TILE_WEIGHTS}')
+    if kind == 'uniform':
+        return np.ones(T, dtype=np.float32)
+    if isinstance(sigma, bool) or not isinstance(sigma, (int, float)) or not TILE_SIGMA[0] <= sigma <= TILE_SIGMA[1]:
+        raise ValueError(f'sigma {sigma!r}: a number in {TILE_SIGMA[0]} .. {TILE_SIGMA[1]} (the share of the tile extent)')
+    x = (np.arange(T, dtype=np.float64) - (T - 1) / 2.0) / (float(sigma) * T)
+    return np.maximum(np.exp(-0.5 * x * x), TILE_WEIGHT_FLOOR).astype(np.float32)
+
+
+def tile_offsets(shape, tile, stride=None):
+    """([h0 ...], [w0 ...], [d0 ...]): `window_offsets` per axis; the tiles are their Cartesian product, visited with h0 outermost and d0 innermost.
+    `stride` None: max(1, T // 2) per axis.  A tile larger than the volume is refused (nothing is padded)."""
+    shape, tile = _triple(shape, 'shape'), _triple(tile, 'tile')
+    stride = tuple(max(1, t // 2) for t in tile) if stride is None else _triple(stride, 'stride')
+    if any(t > n for t, n in zip(tile, shape)):
+        raise ValueError(f'tile {tile} does not fit the volume {shape}: no padding past the border')
+    return tuple(window_offsets(n, t, s) for n, t, s in zip(shape, tile, stride))
+
+
+def tile_norm(n, T, offsets, w, scale=1):
+    """(n,) float32: the summed weight of one axis, n[x] = scale * sum over the offsets o of w[x - o], summed in float64 from the fp32 weights and
+    rounded once.  The summed weight of a voxel is the product of its three axis sums (the tiles are a Cartesian product); `scale` carries
+    the number of views into the depth axis."""
+    w = np.asarray(w)
+    if w.dtype != np.float32 or w.shape != (int(T),):
+        raise ValueError(f'weights of dtype {w.dtype} and shape {w.shape}: float32 ({T},)')
+    s = np.zeros(int(n), dtype=np.float64)
+    for o in offsets:
+        if not 0 <= o <= n - T:
+            raise ValueError(f'offset {o} outside [0, {n - T}]')
+        s[o:o + T] += w.astype(np.float64)
+    return (s * float(scale)).astype(np.float32)
+
+
+def tile_views(mirror=''):
+    """the flag masks of the 2^len(mirror) mirrored views, in launch order: `mirror` names distinct axes of 'hwd'; view v counts in binary over
+    the named axes in h, w, d order, the first named axis the lowest bit; view 0 is the identity.  Bits: patch3d.FLIP_H | FLIP_W | FLIP_D."""
+    if not isinstance(mirror, str) or any(a not in 'hwd' for a in mirror) or len(set(mirror)) != len(mirror):
+        raise ValueError(f'mirror {mirror!r}: distinct letters of "hwd" (or the empty string)')
+    bits = [patch3d.FLIP_BITS[a] for a in 'hwd' if a in mirror]
+    return [sum(b for i, b in enumerate(bits) if v >> i & 1) for v in range(1 << len(bits))]
+
+
+def predict_tiles(model, loader, tile, stride=None, weight='gaussian', sigma=0.125, mirror='', limit=None):
+    """`predict_volumes` tile by tile: the net runs on (TH, TW, TD) tiles that overlap along all three axes (`tile_offsets`), the sigmoid
+    probabilities are blended with a separable weight (`tile_weights`) and averaged over the mirrored views of `mirror` (`tile_views`), each view
+    put back before it is added.  Yields `predict_volumes`' dict plus 'tiles', the list of origins (h0, w0, d0), and 'views', the list of flag
+    masks, both in launch order; `acc` holds the weighted sums.  The rule -- offsets, views, weights, fp32 order, normalisation by the product
+    of three axis sums -- is stated in include/mrdis.h and is this package's own convention.
+
+    Eval mode, no_grad; an `NVNet3D` runs its `unet` only.  Per batch: per tile and view one gather of the inputs (`loader.tile`), one forward
+    and one `tilepred.tile_accum` launch, then one `tilepred.tile_label_volume`; the weights and axis sums are uploaded once; nothing syncs with the
+    host.  The batches are those of `loader.plain_plan`, and no random stream is touched.  The loader must serve the items as stored."""
+    ds = loader.dataset
+    if ds.aug or ds.dropoff:
+        raise ValueError('predict_tiles reads the volumes as stored: the loader must have aug=False and dropoff=False')
+    shape = tuple(ds.store.shape)
+    tile = _triple(tile, 'tile')
+    offsets = tile_offsets(shape, tile, stride)
+    views = tile_views(mirror)
+    w = [tile_weights(t, weight, sigma) for t in tile]
+    norms = [tile_norm(n, t, o, wa, len(views) if a == 2 else 1) for a, (n, t, o, wa) in enumerate(zip(shape, tile, offsets, w))]
+    origins = [(h0, w0, d0) for h0 in offsets[0] for w0 in offsets[1] for d0 in offsets[2]]
+    net = model.unet if isinstance(model, NVNet3D) else model
+    C = net.out_channels
+    dev = ds.store.device
+    w = tuple(torch.from_numpy(a).to(dev) for a in w)
+    norms = tuple(torch.from_numpy(a).to(dev) for a in norms)
+    relabel = ds.dataset_name == 'BraTS'
+    was_training = net.training
+    net.eval()
+    try:
+        with torch.no_grad():
+            for k, _, metas in loader.plain_plan(limit):
+                subj_id = [m[0] for m in metas]
+                acc = torch.zeros((len(metas), *shape, C), dtype=torch.float32, device=dev)
+                ptrs = None
+                for origin in origins:
+                    for flips in views:
+                        batch = loader.tile(k, metas, origin, flips=flips, tile=tile)
+                        if batch['subj_id'] != subj_id:
+                            raise RuntimeError(f'tile {origin} of batch {k} serves {batch["subj_id"]}, not {subj_id}')
+                        if ptrs is None:
+                            ptrs = loader.target_ptrs(batch)
+                        tilepred.tile_accum(net(batch['inputs'])[0], acc, w, origin, flips)
+                        del batch
+                labels, counts = tilepred.tile_label_volume(acc, norms, ptrs, relabel=relabel)
+                yield {'subj_id': subj_id, 'labels': labels, 'counts': counts, 'acc': acc, 'target_ptrs': ptrs, 'tiles': list(origins),
+                       'views': list(views)}
     finally:
         net.train(was_training)

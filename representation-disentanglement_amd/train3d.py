@@ -36,6 +36,7 @@ from .data3d import VolumeData3D, VolumeStore3D, patch_args, patch_warp_args
 from .prep import build_store_from_raw, ensure_fold_lists, save_nifti
 from .postproc import CONNECTIVITIES, KEEP_MODES, STATS_COLUMNS, clean_labels, write_stats_csv
 from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, predict_volumes, seg_metrics_from_counts
+from .model3d import TILE_WEIGHTS, predict_tiles, tile_offsets, tile_views, tile_weights
 from .surfdist import BRATS_REGIONS, SCORE_KEYS, region_scores
 from .lesion import MAX_DILATION, lesion_csv_header, lesion_csv_values, lesion_scores
 from .train import parse_overrides, save_config_file, save_result_stat
@@ -69,6 +70,11 @@ DEFAULT_CONFIG_3D = {
     'predict_set': 'test',             # phase predict: the loader whose subjects are predicted (train | val | test; it must serve them as stored)
     'predict_stride': None,            # depth stride of the sliding window; None: half the trained depth
     'predict_flip': False,             # also average the prediction of the H-flipped input
+    'predict_tile': None,              # [TH, TW, TD]: predict tile by tile (model3d.predict_tiles; each a multiple of 8, at most the volume); null: the depth window over the full planes
+    'predict_tile_stride': None,       # predict_tile only: [SH, SW, SD], the stride of the tiles; null: half the tile
+    'predict_weight': 'gaussian',      # predict_tile only: gaussian | uniform, the weight of a tile position in the blend
+    'predict_sigma': 0.125,            # predict_tile only, gaussian: the standard deviation as a share of the tile extent, 0.05 .. 1
+    'predict_mirror': '',              # predict_tile only: the axes of 'hwd' whose mirrored views are averaged in (2^n forwards per tile)
     'predict_regions': False,          # phase predict: also write predict_regions.csv (Dice, sensitivity, specificity, HD95 of WT / TC / ET; BraTS only)
     'predict_lesions': False,          # phase predict / score / postprocess: also write predict_lesions.csv (lesion-wise Dice and HD95 of WT / TC / ET; BraTS only)
     'lesion_dilation': 3,              # lesion.lesion_scores: dilations of the ground truth by the 18-neighbourhood before it is split into lesions, 0 .. 8
@@ -131,6 +137,7 @@ def load_config3d(path=None, overrides=None):
         cfg['predict_stride'] = int(cfg['predict_stride'])
         if cfg['predict_stride'] < 1:
             raise ValueError(f'predict_stride {cfg["predict_stride"]}: at least 1 (or null: half the trained depth)')
+    check_predict_tile(cfg)
     if not isinstance(cfg['predict_regions'], bool):
         raise ValueError(f'predict_regions {cfg["predict_regions"]!r}: true or false')
     if (cfg['predict_regions'] or cfg['phase'] == 'score') and cfg['dataset_name'] != 'BraTS':
@@ -162,6 +169,48 @@ def load_config3d(path=None, overrides=None):
     if not isinstance(sub, str) or os.path.isabs(sub) or any(p in ('.', '..') for p in sub.replace('\\', '/').split('/')):
         raise ValueError(f'score_subdir {sub!r}: a relative sub-directory of result_<predict_set>/ (or the empty string)')
     return cfg
+
+
+NET_DIVISOR = 8                        # UNet3D halves its input three times and adds the skips back: every extent a multiple of 8
+
+
+def check_predict_tile(cfg, shape=None):
+    """the tile-wise prediction keys of a config, normalised in place (lists of int); ValueError naming the key.  `shape`: the stored volumes'
+    (H, W, D), where known -- the tile must fit it.  With predict_tile null the other four keys are not read."""
+    if cfg['predict_tile'] is None:
+        return
+    for key in ('predict_tile', 'predict_tile_stride'):
+        v = cfg[key]
+        if v is None and key == 'predict_tile_stride':
+            continue
+        try:
+            ok = not isinstance(v, str) and len(v) == 3 and all(not isinstance(x, bool) and isinstance(x, int) and x >= 1 for x in v)
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError(f'{key} {v!r}: null or three integers >= 1')
+        cfg[key] = [int(x) for x in v]
+    if any(t % NET_DIVISOR for t in cfg['predict_tile']):
+        raise ValueError(f'predict_tile {cfg["predict_tile"]}: every extent a multiple of {NET_DIVISOR} (the U-Net halves its input three times)')
+    if cfg['predict_stride'] is not None:
+        raise ValueError('predict_stride belongs to the depth window: with predict_tile set predict_tile_stride: [SH, SW, SD]')
+    if cfg['predict_flip']:
+        raise ValueError('predict_flip belongs to the depth window: with predict_tile set predict_mirror: h')
+    if cfg['predict_weight'] not in TILE_WEIGHTS:
+        raise ValueError(f'predict_weight {cfg["predict_weight"]!r}: one of {TILE_WEIGHTS}')
+    try:
+        tile_weights(1, cfg['predict_weight'], cfg['predict_sigma'])
+    except ValueError as e:
+        raise ValueError(f'predict_sigma: {e}') from None
+    try:
+        tile_views(cfg['predict_mirror'])
+    except ValueError as e:
+        raise ValueError(f'predict_mirror: {e}') from None
+    if shape is not None:
+        try:
+            tile_offsets(shape, cfg['predict_tile'], cfg['predict_tile_stride'])
+        except ValueError as e:
+            raise ValueError(f'predict_tile: {e}') from None
 
 
 def region_csv_header():
@@ -265,6 +314,8 @@ class Run3D:
                                 patch_warp=cfg['patch_warp'], patch_rot=cfg['patch_rot'], patch_zoom=cfg['patch_zoom'])
         self.data = data
         self.loaders = {'train': data.trainLoader, 'val': data.valLoader, 'test': data.testLoader}
+        if cfg['phase'] == 'predict':
+            check_predict_tile(cfg, self.loaders[cfg['predict_set']].dataset.store.shape)      # the tile must fit the volumes: before any launch
         ds = data.trainLoader.dataset
         H, W, _ = ds.store.shape
         patch = getattr(ds, 'patch_size', None)
@@ -408,7 +459,8 @@ class Run3D:
         return stat
 
     def predict(self, set_=None):
-        """whole-volume sliding-window prediction (model3d.predict_volumes) of every subject the `set_` loader serves (None: `predict_set`):
+        """whole-volume prediction -- the sliding depth window (model3d.predict_volumes) or, with `predict_tile`, overlapping tiles blended by
+        `predict_weight` and averaged over the views of `predict_mirror` (model3d.predict_tiles) -- of every subject the `set_` loader serves (None: `predict_set`):
         writes <ckpt_path>/result_<set>/<subj_id>_seg.npy -- uint8 (H, W, D), the store's own geometry and labels (BraTS: 0 / 1 / 2 / 4) -- and
         result_<set>/predict.csv with a header and one `subj_id,dice,iou` row per subject (the reference's Dice / IoU over the FULL depth);
         returns their means.  One D2H copy of the labels per batch, one of all counts at the end; no window syncs with the host.
@@ -430,8 +482,14 @@ class Run3D:
         subj, counts, regions, lesions = [], [], [], []
         nifti = self._nifti_writer(set_)
         post = _PostWriter(out_dir, cfg['predict_regions'], nifti, self.lesions if cfg['predict_lesions'] else None) if cfg['predict_post'] else None
-        for res in predict_volumes(self.model, self.loaders[set_], stride=cfg['predict_stride'], flip=cfg['predict_flip'],
-                                   limit=cfg['max_batches'] or None):
+        if cfg['predict_tile'] is None:
+            results = predict_volumes(self.model, self.loaders[set_], stride=cfg['predict_stride'], flip=cfg['predict_flip'],
+                                      limit=cfg['max_batches'] or None)
+        else:       # tile by tile (model3d.predict_tiles): the same dict, so everything below is what it was
+            check_predict_tile(cfg, self.loaders[set_].dataset.store.shape)
+            results = predict_tiles(self.model, self.loaders[set_], cfg['predict_tile'], stride=cfg['predict_tile_stride'], weight=cfg['predict_weight'],
+                                    sigma=cfg['predict_sigma'], mirror=cfg['predict_mirror'], limit=cfg['max_batches'] or None)
+        for res in results:
             if cfg['predict_regions']:
                 regions.append(region_scores(res['labels'], res['target_ptrs']))
             if cfg['predict_lesions']:
