@@ -461,6 +461,47 @@ int mrdis_patch_gather(const void* table, int ld_table, const int* origins, floa
 int mrdis_patch_warp(const void* table, int ld_table, const int* origins, float* out, float* mask, int B, int M, int H, int W, int D,
                      int PH, int PW, int PD, int mode, int K, int relabel, void* stream);
 
+/* ---- intensity augmentation of the gathered training patches (csrc/mrdis_tone.hip): Gaussian blur, contrast, gamma and additive noise.  This
+ * package's conventions (the reference has none).  x, y: (B, PH, PW, PD, M) dense fp32, the layout mrdis_patch_gather / mrdis_patch_warp write;
+ * scale, shift and the marker rule are already applied.  A voxel is BACKGROUND iff its value equals -10.0f exactly, every other one is
+ * tissue; background voxels leave every call as -10 exactly and enter no sum.  An item or contrast without a flag leaves all three calls bit
+ * for bit as it went in.  Any M in 1 .. 64, any extents >= 1 with PH PW PD < 2^31, B in 1 .. 65535.
+ * table (B, ld_table) 64-bit words in device memory; the calls read the block of 1 + 5 M words at word `col` of a row (after the 2 M + 7 or
+ *   2 M + 12 words of the gathers): word 0 = seed_lo | seed_hi << 32, then five words per contrast as ten 32-bit halves, the low half first:
+ *   flags, g0, g1, g2, g3, g4, f, gamma, std, 0 (fp32 bits but for the flags).  Flag bits: MRDIS_TONE_BLUR 1, MRDIS_TONE_CONTRAST 2,
+ *   MRDIS_TONE_GAMMA 4, MRDIS_TONE_INVERT 8 (the inverted gamma curve), MRDIS_TONE_NOISE 16.  The taps are
+ *   g[t] = exp(-t^2 / (2 sigma^2)) / (g'0 + 2 sum_{t=1..4} g'[t]) (g' the unnormalised ones), float64 on the host, rounded once to fp32.
+ * mrdis_patch_blur, out of place (x == y: MRDIS_EINVAL).  A contrast with the blur flag clear: y = x bit for bit.  A flagged one: the
+ *   normalised convolution over tissue, m = (x != -10), xm = m ? x : 0.  Three passes along d, then w, then h, starting from N = xm, D = m:
+ *   N'[p] = sum_t g[|t|] N[p + t e] and D'[p] = sum_t g[|t|] D[p + t e], e the pass's axis, t = -4 .. 4 in increasing order, each sum an fp32
+ *   fmaf chain from 0 over the t with p + t e inside the patch (nothing is padded: the patch border renormalises as the background does).
+ *   After the third pass y = m ? N / D : -10 (D > 0 wherever m holds: g0 > 0).  Launches: 2 where M == 4 and x and y are 16-byte aligned
+ *   (a voxel's four contrasts as one 16-byte access), else 3; 3 always under the debug_volgen switch.  Both forms give the same bits.
+ * mrdis_patch_stats: stats (B, M, 4) 32-bit words = fp32 lo (minimum over tissue), fp32 hi (maximum), fp32 mean = (float)(sum / n) with the
+ *   sum in float64 in a fixed order, int32 n (tissue count); n = 0: the first three are 0.  2 launches; no atomics: two runs give the same bits.
+ * mrdis_patch_tone, in place on tissue voxels, per contrast, each step only where its flag is set, in this order:
+ *   contrast  v = min(max(fmaf(v - mean, f, mean), lo), hi)
+ *   gamma     only if hi > lo: rg = hi - lo, t = min(max((v - lo) / rg, 0), 1); inverted: t = 1 - t; t = powf(t, gamma); inverted: t = 1 - t;
+ *             v = fmaf(t, rg, lo)
+ *   noise     v = fmaf(std, z, v), z = (float)(2 S - 4080) * C, S the integer sum of the 16 bytes of Philox4x32-10 (multipliers 0xD2511F53,
+ *             0xCD9E8D57; key increments 0x9E3779B9, 0xBB67AE85) on the counter (p, m, 0, 0), p = (i PW + j) PD + k the voxel's flat index in
+ *             the patch, under the key (seed_lo, seed_hi); C = 0x3addb446, the fp32 nearest to 349520^-1/2: mean 0, variance 1, |z| < 6.91.
+ *   1 launch.
+ * Refused before any launch: a NULL pointer, x == y, col < 0, ld_table < col + 1 + 5 M, B < 1, M outside 1 .. 64, an extent < 1 (MRDIS_EINVAL);
+ * B > 65535 or PH PW PD >= 2^31 (MRDIS_EUNSUPPORTED); x, y or stats not 4-byte, table not 8-byte, workspace not 16-byte aligned (MRDIS_EALIGN);
+ * a workspace below the query's size (MRDIS_EWORKSPACE).  Counted once per call as "patchblur" / "patchstats" / "patchtone".               */
+#define MRDIS_TONE_BLUR 1
+#define MRDIS_TONE_CONTRAST 2
+#define MRDIS_TONE_GAMMA 4
+#define MRDIS_TONE_INVERT 8
+#define MRDIS_TONE_NOISE 16
+size_t mrdis_patch_blur_workspace(int B, int M, int PH, int PW, int PD);
+int mrdis_patch_blur(const float* x, float* y, const void* table, int ld_table, int col, int B, int M, int PH, int PW, int PD,
+                     void* workspace, size_t workspace_bytes, void* stream);
+size_t mrdis_patch_stats_workspace(int B, int M, int PH, int PW, int PD);
+int mrdis_patch_stats(const float* x, void* stats, int B, int M, int PH, int PW, int PD, void* workspace, size_t workspace_bytes, void* stream);
+int mrdis_patch_tone(float* x, const void* stats, const void* table, int ld_table, int col, int B, int M, int PH, int PW, int PD, void* stream);
+
 /* ---- objective of the 3-D nets (model3d.nvnet_loss) fused: soft Dice of sigmoid(uout) against `target`, GLOBAL over the batch, plus
  * w_l2 times the mean squared error of vout against x (csrc/mrdis_loss3d.hip).  uout / target: fp32 of one shape (shape_ut, nd_ut <= 8
  * extents) and ONE dense memory layout, given by their element strides; vout / x likewise with shape_vx, or both NULL for the Dice-only

@@ -63,6 +63,7 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
     X(VOLGATHER, "volgather") /* mrdis_volgather.hip: the 3-D batch gather, one count per mrdis_volume_gather call */ \
     X(FGCOUNT, "fgcount") X(PATCHORIGIN, "patchorigin") X(PATCHGATHER, "patchgather") /* mrdis_patch.hip: one count per mrdis_fg_block_counts / mrdis_patch_origins / mrdis_patch_gather call */ \
     X(PATCHWARP, "patchwarp") /* mrdis_warp.hip: one count (and one launch) per mrdis_patch_warp call */ \
+    X(PATCHBLUR, "patchblur") X(PATCHSTATS, "patchstats") X(PATCHTONE, "patchtone") /* mrdis_tone.hip: one count per mrdis_patch_blur / mrdis_patch_stats / mrdis_patch_tone call */ \
     X(LOSS3D, "loss3d") X(SEGCOUNTS, "segcounts") /* mrdis_loss3d.hip: one count per mrdis_nvnet_loss_fwd / _bwd call; one per mrdis_seg_counts call */ \
     X(SEGACCUM, "segaccum") X(SEGLABELS, "seglabels") /* mrdis_segvol.hip: one count per mrdis_seg_accum / mrdis_seg_label_volume call */ \
     X(TILEACCUM, "tileaccum") X(TILELABELS, "tilelabels") /* mrdis_segvol.hip, tile-wise prediction: one count per mrdis_tile_accum / mrdis_tile_label_volume call */ \

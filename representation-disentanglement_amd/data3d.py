@@ -28,7 +28,14 @@ With `patch_warp` > 0 (and aug) a step 4b follows the flips: one `r = rand(5)` p
 `angle_a = (2 r[1 + a] - 1) patch_rot[a]` degrees about the H, W, D axes, `zoom = lo + r[4] (hi - lo)` over `patch_zoom` -- and the batch is
 gathered by patch3d.patch_warp (csrc/mrdis_warp.hip: integer coordinates, exact labels) instead of patch_gather.  With `patch_warp` = 0
 no draw is added and every stream, batch and checkpoint is what it was.
-and the device turns the draws into the patch origin (patch3d's docstring: pick, clamping instead of padding).  The `== min()` rule compares
+With any of `patch_blur`, `patch_contrast`, `patch_gamma`, `patch_noise` > 0 (and aug) a step 4c follows the warp draw (or the flips), before scale
+and shift, always in full: `r = rand(4 + 6 M)` and the noise seed `randint(0, 2**32, size=2, dtype=np.uint32)`.  The item coins are
+`r[0] < patch_blur`, `r[1] < patch_contrast`, `r[2] < patch_gamma`, `r[3] < patch_noise`; per contrast m, q = r[4 + 6 m:10 + 6 m]: blurred iff
+the blur coin and `q[0] < 0.5`, `sigma = lo + q[1] (hi - lo)`, the contrast factor, the gamma exponent and the noise deviation likewise from
+q[2], q[3], q[5] over their ranges, and the inverted gamma curve iff `q[4] < patch_gamma_invert`; every value rounded once to fp32; an absent or
+dropped contrast gets no flag.  The gathered inputs then pass through tone3d.patch_intensify (csrc/mrdis_tone.hip).  With the four shares at 0
+no draw is added and no kernel launches.
+The device turns the draws into the patch origin turns the draws into the patch origin (patch3d's docstring: pick, clamping instead of padding).  The `== min()` rule compares
 with the minimum of the whole stored volume.  The evaluation loaders serve the centre patch, without a draw; `crop()` is then the centre
 depth window of the trained depth PD, so the windowed reads slide PD over the full H x W.
 The commented-out mean-image imputation (`img_mean`, `BraTS_mean.npy`) and the `missing` argument the reference never reads are not built.
@@ -38,7 +45,7 @@ import os
 import numpy as np
 import torch
 
-from . import hip, patch3d
+from . import hip, patch3d, tone3d
 from .data import VolumeStore, BatchLoader
 
 Z0 = 45                     # util.py:766-769
@@ -143,6 +150,39 @@ def patch_warp_args(patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4
     return float(patch_warp), tuple(float(v) for v in patch_rot), tuple(float(v) for v in patch_zoom)
 
 
+INTENSITY_DEFAULTS = {'patch_blur': 0.0, 'patch_blur_sigma': (0.5, 1.0), 'patch_contrast': 0.0, 'patch_contrast_range': (0.75, 1.25), 'patch_gamma': 0.0,
+                      'patch_gamma_range': (0.7, 1.5), 'patch_gamma_invert': 0.25, 'patch_noise': 0.0, 'patch_noise_std': (0.0, 0.3)}
+_INTENSITY_RANGES = {'patch_blur_sigma': (0.25, 1.0, 'sigma in voxels (the tap radius is 4)'), 'patch_contrast_range': (0.5, 2.0, 'the contrast factor'),
+                     'patch_gamma_range': (0.5, 2.0, 'the gamma exponent'), 'patch_noise_std': (0.0, 1.0, 'the standard deviation of the noise, store units')}
+
+
+def patch_intensity_args(**keys):
+    """the nine intensity keys (INTENSITY_DEFAULTS for those not given) -> a dict of them, checked: the shares `patch_blur`, `patch_contrast`,
+    `patch_gamma`, `patch_gamma_invert`, `patch_noise` in 0 .. 1; `patch_blur_sigma` [lo, hi] in 0.25 .. 1, `patch_contrast_range` and
+    `patch_gamma_range` in 0.5 .. 2, `patch_noise_std` in 0 .. 1, each with lo <= hi; else ValueError naming the key (TypeError: no such key)"""
+    unknown = sorted(set(keys) - set(INTENSITY_DEFAULTS))
+    if unknown:
+        raise TypeError(f'no intensity key {unknown}: one of {sorted(INTENSITY_DEFAULTS)}')
+    num = lambda v: not isinstance(v, bool) and isinstance(v, (int, float)) and np.isfinite(v)
+    out = {}
+    for key, dflt in INTENSITY_DEFAULTS.items():
+        v = keys.get(key, dflt)
+        if key not in _INTENSITY_RANGES:
+            if not num(v) or not 0.0 <= v <= 1.0:
+                raise ValueError(f'{key} {v!r}: a share, 0 .. 1')
+            out[key] = float(v)
+            continue
+        a, b, what = _INTENSITY_RANGES[key]
+        try:
+            ok = len(v) == 2 and all(num(e) and a <= e <= b for e in v) and v[0] <= v[1]
+        except TypeError:
+            ok = False
+        if not ok:
+            raise ValueError(f'{key} {v!r}: [lo, hi] of {what}, lo <= hi, both in {a} .. {b}')
+        out[key] = (float(v[0]), float(v[1]))
+    return out
+
+
 class VolumeDataset3D:
     """ZeroDoseDataset3D (util.py:723-810) over a VolumeStore3D: `meta(idx)` is the host part of `__getitem__`.  `patch_size` (PH, PW, PD):
     patch training, see the module docstring; `patch_centre`: the deterministic centre patch instead of a random one (evaluation)."""
@@ -151,16 +191,19 @@ class VolumeDataset3D:
     FG_CLASSES = {'BraTS': (1, 2, 4)}      # the label values a foreground patch may be centred on
 
     def __init__(self, dataset_name, store, subj_list, contrast_list=('T1',), aug=False, dropoff=False, patch_size=None, patch_fg=0.0,
-                 patch_flips='h', patch_centre=False, patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4)):
+                 patch_flips='h', patch_centre=False, patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4), **intensity):
         self.dataset_name, self.store = dataset_name, store
         self.subj_list, self.contrast_list = list(subj_list), list(contrast_list)
         self.aug, self.dropoff = aug, dropoff
-        self.set_patch(patch_size, patch_fg, patch_flips, patch_centre, patch_warp, patch_rot, patch_zoom)
+        self.set_patch(patch_size, patch_fg, patch_flips, patch_centre, patch_warp, patch_rot, patch_zoom, **intensity)
 
-    def set_patch(self, patch_size, patch_fg=0.0, patch_flips='h', patch_centre=False, patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4)):
+    def set_patch(self, patch_size, patch_fg=0.0, patch_flips='h', patch_centre=False, patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4),
+                  **intensity):
+        """`intensity`: the keys of `patch_intensity_args` (patch_blur .. patch_noise_std), kept checked in `self.intensity`"""
         self.patch_size, self.patch_fg, self.patch_flips = patch_args(patch_size, patch_fg, patch_flips)
         self.patch_centre = bool(patch_centre)
         self.patch_warp, self.patch_rot, self.patch_zoom = patch_warp_args(patch_warp, patch_rot, patch_zoom)
+        self.intensity = patch_intensity_args(**intensity)
         if self.patch_size is None:
             return
         if self.patch_fg > 0 and self.dataset_name not in self.FG_CLASSES:
@@ -188,7 +231,8 @@ class VolumeDataset3D:
         reference's own stream, draw for draw) or the loader's own np.random.RandomState (data-parallel runs, see BatchLoader).  `plain`: the item as
         stored -- nothing dropped, not augmented -- and no draw from any stream (the windowed reads of VolumeLoader3D.batches(z0=...)).
         In patch mode (and not `plain`) a ninth element follows: (fg, the five uint32 draws, (flip h, flip w, flip d), centre), and with
-        `patch_warp` > 0 on an augmenting, non-centre dataset three more in it: (warp, (angle h, w, d) in degrees, zoom)."""
+        `patch_warp` > 0 on an augmenting, non-centre dataset three more in it: (warp, (angle h, w, d) in degrees, zoom); where the dataset
+        `intensifies()` one more after those: (seed (2,) uint32, flags (M,) of tone3d.BLUR | .., sigma, f, gamma, std, each (M,) float32)."""
         rng = np.random if rng is None else rng
         subj_id = str(self.subj_list[idx])
         ptrs = [self.store.ptr(subj_id + '/' + c) for c in self.contrast_list]
@@ -202,7 +246,7 @@ class VolumeDataset3D:
             if rng.rand() > 0.8:
                 drop = int(rng.choice(np.where(mask == 1)[0], 1)[0])
         if self.patch_size is not None:
-            return (subj_id, 0, ptrs, drop, tptr) + self._patch_draws(rng)
+            return (subj_id, 0, ptrs, drop, tptr) + self._patch_draws(rng, [bool(p) and m != drop for m, p in enumerate(ptrs)])
         flip, scale, shift = False, 1.0, 0.0
         if self.aug:                                                  # :798-804
             flip = bool(rng.rand() > 0.5)
@@ -210,14 +254,15 @@ class VolumeDataset3D:
             shift = 0.2 * (rng.rand() - 0.5)
         return subj_id, 0, ptrs, drop, tptr, flip, scale, shift
 
-    def _patch_draws(self, rng):
+    def _patch_draws(self, rng, present):
         """the tail of a patch-mode meta, drawn in the order of the module docstring: (flip h, scale, shift, (fg, u[5], flips, centre)), the last
-        tuple followed by (warp, angles, zoom) where `warps()`"""
+        tuple followed by (warp, angles, zoom) where `warps()` and by the intensity draws where `intensifies()`.  present: per contrast, whether
+        the item has it (and it is not dropped)"""
         if self.patch_centre:
             return False, 1.0, 0.0, (False, np.zeros(5, dtype=np.uint32), (False, False, False), True)
         fg = bool(rng.rand() < self.patch_fg) if self.patch_fg > 0 else False
         u = rng.randint(0, 2 ** 32, size=5, dtype=np.uint32)
-        flips, scale, shift, warp = [False, False, False], 1.0, 0.0, ()
+        flips, scale, shift, warp, tone = [False, False, False], 1.0, 0.0, (), ()
         if self.aug:
             for i, axis in enumerate('hwd'):
                 if axis in self.patch_flips:
@@ -226,13 +271,44 @@ class VolumeDataset3D:
                 r = rng.rand(5)
                 lo, hi = self.patch_zoom
                 warp = (bool(r[0] < self.patch_warp), tuple(float((2 * r[1 + a] - 1) * self.patch_rot[a]) for a in range(3)), float(lo + r[4] * (hi - lo)))
+            if self.intensifies():                                    # 4 + 6 M doubles and the seed, always
+                tone = (self._intensity_draws(rng, present),)
             scale = 1 + 0.2 * (rng.rand() - 0.5)
             shift = 0.2 * (rng.rand() - 0.5)
-        return flips[0], scale, shift, (fg, u, tuple(flips), False) + warp
+        return flips[0], scale, shift, (fg, u, tuple(flips), False) + warp + tone
+
+    def _intensity_draws(self, rng, present):
+        """step 4c of the module docstring -> (seed, flags, sigma, f, gamma, std)"""
+        k, M = self.intensity, len(self.contrast_list)
+        r = rng.rand(4 + 6 * M)
+        seed = rng.randint(0, 2 ** 32, size=2, dtype=np.uint32)
+        blur_on, contrast_on, gamma_on, noise_on = r[0] < k['patch_blur'], r[1] < k['patch_contrast'], r[2] < k['patch_gamma'], r[3] < k['patch_noise']
+        q = r[4:].reshape(M, 6)
+        span = lambda key, col: (k[key][0] + q[:, col] * (k[key][1] - k[key][0])).astype(np.float32)
+        flags = []
+        for m in range(M):
+            f = 0
+            if present[m]:
+                f |= tone3d.BLUR if blur_on and q[m, 0] < 0.5 else 0
+                f |= tone3d.CONTRAST if contrast_on else 0
+                f |= (tone3d.GAMMA | (tone3d.INVERT if q[m, 4] < k['patch_gamma_invert'] else 0)) if gamma_on else 0
+                f |= tone3d.NOISE if noise_on else 0
+            flags.append(f)
+        return seed, tuple(flags), span('patch_blur_sigma', 1), span('patch_contrast_range', 2), span('patch_gamma_range', 3), span('patch_noise_std', 5)
 
     def warps(self):
         """whether this dataset's batches go through patch3d.patch_warp: patch mode, augmenting, not the centre patch, patch_warp > 0"""
         return self.patch_size is not None and bool(self.aug) and not self.patch_centre and self.patch_warp > 0
+
+    def intensifies(self):
+        """whether this dataset's inputs go through tone3d.patch_intensify: patch mode, augmenting, not the centre patch, and any of patch_blur,
+        patch_contrast, patch_gamma, patch_noise above 0"""
+        return (self.patch_size is not None and bool(self.aug) and not self.patch_centre
+                and any(self.intensity[key] > 0 for key in ('patch_blur', 'patch_contrast', 'patch_gamma', 'patch_noise')))
+
+    def tone_col(self):
+        """the word of a `patch_table` row at which the intensity block starts"""
+        return 2 * len(self.contrast_list) + patch3d.TABLE_EXTRA + (patch3d.WARP_EXTRA if self.warps() else 0)
 
 
 class VolumeLoader3D(BatchLoader):
@@ -244,16 +320,20 @@ class VolumeLoader3D(BatchLoader):
     Batch order, rank / world / equal_steps and the loader's own stream under world > 1 are BatchLoader's (see its docstring); here that
     stream carries ALL per-item draws, drop-off and augmentation, for the same reason.
 
-    `patch_size` (with `patch_fg`, `patch_flips`, `patch_centre`, `patch_warp`, `patch_rot`, `patch_zoom`): puts the dataset into patch mode
+    `patch_size` (with `patch_fg`, `patch_flips`, `patch_centre`, `patch_warp`, `patch_rot`, `patch_zoom` and the intensity keys of
+    `patch_intensity_args`; an intensifying loader adds three launches -- blur, statistics, tone -- on the inputs): puts the dataset into patch mode
     (VolumeDataset3D.set_patch; None leaves it as it was built).  A batch is then three launches -- origins, inputs, targets -- of (PH, PW, PD) patches, and carries 'origins' (B, 4) int32
     on the device: h0, w0, d0 and the index of the class a foreground patch was centred on (-1: uniform or centre)."""
 
     def __init__(self, dataset, batch_size, shuffle=False, rank=0, world=1, equal_steps=False, generator=None, region_channels=0,
-                 patch_size=None, patch_fg=0.0, patch_flips='h', patch_centre=False, patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4)):
+                 patch_size=None, patch_fg=0.0, patch_flips='h', patch_centre=False, patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4),
+                 **intensity):
         super().__init__(dataset, batch_size, shuffle, rank, world, equal_steps, generator)
         self.region_channels = int(region_channels)
         if patch_size is not None:
-            dataset.set_patch(patch_size, patch_fg, patch_flips, patch_centre, patch_warp, patch_rot, patch_zoom)
+            dataset.set_patch(patch_size, patch_fg, patch_flips, patch_centre, patch_warp, patch_rot, patch_zoom, **intensity)
+        else:
+            patch_intensity_args(**intensity)                         # (read only with patch_size; a misspelt key is still an error)
 
     def _table_head(self, metas, width, crop, aug):
         """(B, width) int64 with the 2 M + 3 words every gather reads (include/mrdis.h mrdis_volume_gather) filled in and zeros beyond, and the
@@ -285,12 +365,17 @@ class VolumeLoader3D(BatchLoader):
         """the per-batch table of mrdis_patch_origins / mrdis_patch_gather (include/mrdis.h: the words of `table`, the minima those of the whole
         volumes, then the prefix pointer, the flags and the packed draws), on the host, and the host twin of `mask`.  Where the dataset
         `warps()` the rows are patch3d.WARP_EXTRA words longer (mrdis_patch_warp): the WARP flag and the packed Q16 matrix of the items that drew
-        a warp, zeros for the others."""
+        a warp, zeros for the others.  Where it `intensifies()` they are tone3d.TONE_EXTRA(M) words longer still, from word `tone_col()`: the
+        block of tone3d.pack_tone."""
         ds, st = self.dataset, self.dataset.store
         M = len(ds.contrast_list)
         classes = ds.FG_CLASSES.get(ds.dataset_name, ())
-        tab, mask_host = self._table_head(metas, 2 * M + patch3d.TABLE_EXTRA + (patch3d.WARP_EXTRA if ds.warps() else 0), (0, st.shape[2]), ds.aug)
+        col = ds.tone_col()
+        tab, mask_host = self._table_head(metas, col + (tone3d.TONE_EXTRA(M) if ds.intensifies() else 0), (0, st.shape[2]), ds.aug)
         for r, (subj_id, _, _, _, tptr, _, _, _, (fg, u, flips, centre, *warp)) in enumerate(metas):
+            if ds.intensifies():
+                *warp, tone = warp
+                tab[r, col:] = tone3d.pack_tone(*tone)
             flags = (patch3d.AUG if ds.aug else 0) | (patch3d.FG if fg else 0) | (patch3d.CENTRE if centre else 0)
             for axis, on in zip('hwd', flips):
                 flags |= patch3d.FLIP_BITS[axis] if on else 0
@@ -363,6 +448,8 @@ class VolumeLoader3D(BatchLoader):
         gather = patch3d.patch_warp if ds.warps() else patch3d.patch_gather
         batch = self._sample(k, metas, mask_host, lambda **kw: gather(d, origins, M, st.shape, ds.patch_size, **kw))
         batch['origins'] = origins
+        if ds.intensifies():                                          # blur, statistics, tone: three more calls, on the inputs only
+            batch['inputs'] = tone3d.patch_intensify(batch['inputs'], d, ds.tone_col(), M)
         return batch
 
     def window(self, k, metas, z0, flip=False):
@@ -445,16 +532,19 @@ class VolumeData3D:
 
     def __init__(self, dataset_name, data_path, norm_type='mean', batch_size=16, fold=0, shuffle=True, contrast_list=('T1',), aug=False,
                  dropoff=False, store=None, device='cuda:0', rank=0, world=1, generator=None, region_channels=0, patch_size=None, patch_fg=0.0,
-                 patch_flips='h', patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4)):
+                 patch_flips='h', patch_warp=0.0, patch_rot=(30, 30, 30), patch_zoom=(0.7, 1.4), **intensity):
         h5, *lists = self.file_names(dataset_name, norm_type, fold)
         if store is None:
             store = VolumeStore3D.from_h5(os.path.join(data_path, h5), device)
         self.store = store
         subj = [load_subj_list(os.path.join(data_path, f)) for f in lists]
-        # patch mode: random patches for the train loader, the centre patch (no draw, no foreground share, no warp) for the evaluation loaders
+        # patch mode: random patches for the train loader, the centre patch (no draw, no foreground share, no warp, no intensity change) for the
+        # evaluation loaders
+        intensity = patch_intensity_args(**intensity)
         mk = lambda s, a, d, centre: VolumeDataset3D(dataset_name, store, s, contrast_list=contrast_list, aug=a, dropoff=d, patch_size=patch_size,
                                                      patch_fg=0.0 if centre else patch_fg, patch_flips=patch_flips, patch_centre=centre,
-                                                     patch_warp=0.0 if centre else patch_warp, patch_rot=patch_rot, patch_zoom=patch_zoom)
+                                                     patch_warp=0.0 if centre else patch_warp, patch_rot=patch_rot, patch_zoom=patch_zoom,
+                                                     **({} if centre else intensity))
         kw = dict(rank=rank, world=world, generator=generator, region_channels=region_channels)
         self.trainLoader = VolumeLoader3D(mk(subj[0], aug, dropoff, False), batch_size, shuffle=shuffle, equal_steps=True, **kw)
         self.valLoader = VolumeLoader3D(mk(subj[1], False, dropoff, True), batch_size, shuffle=False, **kw)

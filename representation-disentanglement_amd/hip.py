@@ -94,6 +94,11 @@ _SIGS = {
     'mrdis_patch_origins': (_I, [_P, _I, _P, _P, _I] + [_I] * 8 + [_P]),
     'mrdis_patch_gather': (_I, [_P, _I, _P, _P, _P] + [_I] * 11 + [_P]),
     'mrdis_patch_warp': (_I, [_P, _I, _P, _P, _P] + [_I] * 11 + [_P]),
+    'mrdis_patch_blur_workspace': (_Z, [_I] * 5),
+    'mrdis_patch_blur': (_I, [_P, _P, _P] + [_I] * 7 + [_P, _Z, _P]),
+    'mrdis_patch_stats_workspace': (_Z, [_I] * 5),
+    'mrdis_patch_stats': (_I, [_P, _P] + [_I] * 5 + [_P, _Z, _P]),
+    'mrdis_patch_tone': (_I, [_P, _P, _P] + [_I] * 7 + [_P]),
     'mrdis_nvnet_loss_workspace': (_Z, [_L, _L]),
     'mrdis_nvnet_loss_fwd': (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_double, _P, _P, _P, _Z, _P]),
     'mrdis_nvnet_loss_bwd': (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _I, _c.c_double, _P, _P, _P, _P, _P]),
@@ -241,6 +246,9 @@ PATCH_MAX_CLASSES = 8             # include/mrdis.h MRDIS_PATCH_MAX_CLASSES
 # rotated and zoomed training patches (csrc/mrdis_warp.hip; the wrapper lives in warp3d.py): one count, and one launch, per mrdis_patch_warp call
 # (two per batch of a loader with patch_warp > 0, in place of the two 'patchgather').
 WARP_FAMILIES = ('patchwarp',)
+# intensity augmentation of the training patches (csrc/mrdis_tone.hip; the wrappers live in tone3d.py): one count per mrdis_patch_blur /
+# mrdis_patch_stats / mrdis_patch_tone call (one each per batch of a loader with a patch_blur / _contrast / _gamma / _noise share above 0).
+TONE_FAMILIES = ('patchblur', 'patchstats', 'patchtone')
 # the fused objective of the 3-D nets and the segmentation counts (csrc/mrdis_loss3d.hip): 'loss3d' counts one per mrdis_nvnet_loss_fwd and one per
 # mrdis_nvnet_loss_bwd call, 'segcounts' one per mrdis_seg_counts call.
 LOSS3D_FAMILIES = ('loss3d', 'segcounts')
@@ -283,7 +291,7 @@ EXPORT_FAMILIES = ('export',)
 ELEM_FAMILIES = ('stat_vec', 'stat_scalar', 'stat_interp', 'spade_up2_onepass', 'spade_up2_twopass', 'bil_fwd_x2', 'bil_fwd_general',
                  'bil_bwd_x2', 'bil_bwd_tight3', 'bil_bwd_tight5', 'bil_bwd_general', 'elem_v1')
 # every name of csrc/mrdis_common.h MRDIS_COUNTERS: what launch_counts() hands out, ELEM_FAMILIES on request (tests/test_abi.py pins the union)
-LAUNCH_COUNTERS = (WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + PATCH_FAMILIES + WARP_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + TILEPRED_FAMILIES
+LAUNCH_COUNTERS = (WINO_FAMILIES + VARIANT_FAMILIES + LATENT_FAMILIES + OUTDEC_FAMILIES + CONV3D_FAMILIES + DATA_FAMILIES + PATCH_FAMILIES + WARP_FAMILIES + TONE_FAMILIES + LOSS3D_FAMILIES + SEGVOL_FAMILIES + TILEPRED_FAMILIES
                     + SYNTH_FAMILIES + SEG2D_FAMILIES + FUSE_FAMILIES + SURFDIST_FAMILIES + CC_FAMILIES + PREP_FAMILIES + EXPORT_FAMILIES + LESION_FAMILIES)
 ALL_COUNTERS = LAUNCH_COUNTERS + ELEM_FAMILIES
 SYNTH_MAX_SRC = 8                 # include/mrdis.h MRDIS_SYNTH_MAX_SRC

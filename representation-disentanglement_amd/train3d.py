@@ -32,7 +32,7 @@ import torch.distributed as dist
 import yaml
 
 from . import hip
-from .data3d import VolumeData3D, VolumeStore3D, patch_args, patch_warp_args
+from .data3d import INTENSITY_DEFAULTS, VolumeData3D, VolumeStore3D, patch_args, patch_intensity_args, patch_warp_args
 from .prep import build_store_from_raw, ensure_fold_lists, save_nifti
 from .postproc import CONNECTIVITIES, KEEP_MODES, STATS_COLUMNS, clean_labels, write_stats_csv
 from .model3d import NVNet3D, UNet3D, nvnet_loss, nvnet_loss_hip, predict_volumes, seg_metrics_from_counts
@@ -60,6 +60,15 @@ DEFAULT_CONFIG_3D = {
     'patch_warp': 0.0,                 # patch_size only, with aug: the share of training patches rotated and zoomed on the device (patch3d.patch_warp); 0: off
     'patch_rot': [30, 30, 30],         # patch_warp only: the largest absolute rotation about the H, W and D axes in degrees, each in 0 .. 45
     'patch_zoom': [0.7, 1.4],          # patch_warp only: [lo, hi] of the zoom, lo <= hi in 0.5 .. 2; above 1 magnifies
+    'patch_blur': 0.0,                 # patch_size only, with aug: the share of training items whose contrasts may be blurred on the device (tone3d.py; each contrast with probability 1 / 2); 0: off
+    'patch_blur_sigma': [0.5, 1.0],    # patch_blur only: [lo, hi] of sigma in voxels, lo <= hi in 0.25 .. 1 (the tap radius is 4)
+    'patch_contrast': 0.0,             # patch_size only, with aug: the share of training items with a contrast change about the tissue mean; 0: off
+    'patch_contrast_range': [0.75, 1.25],      # patch_contrast only: [lo, hi] of the factor, lo <= hi in 0.5 .. 2
+    'patch_gamma': 0.0,                # patch_size only, with aug: the share of training items with a gamma curve over the tissue range; 0: off
+    'patch_gamma_range': [0.7, 1.5],   # patch_gamma only: [lo, hi] of the exponent, lo <= hi in 0.5 .. 2
+    'patch_gamma_invert': 0.25,        # patch_gamma only: the share of the gamma'd contrasts that take the inverted curve 1 - (1 - t) ** gamma
+    'patch_noise': 0.0,                # patch_size only, with aug: the share of training items with additive noise; 0: off
+    'patch_noise_std': [0.0, 0.3],     # patch_noise only: [lo, hi] of the standard deviation in store units, lo <= hi in 0 .. 1
     'epochs': 300, 'lr': 1e-4, 'weight_decay': 1e-5,
     'lr_schedule': 'poly',             # none | poly: lr * (1 - epoch / epochs) ** 0.9
     'fused_loss': True,                # false: the torch composition `nvnet_loss`
@@ -125,6 +134,8 @@ def load_config3d(path=None, overrides=None):
         cfg['patch_size'] = list(cfg['patch_size'])
         cfg['patch_warp'], rot, zoom = patch_warp_args(cfg['patch_warp'], cfg['patch_rot'], cfg['patch_zoom'])
         cfg['patch_rot'], cfg['patch_zoom'] = list(rot), list(zoom)
+        for key, v in patch_intensity_args(**{key: cfg[key] for key in INTENSITY_DEFAULTS}).items():
+            cfg[key] = list(v) if isinstance(v, tuple) else v
         if cfg['model_name'] == 'NVNet3D' and any(v % 16 for v in cfg['patch_size']):
             raise ValueError(f'patch_size {cfg["patch_size"]}: every extent a multiple of 16 for NVNet3D (its VAE branch decodes from 1 / 16 of the input)')
         if cfg['patch_fg'] > 0 and cfg['dataset_name'] != 'BraTS':
@@ -311,7 +322,8 @@ class Run3D:
             data = VolumeData3D(cfg['dataset_name'], cfg['data_path'], norm_type=cfg['norm_type'], batch_size=cfg['batch_size'], fold=cfg['fold'],
                                 shuffle=True, contrast_list=cfg['contrast_list'], aug=cfg['aug'], dropoff=cfg['dropoff'], store=store,
                                 device=dev, region_channels=3, patch_size=cfg['patch_size'], patch_fg=cfg['patch_fg'], patch_flips=cfg['patch_flips'],
-                                patch_warp=cfg['patch_warp'], patch_rot=cfg['patch_rot'], patch_zoom=cfg['patch_zoom'])
+                                patch_warp=cfg['patch_warp'], patch_rot=cfg['patch_rot'], patch_zoom=cfg['patch_zoom'],
+                                **({key: cfg[key] for key in INTENSITY_DEFAULTS} if cfg['patch_size'] is not None else {}))
         self.data = data
         self.loaders = {'train': data.trainLoader, 'val': data.valLoader, 'test': data.testLoader}
         if cfg['phase'] == 'predict':
