@@ -1173,7 +1173,7 @@ static int run_bwgrad_s2(const void* x, int ldx, const void* dy, int lddy, float
     }
 #define BWP_CASE(a, b_, HF) if (pl.wci == a && pl.wco == b_ && (Ci == 16) == HF) { \
         if (!mrdis_lds_optin((const void*)bwgrad_pack_kernel<a, b_, HF>, 128 * 1024)) return MRDIS_ELAUNCH; \
-        MRDIS_LAUNCH((bwgrad_pack_kernel<a, b_, HF>), dim3(pl.grid, 4), dim3(512), pl.lds, s, pl.pk); }
+        mrdis_count(MRDIS_CNT_BWGRAD_S2); MRDIS_LAUNCH((bwgrad_pack_kernel<a, b_, HF>), dim3(pl.grid, 4), dim3(512), pl.lds, s, pl.pk); }
     BWP_CASE(1, 1, true) else BWP_CASE(1, 2, true) else BWP_CASE(1, 1, false) else BWP_CASE(1, 2, false) else BWP_CASE(2, 1, false) else BWP_CASE(2, 2, false)
     else return MRDIS_EUNSUPPORTED;
 #undef BWP_CASE
@@ -1263,7 +1263,7 @@ int mrdis_run_bwgrad(const void* x, int ldx, const void* dy, int lddy, float* dw
     const int grid = p.splits * p.nCiB * p.nCoB;
 #define BW_CASE_H(a, b_, TS, HF) if (pl.wci == a && pl.wco == b_) { \
         if (!mrdis_lds_optin((const void*)bwgrad_kernel<a, b_, TS, HF>, 128 * 1024)) return MRDIS_ELAUNCH; \
-        MRDIS_LAUNCH((bwgrad_kernel<a, b_, TS, HF>), dim3(grid), dim3(512), pl.lds, s, p); }
+        mrdis_count(MRDIS_CNT_BWGRAD); MRDIS_LAUNCH((bwgrad_kernel<a, b_, TS, HF>), dim3(grid), dim3(512), pl.lds, s, p); }
 #define BW_CASE(a, b_, TS) BW_CASE_H(a, b_, TS, false)
     bool done2 = false;
     if (st_bf16 && Ci % 32 == 0 && mrdis_opt(MRDIS_OPT_WINO_PIPE)) {              // pipelined form (bwgrad2_kernel); needs both images twice in LDS
@@ -1278,14 +1278,14 @@ int mrdis_run_bwgrad(const void* x, int ldx, const void* dy, int lddy, float* dw
         if (canon && xb < 0xffffffe0LL && yb < 0xffffffe0LL && lds3 <= 160 * 1024 && pl.wci * npix3 <= 512 && p.tiles >= 3 * p.splits && mrdis_opt(MRDIS_OPT_MODE) != 3010) {
 #define BW3_CASE(a, b_) if (pl.wci == a && pl.wco == b_) { \
             if (!mrdis_lds_optin((const void*)bwgrad3_kernel<a, b_>, 160 * 1024)) return MRDIS_ELAUNCH; \
-            MRDIS_LAUNCH((bwgrad3_kernel<a, b_>), dim3(grid), dim3(512), lds3, s, p, (unsigned)xb, (unsigned)yb); done2 = true; }
+            mrdis_count(MRDIS_CNT_BWGRAD3); MRDIS_LAUNCH((bwgrad3_kernel<a, b_>), dim3(grid), dim3(512), lds3, s, p, (unsigned)xb, (unsigned)yb); done2 = true; }
             BW3_CASE(1, 1) else BW3_CASE(1, 2) else BW3_CASE(2, 1) else BW3_CASE(2, 2)
 #undef BW3_CASE
         }
         if (!done2 && canon && xb < 0xffffffe0LL && yb < 0xffffffe0LL && lds2 <= 150 * 1024 && p.tiles >= 2 * p.splits) {
 #define BW2_CASE(a, b_) if (pl.wci == a && pl.wco == b_) { \
             if (!mrdis_lds_optin((const void*)bwgrad2_kernel<a, b_>, 150 * 1024)) return MRDIS_ELAUNCH; \
-            MRDIS_LAUNCH((bwgrad2_kernel<a, b_>), dim3(grid), dim3(512), lds2 < 32768 ? 32768 : lds2, s, p, (unsigned)xb, (unsigned)yb); done2 = true; }
+            mrdis_count(MRDIS_CNT_BWGRAD2); MRDIS_LAUNCH((bwgrad2_kernel<a, b_>), dim3(grid), dim3(512), lds2 < 32768 ? 32768 : lds2, s, p, (unsigned)xb, (unsigned)yb); done2 = true; }
             BW2_CASE(1, 1) else BW2_CASE(1, 2) else BW2_CASE(2, 1) else BW2_CASE(2, 2)
 #undef BW2_CASE
         }

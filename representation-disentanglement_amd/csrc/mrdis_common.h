@@ -54,7 +54,8 @@ void mrdis_opt_note(int id, long long value);      // diagnostics a launcher lea
 #define MRDIS_COUNTERS(X) \
     X(WINO, "wino") X(WINO_SPADE, "wino_spade") X(WINO2, "wino2") X(WINO2_SPADE, "wino2_spade") X(WINO4, "wino4") X(WINO4_SPADE, "wino4_spade") X(WINO4N, "wino4n") \
     X(WINO4R, "wino4r") X(WINO_WGRAD, "wino_wgrad") X(WINO_WGRAD2, "wino_wgrad2") X(WINO4_WGRAD, "wino4_wgrad") X(BCONV3, "bconv3") X(BCONV3_SPADE, "bconv3_spade") \
-    X(BCONV4, "bconv4") X(BCONV4_SPADE, "bconv4_spade") X(SPLIT6_C4, "split6_c4") X(SPLIT6_C16, "split6_c16") X(SPLIT6_WGRAD16, "split6_wgrad16") X(SPLIT6_CO4, "split6_co4") \
+    X(BCONV4, "bconv4") X(BCONV4_SPADE, "bconv4_spade") X(BWGRAD, "bwgrad") X(BWGRAD2, "bwgrad2") X(BWGRAD3, "bwgrad3") X(BWGRAD_S2, "bwgrad_s2") /* mrdis_bf16.hip: bwgrad_kernel, bwgrad2_kernel, bwgrad3_kernel, bwgrad_pack_kernel; their reduce launch is not counted */ \
+    X(SPLIT6_C4, "split6_c4") X(SPLIT6_C16, "split6_c16") X(SPLIT6_WGRAD16, "split6_wgrad16") X(SPLIT6_CO4, "split6_co4") \
     X(SPLIT6_C3D, "split6_c3d") X(SPLIT6_W3D, "split6_w3d") X(SPLIT6_TAP, "split6_tap") X(ZSEARCH, "zsearch") \
     X(CONV2SRC, "conv2src") X(ANA_ACT, "ana_act") /* mrdis_encs.hip: the others-variant kernels */ \
     X(KL, "kl") X(AVGPOOL, "avgpool") /* mrdis_latent.hip: the KL term and mean compaction */ \

@@ -220,6 +220,7 @@ def options_restore(snap):
 
 KERNEL_FAMILIES = WINO_FAMILIES = ('wino', 'wino_spade', 'wino2', 'wino2_spade', 'wino4', 'wino4_spade', 'wino4n', 'wino4r', 'wino_wgrad', 'wino_wgrad2', 'wino4_wgrad', 'bconv3', 'bconv3_spade', 'bconv4', 'bconv4_spade',
                                    'split6_c4', 'split6_c16', 'split6_wgrad16', 'split6_co4', 'split6_c3d', 'split6_w3d', 'split6_tap',
+                                   'bwgrad', 'bwgrad2', 'bwgrad3', 'bwgrad_s2',      # the bf16 weight gradients (csrc/mrdis_bf16.hip): bwgrad_kernel, its two pipelined forms, the stride-2 parity-class launch
                                    'all',        # 'all': every kernel launch of the library (bench.py: library_launches_per_step)
                                    'zsearch')    # mrdis_cosine_top1 (nearest-neighbour modality-code search)
 # the kernels of the `others` variants (csrc/mrdis_encs.hip): the modality encoder's two-source first layer (mod_enc_s) and the anatomy

@@ -10,7 +10,14 @@ number of launches, the kernels a fresh process launches for the call alone (`ld
 buffer prefilled with NaN: the neighbouring channels must still hold the same NaN bits afterwards.
 
 kappa (tests/conv_check.py KAPPA): measured worst |got - ref| / (u A) per kernel and direction over all rows (profiles/conv_path_margins.txt,
-recorded with MRDIS_DUMP_MEASURED=<dir>), times about 4."""
+recorded with MRDIS_DUMP_MEASURED=<dir>), times about 4.
+
+The bf16 weight-gradient family (csrc/mrdis_bf16.hip: bwgrad_kernel, bwgrad2_kernel, bwgrad3_kernel, bwgrad_pack_kernel; counters 'bwgrad',
+'bwgrad2', 'bwgrad3', 'bwgrad_s2') has one row per instantiation (BW_ROWS): the instantiation follows from (Ci, Co, storage) and stands in the
+row id, the counter proves the kernel, tests/bwgrad_plan.py replays the planner for 256 CUs and says which (tiles, slabs) made it so.  Their kappa
+is 4x the worst ratio of the same sums evaluated in plain fp32 on the CPU (tests/test_conv_check.py), not of the kernels.  The rows kept under
+debug_mode 3010 (bwgrad2_kernel) must also equal the bwgrad3_kernel result of the same call bit for bit (`twin`)."""
+import functools
 import json
 import os
 import subprocess
@@ -39,13 +46,18 @@ NOT_IN_TABLE = {
 KAPPA = CC.KAPPA
 
 
-def R(rid, op, geom, expect, opts=None, dtype='f32', img=None, lrelu=False, bias=True, sink=False, chain=None, kname=None, launches=None, lds_kernel=None):
+def R(rid, op, geom, expect, opts=None, dtype='f32', img=None, lrelu=False, bias=True, sink=False, chain=None, kname=None, launches=None, lds_kernel=None,
+      twin=None, fallback=False, in_pad=None):
     """geom = (N, Ci, Co, H, W, k, stride, pad); expect = the counted families that must launch (() for uncounted paths, then kname names the
     path); chain = options under which the next kernel of the dispatcher takes the call (its result must differ); launches = the number of
     library launches the call makes; lds_kernel = a kernel that must be among those a fresh process launches for this call alone (hip.dynamic_lds
-    names the kernels launched with dynamic LDS; the tap-table kernel must not be among them); dtype: 'f32' | 'bf16' | one of MIXED"""
+    names the kernels launched with dynamic LDS; the tap-table kernel must not be among them); dtype: 'f32' | 'bf16' | one of MIXED | 'bf16m'
+    (weight gradients: fp32 views, MRDIS_DT_F32_BF16M); twin = (options, family): the same call under these options must launch that other family
+    and return the same bits; fallback: hip.fallbacks['conv2d_bwd_weight_bf16'] must rise by one during the row (the bf16 kernels declined and
+    the fp32 kernels ran between two view casts); in_pad = (left, right) channels around the input slices instead of (PAD_C, PAD_C)"""
     return pytest.param(dict(op=op, geom=geom, expect=tuple(expect), opts=opts or {}, dtype=dtype, img=img, lrelu=lrelu, bias=bias, sink=sink,
-                             chain=chain, kname=kname or expect[0], launches=launches, lds_kernel=lds_kernel), id=rid)
+                             chain=chain, kname=kname or expect[0], launches=launches, lds_kernel=lds_kernel, twin=twin, fallback=fallback,
+                             in_pad=in_pad), id=rid)
 
 
 W2 = {'wino': 2}                       # Winograd wherever it applies (the size policy takes these kernels only on big grids)
@@ -53,7 +65,7 @@ NOW16 = {'debug_now16': 1}             # turns off the 1x1 head, the Cout = 16 f
 # uncounted rows without a chain: the last kernel of the dispatcher's order for their call (nothing after it to compare with), where all counters
 # at 0 and no declining kernel before it is the proof
 TERMINAL = {'direct': 'the tap-table direct kernel (run_tapconv)', 'direct_s2': 'the tap-table kernel on the four stride-2 parity classes',
-            'wgrad': 'the generic weight-gradient kernel (plan_wgrad)', 'bconv': 'the generic bf16 tap kernel', 'bwgrad': 'the generic bf16 weight-gradient kernel'}
+            'wgrad': 'the generic weight-gradient kernel (plan_wgrad)', 'bconv': 'the generic bf16 tap kernel'}
 # uncounted rows whose kernel computes the same bits as the next one and launches no kernel with dynamic LDS (so lds_kernel cannot name it)
 SAME_BITS = {'pw dgrad': 'the <= 8 products of a 1x1 data gradient are summed in the same order by the generic kernel; all counters 0 is the proof'}
 MIXED = ('xb_yf', 'xf_yb')             # bf16 x / fp32 y and fp32 x / bf16 y (MRDIS_DT_XBF16_YF32 / _XF32_YBF16)
@@ -97,7 +109,12 @@ ROWS = [
     R('bconv4_spade', 'spade', (4, 32, 16, 16, 32, 3, 1, 1), ['bconv4_spade'], {'bconv4': 2}, dtype='bf16'),
     R('bconv4_spade ragged', 'spade', (3, 64, 64, 21, 47, 3, 1, 1), ['bconv4_spade'], {'bconv4': 2}, dtype='bf16'),
     R('bconv generic (bf16 stride 2)', 'fwd', (2, 32, 64, 16, 24, 4, 2, 1), [], dtype='bf16', kname='bconv'),
-    R('bwgrad bf16', 'wgrad', (2, 32, 64, 23, 37, 3, 1, 1), [], dtype='bf16', sink=True, kname='bwgrad'),
+    # bf16 views the bf16 weight-gradient family declines: hip.conv2d_bwd_weight runs the fp32 generic kernel between two view casts and counts
+    # the fallback.  1702 positions (plan_bwgrad wants 4096); a pixel stride of Ci + 12 channels (run_bwgrad wants a multiple of 8) at the
+    # 4096-position geometry that the family otherwise takes ('bwgrad<1,2,__bf16> 4096 positions' below); stride 2 with the family switched off
+    R('wgrad bf16 tiny-map fallback', 'wgrad', (2, 32, 64, 23, 37, 3, 1, 1), [], dtype='bf16', sink=True, kname='wgrad', fallback=True),
+    R('wgrad bf16 fallback pixel stride % 8 != 0', 'wgrad', (1, 32, 64, 64, 64, 3, 1, 1), [], {'wino': 0}, dtype='bf16', kname='wgrad', fallback=True, in_pad=(8, 4)),
+    R('wgrad bf16 s2 fallback (debug_now16)', 'wgrad', (8, 32, 24, 34, 38, 3, 2, 1), [], NOW16, dtype='bf16', sink=True, kname='wgrad', fallback=True),
     # ---- six-product kernels (option split6)
     R('split6_c4 fwd', 'fwd', (2, 4, 32, 3, 5, 3, 1, 1), ['split6_c4'], {'split6': 1}, lrelu=True),
     R('split6_c4 fwd cout tail', 'fwd', (1, 4, 20, 33, 47, 3, 1, 1), ['split6_c4'], {'split6': 1}),
@@ -156,6 +173,69 @@ ROWS = [
     R('wgrad_c4 fp32 x, bf16 dy (4 -> C)', 'wgrad', (2, 4, 32, 200, 256, 3, 1, 1), [], dtype='xf_yb', kname='wgrad_c4_mixed'),
 ]
 
+# ---- the bf16 weight-gradient family (csrc/mrdis_bf16.hip).  Every row is a wgrad row with need_bias on channel slices, alternately with and
+# without a bias sink, and expects exactly one of 'bwgrad' | 'bwgrad2' | 'bwgrad3' | 'bwgrad_s2'.  The instantiation <WCI,WCO[,TS][,HALF]> in the id
+# follows from the channels: WCI = 2 iff Ci % 64 == 0, WCO = 2 iff Co > 32, HALF iff Ci = 16, TS = float for 'bf16m' (fp32 views).
+# tiles / slabs: what plan_bwgrad gives on 256 CUs (tests/bwgrad_plan.py; tests/test_conv_check.py holds these rows to it): bwgrad3_kernel needs
+# tiles >= 3 slabs, bwgrad2_kernel tiles >= 2 slabs.  The slab count is also what bwgrad_reduce_kernel walks: its wave w sums the slabs w, w + 16,
+# ... four at a time while k + 48 < slabs, then one at a time -- <= 16 slabs: at most one per wave; 17 .. 48: the tail loop alone; >= 65: the
+# unrolled body and the tail in the same wave.
+BW3 = {         # 3x3 stride 1 pad 1, bf16 views, defaults -> bwgrad3_kernel; (N, Ci, Co, H, W)
+    '<1,1> ragged in H and W': (5, 96, 16, 129, 33),             # 330 tiles / 86 slabs (reduce: unrolled body + tail); the last tile row holds 1 of 4 rows, the last column 1 of 32
+    '<1,2> cout tail 72 of 128': (2, 96, 72, 129, 33),           # 132 / 43 (reduce: tail loop alone)
+    '<2,1>': (3, 256, 16, 129, 33),                              # 198 / 64
+    '<2,2>': (3, 128, 72, 129, 33),                              # 198 / 64
+    '<2,2> many-image tiles': (193, 128, 256, 8, 8),             # 97 / 32; NB = 2 images per tile, the last tile has one
+    '<2,2> tiles narrower than 32': (25, 128, 256, 33, 15),      # 125 / 32; TW = 16, TH = 8
+    '<2,2> 16 slabs': (2, 256, 256, 65, 33),                     # 68 / 16 (reduce: one slab per wave)
+}
+M3010 = {'debug_mode': 3010}           # keeps bwgrad2_kernel where bwgrad3_kernel would run
+S2 = {          # stride 2 pad 1, bf16 views -> bwgrad_pack_kernel, the four parity classes in one launch; (N, Ci, Co, H, W, k)
+    '<1,1,false> 3x3': (8, 32, 24, 34, 38, 3),                   # 40 tiles / 40 slabs per class; 17 x 19 class maps
+    '<1,2,false> 4x4': (8, 96, 40, 34, 38, 4),                   # 40 / 22
+    '<2,1,false> 3x3': (8, 64, 32, 36, 60, 3),                   # 40 / 40; 18 x 30 class maps
+    '<2,2,false> 4x4': (6, 64, 40, 52, 76, 4),                   # 84 / 64; 26 x 38 class maps
+    '<1,1,HALF> 3x3': (16, 16, 32, 32, 48, 3),                   # 64 / 64
+    '<1,2,HALF> 4x4': (8, 16, 40, 34, 38, 4),                    # 40 / 40
+}
+
+
+def _bw_rows():
+    rows = []
+
+    def add(rid, shape, fam, opts=None, dtype='bf16', k=3, st=1, twin=None):
+        rows.append(R(rid, 'wgrad', tuple(shape) + (k, st, 1), [fam], opts, dtype=dtype, sink=len(rows) % 2 == 0, twin=twin, launches=2))       # the kernel + the reduce
+    for name, shape in BW3.items():
+        add(f'bwgrad3{name}', shape, 'bwgrad3')
+    for name, shape in BW3.items():        # the same calls on bwgrad2_kernel: the result must be the bwgrad3_kernel one bit for bit
+        add(f'bwgrad2{name} (debug_mode 3010)', shape, 'bwgrad2', M3010, twin=({'debug_mode': -1}, 'bwgrad3'))
+    add('bwgrad2<1,1> natural window', (3, 96, 16, 129, 33), 'bwgrad2')                     # 198 / 86: 2 slabs <= tiles < 3 slabs, defaults
+    add('bwgrad<1,2,__bf16> cout tail 72 (wino_pipe 0)', BW3['<1,2> cout tail 72 of 128'], 'bwgrad', {'wino_pipe': 0})      # 132 / 43
+    add('bwgrad<2,1,__bf16> (wino_pipe 0)', BW3['<2,1>'], 'bwgrad', {'wino_pipe': 0})                                       # 198 / 64
+    # small grids, defaults: tiles = slabs (one tile per workgroup), so neither pipelined form applies
+    add('bwgrad<1,1,__bf16>', (1, 32, 16, 65, 65), 'bwgrad')                                # 51 / 51 (reduce: the unrolled body in waves 0 .. 2 only)
+    add('bwgrad<1,2,__bf16> cout tail 40', (1, 32, 40, 65, 65), 'bwgrad')                   # 51 / 51
+    add('bwgrad<2,1,__bf16>', (1, 64, 16, 65, 65), 'bwgrad')                                # 51 / 51
+    add('bwgrad<2,2,__bf16> cout tail 40', (1, 64, 40, 65, 65), 'bwgrad')                   # 51 / 51
+    add('bwgrad<1,1,__bf16,HALF>', (1, 16, 24, 65, 65), 'bwgrad')                           # 51 / 51
+    add('bwgrad<1,2,__bf16,HALF>', (1, 16, 40, 65, 65), 'bwgrad')                           # 51 / 51
+    add('bwgrad<1,2,__bf16> 4096 positions', (1, 32, 64, 64, 64), 'bwgrad')                 # 32 / 32: the smallest map plan_bwgrad takes
+    add('bwgrad<1,2,__bf16> many-image tiles', (64, 32, 64, 8, 8), 'bwgrad')                # 32 / 32; NB = 2
+    # fp32 views, bf16 MFMA operands (MRDIS_DT_F32_BF16M; taken for Co > 32 or Ci >= 128)
+    add('bwgrad<1,2,float>', (1, 32, 40, 65, 65), 'bwgrad', dtype='bf16m')                  # 51 / 51
+    add('bwgrad<2,2,float>', (1, 64, 72, 65, 67), 'bwgrad', dtype='bf16m')                  # 51 / 51
+    add('bwgrad<2,1,float>', (1, 128, 16, 65, 65), 'bwgrad', dtype='bf16m')                 # 51 / 51
+    add('bwgrad<1,2,float> 96 cin', (1, 96, 40, 33, 130), 'bwgrad', dtype='bf16m')          # 45 / 45
+    add('bwgrad<1,1,float> 160 cin', (1, 160, 16, 65, 65), 'bwgrad', dtype='bf16m')         # 51 / 51; Co <= 32 needs Ci >= 128, WCI = 1 needs Ci % 64 != 0
+    for name, shape in S2.items():
+        add(f'bwgrad_s2{name}', shape[:5], 'bwgrad_s2', k=shape[5], st=2)
+    return rows
+
+
+BW_ROWS = _bw_rows()
+ROWS += BW_ROWS
+
+
 @pytest.fixture(autouse=True)
 def _cpu_threads():
     """the float64 references on at most 16 CPU threads"""
@@ -177,12 +257,13 @@ def tkc(w):
     return w.permute(2, 3, 0, 1).reshape(-1, w.shape[0], w.shape[1]).contiguous().to(DEV)
 
 
-def in_slice(t, dtype, seed):
-    """t (N, C, H, W) as a channel slice (ld = C + 2 PAD_C) of a wider NHWC device buffer"""
+def in_slice(t, dtype, seed, pad=None):
+    """t (N, C, H, W) as a channel slice (ld = C + 2 PAD_C; C + left + right for pad = (left, right)) of a wider NHWC device buffer"""
     N, C, H, W = t.shape
-    wide = torch.cat([rnd((N, PAD_C, H, W), seed), t, rnd((N, PAD_C, H, W), seed + 1)], 1)
+    left, right = pad or (PAD_C, PAD_C)
+    wide = torch.cat([rnd((N, left, H, W), seed), t, rnd((N, right, H, W), seed + 1)], 1)
     wide = wide.to(DEV).contiguous(memory_format=torch.channels_last).to(dtype)
-    return wide[:, PAD_C:PAD_C + C]
+    return wide[:, left:left + C]
 
 
 def out_slice(N, C, H, W, dtype):
@@ -207,6 +288,31 @@ def wino_image(hip, w, R_, S, flip, spadeC=0):
     return img
 
 
+@functools.lru_cache(maxsize=4)
+def wgrad_operands(geom, dtype, seed=0):
+    """the operands of a weight-gradient row and its float64 reference -> (x, dy, ref_w, A_w, ref_b, A_b); shared by the rows of one geometry, by a
+    row and its twin, and by tests/test_conv_check.py: treat as read-only.  dw is referred to the values the kernel multiplies (bf16-rounded for
+    bf16 views and for 'bf16m'), the bias to the values it sums: the view's own, so for 'bf16m' the fp32 dy before the rounding"""
+    N, Ci, Co, H, W, k, st, pad = geom
+    Ho, Wo = (H + 2 * pad - k) // st + 1, (W + 2 * pad - k) // st + 1
+    x, dy = rnd((N, Ci, H, W), 1 + seed), rnd((N, Co, Ho, Wo), 4 + seed)
+    x_in = CC.bf16_round if dtype in ('bf16', 'xb_yf', 'bf16m') else (lambda t: t.double())
+    y_in = CC.bf16_round if dtype in ('bf16', 'xf_yb', 'bf16m') else (lambda t: t.double())
+    ref_w, A_w, ref_b, A_b = CC.wgrad_ref(x_in(x), y_in(dy), k, k, st, pad)
+    if dtype == 'bf16m':
+        ref_b, A_b = dy.double().sum((0, 2, 3)), dy.double().abs().sum((0, 2, 3))
+    return x, dy, ref_w, A_w, ref_b, A_b
+
+
+def wgrad_yardstick(row, seed=0):
+    """{'dw': ratio, 'db': ratio} of the row's sums evaluated in plain fp32 by torch on the CPU (CC.wgrad_fp32) against the row's float64
+    reference: the rounding error that any fp32 accumulation of these sums carries, which the row's kappa is 4x of"""
+    x, dy, ref_w, A_w, ref_b, A_b = wgrad_operands(row['geom'], row['dtype'], seed)
+    k, st, pad = row['geom'][5:]
+    dw, db = CC.wgrad_fp32(x, dy, k, st, pad, rounded_bias=row['dtype'] != 'bf16m')
+    return {'dw': CC.ratio(dw, ref_w, A_w), 'db': CC.ratio(db, ref_b, A_b)}
+
+
 def counted(hip):
     """the launch counters since the last reset ('all': every launch of the library)"""
     return {f: n for f, n in hip.launch_counts(reset=True).items() if f != 'zsearch'}
@@ -225,10 +331,13 @@ def run_row(hip, row, seed=0):
     w_in = CC.bf16_round if bf else (lambda t: t.double())              # (the mixed-storage kernels read the fp32 filter)
     u_y = CC.U_BF16 if ydt is B16 else 0.0
     u_x = CC.U_BF16 if xdt is B16 else 0.0
-    x = rnd((N, Ci, H, W), 1 + seed)
+    if op == 'wgrad':
+        x, dy, ref_w, A_w, ref_b, A_b = wgrad_operands(row['geom'], dtype, seed)
+    else:
+        x = rnd((N, Ci, H, W), 1 + seed)
+        dy = rnd((N, Co, Ho, Wo), 4 + seed)
     w = rnd((Co, Ci, k, k), 2 + seed, (Ci * k * k) ** -0.5)
     b = rnd((Co,), 3 + seed, 0.1) if row['bias'] else None
-    dy = rnd((N, Co, Ho, Wo), 4 + seed)
     wt, wk = tck(w), tkc(w)
     if dtype in MIXED and k == 3 and 4 in (Ci, Co):      # the 3x3 layers with a four-channel side take the filter with that side padded to 16 (zeros)
         T = k * k
@@ -270,9 +379,9 @@ def run_row(hip, row, seed=0):
     elif op == 'wgrad':
         s0 = rnd((Co,), 5 + seed)
         sink = s0.to(DEV) if row['sink'] else None
-        dw, db = hip.conv2d_bwd_weight(in_slice(x, xdt, 11), in_slice(dy, ydt, 13), k, k, st, pad, need_bias=True, bias_sink=sink)
+        dw, db = hip.conv2d_bwd_weight(in_slice(x, xdt, 11, row['in_pad']), in_slice(dy, ydt, 13, row['in_pad']), k, k, st, pad, need_bias=True, bias_sink=sink,
+                                       dtype=hip.DT_F32_BF16M if dtype == 'bf16m' else hip.DT_F32)
         c = counted(hip)
-        ref_w, A_w, ref_b, A_b = CC.wgrad_ref(x_in(x), y_in(dy), k, k, st, pad)
         got_w = dw.reshape(k, k, Ci, Co).permute(3, 2, 0, 1)
         res['dw'] = (got_w, ref_w, A_w, 0.0, None)
         if row['sink']:
@@ -332,16 +441,23 @@ def test_conv_path(mrdis, row, request):
     hip = mrdis.hip
     for name, v in row['opts'].items():
         hip.set_option(name, v)
+    fell = hip.fallbacks['conv2d_bwd_weight_bf16']
     res, c, prim = run_row(hip, row)
     expect = set(row['expect'])
     fam = {f: n for f, n in c.items() if f != 'all'}
     assert all(fam[f] > 0 for f in expect) and all(n == 0 for f, n in fam.items() if f not in expect), (row['expect'], {f: n for f, n in fam.items() if n})
+    assert hip.fallbacks['conv2d_bwd_weight_bf16'] - fell == (1 if row['fallback'] else 0), 'the bf16 weight-gradient fallback'
+    if row['expect'] and row['expect'][0].startswith('bwgrad'):
+        assert fam[row['expect'][0]] == 1, fam[row['expect'][0]]               # counted once per launch
     if row['launches'] is not None:
         assert c['all'] == row['launches'], (row['launches'], c['all'])
     kappa = KAPPA[(row['kname'], row['op'])]
     for name, (got, ref, A, u_out, extra) in res.items():
         r = CC.ratio(got, ref, A, u_out, extra)
-        dump_measured('conv_path_margins.jsonl', dict(row=request.node.callspec.id, kernel=row['kname'], op=row['op'], out=name, ratio=r, kappa=kappa))
+        rec = dict(row=request.node.callspec.id, kernel=row['kname'], op=row['op'], out=name, ratio=r, kappa=kappa)
+        if os.environ.get('MRDIS_DUMP_MEASURED') and row['kname'].startswith('bwgrad'):        # beside it, the plain fp32 evaluation kappa derives from
+            rec['yardstick'] = wgrad_yardstick(row)['dw' if name == 'dw' else 'db']
+        dump_measured('conv_path_margins.jsonl', rec)
         CC.check(got, ref, A, kappa, u_out, extra, what=f'{row["kname"]} {row["op"]} {name}')
     if row['lds_kernel'] is not None:
         names = kernels_in_fresh_process(request.node.callspec.id)
@@ -351,6 +467,15 @@ def test_conv_path(mrdis, row, request):
             hip.set_option(name, v)
         _, c2, prim2 = run_row(hip, row)
         assert not torch.equal(prim.float(), prim2.float()), f'{row["kname"]}: the same bits as the kernel the options {row["chain"]} pick'
+    if row['twin'] is not None:
+        topts, tfam = row['twin']
+        assert tfam not in expect
+        for name, v in topts.items():
+            hip.set_option(name, v)
+        res2, c2, _ = run_row(hip, row)
+        assert {f for f, n in c2.items() if n and f != 'all'} == {tfam}, (tfam, {f: n for f, n in c2.items() if n})
+        for name in res:
+            assert torch.equal(res[name][0], res2[name][0]), f'{name}: {row["kname"]} and {tfam} differ in some bit'
 
 
 def test_table_covers_every_family(mrdis):
@@ -365,3 +490,100 @@ def test_table_covers_every_family(mrdis):
         # (mixed storage), or by being the last kernel of the dispatcher's order
         assert (row['expect'] or row['chain'] or row['launches'] or row['lds_kernel'] or row['dtype'] in MIXED or row['kname'] in TERMINAL
                 or p.id in SAME_BITS), p.id
+
+
+# ---------------------------------------------------------------- the bf16 weight gradients through the C ABI (mrdis_conv2d_bwd_weight)
+EUNSUPPORTED, EWORKSPACE, EALIGN = -2, -3, -5          # include/mrdis.h
+GUARD = 64          # floats on each side of dw and dbias
+
+
+def _abi_call(hip, geom, dw, db, ws=None, ws_bytes=None, accumulate=0, seed=0):
+    """mrdis_conv2d_bwd_weight on bf16 channel slices of the row's operands -> the return code"""
+    import bwgrad_plan as P
+    lib = hip.load()
+    N, Ci, Co, H, W, k, st, pad = geom
+    Ho, Wo = (H + 2 * pad - k) // st + 1, (W + 2 * pad - k) // st + 1
+    x, ldx = hip.nhwc(in_slice(rnd((N, Ci, H, W), 1 + seed), B16, 11))
+    dy, lddy = hip.nhwc(in_slice(rnd((N, Co, Ho, Wo), 4 + seed), B16, 13))
+    if ws is None:
+        nb = max(int(lib.mrdis_conv2d_bwd_weight_workspace(N, H, W, Ci, Co, k, k, st, pad)), (P.plan(N, Ci, Co, H, W, k, st, pad) or {'ws': 0})['ws'], 16)
+        ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    torch.cuda.synchronize()
+    rc = lib.mrdis_conv2d_bwd_weight(x.data_ptr(), ldx, dy.data_ptr(), lddy, dw.data_ptr(), db.data_ptr(), ws.data_ptr(),
+                                     ws.numel() if ws_bytes is None else ws_bytes, N, H, W, Ci, Co, k, k, st, pad, accumulate, hip.DT_BF16, hip._stream())
+    torch.cuda.synchronize()
+    return rc
+
+
+def _guarded(n):
+    """(a NaN-prefilled fp32 buffer of n + 2 GUARD floats, its n-float middle)"""
+    buf = torch.full((n + 2 * GUARD,), float('nan'), device=DEV)
+    return buf, buf[GUARD:GUARD + n]
+
+
+def test_bwgrad_abi_refusals_launch_nothing(mrdis):
+    """what the bf16 weight-gradient family refuses comes back as a code with no kernel launched ('all' unchanged): a workspace one byte short of
+    what the planned slabs need, a workspace that is not 16-byte aligned, and bf16 views outside its domain -- Co = 12, Ci = 48, 4x4 maps whose
+    eight-image tile has too many halo positions, stride 2 on an odd height (bf16 views have no fp32 kernel behind them in the C call: the
+    Python wrapper owns that fallback)"""
+    import bwgrad_plan as P
+    hip = mrdis.hip
+    lib = hip.load()
+
+    def refused(geom, want, **kw):
+        N, Ci, Co = geom[:3]
+        k = geom[5]
+        dw, db = torch.zeros(k * k * Ci * Co, device=DEV), torch.zeros(Co, device=DEV)
+        hip.launch_counts(reset=True)
+        rc = _abi_call(hip, geom, dw, db, **kw)
+        c = hip.launch_counts()
+        assert rc == want and c['all'] == 0, (geom, rc, want, c['all'])
+        assert not dw.any() and not db.any()
+
+    geom = (8, 16, 40, 34, 38, 4, 2, 1)                                         # 'bwgrad_s2<1,2,HALF> 4x4': 40 slabs
+    need = P.plan(*geom[:5], k=4, stride=2)['ws']
+    # for this layer the slabs of this family are the largest request of any weight-gradient kernel, so the library's figure is this family's
+    # and one byte less is refused by run_bwgrad_s2 itself
+    assert need == 4 * 40 * (16 * 16 * 40 + 40) + 256 == int(lib.mrdis_conv2d_bwd_weight_workspace(8, 34, 38, 16, 40, 4, 4, 2, 1))
+    ws = torch.empty(need + 32, dtype=torch.uint8, device=DEV)
+    refused(geom, EWORKSPACE, ws=ws, ws_bytes=need - 1)
+    refused(geom, EALIGN, ws=ws[8:], ws_bytes=need)
+    refused((2, 96, 72, 129, 33, 3, 1, 1), EWORKSPACE, ws_bytes=P.plan(2, 96, 72, 129, 33)['ws'] - 1)      # stride 1, 43 slabs (the buffer itself is full size)
+    refused((2, 96, 12, 129, 33, 3, 1, 1), EUNSUPPORTED)                        # Co % 8 != 0
+    refused((2, 48, 72, 129, 33, 3, 1, 1), EUNSUPPORTED)                        # Ci % 32 != 0 and not 16
+    refused((256, 32, 64, 4, 4, 3, 1, 1), EUNSUPPORTED)                         # 4096 positions, but 8 x 6 x 6 halo positions per tile
+    refused((8, 32, 24, 33, 38, 3, 2, 1), EUNSUPPORTED)                         # stride 2, odd H
+    dw, db = torch.zeros(16 * 16 * 40, device=DEV), torch.zeros(40, device=DEV)   # and with exactly the bytes it needs the same call runs
+    hip.launch_counts(reset=True)
+    assert _abi_call(hip, geom, dw, db, ws=ws, ws_bytes=need) == 0
+    c = hip.launch_counts()
+    assert c['bwgrad_s2'] == 1 and c['all'] == 2 and dw.any() and db.any()
+
+
+@pytest.mark.parametrize('geom,fam', [((1, 16, 40, 65, 65, 3, 1, 1), 'bwgrad'), ((2, 96, 72, 129, 33, 3, 1, 1), 'bwgrad3'), ((8, 16, 40, 34, 38, 4, 2, 1), 'bwgrad_s2')],
+                         ids=['bwgrad<1,2,__bf16,HALF>', 'bwgrad3<1,2> cout tail 72', 'bwgrad_s2<1,2,HALF>'])
+def test_bwgrad_abi_stores_stay_inside_dw_and_dbias(mrdis, geom, fam):
+    """dw and dbias in the middle of NaN-prefilled buffers: the 64 floats on each side keep their bits (a HALF block's rows 16 .. 31 and the
+    couts 72 .. 127 of a cout tail have nowhere to go), the middles equal what the wrapper returns for the same call (checked against float64 by
+    the row of this geometry), and accumulate_bias adds exactly: prefill + db"""
+    hip = mrdis.hip
+    N, Ci, Co, H, W, k, st, pad = geom
+    wbuf, dw = _guarded(k * k * Ci * Co)
+    bbuf, db = _guarded(Co)
+    hip.launch_counts(reset=True)
+    assert _abi_call(hip, geom, dw, db) == 0
+    c = hip.launch_counts()
+    assert c[fam] == 1 and c['all'] == 2, {f: n for f, n in c.items() if n}
+    nan = torch.full((1,), float('nan')).view(torch.int32).item()
+    for buf in (wbuf, bbuf):
+        sides = torch.cat([buf[:GUARD], buf[-GUARD:]]).view(torch.int32)
+        assert bool((sides == nan).all()), 'a store landed outside dw / dbias'
+    assert torch.isfinite(dw).all() and torch.isfinite(db).all()
+    Ho, Wo = (H + 2 * pad - k) // st + 1, (W + 2 * pad - k) // st + 1
+    dw_w, db_w = hip.conv2d_bwd_weight(in_slice(rnd((N, Ci, H, W), 1), B16, 11), in_slice(rnd((N, Co, Ho, Wo), 4), B16, 13), k, k, st, pad, need_bias=True)
+    assert torch.equal(dw_w.reshape(-1), dw) and torch.equal(db_w, db)
+    pre = rnd((Co,), 7).to(DEV)
+    acc = pre.clone()
+    wbuf2, dw2 = _guarded(k * k * Ci * Co)
+    assert _abi_call(hip, geom, dw2, acc, accumulate=1) == 0
+    assert torch.equal(acc, pre + db) and torch.equal(dw2, dw)

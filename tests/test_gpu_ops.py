@@ -1245,19 +1245,50 @@ def test_conv_bf16_mfma(mrdis, case):
     close(db, gy.sum((0, 2, 3)), rtol=2e-5, what='dbias (fp32 sum)')
 
 
-@pytest.mark.parametrize('case', [(8, 64, 128, 64, 64), (5, 32, 64, 50, 70), (3, 128, 256, 33, 47), (16, 64, 32, 32, 32), (2, 32, 40, 96, 128), (40, 128, 128, 16, 16)], ids=str)
+# (N, Ci, Co, H, W) -> (the kernel under debug_mode 3010, the kernel with defaults): the counters of csrc/mrdis_bf16.hip, as plan_bwgrad decides on
+# 256 CUs (tests/bwgrad_plan.py).  bwgrad3_kernel needs tiles >= 3 slabs, bwgrad2_kernel tiles >= 2 slabs: the first six cases (the original
+# ones) never reach bwgrad3_kernel, so both of their calls launch the same kernel and the equality says nothing about the pair; the last four do.
+BWGRAD_PAIR = {
+    (8, 64, 128, 64, 64): ('bwgrad2', 'bwgrad2'),          # 256 tiles / 128 slabs
+    (5, 32, 64, 50, 70): ('bwgrad', 'bwgrad'),             # 195 / 195
+    (3, 128, 256, 33, 47): ('bwgrad', 'bwgrad'),           # 54 / 32
+    (16, 64, 32, 32, 32): ('bwgrad', 'bwgrad'),            # 128 / 128
+    (2, 32, 40, 96, 128): ('bwgrad', 'bwgrad'),            # 192 / 192
+    (40, 128, 128, 16, 16): ('bwgrad', 'bwgrad'),          # 80 / 64
+    (5, 96, 16, 129, 33): ('bwgrad2', 'bwgrad3'),          # 330 / 86: ragged in H and W
+    (2, 96, 72, 129, 33): ('bwgrad2', 'bwgrad3'),          # 132 / 43: cout tail 72 of 128
+    (193, 128, 256, 8, 8): ('bwgrad2', 'bwgrad3'),         # 97 / 32: two images per tile, the last tile has one
+    (25, 128, 256, 33, 15): ('bwgrad2', 'bwgrad3'),        # 125 / 32: 16-wide tiles
+}
+
+
+@pytest.mark.parametrize('case', list(BWGRAD_PAIR), ids=str)
 def test_bf16_weight_gradient_lds_dma_bit_identical(mrdis, case):
     """bwgrad3_kernel (mrdis_bf16.hip, round 5: both images by LDS-DMA into a ring of three stages, dbias from the LDS image) against bwgrad2_kernel
-    (register staging; option debug_mode 3010 keeps it): dw and dbias BIT-IDENTICAL on bf16 views -- ragged tiles, a cout tail (40), every (ci, co) block shape,
-    many-image tiles; and against torch fp32 on the bf16-valued operands up to the order of the fp32 sums."""
+    (register staging; option debug_mode 3010 keeps it): dw and dbias BIT-IDENTICAL on bf16 views -- ragged tiles, a cout tail, every (ci, co) block shape,
+    many-image tiles; and against torch fp32 on the bf16-valued operands up to the order of the fp32 sums.  The launch counters say which kernel
+    each of the two calls ran (BWGRAD_PAIR): where the geometry reaches bwgrad3_kernel the two calls must have launched different kernels."""
     N, Ci, Co, H, W = case
     hip = mrdis.hip
     B16 = torch.bfloat16
     x = rnd((N, Ci, H, W), 1).to(B16); gy = rnd((N, Co, H, W), 2).to(B16)
     xd, gyd = cl(x), cl(gy)
+    fams = ('bwgrad', 'bwgrad2', 'bwgrad3', 'bwgrad_s2')
+
+    def ran():
+        c = hip.launch_counts(reset=True)
+        got = [f for f in fams if c[f]]
+        assert len(got) == 1 and c[got[0]] == 1, c
+        return got[0]
     with hip.option('debug_mode', 3010):
+        hip.launch_counts(reset=True)
         dw2, db2 = hip.conv2d_bwd_weight(xd, gyd, 3, 3, 1, 1, need_bias=True)
+        k2 = ran()
     dw3, db3 = hip.conv2d_bwd_weight(xd, gyd, 3, 3, 1, 1, need_bias=True)
+    k3 = ran()
+    assert (k2, k3) == BWGRAD_PAIR[case], (k2, k3)
+    if 'bwgrad3' in BWGRAD_PAIR[case]:
+        assert k2 != k3
     assert torch.equal(dw2, dw3) and torch.equal(db2, db3)
     wz = torch.zeros(Co, Ci, 3, 3, requires_grad=True)
     F.conv2d(x.float(), wz, None, 1, 1).backward(gy.float())
